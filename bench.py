@@ -1,8 +1,18 @@
 #!/usr/bin/env python
 """Headline benchmark: EditNet decode-steps/sec at B=128 (36x2048 features, prev-caption len 20).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, picks the stream count (untimed probe, below), times exactly K steps in ONE window, writes
+the outputs of the last timed step if `--dump-outputs DIR` is given and prints the result line.  `--full` adds everything
+else: the repeated windows (`repeat`; `value` is then the median window when a window is shorter than 0.5 s), the
+single-stream and pipelined figures, the XE forward, the per-kernel profile (`roofline`, `kernels`), `train`, `secondary`,
+`cpu_baseline` and `experimental`.
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller (rank 0's batch): DIR/seq.npy (greedy token ids,
+float64, B x 18) and DIR/seq_logp.npy (their log-probabilities, float32, B x 18).  Inputs and weights are seeded, so two
+runs with the same arguments decode the same batch.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment re-launches itself under
 `torch.distributed.run` with N ranks (one per GPU, RCCL); under torchrun the flag is informational and
@@ -23,7 +33,7 @@ decodes; nothing is skipped or shared).  By default (`--streams 0`) an untimed p
 count among 3 / 7 / 11 (`batches_in_flight_per_gpu`, `stream_probe_decode_steps_per_sec`); `--streams N` pins it;
 `single_stream_*` (top level) is the one-batch-at-a-time figure measured in the same run.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (`--full` only):
   roofline      dominant kernel = the fp32-MFMA grouped GEMM `gemm_nt_f32`; achieved = algorithmic FLOPs of its
                 launches / their summed duration, measured with HIP events on the launch stream in a second,
                 identical, profiled pass (`value` comes from the un-instrumented pass)
@@ -219,6 +229,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=300, help="timed bench steps (complete B=128 decodes); default gives a ~1 s region")
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline (repeated windows, single-stream / pipelined figures, "
+                         "XE forward, per-kernel profile, train, secondary, cpu_baseline, experimental); the --no-* and "
+                         "--repeat / --train-steps options apply to these")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/seq.npy (float64) and DIR/seq_logp.npy (float32)")
     ap.add_argument("--repeat", type=int, default=5, help="extra repetitions of the timed region (median reported under 'repeat')")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true")
@@ -329,19 +345,27 @@ def main():
             args.streams = best
             stream_probe = {str(n): round(48 * STEPS_PER_DECODE / t, 1) for n, t in stream_probe.items()}
             run(args.warmup)
-        elapsed, (seq, _) = timed_region()                 # the first window of exactly K timed steps
-        # short regions (the driver's --steps 20 is a 60-ms window) are repeated at least 15 times and `value` is the MEDIAN
-        # window: one window of 20 decodes moves by a few percent with host jitter; every window is exactly K steps between
-        # barrier + synchronize on both sides, max over ranks
-        n_win = max(args.repeat, int(os.environ.get("SET_BENCH_MIN_WINDOWS", "15"))) if elapsed < 0.5 else args.repeat
-        windows = [timed_region()[0] for _ in range(max(0, n_win - 1))]
+        elapsed, out = timed_region()                      # the first window of exactly K timed steps
         first_elapsed = elapsed
-        if elapsed < 0.5:
-            elapsed = _median([elapsed] + windows)
+        windows = []
+        if args.full:
+            # short regions (the driver's --steps 20 is a 60-ms window) are repeated at least 15 times and `value` is the
+            # MEDIAN window: one window of 20 decodes moves by a few percent with host jitter; every window is exactly K steps
+            # between barrier + synchronize on both sides, max over ranks
+            n_win = max(args.repeat, int(os.environ.get("SET_BENCH_MIN_WINDOWS", "15"))) if elapsed < 0.5 else args.repeat
+            for _ in range(max(0, n_win - 1)):
+                e, out = timed_region()
+                windows.append(e)
+            if elapsed < 0.5:
+                elapsed = _median([elapsed] + windows)
+        seq, seq_logp = out
+        if args.dump_outputs and rank == 0:
+            # the last timed decode's (seq, seq_logp), copied to the host before anything else reuses the workspaces
+            dump = {"seq": seq.cpu().numpy().astype("float64"), "seq_logp": seq_logp.float().cpu().numpy()}
 
         single = None
         pipelined = None
-        if streams is not None and rank == 0:
+        if args.full and streams is not None and rank == 0:
             # one batch at a time (what a caller that issues one decode after the other sees): windows of K decodes until
             # >= 0.5 s has been timed (3 ... 15 windows), median window — a single 80-ms window right after the multi-stream
             # region measured anything between 3.4 k and 4.7 k on the same build
@@ -395,9 +419,11 @@ def main():
             streams = keep
         # secondary figure: teacher-forced XE forward (editnet.py:479-548, eval mode), same batch, 19 timesteps
         xe_rate = None
-        caps_np, clen_np = synth.captions(seed, B, V, 20, 20)
-        caps, clen = torch.from_numpy(caps_np).to(dev), torch.from_numpy(clen_np).to(dev)
-        if rank == 0:
+        caps = clen = None
+        if args.full:
+            caps_np, clen_np = synth.captions(seed, B, V, 20, 20)
+            caps, clen = torch.from_numpy(caps_np).to(dev), torch.from_numpy(clen_np).to(dev)
+        if args.full and rank == 0:
             xe_fwd = lambda: editnet.DecoderC.forward(dec, X, caps, clen, prev, plen, False, 0.0)
             for _ in range(2):
                 xe_fwd()
@@ -409,7 +435,7 @@ def main():
             torch.cuda.synchronize(dev)
             xe_rate = nx * STEPS_PER_DECODE / (time.perf_counter() - tx)
         prof = None
-        if rank == 0 and not args.no_profile:
+        if args.full and rank == 0 and not args.no_profile:
             keep, streams = streams, None                 # per-kernel timing is taken on ONE stream
             lib = _lib.load()
             lib.set_profile_enable(1)
@@ -423,8 +449,14 @@ def main():
             lib.set_profile_enable(0)
             streams = keep
 
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in dump.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
+
     train = None
-    if not args.no_train:
+    if args.full and not args.no_train:
         try:
             train = train_leg(args, dec, wm, X, caps, clen, prev, plen, dev, dist, rank, world, barrier, max_over_ranks)
         except Exception as e:          # the secondary leg must never take the headline line down with it
@@ -437,7 +469,6 @@ def main():
 
     n_gpus = world
     total_steps = n_gpus * args.steps * STEPS_PER_DECODE
-    rates = sorted(total_steps / e for e in [first_elapsed] + windows)
     line = {
         "metric": "decode-steps/sec (B=128, 36x2048 feats, seqlen=20)",
         "value": round(total_steps / elapsed, 2),
@@ -460,12 +491,6 @@ def main():
         "single_caller_pipelined": pipelined,
         "batches_in_flight_per_gpu": max(1, args.streams),
         "stream_probe_decode_steps_per_sec": stream_probe,
-        "repeat": {"windows": len(rates), "steps_per_window": args.steps, "median": round(_median(rates), 2),
-                   "min": round(rates[0], 2), "max": round(rates[-1], 2), "timed_region_s": round(elapsed, 4),
-                   "value_is": "median window" if first_elapsed < 0.5 else "first window",
-                   # rounds 1-2 reported the FIRST window; kept as a named field so that round-over-round comparisons stay
-                   # like for like
-                   "first_window": round(total_steps / first_elapsed, 2)},
         # SURVEY.md 8d's own bound: 16.88 GFLOP per B=128 timestep against the 157.3 TFLOP/s fp32-MFMA peak (107 us)
         "end_to_end_frac": round(SURVEY_GFLOP_PER_TIMESTEP * 1e9 * (total_steps / elapsed) / n_gpus / (PEAK_FP32_MFMA_TFLOPS * 1e12), 4),
         # the same with the FLOPs the path actually EXECUTES per decode (207.9 GFLOP of step GEMMs with the token
@@ -483,6 +508,14 @@ def main():
                    "xe_forward_single_stream_decode_steps_per_sec": None if xe_rate is None else round(xe_rate, 2),
                    "distinct_tokens_in_last_batch": int(torch.unique(seq).numel())},
     }
+    if args.full:
+        rates = sorted(total_steps / e for e in [first_elapsed] + windows)
+        line["repeat"] = {"windows": len(rates), "steps_per_window": args.steps, "median": round(_median(rates), 2),
+                          "min": round(rates[0], 2), "max": round(rates[-1], 2), "timed_region_s": round(elapsed, 4),
+                          "value_is": "median window" if first_elapsed < 0.5 else "first window",
+                          # rounds 1-2 reported the FIRST window; kept as a named field so that round-over-round comparisons
+                          # stay like for like
+                          "first_window": round(total_steps / first_elapsed, 2)}
     if prof is not None:
         by = {p["tag"]: p for p in prof}
         gemm_tags = sorted((t for t in by if t.startswith("gemm_nt_f32")), key=lambda t: -by[t]["ms"])
@@ -513,12 +546,12 @@ def main():
         line["kernels"] = {p["tag"]: _kernel(p) for p in prof}
     if train is not None:
         line["train"] = train
-    if not args.no_secondary and n_gpus == 1:
+    if args.full and not args.no_secondary and n_gpus == 1:
         from tools import secondary
         line["secondary"] = secondary.all_secondary(dev)
-    if not args.no_cpu_baseline and n_gpus == 1:
+    if args.full and not args.no_cpu_baseline and n_gpus == 1:
         line["cpu_baseline"] = cpu_baseline()
-    if not args.no_secondary and n_gpus == 1 and os.environ.get("SET_LIB_VARIANT") != "exp":
+    if args.full and not args.no_secondary and n_gpus == 1 and os.environ.get("SET_LIB_VARIANT") != "exp":
         line["experimental"] = experimental_leg(args, line)
     print(json.dumps(line))
     if dist is not None:
@@ -540,7 +573,7 @@ def experimental_leg(args, line):
            "fp32_value_this_run": line.get("value")}
     try:
         env = dict(os.environ, SET_LIB_VARIANT="exp", SET_GEMM_SPLIT="1")
-        cmd = [sys.executable, os.path.join(here, "bench.py"), "--no-cpu-baseline", "--no-train", "--no-secondary", "--repeat", "2",
+        cmd = [sys.executable, os.path.join(here, "bench.py"), "--full", "--no-cpu-baseline", "--no-train", "--no-secondary", "--repeat", "2",
                "--steps", str(max(args.steps, 60)), "--warmup", str(args.warmup)]
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=420)
         lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

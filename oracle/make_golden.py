@@ -20,7 +20,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from oracle import cases, ref_slice  # noqa: E402
+from oracle import cases, golden_io, ref_slice  # noqa: E402
 
 OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
 T_ = torch.from_numpy
@@ -197,8 +197,8 @@ def make_editnet(name, adaptive=False):
                 full = np.stack([s[k] for s in steps])
                 out["greedy_" + k + "_slice"] = full[:, :keepB, :32].astype(np.float32)
                 out["greedy_" + k + "_sum"] = full.astype(np.float64).sum(2)
-    np.savez_compressed(os.path.join(OUT, name + ".npz"), **out)
-    sz = os.path.getsize(os.path.join(OUT, name + ".npz"))
+    golden_io.save(os.path.join(OUT, name), out)
+    sz = golden_io.size(os.path.join(OUT, name))
     print("%-28s %8.1f KiB   greedy margin min %.2e  steps %d" % (name, sz / 1024, out["greedy_margin"].min(), len(steps)))
 
 
@@ -287,8 +287,8 @@ def make_dcnet(name):
                 full = np.stack([s[k] for s in steps])
                 out["greedy_" + k + "_slice"] = full[:, :, :32].astype(np.float32)
                 out["greedy_" + k + "_sum"] = full.astype(np.float64).sum(2)
-    np.savez_compressed(os.path.join(OUT, name + ".npz"), **out)
-    sz = os.path.getsize(os.path.join(OUT, name + ".npz"))
+    golden_io.save(os.path.join(OUT, name), out)
+    sz = golden_io.size(os.path.join(OUT, name))
     print("%-28s %8.1f KiB   greedy margin min %.2e  steps %d" % (name, sz / 1024, out["greedy_margin"].min(), len(steps)))
 
 

@@ -26,7 +26,7 @@ from torch.nn.utils.rnn import pack_padded_sequence
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from oracle import cases, philox_np as PH, ref_slice  # noqa: E402
+from oracle import cases, golden_io, philox_np as PH, ref_slice  # noqa: E402
 from oracle.make_golden import OUT, T_, _np, _summ_logits  # noqa: E402
 
 # (case, seed, scheduled-sampling probability)
@@ -281,12 +281,12 @@ def main(argv):
         o = make_dcnet(name, seed) if name in cases.DCNET_CASES else make_editnet(name, seed, ss)
         files.setdefault(name, {}).update(o)
     for name, o in files.items():
-        path = os.path.join(OUT, "train_" + name + ".npz")
-        np.savez_compressed(path, **o)
+        stem = os.path.join(OUT, "train_" + name)
+        golden_io.save(stem, o)
         extra = ""
         if "train_ss.draw_margin_min" in o:
             extra = "  ss: %d words replaced, min draw margin %.2e" % (o["train_ss.n_replaced"], o["train_ss.draw_margin_min"])
-        print("%-30s %8.1f KiB  loss %.6f%s" % ("train_" + name, os.path.getsize(path) / 1024, o["train.loss"], extra))
+        print("%-30s %8.1f KiB  loss %.6f%s" % ("train_" + name, golden_io.size(stem) / 1024, o["train.loss"], extra))
 
 
 if __name__ == "__main__":

@@ -12,7 +12,7 @@ import os
 
 import numpy as np
 
-from oracle import cases
+from oracle import cases, golden_io
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 LOGIT_TOL = 1e-4
@@ -22,7 +22,7 @@ MARGIN_MIN = 2.5e-4      # two logits each within LOGIT_TOL can swap only below 
 
 
 def load(name):
-    return dict(np.load(os.path.join(GOLDEN, name + ".npz")))
+    return golden_io.load(os.path.join(GOLDEN, name))
 
 
 def maxerr(a, b):

@@ -175,7 +175,7 @@ def test_bench_gpus_two_devices_nccl():
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "SET_BENCH_ONE_DEVICE", "SET_BENCH_BACKEND"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "4", "--warmup", "2",
                           "--repeat", "1", "--no-profile", "--no-cpu-baseline", "--no-secondary", "--train-steps", "2"],
                          env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -195,7 +195,7 @@ def test_bench_gpus_flag_spawns_ranks():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, SET_BENCH_ONE_DEVICE="1", SET_BENCH_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
                           "--repeat", "1", "--no-profile", "--no-cpu-baseline", "--no-secondary", "--train-steps", "2"],
                          env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -217,7 +217,7 @@ def test_bench_gpus_eight_ranks_one_device_gloo():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, SET_BENCH_ONE_DEVICE="1", SET_BENCH_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "8", "--steps", "2", "--warmup", "1",
                           "--repeat", "1", "--streams", "1", "--no-profile", "--no-cpu-baseline", "--no-secondary",
                           "--train-steps", "2"], env=env, capture_output=True, text=True, timeout=1500)
     assert out.returncode == 0, out.stderr[-2000:]

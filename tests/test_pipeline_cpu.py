@@ -109,9 +109,10 @@ def _fixed_dataset(tmp_path, n_train=17, n_val=9, R=36, F=32, cpi=5, seed=3):
 
 def test_fixed_reader_matches_the_reference_getitem(tmp_path):
     """FixedFeatureReader against COCOTrainDataset.__getitem__ (editnet.py:46-74): the split test on objdet[0], the row
-    objdet[1], fp32 features; when /root/reference is present the reference's OWN __getitem__ (AST-sliced, its HDF5 datasets
-    replaced by the same arrays) produces the expected tuples, otherwise its restatement below does."""
-    from oracle import ref_slice
+    objdet[1], fp32 features.  The expected tensors are what the reference's OWN __getitem__ (AST-sliced, its HDF5 datasets
+    replaced by the same arrays) returned for every sample of this dataset (tests/golden/reader_getitem.npz,
+    oracle/make_reader_golden.py); the restatement below must agree with them."""
+    import parity
     ds = _fixed_dataset(tmp_path)
     cpi = ds["cpi"]
     n = len(ds["captions"])
@@ -120,15 +121,10 @@ def test_fixed_reader_matches_the_reference_getitem(tmp_path):
         od = ds["objdet"][i // cpi]
         return torch.from_numpy((ds["va"] if od[0] == "v" else ds["tr"])[od[1]].copy())
 
-    getitem = restated
-    if ref_slice.have_reference():
-        cls = ref_slice.load_classes("editnet.py", ("COCOTrainDataset",))["COCOTrainDataset"]
-        obj = cls.__new__(cls)
-        obj.train_features, obj.val_features, obj.cpi = ds["tr"], ds["va"], cpi
-        obj.captions, obj.caplens, obj.names = ds["captions"], ds["caplens"], ds["names"]
-        obj.caption_util, obj.objdet, obj.dataset_size = ds["util"], ds["objdet"], n
-        getitem = lambda i: obj[i][0]
-        assert torch.equal(obj[7][0], restated(7))
+    ref_img = parity.load("reader_getitem")["img"]
+    assert ref_img.shape == (n, 36, 32) and ref_img.dtype == np.float32
+    getitem = lambda i: torch.from_numpy(ref_img[i].copy())
+    assert all(torch.equal(getitem(i), restated(i)) for i in range(n))
     order = np.random.default_rng(0).permutation(n)
     batches = [order[i:i + 8].tolist() for i in range(0, n, 8)]                     # ragged last batch, > ring depth
     refs = [[tuple(ds["objdet"][i // cpi][:2]) for i in b] for b in batches]

@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 OUT=${1:-gpurun_out/pmc_bench}
 KERNEL=${2:-"gemm_nt_f32<64, 64|gemm_nt_f32_asm<"}     # the 64x64 GEMM, compiler-scheduled and hand-written k-loop
 rm -rf $OUT; mkdir -p $OUT
-BENCH="python bench.py --steps 3 --warmup 1 --repeat 1 --streams ${PMC_STREAMS:-3} --no-cpu-baseline --no-profile --no-train --no-secondary"
+BENCH="python bench.py --full --steps 3 --warmup 1 --repeat 1 --streams ${PMC_STREAMS:-3} --no-cpu-baseline --no-profile --no-train --no-secondary"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -o fetch -- $BENCH > $OUT/fetch.log 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/write -o write -- $BENCH > $OUT/write.log 2>&1
 if [ -z "$PMC_NO_SQ" ]; then

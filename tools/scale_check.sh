@@ -39,10 +39,10 @@ PORT=29770
 for N in 1 2 4 8; do
     [ "$N" -gt "$NDEV" ] && continue
     if [ "$N" -eq 1 ]; then
-        timeout 1800 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > "$LOG/bench_n$N.json" 2> "$LOG/bench_n$N.err"
+        timeout 1800 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > "$LOG/bench_n$N.json" 2> "$LOG/bench_n$N.err"
     else
         timeout 1800 python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port $((PORT + N)) \
-            bench.py --gpus "$N" --steps 20 --warmup 5 > "$LOG/bench_n$N.json" 2> "$LOG/bench_n$N.err"
+            bench.py --full --gpus "$N" --steps 20 --warmup 5 > "$LOG/bench_n$N.json" 2> "$LOG/bench_n$N.err"
     fi
     echo "bench --gpus $N rc=$?"
 done
