@@ -204,8 +204,12 @@ int set_editnet_greedy_begun(const SetEditNetWeights* w, const SetEditNetDims* d
  * Outputs (device): hist_parent / hist_word (max_picks, 4) = parent slot and appended word of every slot after every pick —
  * the host follows them back to read a sequence; best_score / best_word [1] and result [4] = {pick index of the best
  * completed hypothesis (-1: none), its parent slot, hypotheses still alive, picks made}.  A time-out poisons best_score with
- * NaN and result[2..3] = -1 (SET_ERR_FAULT at the next call).  SET_ERR_UNSUPPORTED (take set_editnet_step +
- * set_beam_pick_f32): no token table, k > 4, adaptive features, dimensions the persistent launch does not cover, another
+ * NaN and result[2..3] = -1 (SET_ERR_FAULT at the next call).  Adaptive features (d->adaptive, the reference's
+ * adaptive_features/editnet_adaptive.py:614-735): image_mean (k, F) is the image's own mean (NULL: the mean over all R
+ * regions), R even and <= 128; the zero-padded regions are masked in the visual attention (scores -1e10, weights exactly 0),
+ * on a kernel instantiation with room for 128 regions.  SET_ERR_UNSUPPORTED (take set_editnet_step +
+ * set_beam_pick_f32): no token table, k > 4, an odd R or more than 128 adaptive regions (36 fixed ones), dimensions the
+ * persistent launch does not cover, another
  * process owns the device's persistent launches — all answered BEFORE anything is touched; only a device whose LDS limit or
  * resident-workgroup capacity turns out too small is answered after the prologue has been written into `ws` (outputs
  * untouched; the answer is the same for every later call with these dims, so a caller remembers it).

@@ -141,6 +141,7 @@ __device__ __forceinline__ void pd_mma(f32x4& acc, const f32x4 (&w)[KB], const f
 
 // ---- EditNet: arguments of decode_persistent_wide.hip (1 .. 16 rows; greedy, teacher-forced and beam mode)
 constexpr int PDEC_RREG = 36;      // image regions whose hoisted x2h products a thread keeps in registers
+constexpr int PDEC_RREG_WIDE = 128; // ... in the beam instantiation for adaptive features (10 - 100 zero-padded regions, masked)
 
 struct PDecEditArgs {
     // weights (nn.Linear layout, used in place)
@@ -177,7 +178,11 @@ struct PDecEditArgs {
     // teacher-forced mode (set_editnet_xe_forward, editnet.py:505-546): words from caps, scores of the first bt rows written
     // out, no pick and no sixth exchange
     const long long* caps; long long caps_stride;
-    float* predictions; long long ld_pred_b;     // (B, maxT, V)
+    union {                                      // (one of the two modes: the argument block keeps its size and layout)
+        float* predictions;                      // (B, maxT, V) teacher-forced mode
+        const float* rmask;                      // (B, R) beam mode over adaptive features (RREG > 64): 0 = padded region
+    };
+    long long ld_pred_b;
     int dlen[PDW_MAXB];                          // decode lengths, descending
     int stamp_wg;
     unsigned long long* stamps;
@@ -191,9 +196,10 @@ struct PDecEditArgs {
 };
 
 // the wide variant's launch (decode_persistent_wide.hip); P is complete except for the exchange pointers it lays out itself
-int editnet_persistent_wide_launch(PDecEditArgs& P, void* xbuf, PersistentGuard& guard, hipStream_t s, bool* unsupported, bool beam = false);
-size_t editnet_persistent_wide_xbytes(int B, int D, int A);
-bool editnet_persistent_wide_ok(int B, int D, int A, int T, int R, int V);
+int editnet_persistent_wide_launch(PDecEditArgs& P, void* xbuf, PersistentGuard& guard, hipStream_t s, bool* unsupported, bool beam = false,
+                                   bool wide_regions = false);
+size_t editnet_persistent_wide_xbytes(int B, int D, int A, int R = 0);
+bool editnet_persistent_wide_ok(int B, int D, int A, int T, int R, int V, bool wide_regions);   // (default: set_common.h)
 
 // host side of the stamps: buffer for a launch (or NULL) and the report after it
 inline int pd_stamps_begin(unsigned long long** out, int* wg, hipStream_t s) {

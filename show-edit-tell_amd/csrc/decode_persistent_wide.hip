@@ -42,15 +42,22 @@ namespace {
 constexpr int PW_U = 16;           // 16-byte requests a lane keeps in flight while it fills LDS from an exchange buffer
 constexpr int PW_BEAM_K = 4;       // beam mode: hypotheses (= rows) at most
 constexpr int PW_BEAM_W = 12;      // ... words a workgroup publishes per row: max, sum exp, 4 x (value, index), 2 pads
-constexpr int PW_RS = PDEC_RREG + 1;   // row strides of the hoisted-product tables in LDS: odd, so that the (thread, index) gathers
-constexpr int PW_TS = PDEC_TMAX + 1;   // of 256 threads spread over all banks
+constexpr int PW_TS = PDEC_TMAX + 1;   // row strides of the hoisted-product tables in LDS: odd (region table: RREG + 1), so that the
+                                       // (thread, index) gathers of 256 threads spread over all banks
+// visual scores per row in LDS and in the exchange: 64, or the region capacity above that
+constexpr int pw_vcols(int rreg) { return rreg > 64 ? rreg : 64; }
 
 }  // namespace
 
 // BEAM: the rows are the k <= PW_BEAM_K hypotheses of ONE image and the loop is the reference's beam search (editnet.py:643-713)
 // instead of the greedy loop — see "beam mode" below.
-template <bool BEAM>
+// RREG: region capacity of the hoisted region products in LDS.  PDEC_RREG (36) for fixed features; PDEC_RREG_WIDE (128) for the
+// beam search over adaptive features (editnet_adaptive.py:614-735): up to 128 zero-padded regions whose scores are masked to
+// -1e10 where P.rmask == 0 (step_attention_k), two scores per lane in the softmax.  The masked weights underflow to exactly 0,
+// which is the reference's truncation to max(att_masks.sum(1)): all rows of a beam launch are the same image.
+template <bool BEAM, int RREG>
 __global__ void __launch_bounds__(PDEC_THREADS, 1) editnet_persistent_wide_k(const PDecEditArgs P) {
+    constexpr int RS = RREG + 1, VC = pw_vcols(RREG);
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __shared__ long long sTok[PDW_MAXB];
     __shared__ int sUnf[PDW_MAXB], sJs[PDW_MAXB];
@@ -63,12 +70,12 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) editnet_persistent_wide_k(con
     float* sX = smem;                                    // (B, LDH): h1 -> attend_cap -> c_new -> h2 -> triples (B, G, 4) in turn
     float* sRed = sX + B * LDH;                          // [4 waves][3 tiles][16][16]
     float* sAlc = sRed + 4 * 3 * 256;                    // (B, TMAX) caption scores -> weights
-    float* sAlv = sAlc + PDW_MAXB * PDEC_TMAX;           // (B, 64) visual scores -> weights
-    float* sG = sAlv + PDW_MAXB * 64;                    // (B, 16) copy_lstm gate pre-activations
+    float* sAlv = sAlc + PDW_MAXB * PDEC_TMAX;           // (B, VC) visual scores -> weights
+    float* sG = sAlv + PDW_MAXB * VC;                    // (B, 16) copy_lstm gate pre-activations
     float* sZ = sG + PDW_MAXB * 16;                      // (B, 8) [sum alpha P_z (4) | sum alpha P_s (4)] of the owned columns
     float* sM = sZ + PDW_MAXB * 8;                       // (B, 8) [context_gate.W h1 (4) | tc_affine.W h1 (4)]
     float* sPv = sM + PDW_MAXB * 8;                      // (B, 16, RREG) hoisted region products of the owned gate rows
-    float* sPz = sPv + B * 16 * PW_RS;                   // (B, 8, TMAX) hoisted caption-context products of the owned columns
+    float* sPz = sPv + B * 16 * RS;                   // (B, 8, TMAX) hoisted caption-context products of the owned columns
     float* sCon = sPz + B * 8 * PW_TS;               // [cap_decoder_att.b | cap_full_att.w | decoder_att.b | full_att.w] (4, A)
     const float* sF = sX;
     // beam mode only: every workgroup's per-slice candidates, the previous timestep's h2h products (added through the parent
@@ -133,7 +140,7 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) editnet_persistent_wide_k(con
         bg = P.ca_gate_b[pd]; bsc = P.ca_sc_b[pd]; btc = P.ca_tc_b[pd]; bcn = P.cl_cnew_b[pd]; bcm = P.cl_cmem_b[pd];
     }
     if (gcol) {
-        for (int rr = 0; rr < PDEC_RREG; ++rr) sPv[tid * PW_RS + rr] = rr < R ? P.pv[((long long)cb * R + rr) * 4 * D + ccol] : 0.f;
+        for (int rr = 0; rr < RREG; ++rr) sPv[tid * RS + rr] = rr < R ? P.pv[((long long)cb * R + rr) * 4 * D + ccol] : 0.f;
         b2 = P.cl_x2h_b[ccol] + P.cl_h2h_b[ccol];
     }
     if (zrole)
@@ -156,12 +163,14 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) editnet_persistent_wide_k(con
     const float cs_mask = P.mask[(long long)cs_b * T + cs_t];
     const f32x4 va1_0 = *reinterpret_cast<const f32x4*>(P.att1 + ((long long)vs_b * R + vs_r) * A + a_lo);
     const f32x4 va1_1 = *reinterpret_cast<const f32x4*>(P.att1 + ((long long)vs_b * R + vs_r) * A + a_hi);
+    bool vs_pad = false;                                 // adaptive features: this wave's region is padding (editnet_adaptive.py:453)
+    if constexpr (RREG > 64) vs_pad = vs_on && P.rmask[(long long)vs_b * R + vs_r] == 0.f;
     // exchange buffers
     const __amdgpu_buffer_rsrc_t h1rs = __builtin_amdgcn_make_buffer_rsrc(P.x_h1, 0, B * D * 8, 0x00027000);
     const __amdgpu_buffer_rsrc_t a2rs = __builtin_amdgcn_make_buffer_rsrc(P.x_a2, 0, B * 2 * A * 8, 0x00027000);
     const __amdgpu_buffer_rsrc_t gtrs = __builtin_amdgcn_make_buffer_rsrc(P.x_gt, 0, B * D * 8, 0x00027000);
     const __amdgpu_buffer_rsrc_t csrs = __builtin_amdgcn_make_buffer_rsrc(P.x_cs, 0, B * PDEC_TMAX * 8, 0x00027000);
-    const __amdgpu_buffer_rsrc_t vsrs = __builtin_amdgcn_make_buffer_rsrc(P.x_vs, 0, B * 64 * 8, 0x00027000);
+    const __amdgpu_buffer_rsrc_t vsrs = __builtin_amdgcn_make_buffer_rsrc(P.x_vs, 0, B * (RREG > 64 ? pw_vcols(R) : 64) * 8, 0x00027000);
     const __amdgpu_buffer_rsrc_t cnrs = __builtin_amdgcn_make_buffer_rsrc(P.x_cn, 0, B * D * 8, 0x00027000);
     const __amdgpu_buffer_rsrc_t h2rs = __builtin_amdgcn_make_buffer_rsrc(P.x_h2, 0, B * D * 8, 0x00027000);
     const __amdgpu_buffer_rsrc_t fcrs = __builtin_amdgcn_make_buffer_rsrc(P.x_fc, 0, B * G * 32, 0x00027000);
@@ -299,13 +308,14 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) editnet_persistent_wide_k(con
             float sc = vfw0[0] * fmaxf(x0[0], 0.f) + vfw0[1] * fmaxf(x0[1], 0.f) + vfw0[2] * fmaxf(x0[2], 0.f) + vfw0[3] * fmaxf(x0[3], 0.f);
             sc += vfw1[0] * fmaxf(x1[0], 0.f) + vfw1[1] * fmaxf(x1[1], 0.f) + vfw1[2] * fmaxf(x1[2], 0.f) + vfw1[3] * fmaxf(x1[3], 0.f);
             vs_val = pw_wsum(sc) + vbf;
+            if (vs_pad) vs_val = -1e10f;
         }
         ++tag;                                                   // X3a: caption scores + visual scores
         if (cs_on && lane == 0) ll_put(csrs, cs_b * T + cs_t, cs_val, tag);
         if (vs_on && lane == 0) ll_put(vsrs, vs_b * R + vs_r, vs_val, tag);
         PD_STAMP(5);
         PW_STAGE(csrs, sAlc, B, T, PDEC_TMAX);                   // (T and R are even: editnet_persistent_wide_ok)
-        PW_STAGE(vsrs, sAlv, B, R, 64);
+        PW_STAGE(vsrs, sAlv, B, R, VC);
         pd_load_if(wa, pT6, v6);                                 // S5's (short) tile and fc's first one stream under the softmaxes
         pd_load_if(wc, pF[0], vF[0]);                            // and the attend_cap exchange
         PW_SYNC();
@@ -329,12 +339,20 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) editnet_persistent_wide_k(con
                     const float aj = pw_lane(al, js);
                     if (lane == 0) { sJs[b] = js; sWj[b] = aj * 1.f + (1.f - aj); }   // the reference's fp32 expression (editnet.py:417-418)
                 }
-                {
+                if constexpr (RREG <= 64) {
                     const float sc = lane < R ? sAlv[b * 64 + lane] : -INFINITY;
                     const float m = pw_wmax(sc);
                     const float ex = lane < R ? expf(sc - m) : 0.f;
                     const float sum = pw_wsum(ex);
                     if (lane < R) sAlv[b * 64 + lane] = ex / sum;
+                } else {                                         // up to 128 scores: lane l holds regions l and l + 64
+                    const int l1 = lane + 64;
+                    const float sc0 = lane < R ? sAlv[b * VC + lane] : -INFINITY, sc1 = l1 < R ? sAlv[b * VC + l1] : -INFINITY;
+                    const float m = pw_wmax(fmaxf(sc0, sc1));
+                    const float ex0 = lane < R ? expf(sc0 - m) : 0.f, ex1 = l1 < R ? expf(sc1 - m) : 0.f;
+                    const float sum = pw_wsum(ex0 + ex1);
+                    if (lane < R) sAlv[b * VC + lane] = ex0 / sum;
+                    if (l1 < R) sAlv[b * VC + l1] = ex1 / sum;
                 }
             }
         }
@@ -373,7 +391,7 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) editnet_persistent_wide_k(con
         if (gcol) {
             const int o = cb * 16 + crr;
             float s = 0.f;
-            for (int rr = 0; rr < R; ++rr) s += sAlv[cb * 64 + rr] * sPv[tid * PW_RS + rr];
+            for (int rr = 0; rr < R; ++rr) s += sAlv[cb * VC + rr] * sPv[tid * RS + rr];
             float g2 = ((sRed[2 * 256 + o] + sRed[5 * 256 + o]) + sRed[8 * 256 + o]) + sRed[11 * 256 + o];
             if (BEAM) {                                          // + copy_lstm.h2h h2 of the PARENT hypothesis (S1' of the previous timestep)
                 const int op = sPar[cb] * 16 + crr;
@@ -738,37 +756,43 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) editnet_persistent_wide_k(con
     }
 }
 
-static int pwide_lds_floats(int B, int D, int A, bool beam = false) {
-    const int base = B * (D + 4) + 4 * 3 * 256 + PDW_MAXB * (PDEC_TMAX + 64 + 16 + 8 + 8) + B * 16 * PW_RS + B * 8 * PW_TS + 4 * A;
+static int pwide_lds_floats(int B, int D, int A, bool beam = false, int rreg = PDEC_RREG) {
+    const int base = B * (D + 4) + 4 * 3 * 256 + PDW_MAXB * (PDEC_TMAX + pw_vcols(rreg) + 16 + 8 + 8) + B * 16 * (rreg + 1) + B * 8 * PW_TS + 4 * A;
     return base + (beam ? B * (D / 4) * PW_BEAM_W + 4 * 256 + 2 * PW_BEAM_K * 4 + PW_BEAM_K * PW_BEAM_K * 2 : 0);
 }
 
 // [status line | h1 | attend_cap | c_new | h2 | projections | caption scores | visual scores | fc triples] as flag-in-data words
-size_t editnet_persistent_wide_xbytes(int B, int D, int A) {
+// (visual scores: 64 per row, R per row above 64 regions)
+size_t editnet_persistent_wide_xbytes(int B, int D, int A, int R) {
     if (B > PDW_MAXB) return 0;
-    return 128 + (size_t)B * D * 8 * 4 + (size_t)B * 2 * A * 8 + (size_t)B * PDEC_TMAX * 8 + (size_t)B * 64 * 8 + (size_t)B * (D / 4) * 32 +
+    return 128 + (size_t)B * D * 8 * 4 + (size_t)B * 2 * A * 8 + (size_t)B * PDEC_TMAX * 8 + (size_t)B * pw_vcols(R) * 8 + (size_t)B * (D / 4) * 32 +
            (B <= PW_BEAM_K ? (size_t)B * (D / 4) * PW_BEAM_W * 8 : 0);       // + the beam mode's candidate words
 }
 
-bool editnet_persistent_wide_ok(int B, int D, int A, int T, int R, int V) {
+// wide_regions: the PDEC_RREG_WIDE instantiation (adaptive beam search), otherwise the PDEC_RREG one
+bool editnet_persistent_wide_ok(int B, int D, int A, int T, int R, int V, bool wide_regions) {
     if (B < 1 || B > PDW_MAXB) return false;
-    if (D != 64 * PDEC_KB || A != 512 || 2 * A != D || T > PDEC_TMAX || R > PDEC_RREG || R > 64 || (R & 1) || (T & 1)) return false;
+    const int rreg = wide_regions ? PDEC_RREG_WIDE : PDEC_RREG;
+    if (D != 64 * PDEC_KB || A != 512 || 2 * A != D || T > PDEC_TMAX || R > rreg || R > pw_vcols(rreg) || (R & 1) || (T & 1)) return false;
     const int G = D / 4;
     if ((V + G - 1) / G > 16 * PDEC_FC_TILES) return false;
     if (B * R > 4 * G || B * T > 4 * G) return false;               // one score of each kind per wave
     if (4 * G != 2 * A) return false;                                // the triples (B, G, 4) take the projections' place
-    const int lds = pwide_lds_floats(B, D, A) * (int)sizeof(float);
+    const int lds = pwide_lds_floats(B, D, A, false, rreg) * (int)sizeof(float);
     if (lds > 156 * 1024 || lds + 4096 > persistent_lds_limit()) return false;
     return true;
 }
 
-static int g_pwide_capacity[2][64] = {};
-static int g_pwide_capacity_lds[2][64] = {};
+// residency and LDS configuration per instantiation: [0] greedy / teacher-forced, [1] beam, [2] beam over up to 128 masked regions
+static int g_pwide_capacity[3][64] = {};
+static int g_pwide_capacity_lds[3][64] = {};
 
-int editnet_persistent_wide_launch(PDecEditArgs& P, void* xbuf, PersistentGuard& guard, hipStream_t s, bool* unsupported, bool beam) {
+int editnet_persistent_wide_launch(PDecEditArgs& P, void* xbuf, PersistentGuard& guard, hipStream_t s, bool* unsupported, bool beam,
+                                   bool wide_regions) {
     *unsupported = true;
     const int B = P.B, D = P.D, A = P.A, G = D / 4;
-    if (!editnet_persistent_wide_ok(B, D, A, P.T, P.R, P.V)) return SET_OK;
+    if (wide_regions && (!beam || !P.rmask)) return SET_OK;          // the wide instantiation is the adaptive beam search only
+    if (!editnet_persistent_wide_ok(B, D, A, P.T, P.R, P.V, wide_regions)) return SET_OK;
     if (beam && (B > PW_BEAM_K || P.caps || (long long)B * P.V >= 0x7fffffffLL)) return SET_OK;
     {
         char* x = (char*)xbuf;
@@ -779,19 +803,21 @@ int editnet_persistent_wide_launch(PDecEditArgs& P, void* xbuf, PersistentGuard&
         P.x_h2 = x; x += (size_t)B * D * 8;
         P.x_a2 = x; x += (size_t)B * 2 * A * 8;
         P.x_cs = x; x += (size_t)B * PDEC_TMAX * 8;
-        P.x_vs = x; x += (size_t)B * 64 * 8;
+        P.x_vs = x; x += (size_t)B * pw_vcols(P.R) * 8;
         P.x_fc = x; x += (size_t)B * G * 32;
         P.x_fcb = x;
     }
-    const void* kern = beam ? reinterpret_cast<const void*>(&editnet_persistent_wide_k<true>)
-                            : reinterpret_cast<const void*>(&editnet_persistent_wide_k<false>);
-    const int lds = pwide_lds_floats(B, D, A, beam) * (int)sizeof(float);
-    static bool configured[2][64] = {};
-    int lds_max = pwide_lds_floats(beam ? PW_BEAM_K : PDW_MAXB, D, A, beam) * (int)sizeof(float);
+    const int inst = wide_regions ? 2 : (beam ? 1 : 0), rreg = wide_regions ? PDEC_RREG_WIDE : PDEC_RREG;
+    const void* kern = inst == 2 ? reinterpret_cast<const void*>(&editnet_persistent_wide_k<true, PDEC_RREG_WIDE>)
+                     : inst == 1 ? reinterpret_cast<const void*>(&editnet_persistent_wide_k<true, PDEC_RREG>)
+                                 : reinterpret_cast<const void*>(&editnet_persistent_wide_k<false, PDEC_RREG>);
+    const int lds = pwide_lds_floats(B, D, A, beam, rreg) * (int)sizeof(float);
+    static bool configured[3][64] = {};
+    int lds_max = pwide_lds_floats(beam ? PW_BEAM_K : PDW_MAXB, D, A, beam, rreg) * (int)sizeof(float);
     if (lds_max > 156 * 1024) lds_max = 156 * 1024;
-    if (lds > lds_max || guard.set_lds(kern, lds_max, configured[beam ? 1 : 0]) != SET_OK) return SET_OK;
-    int& cap = g_pwide_capacity[beam ? 1 : 0][guard.dev];
-    int& cap_lds = g_pwide_capacity_lds[beam ? 1 : 0][guard.dev];
+    if (lds > lds_max || guard.set_lds(kern, lds_max, configured[inst]) != SET_OK) return SET_OK;
+    int& cap = g_pwide_capacity[inst][guard.dev];
+    int& cap_lds = g_pwide_capacity_lds[inst][guard.dev];
     if (cap == 0 || lds > cap_lds) {
         int per_cu = 0, cus = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, PDEC_THREADS, (size_t)lds) != hipSuccess ||
@@ -810,10 +836,11 @@ int editnet_persistent_wide_launch(PDecEditArgs& P, void* xbuf, PersistentGuard&
     const double wbytes = 4.0 * ((double)P.V * D + 5.0 * 4 * D * D + 3.0 * D * D + 2.0 * A * D);
     ProfScope ps(beam ? "persistent_beam" : "persistent_decode", s, 2.0 * B * wbytes / 4.0 * P.max_len, wbytes * P.max_len);
     SET_TRY(guard.serialise(s));
-    SET_HIP_TRY(hipMemsetAsync(xbuf, 0, editnet_persistent_wide_xbytes(B, D, A), s));    // no word of an earlier decode may carry a tag of this one
+    SET_HIP_TRY(hipMemsetAsync(xbuf, 0, editnet_persistent_wide_xbytes(B, D, A, P.R), s));    // no word of an earlier decode may carry a tag of this one
     SET_TRY(pd_stamps_begin(&P.stamps, &P.stamp_wg, s));
-    if (beam) hipLaunchKernelGGL(editnet_persistent_wide_k<true>, dim3(G), dim3(PDEC_THREADS), lds, s, P);
-    else hipLaunchKernelGGL(editnet_persistent_wide_k<false>, dim3(G), dim3(PDEC_THREADS), lds, s, P);
+    if (inst == 2) hipLaunchKernelGGL((editnet_persistent_wide_k<true, PDEC_RREG_WIDE>), dim3(G), dim3(PDEC_THREADS), lds, s, P);
+    else if (inst == 1) hipLaunchKernelGGL((editnet_persistent_wide_k<true, PDEC_RREG>), dim3(G), dim3(PDEC_THREADS), lds, s, P);
+    else hipLaunchKernelGGL((editnet_persistent_wide_k<false, PDEC_RREG>), dim3(G), dim3(PDEC_THREADS), lds, s, P);
     SET_LAUNCH_CHECK();
     SET_TRY(guard.launched(s));
     SET_TRY(pd_stamps_report(P.stamps, P.stamp_wg, 16, P.max_len, s));
@@ -827,13 +854,23 @@ int editnet_persistent_wide_launch(PDecEditArgs& P, void* xbuf, PersistentGuard&
 // 4 at every row count — B = 4: 1.24 vs 1.28 ms, B = 8: 1.41 vs 1.67 ms — so that kernel was removed).
 // ---------------------------------------------------------------------------------------------
 // exchange region of one decode (laid out by decode_persistent_wide.hip)
-size_t editnet_persistent_xbytes(int B, int D, int A) { return B > PDW_MAXB ? 0 : editnet_persistent_wide_xbytes(B, D, A); }
+size_t editnet_persistent_xbytes(int B, int D, int A, int R) { return B > PDW_MAXB ? 0 : editnet_persistent_wide_xbytes(B, D, A, R); }
 
 bool editnet_persistent_ok(const SetEditNetDims* d, int max_len) {
     const int on = env_int("SET_DEC_PERSISTENT", 1);                 // (read per call: tests and A/B runs flip it inside one process)
     const int maxb = env_int("SET_DEC_PERSISTENT_MAXB", PDW_MAXB);
     if (!on || d->B > maxb || max_len < 1 || d->adaptive) return false;
     return editnet_persistent_wide_ok(d->B, d->D, d->A, d->T, d->R, d->V) && !persistent_disabled();
+}
+
+// set_editnet_beam_persistent: the k <= 4 hypotheses of one image as the rows of one launch.  Fixed features under the same
+// conditions as the greedy launch; adaptive features (greedy and XE stay on the per-step kernels) on the instantiation with
+// room for 128 masked regions
+bool editnet_persistent_beam_ok(const SetEditNetDims* d) {
+    if (d->B > PW_BEAM_K) return false;
+    if (!d->adaptive) return editnet_persistent_ok(d, 1);
+    if (!env_int("SET_DEC_PERSISTENT", 1) || d->B > env_int("SET_DEC_PERSISTENT_MAXB", PDW_MAXB) || persistent_disabled()) return false;
+    return editnet_persistent_wide_ok(d->B, d->D, d->A, d->T, d->R, d->V, true);
 }
 
 // the greedy loop after the prologue (set_editnet_begin).  pv = X x2h[:, 2D:]^T (B, R, 4D), xbuf = exchange region.
@@ -843,9 +880,10 @@ int editnet_persistent_greedy(const SetEditNetWeights* w, const SetEditNetDims* 
                               const float* pv, void* xbuf, long long* it, int* unfinished, int* alive, long long start_idx,
                               long long end_idx, int max_len, long long* seq, float* seq_logp, hipStream_t s,
                               const PDecTeacher* teach, const PDecBeam* beam) {
+    const bool wide = beam && d->adaptive;              // adaptive beam search: region mask, up to 128 regions
     if (beam) {         // beam mode lives in the wide variant, whatever the row count
-        if (!env_int("SET_DEC_PERSISTENT", 1) || max_len < 1 || d->adaptive || persistent_disabled() ||
-            !editnet_persistent_wide_ok(d->B, d->D, d->A, d->T, d->R, d->V)) return SET_ERR_UNSUPPORTED;
+        if (!env_int("SET_DEC_PERSISTENT", 1) || max_len < 1 || (d->adaptive && !beam->rmask) || persistent_disabled() ||
+            !editnet_persistent_wide_ok(d->B, d->D, d->A, d->T, d->R, d->V, wide)) return SET_ERR_UNSUPPORTED;
     } else if (!editnet_persistent_ok(d, max_len)) return SET_ERR_UNSUPPORTED;
     const int B = d->B, D = d->D, A = d->A, F = d->F, G = D / 4;
     PDecEditArgs P{};
@@ -872,9 +910,10 @@ int editnet_persistent_greedy(const SetEditNetWeights* w, const SetEditNetDims* 
     if (beam) {
         P.bm_hist_par = beam->hist_par; P.bm_hist_word = (long long*)beam->hist_word; P.bm_best_score = beam->best_score;
         P.bm_best_word = (long long*)beam->best_word; P.bm_result = beam->result;
+        if (wide) P.rmask = beam->rmask;
     }
     bool unsupported = true;
-    const int rc = editnet_persistent_wide_launch(P, xbuf, guard, s, &unsupported, beam != nullptr);      // (lays out the exchange region)
+    const int rc = editnet_persistent_wide_launch(P, xbuf, guard, s, &unsupported, beam != nullptr, wide);      // (lays out the exchange region)
     return rc != SET_OK ? rc : (unsupported ? SET_ERR_UNSUPPORTED : SET_OK);
 }
 

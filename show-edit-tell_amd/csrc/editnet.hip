@@ -122,7 +122,7 @@ static EditNetWs carve(const SetEditNetDims* d, void* base) {
     {
         const size_t pb = B <= (size_t)PDW_MAXB ? B : 0;             // only small batches take the persistent decode
         w.pd_pv = c.take<float>(pb * R * 4 * D);
-        w.pd_x = c.take<char>(editnet_persistent_xbytes((int)B, (int)D, (int)A));
+        w.pd_x = c.take<char>(editnet_persistent_xbytes((int)B, (int)D, (int)A, (int)R));
     }
     w.bytes = c.off;
     return w;
@@ -242,8 +242,10 @@ int editnet_encoder(const SetEditNetWeights* w, const int64_t* seq, const int64_
     return SET_OK;
 }
 
+// beam_pv: the persistent beam launch follows (set_editnet_beam_persistent, which has checked its conditions): compute Pv even where
+// the greedy launch would not take these dims (adaptive features)
 static int begin_impl(const SetEditNetWeights* w, const SetEditNetDims* d, const float* X, const float* image_mean,
-                      const int64_t* prev, const int64_t* prevlen, EditNetWs& ws, hipStream_t st) {
+                      const int64_t* prev, const int64_t* prevlen, EditNetWs& ws, hipStream_t st, bool beam_pv = false) {
     const int B = d->B, T = d->T, R = d->R, F = d->F, D = d->D, A = d->A;
     const int tgt = gemm_target_wgs();
     // ---- caption encoder (editnet.py:319-348)
@@ -272,7 +274,7 @@ static int begin_impl(const SetEditNetWeights* w, const SetEditNetDims* d, const
         GemmProb p[2];
         p[0] = direct_prob(ws.fe, D, B * R, D, w->va_emb_b, SET_ACT_RELU);                // editnet.py:441
         p[0].add(X, F, w->va_emb_w, F, F);
-        const bool pv = editnet_persistent_ok(d, 1);
+        const bool pv = beam_pv || editnet_persistent_ok(d, 1);
         if (pv) {
             p[1] = direct_prob(ws.pd_pv, 4LL * D, B * R, 4 * D, nullptr, SET_ACT_NONE);
             p[1].add(X, F, w->cl_x2h_w + 2 * D, 2LL * D + F, F);
@@ -615,14 +617,12 @@ int set_editnet_beam_persistent(const SetEditNetWeights* w, const SetEditNetDims
     if (start_idx < 0 || start_idx >= d->V) return SET_ERR_ARG;
     // (nothing is touched before the checks that can answer SET_ERR_UNSUPPORTED)
     if (!(w->tok_table && (d->D % 64 == 0) && env_int("SET_NO_FUSED", 0) == 0)) return SET_ERR_UNSUPPORTED;
-    if (d->B > 4 || d->adaptive || !env_int("SET_DEC_PERSISTENT", 1) || persistent_disabled() ||
-        !editnet_persistent_wide_ok(d->B, d->D, d->A, d->T, d->R, d->V) || !editnet_persistent_ok(d, 1))
-        return SET_ERR_UNSUPPORTED;
+    if (!editnet_persistent_beam_ok(d)) return SET_ERR_UNSUPPORTED;       // (adaptive features: even R <= 128, masked regions)
     EditNetWs W;
     SET_TRY(prep(d, ws, ws_bytes, &W));
     hipStream_t st = (hipStream_t)stream;
-    SET_TRY(begin_impl(w, d, X, image_mean, prev, prevlen, W, st));      // (includes Pv = X x2h[:, 2D:]^T: editnet_persistent_ok)
-    const PDecBeam beam{hist_parent, hist_word, best_score, best_word, result};
+    SET_TRY(begin_impl(w, d, X, image_mean, prev, prevlen, W, st, true));      // (includes Pv = X x2h[:, 2D:]^T and the region mask)
+    const PDecBeam beam{hist_parent, hist_word, best_score, best_word, result, d->adaptive ? W.rmask : nullptr};
     return editnet_persistent_greedy(w, d, W.pre1, W.att1, W.att1_c, W.mask, W.cap_proj, W.mem_proj, W.Mem, W.pd_pv, W.pd_x, W.it,
                                      W.unfinished, W.alive, start_idx, end_idx, max_picks, nullptr, nullptr, st, nullptr, &beam);
 }

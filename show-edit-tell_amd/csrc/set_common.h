@@ -264,7 +264,8 @@ int persistent_encoder(const float* w_hh, const float* xg, long long ld_xg_row, 
                        int B, int D, int T, hipStream_t s);
 
 struct PDecTeacher { const int64_t* caps; long long caps_stride; float* predictions; const int* host_decode_lengths; };   // teacher-forced mode
-struct PDecBeam { int* hist_par; int64_t* hist_word; float* best_score; int64_t* best_word; int* result; };                // beam mode (one image, rows = hypotheses)
+// beam mode (one image, rows = hypotheses); rmask != NULL: adaptive features (region mask (B, R), up to PDEC_RREG_WIDE regions)
+struct PDecBeam { int* hist_par; int64_t* hist_word; float* best_score; int64_t* best_word; int* result; const float* rmask = nullptr; };
 // decode_persistent.hip: the greedy loop of a small batch as one launch with grid barriers
 constexpr int PDEC_MAXB = 8;          // rows of the <= 8-row persistent decode kernels
 constexpr int PDW_MAXB = 16;          // rows of the wide EditNet variant (decode_persistent_wide.hip): one full 16-row MFMA tile
@@ -275,9 +276,10 @@ int dcnet_persistent_greedy(const SetDcnetWeights* w, const SetDcnetDims* d, con
                             long long start_idx, long long end_idx, int max_len, long long* seq, float* seq_logp,
                             hipStream_t s, const PDecTeacher* teach = nullptr);
 
-size_t editnet_persistent_xbytes(int B, int D, int A);
+size_t editnet_persistent_xbytes(int B, int D, int A, int R = 0);   // R > 64: room for R visual scores per row
 bool editnet_persistent_ok(const SetEditNetDims* d, int max_len);
-bool editnet_persistent_wide_ok(int B, int D, int A, int T, int R, int V);    // decode_persistent_wide.hip
+bool editnet_persistent_wide_ok(int B, int D, int A, int T, int R, int V, bool wide_regions = false);    // decode_persistent_wide.hip
+bool editnet_persistent_beam_ok(const SetEditNetDims* d);                      // one image's beam search as one launch (k <= 4)
 bool persistent_disabled();                                                   // encoder_persistent.hip: a persistent launch timed out earlier
 int editnet_persistent_greedy(const SetEditNetWeights* w, const SetEditNetDims* d, const float* pre1, const float* att1,
                               const float* att1_c, const float* mask, const float* capP, const float* memQ, const float* Mem,

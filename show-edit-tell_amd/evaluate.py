@@ -47,7 +47,10 @@ class _FusedModel:
 
 
 class _FusedEditNet(_FusedModel):
-    def __init__(self, decoder, X, prev, plen, k, max_steps):
+    """image_mean (NI, F) or None: the attention LSTM's image input (adaptive features: the mean over the valid regions,
+    editnet_adaptive.py:625-633); None = the mean over all R regions (editnet.py:503)."""
+
+    def __init__(self, decoder, X, prev, plen, k, max_steps, image_mean=None):
         import ctypes as C
         from . import _lib
         from ._lib import check, ptr, stream_of
@@ -59,8 +62,8 @@ class _FusedEditNet(_FusedModel):
         d_img = decoder._dims(NI, T, R, max_steps + 1)
         self.w = decoder._weights(d_img)
         ws_img = torch.empty(lib.set_editnet_workspace_bytes(C.byref(d_img)), dtype=torch.uint8, device=dev)
-        check(lib.set_editnet_begin(C.byref(self.w), C.byref(d_img), ptr(X), None, ptr(prev), ptr(plen), ptr(ws_img),
-                                    ws_img.numel(), self.st), "set_editnet_begin")
+        check(lib.set_editnet_begin(C.byref(self.w), C.byref(d_img), ptr(X), None if image_mean is None else ptr(image_mean),
+                                    ptr(prev), ptr(plen), ptr(ws_img), ws_img.numel(), self.st), "set_editnet_begin")
         self.B = B = NI * k
         self.dims = d_b = decoder._dims(B, T, R, max_steps + 1)
         self.ws = ws_b = torch.empty(lib.set_editnet_workspace_bytes(C.byref(d_b)), dtype=torch.uint8, device=dev)
@@ -167,7 +170,8 @@ def _fused_beam(models, NI, k, V, word_map, dev, max_steps, poll=4, return_score
 def beam_search_editnet_batched(decoder, image_features, previous_caption, prev_caplen, word_map, beam_size=3,
                                 max_steps=50, return_scores=False):
     """image_features (NI,R,F), previous_caption (NI,T), prev_caplen (NI,1) -> list of NI token lists
-    (with return_scores: also the list of their scores; NaN where the step limit was hit)."""
+    (with return_scores: also the list of their scores; NaN where the step limit was hit).  The attention LSTM sees the mean
+    over all R regions; adaptive features (zero-padded regions, an image mean per image): beam_search_adaptive_batched."""
     decoder.eval()
     X = image_features.float().contiguous()
     prev = previous_caption.long().contiguous()
@@ -192,7 +196,7 @@ def beam_search_dcnet_batched(dae, previous_caption, prev_caplen, word_map, beam
 def beam_search_ensemble_batched(decoder, dae, image_features, previous_caption, prev_caplen, word_map, beam_size=3,
                                  max_steps=50, return_scores=False):
     """eval_full.py:88-218 for NI images at once: both models step on the same words, the epilogue averages
-    their softmax probabilities."""
+    their softmax probabilities.  Fixed features (image mean over all R regions); adaptive features: beam_search_adaptive*."""
     decoder.eval()
     dae.eval()
     X = image_features.float().contiguous()
@@ -210,16 +214,18 @@ def beam_search_ensemble_batched(decoder, dae, image_features, previous_caption,
 # 50-step limit was hit).  NI = 1 case of the batched on-device search above.
 # ------------------------------------------------------------------------------------------------
 @torch.no_grad()
-def _beam_search_editnet_persistent(decoder, image_features, previous_caption, prev_caplen, word_map, beam_size, max_steps=50):
+def _beam_search_editnet_persistent(decoder, image_features, previous_caption, prev_caplen, word_map, beam_size, max_steps=50,
+                                    image_mean=None):
     """ONE image, k <= 4: prologue + one persistent launch for the whole search (include/set_hip.h
     set_editnet_beam_persistent; the rows of the launch are the k hypotheses).  Returns None when the library answers
     SET_ERR_UNSUPPORTED (no token table yet, k > 4, dimensions outside the persistent launch): the caller takes the
-    per-step search."""
+    per-step search.  image_mean (1, F): the adaptive model's image input (beam_search_adaptive); an adaptive decoder
+    without one is refused here (the fixed-feature entries keep their routing)."""
     import ctypes as C
     from . import _lib
     from ._lib import check, ptr, stream_of
     k = int(beam_size)
-    if k < 1 or k > 4 or image_features.shape[0] != 1 or getattr(decoder, "_adaptive", 0):
+    if k < 1 or k > 4 or image_features.shape[0] != 1 or (getattr(decoder, "_adaptive", 0) and image_mean is None):
         return None
     decoder.eval()
     lib = _lib.load()
@@ -227,6 +233,7 @@ def _beam_search_editnet_persistent(decoder, image_features, previous_caption, p
     X = image_features.float().expand(k, -1, -1).contiguous()
     prev = previous_caption.long().expand(k, -1).contiguous()
     plen = prev_caplen.reshape(-1).long().expand(k).contiguous()
+    mean = None if image_mean is None else image_mean.float().reshape(1, -1).expand(k, -1).contiguous()
     picks = max_steps + 1
     dims = decoder._dims(k, prev.shape[1], X.shape[1], picks)
     w = decoder._weights(dims)
@@ -239,7 +246,8 @@ def _beam_search_editnet_persistent(decoder, image_features, previous_caption, p
     buf = torch.empty(n_hw + 8 + n_hp + 16 + 8, dtype=torch.uint8, device=dev)
     o_bw, o_hp, o_res, o_bs = n_hw, n_hw + 8, n_hw + 8 + n_hp, n_hw + 8 + n_hp + 16
     base = buf.data_ptr()
-    rc = lib.set_editnet_beam_persistent(C.byref(w), C.byref(dims), ptr(X), None, ptr(prev), ptr(plen), int(word_map['<start>']),
+    rc = lib.set_editnet_beam_persistent(C.byref(w), C.byref(dims), ptr(X), None if mean is None else ptr(mean), ptr(prev), ptr(plen),
+                                         int(word_map['<start>']),
                                          int(word_map['<end>']), picks, base + o_hp, base, base + o_bs, base + o_bw, base + o_res,
                                          ptr(ws), ws.numel(), stream_of(dev))
     if rc == 2:                                                    # SET_ERR_UNSUPPORTED: no output was touched (set_hip.h: answered
@@ -270,7 +278,7 @@ def _beam_search_editnet_persistent(decoder, image_features, previous_caption, p
 def beam_search_editnet(decoder, image_features, previous_caption, prev_caplen, word_map, beam_size=3):
     """The reference's own calling convention, ONE image per call (editnet.py:601-613).  k <= 4 with the token table
     active: one persistent launch (csrc/decode_persistent_wide.hip, beam mode); otherwise the NI = 1 case of the batched
-    search."""
+    search.  Adaptive features (an image mean per image, zero-padded regions): beam_search_adaptive."""
     one = _beam_search_editnet_persistent(decoder, image_features, previous_caption, prev_caplen, word_map, beam_size)
     if one is not None:
         return one
@@ -287,4 +295,49 @@ def beam_search_dcnet(dae, previous_caption, prev_caplen, word_map, beam_size=3)
 def beam_search_ensemble(decoder, dae, image_features, previous_caption, prev_caplen, word_map, beam_size=3):
     seqs, scores = beam_search_ensemble_batched(decoder, dae, image_features, previous_caption, prev_caplen, word_map,
                                                 beam_size, return_scores=True)
+    return seqs[0], scores[0]
+
+
+# ------------------------------------------------------------------------------------------------
+# Adaptive features (adaptive_features/editnet_adaptive.py:614-735): the same search, with the image mean that comes with
+# every image (the mean over its VALID regions) as the attention LSTM's input and the zero-padded regions masked in the
+# visual attention (the region mask of the prologue, replicated with the other invariants).
+# ------------------------------------------------------------------------------------------------
+def _adaptive_args(decoder, image_features, image_mean):
+    if not getattr(decoder, "_adaptive", 0):
+        raise TypeError("beam_search_adaptive*: %s is not an adaptive-features decoder (editnet_adaptive.DecoderC); "
+                        "fixed features: beam_search_editnet*" % type(decoder).__name__)
+    X = image_features.float().contiguous()
+    NI, _, F = X.shape
+    if image_mean is None or tuple(image_mean.shape) != (NI, F):
+        raise ValueError("beam_search_adaptive*: image_mean must have shape (NI, F) = (%d, %d), got %s"
+                         % (NI, F, None if image_mean is None else tuple(image_mean.shape)))
+    return X, image_mean.to(X.device).float().contiguous()
+
+
+@torch.no_grad()
+def beam_search_adaptive_batched(decoder, image_features, image_mean, previous_caption, prev_caplen, word_map, beam_size=3,
+                                 max_steps=50, return_scores=False):
+    """image_features (NI,R,F) zero-padded regions, image_mean (NI,F), previous_caption (NI,T), prev_caplen (NI,1) ->
+    list of NI token lists (with return_scores: also their scores; NaN where the step limit was hit).  NI images at once
+    on the per-step fused kernels."""
+    X, mean = _adaptive_args(decoder, image_features, image_mean)
+    decoder.eval()
+    prev = previous_caption.long().contiguous()
+    plen = prev_caplen.reshape(-1).long().contiguous()
+    m = _FusedEditNet(decoder, X, prev, plen, beam_size, max_steps, image_mean=mean)
+    return _fused_beam([m], X.shape[0], beam_size, decoder.vocab_size, word_map, X.device, max_steps,
+                       return_scores=return_scores)
+
+
+def beam_search_adaptive(decoder, image_features, image_mean, previous_caption, prev_caplen, word_map, beam_size=3):
+    """The reference's adaptive evaluate(), ONE image per call (editnet_adaptive.py:620-735) -> (tokens, score).  k <= 4
+    with the token table active: one persistent launch (beam mode over up to 128 masked regions, even R); otherwise the
+    NI = 1 case of beam_search_adaptive_batched."""
+    X, mean = _adaptive_args(decoder, image_features, image_mean)
+    one = _beam_search_editnet_persistent(decoder, X, previous_caption, prev_caplen, word_map, beam_size, image_mean=mean)
+    if one is not None:
+        return one
+    seqs, scores = beam_search_adaptive_batched(decoder, X, mean, previous_caption, prev_caplen, word_map, beam_size,
+                                                return_scores=True)
     return seqs[0], scores[0]
