@@ -305,6 +305,13 @@ int set_dcnet_xe_forward(const SetDcnetWeights* w, const SetDcnetDims* d, const 
                          int64_t caps_stride, const int* host_decode_lengths, const int64_t* prev,
                          const int64_t* prevlen, float* predictions, void* ws, size_t ws_bytes,
                          void* stream);
+/* set_dcnet_xe_forward that also writes last_hidden (B, D), sorted row order (dcnet_with_mse.py:321,341,
+ * `decoder_last_hidden[:batch_size_t] = h2.clone()`): h2 of row b at its last step t = host_decode_lengths[b] - 1,
+ * before the output dropout; zeros for a row of decode length 0.  last_hidden == NULL: set_dcnet_xe_forward. */
+int set_dcnet_xe_forward_hidden(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* caps,
+                                int64_t caps_stride, const int* host_decode_lengths, const int64_t* prev,
+                                const int64_t* prevlen, float* predictions, float* last_hidden, void* ws,
+                                size_t ws_bytes, void* stream);
 /* names: "enc" (B,T,2C) "final_hidden" (B,2C) "mask" (B,T) "att1_c" (B,T,A) "h1" "c1" "h2" "c2"
  * "emb" "attend_cap" (B,2C) "alpha_c" (B,T) "logits" (B,V) "it" "unfinished" */
 void* set_dcnet_ws_tensor(const SetDcnetDims* d, void* ws, const char* name);
@@ -400,6 +407,12 @@ int set_xe_loss_f32(const float* scores, int64_t stride_b, int64_t stride_t, con
 int set_xe_loss_bwd_f32(const float* scores, int64_t stride_b, int64_t stride_t, const int64_t* targets,
                         int64_t tstride_b, int64_t tstride_t, const int* live, int B, int T, int V, const float* lse,
                         const float* dloss, float* grad, int64_t ld_grad, void* stream);
+/* nn.MSELoss pieces of the DCNet MSE stage (dcnet_with_mse.py:392).  Forward: *out (device, 1 float) = sum over the n
+ * floats of (a[i] - b[i])^2, in one fixed reduction order (the same bits on every call; divide by n for the mean).
+ * Backward: da = s (a - b), db = -da with s = scale * dout[0] (dout NULL: s = scale); da or db may be NULL. */
+int set_mse_sum_f32(const float* a, const float* b, int64_t n, float* out, void* stream);
+int set_mse_bwd_f32(const float* a, const float* b, int64_t n, float scale, const float* dout, float* da, float* db,
+                    void* stream);
 
 /* The tail of the training step — torch.nn.utils.clip_grad_norm_(params, max_norm) followed by torch.optim.Adam.step()
  * (editnet.py:580-581, dcnet.py:399-400, editnet_rl.py:684-686) — over n fp32 tensors in two launches per 40 tensors:

@@ -237,6 +237,8 @@ PROTOTYPES = {
                               _P]),
     "set_dcnet_xe_forward": (_I, [C.POINTER(DcnetWeights), C.POINTER(DcnetDims), _P, _L, C.POINTER(C.c_int), _P, _P,
                                   _P, _P, _Z, _P]),
+    "set_dcnet_xe_forward_hidden": (_I, [C.POINTER(DcnetWeights), C.POINTER(DcnetDims), _P, _L, C.POINTER(C.c_int), _P,
+                                         _P, _P, _P, _P, _Z, _P]),
     "set_dcnet_ws_tensor": (_P, [C.POINTER(DcnetDims), _P, C.c_char_p]),
     "set_linear_workspace_bytes": (_Z, [_I, _I, _I]),
     "set_linear_f32": (_I, [_P, _L, _P, _L, _P, _P, _L, _I, _I, _I, _I, _P, _Z, _P]),
@@ -284,6 +286,8 @@ PROTOTYPES = {
     "set_attention_dvalues_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "set_xe_loss_f32": (_I, [_P, _L, _L, _P, _L, _L, _P, _I, _I, _I, _P, _P, _P, _P]),
     "set_xe_loss_bwd_f32": (_I, [_P, _L, _L, _P, _L, _L, _P, _I, _I, _I, _P, _P, _P, _L, _P]),
+    "set_mse_sum_f32": (_I, [_P, _P, _L, _P, _P]),
+    "set_mse_bwd_f32": (_I, [_P, _P, _L, C.c_float, _P, _P, _P, _P]),
     "set_clip_adam_workspace_bytes": (_Z, [_I, _P]),
     "set_clip_adam_f32": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_float, _I, _P, _P, _Z, _P]),
     "set_colsum_workspace_bytes": (_Z, [_I]),

@@ -711,6 +711,38 @@ def philox_dropout(x, p, seed, offset, training=True):
     return _PhiloxDropout.apply(x, p, seed, offset)
 
 
+class _MseSum(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b):
+        lib = _lib.load()
+        a, b = _c(a), _c(b)
+        out = torch.empty((), dtype=torch.float32, device=a.device)
+        check(lib.set_mse_sum_f32(ptr(a), ptr(b), a.numel(), ptr(out), stream_of(a.device)), "set_mse_sum_f32")
+        ctx.save_for_backward(a, b)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        a, b = ctx.saved_tensors
+        da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
+        db = torch.empty_like(b) if ctx.needs_input_grad[1] else None
+        if da is None and db is None:
+            return None, None
+        d = _c(dout.detach().to(torch.float32))
+        check(_lib.load().set_mse_bwd_f32(ptr(a), ptr(b), a.numel(), 2.0, ptr(d), ptr(da), ptr(db), stream_of(a.device)),
+              "set_mse_bwd_f32")
+        return da, db
+
+
+def mse_sum(a, b):
+    """sum((a - b)^2) over all elements, a 0-dim tensor (nn.MSELoss's numerator, dcnet_with_mse.py:392) on the library's
+    kernels (csrc/loss.hip): one fixed reduction order; gradient 2 (a - b) to a and its negative to b."""
+    if a.shape != b.shape or a.dtype != torch.float32 or b.dtype != torch.float32 or not (a.is_cuda and b.is_cuda):
+        raise _lib.SetError("mse_sum needs two fp32 device tensors of one shape (got %s %s, %s %s)"
+                            % (tuple(a.shape), a.dtype, tuple(b.shape), b.dtype))
+    return _MseSum.apply(a, b)
+
+
 # ------------------------------------------------------------------------------------------------
 # additive attention backward shared by the caption (tanh) and visual (relu) attentions
 # ------------------------------------------------------------------------------------------------

@@ -426,9 +426,12 @@ int set_dcnet_sample(const SetDcnetWeights* w, const SetDcnetDims* d, const int6
                          stream);
 }
 
-int set_dcnet_xe_forward(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* caps, int64_t caps_stride,
-                         const int* host_decode_lengths, const int64_t* prev, const int64_t* prevlen,
-                         float* predictions, void* ws, size_t ws_bytes, void* stream) {
+// dcnet_with_mse.py:321,341 (`decoder_last_hidden[:batch_size_t] = h2.clone()` at every step): last_hidden (B, D, sorted
+// rows) = h2 of row b at its last step t = decode_length[b] - 1, before the output dropout; zero for decode length 0.
+// last_hidden == NULL: set_dcnet_xe_forward.
+int set_dcnet_xe_forward_hidden(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* caps, int64_t caps_stride,
+                                const int* host_decode_lengths, const int64_t* prev, const int64_t* prevlen,
+                                float* predictions, float* last_hidden, void* ws, size_t ws_bytes, void* stream) {
     if (!w || !caps || !host_decode_lengths || !prev || !prevlen || !predictions) return SET_ERR_ARG;
     DcnetWs W;
     SET_TRY(prep(d, ws, ws_bytes, &W));
@@ -441,10 +444,12 @@ int set_dcnet_xe_forward(const SetDcnetWeights* w, const SetDcnetDims* d, const 
     if (caps_stride < maxT) return SET_ERR_ARG;
     SET_TRY(begin_impl(w, d, prev, prevlen, W, st));
     SET_HIP_TRY(hipMemsetAsync(predictions, 0, sizeof(float) * (size_t)B * maxT * V, st));
+    if (last_hidden) SET_HIP_TRY(hipMemsetAsync(last_hidden, 0, sizeof(float) * (size_t)B * d->D, st));   // rows of length 0
     const bool emb_needed = !table_active(w, d);
-    // small batches: the teacher-forced loop as ONE persistent launch too (decode_persistent.hip, words from caps, scores out)
+    // small batches: the teacher-forced loop as ONE persistent launch too (decode_persistent.hip, words from caps, scores out;
+    // with last_hidden the variant that also stores every row's h2 at its own last step)
     if (!emb_needed && dcnet_persistent_ok(d, maxT)) {
-        const PDecTeacher teach{caps, caps_stride, predictions, host_decode_lengths};
+        const PDecTeacher teach{caps, caps_stride, predictions, host_decode_lengths, last_hidden};
         const int rc = dcnet_persistent_greedy(w, d, W.pre1, W.att1_c, W.mask, W.pd_pc, W.pd_x, W.it, W.unfinished, W.alive, 0, -1,
                                                maxT, nullptr, nullptr, st, &teach);
         if (rc != SET_ERR_UNSUPPORTED) return rc;
@@ -466,7 +471,19 @@ int set_dcnet_xe_forward(const SetDcnetWeights* w, const SetDcnetDims* d, const 
         have_a = next_a;
         if (next_a) { a_cur[0] = a_nxt[0]; a_cur[1] = a_nxt[1]; }
     }
+    // step t writes h2 (and h1, c1, c2) of rows [0, bt) only — language_lstm's pointwise kernel with M = bt; the merged F/A
+    // launch only reads h1 / h2 — and bt never grows: the workspace h2 now holds every row's h2 at its own last step, and
+    // begin_impl's zeros for a row of decode length 0
+    if (last_hidden)
+        SET_HIP_TRY(hipMemcpyAsync(last_hidden, W.h2, sizeof(float) * (size_t)B * d->D, hipMemcpyDeviceToDevice, st));
     return SET_OK;
+}
+
+int set_dcnet_xe_forward(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* caps, int64_t caps_stride,
+                         const int* host_decode_lengths, const int64_t* prev, const int64_t* prevlen,
+                         float* predictions, void* ws, size_t ws_bytes, void* stream) {
+    return set_dcnet_xe_forward_hidden(w, d, caps, caps_stride, host_decode_lengths, prev, prevlen, predictions, nullptr, ws,
+                                       ws_bytes, stream);
 }
 
 size_t set_dcnet_token_table_bytes(const SetDcnetDims* d) {

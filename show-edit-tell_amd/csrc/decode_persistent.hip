@@ -65,11 +65,17 @@ struct PDecDcnetArgs {
     int dlen[PDEC_MAXB];                         // decode lengths, descending (0 = free-running)
     int stamp_wg;
     unsigned long long* stamps;                  // diagnostic (SET_PDEC_STAMPS=1): 100-MHz time stamps of workgroup 0, 16 per timestep
+    // (LH, teacher-forced) h2 of every row at its last step t = dlen[b] - 1 (dcnet_with_mse.py:321,341), (B, D).  Last member:
+    // the offsets of the fields above, and so the instructions of the variants without it, stay as they were
+    float* last_h2;
 };
 
 // RES: B <= 4 and T <= PDEC_TREG — a wave scores ONE fixed row, whose hoisted cap_features_att rows (loop-invariant, T x A
-// floats = 160 registers per lane) then stay in registers for the whole decode
-template <bool RES>
+// floats = 160 registers per lane) then stay in registers for the whole decode.
+// LH: teacher-forced only, also write last_h2 (set_dcnet_xe_forward_hidden).  The loop keeps computing every row until the
+// longest caption ends, so no buffer holds a row's h2 at its own last step: the owner of h2[b, u] stores it when t + 1 ==
+// dlen[b].  A template parameter, not a runtime test: the variants without it compile to the same instructions as before.
+template <bool RES, bool LH = false>
 __global__ void __launch_bounds__(PDEC_THREADS, 1) dcnet_persistent_k(const PDecDcnetArgs P) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __shared__ long long sTok[PDEC_MAXB];
@@ -291,7 +297,11 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) dcnet_persistent_k(const PDec
             const float* gp = sG + pb * 16 + pu;
             const float ai = pd_sigm(gp[0]), af = pd_sigm(gp[4]), ag = tanhf(gp[8]), ao = pd_sigm(gp[12]);
             c2 = af * c2 + ai * ag;
-            ll_put(h2rs, pb * D + u0 + pu, ao * tanhf(c2), tag);
+            const float h2v = ao * tanhf(c2);
+            ll_put(h2rs, pb * D + u0 + pu, h2v, tag);
+            if constexpr (LH) {                                  // h2 before the output dropout (dcnet_with_mse.py:341)
+                if (P.dlen[pb] == t + 1) P.last_h2[(long long)pb * D + u0 + pu] = h2v;
+            }
         }
         PD_STAMP(8);
         ll_stage<256, 8>(h2rs, sH2, B, D, LDH, tag, watch, tid);
@@ -440,8 +450,8 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) dcnet_persistent_k(const PDec
     }
 }
 
-static int g_pdec_capacity[64][2] = {};
-static int g_pdec_capacity_lds[64][2] = {};
+static int g_pdec_capacity[64][4] = {};              // [device][RES + 2 LH]
+static int g_pdec_capacity_lds[64][4] = {};
 static int pdec_lds_floats(int B, int D, int A) {
     return 2 * B * (D + 4) + 4 * 3 * 256 + PDEC_MAXB * PDEC_TMAX + PDEC_MAXB * 16 + B * A + B * (D / 4) * 4 + 2 * A + B * 16 * (PDEC_TMAX + 1);
 }
@@ -494,7 +504,9 @@ int dcnet_persistent_greedy(const SetDcnetWeights* w, const SetDcnetDims* d, con
         P.caps = (const long long*)teach->caps; P.caps_stride = teach->caps_stride;
         P.predictions = teach->predictions; P.ld_pred_b = (long long)max_len * d->V;
         for (int b = 0; b < B; ++b) P.dlen[b] = teach->host_decode_lengths[b];
+        P.last_h2 = teach->last_h2;
     }
+    const bool lh = P.caps && P.last_h2;
     const int lds = pdec_lds_floats(B, D, d->A) * (int)sizeof(float);
     PersistentGuard guard;
     if (guard.rc != SET_OK) return guard.rc;
@@ -504,19 +516,23 @@ int dcnet_persistent_greedy(const SetDcnetWeights* w, const SetDcnetDims* d, con
     // residency: every workgroup must be on the chip at once (see encoder_persistent.hip penc_fits)
     // (function attributes are per device; a device whose LDS limit is below the request, e.g. a 64-KB part, is answered with
     // SET_ERR_UNSUPPORTED — the caller's per-step loop — never with a HIP error)
-    static bool configured[2][64] = {};
+    static bool configured[4][64] = {};
     const int lds_max = pdec_lds_floats(PDEC_MAXB, D, d->A) * (int)sizeof(float);
-    if (guard.set_lds(reinterpret_cast<const void*>(&dcnet_persistent_k<true>), lds_max, configured[0]) != SET_OK ||
-        guard.set_lds(reinterpret_cast<const void*>(&dcnet_persistent_k<false>), lds_max, configured[1]) != SET_OK)
+    // the two variants of this call's family (with / without the last_h2 output)
+    const void* k_res = lh ? reinterpret_cast<const void*>(&dcnet_persistent_k<true, true>)
+                           : reinterpret_cast<const void*>(&dcnet_persistent_k<true>);
+    const void* k_gen = lh ? reinterpret_cast<const void*>(&dcnet_persistent_k<false, true>)
+                           : reinterpret_cast<const void*>(&dcnet_persistent_k<false>);
+    if (guard.set_lds(k_res, lds_max, configured[lh ? 2 : 0]) != SET_OK ||
+        guard.set_lds(k_gen, lds_max, configured[lh ? 3 : 1]) != SET_OK)
         return SET_ERR_UNSUPPORTED;
     const bool res = B <= 4 && d->T <= PDEC_TREG;
     // resident workgroups the device admits, asked with the LDS size of THIS batch (re-asked when a larger one comes along)
-    int& cap = g_pdec_capacity[dev][res ? 1 : 0];
-    int& cap_lds = g_pdec_capacity_lds[dev][res ? 1 : 0];
+    int& cap = g_pdec_capacity[dev][(res ? 1 : 0) + (lh ? 2 : 0)];
+    int& cap_lds = g_pdec_capacity_lds[dev][(res ? 1 : 0) + (lh ? 2 : 0)];
     if (cap == 0 || lds > cap_lds) {
         int per_cu = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, res ? reinterpret_cast<const void*>(&dcnet_persistent_k<true>)
-                                                                       : reinterpret_cast<const void*>(&dcnet_persistent_k<false>), PDEC_THREADS,
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, res ? k_res : k_gen, PDEC_THREADS,
                                                          (size_t)lds) != hipSuccess ||
             hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) {
             (void)hipGetLastError();
@@ -534,7 +550,9 @@ int dcnet_persistent_greedy(const SetDcnetWeights* w, const SetDcnetDims* d, con
     SET_TRY(guard.serialise(s));
     SET_HIP_TRY(hipMemsetAsync(xbuf, 0, dcnet_persistent_xbytes(B, D, d->A), s));    // no word of an earlier decode may carry a tag of this one
     SET_TRY(pd_stamps_begin(&P.stamps, &P.stamp_wg, s));
-    if (res) hipLaunchKernelGGL(dcnet_persistent_k<true>, dim3(G), dim3(PDEC_THREADS), lds, s, P);
+    if (lh && res) hipLaunchKernelGGL((dcnet_persistent_k<true, true>), dim3(G), dim3(PDEC_THREADS), lds, s, P);
+    else if (lh) hipLaunchKernelGGL((dcnet_persistent_k<false, true>), dim3(G), dim3(PDEC_THREADS), lds, s, P);
+    else if (res) hipLaunchKernelGGL(dcnet_persistent_k<true>, dim3(G), dim3(PDEC_THREADS), lds, s, P);
     else hipLaunchKernelGGL(dcnet_persistent_k<false>, dim3(G), dim3(PDEC_THREADS), lds, s, P);
     SET_LAUNCH_CHECK();
     SET_TRY(guard.launched(s));

@@ -91,6 +91,41 @@ __global__ void __launch_bounds__(256) xe_loss_bwd_k(const float* scores, long l
     }
 }
 
+// nn.MSELoss of the DCNet MSE stage (dcnet_with_mse.py:392): the sum of squared differences over n floats by ONE workgroup —
+// thread i adds elements i, i + 1024, ... in order, then a fixed tree: the same bits on every call (n = B x D = 128 K floats
+// at the training shape, 1 MB read).  Any n: no vector loads, so no alignment or tail case.
+constexpr int MSE_THREADS = 1024;
+
+__global__ void __launch_bounds__(MSE_THREADS) mse_sum_k(const float* a, const float* b, long long n, float* out) {
+    __shared__ float red[MSE_THREADS / 64];
+    float s = 0.f;
+    for (long long i = threadIdx.x; i < n; i += MSE_THREADS) {
+        const float d = a[i] - b[i];
+        s = fmaf(d, d, s);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float t = 0.f;
+#pragma unroll
+        for (int w = 0; w < MSE_THREADS / 64; ++w) t += red[w];
+        *out = t;
+    }
+}
+
+// da = s (a - b), db = -da, s = scale * dout[0] (dout NULL: scale); either output may be NULL
+__global__ void __launch_bounds__(256) mse_bwd_k(const float* a, const float* b, long long n, float scale, const float* dout,
+                                                 float* da, float* db) {
+    const float s = dout ? scale * dout[0] : scale;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const float g = s * (a[i] - b[i]);
+        if (da) da[i] = g;
+        if (db) db[i] = -g;
+    }
+}
+
 }  // namespace set
 
 using namespace set;
@@ -125,6 +160,23 @@ int set_xe_loss_bwd_f32(const float* scores, int64_t stride_b, int64_t stride_t,
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(xe_loss_bwd_k, dim3((unsigned)(T * B)), dim3(256), 0, s, scores, (long long)stride_b, (long long)stride_t,
                        targets, (long long)tstride_b, (long long)tstride_t, lv, B, V, (int)ld_grad, lse, dloss, grad);
+    SET_LAUNCH_CHECK();
+    return SET_OK;
+}
+
+int set_mse_sum_f32(const float* a, const float* b, int64_t n, float* out, void* stream) {
+    if (!a || !b || !out || n <= 0) return SET_ERR_ARG;
+    hipLaunchKernelGGL(mse_sum_k, dim3(1), dim3(MSE_THREADS), 0, (hipStream_t)stream, a, b, (long long)n, out);
+    SET_LAUNCH_CHECK();
+    return SET_OK;
+}
+
+int set_mse_bwd_f32(const float* a, const float* b, int64_t n, float scale, const float* dout, float* da, float* db,
+                    void* stream) {
+    if (!a || !b || n <= 0 || (!da && !db)) return SET_ERR_ARG;
+    const long long blocks = (n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048;
+    hipLaunchKernelGGL(mse_bwd_k, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, b, (long long)n, scale, dout,
+                       da, db);
     SET_LAUNCH_CHECK();
     return SET_OK;
 }

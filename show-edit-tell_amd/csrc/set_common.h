@@ -263,7 +263,9 @@ int persistent_encoder(const float* w_hh, const float* xg, long long ld_xg_row, 
                        float* Mem, long long ld_out_b, long long ld_out_t, const int* perm, const int* nactive, void* bar,
                        int B, int D, int T, hipStream_t s);
 
-struct PDecTeacher { const int64_t* caps; long long caps_stride; float* predictions; const int* host_decode_lengths; };   // teacher-forced mode
+// teacher-forced mode; last_h2 (DCNet only, may be NULL): h2 of every row at its last step (set_dcnet_xe_forward_hidden)
+struct PDecTeacher { const int64_t* caps; long long caps_stride; float* predictions; const int* host_decode_lengths;
+                     float* last_h2 = nullptr; };
 // beam mode (one image, rows = hypotheses); rmask != NULL: adaptive features (region mask (B, R), up to PDEC_RREG_WIDE regions)
 struct PDecBeam { int* hist_par; int64_t* hist_word; float* best_score; int64_t* best_word; int* result; const float* rmask = nullptr; };
 // decode_persistent.hip: the greedy loop of a small batch as one launch with grid barriers

@@ -295,9 +295,10 @@ class DAE(nn.Module):
 
 
     # ---- grad-enabled path (HIP forward operators, autograd backward) ------------------------
-    def _encoder_autograd(self, src, src_len, seed=None):
+    def _encoder_autograd(self, src, src_len, seed=None, site=None):
         """CaptionEncoder.forward (dcnet.py:220-243): packed BiLSTM == per-row masked recurrences.  The embedding's
-        dropout (dcnet.py:224) is the Philox stream (seed, SITE_ENC_EMBED): row b * Tmax + l, see rng.py."""
+        dropout (dcnet.py:224) is the Philox stream (seed, site): row b * Tmax + l, see rng.py.  `site` defaults to
+        SITE_ENC_EMBED (the previous captions); the MSE stage's ground-truth pass uses SITE_ENC2_EMBED."""
         from . import autograd_ops as A
         from . import rng
         enc = self.caption_encoder
@@ -305,8 +306,9 @@ class DAE(nn.Module):
         lens = src_len.reshape(-1)
         tmax = int(lens.max().item())
         B, Cc = src.shape[0], enc.enc_hid_dim
+        site = rng.SITE_ENC_EMBED if site is None else site
         emb = A.philox_dropout(A.embed_relu(src[:, :tmax], self.embed.embedding.weight), self.embed.dropout.p,
-                               rng.next_seed() if seed is None else seed, rng.offset(rng.SITE_ENC_EMBED), self.embed.training)
+                               rng.next_seed() if seed is None else seed, rng.offset(site), self.embed.training)
         outs, finals = [], []
         for sfx, reverse in (("", False), ("_reverse", True)):      # each direction = one autograd node
             w_ih, w_hh = getattr(lstm, "weight_ih_l0" + sfx), getattr(lstm, "weight_hh_l0" + sfx)
@@ -330,8 +332,11 @@ class DAE(nn.Module):
         h2, c2 = A.lstm_cell(torch.cat([h1, attend_cap], 1), h2, c2, ll.weight_ih, ll.weight_hh, ll.bias_ih, ll.bias_hh)
         return h1, c1, h2, c2
 
-    def _forward_autograd(self, encoded_captions, caption_lengths, encoded_previous_captions, previous_cap_length):
-        """dcnet.py:303-350 over autograd ops."""
+    def _forward_autograd(self, encoded_captions, caption_lengths, encoded_previous_captions, previous_cap_length,
+                          hidden=False):
+        """dcnet.py:303-350 over autograd ops.  hidden=True: the MSE stage's forward (dcnet_with_mse.py:303-343), which also
+        returns gd_final_hidden (the encoder on the sorted ground-truth captions, run first, its own dropout site) and
+        decoder_last_hidden (every row's h2 at its last step, before the output dropout)."""
         from . import autograd_ops as A
         from . import rng
         batch_size = encoded_captions.size(0)
@@ -344,6 +349,9 @@ class DAE(nn.Module):
         decode_lengths = (caption_lengths - 1).tolist()
         seed = self.__dict__["_fwd_seed"] = rng.next_seed()       # one seed per forward call, one Philox offset per site (rng.py)
         training, p_emb, p_out = self.training, self.embed.dropout.p, self.dropout.p
+        gd_final_hidden = None
+        if hidden:                        # dcnet_with_mse.py:322
+            _, gd_final_hidden, _ = self._encoder_autograd(encoded_captions, caption_lengths, seed, rng.SITE_ENC2_EMBED)
         enc, final_hidden, mask = self._encoder_autograd(prev, plen, seed)
         ca = self.caption_attention
         att1_c = A.linear(enc, ca.cap_features_att.weight, ca.cap_features_att.bias)       # loop invariant (dcnet.py:261)
@@ -351,20 +359,35 @@ class DAE(nn.Module):
         if _editnet._XE_SEQUENCE:         # the whole loop as ONE autograd node (dcnet_sequence.py)
             from . import dcnet_sequence as S
             cfg = S.SeqConfig(decode_lengths, training, p_emb, 0.0, p_out, seed)
+            cfg.last_hidden = hidden
             preds = S.dcnet_sequence(cfg, enc, final_hidden, mask, att1_c, encoded_captions, S.dae_params(self))
+            if hidden:
+                preds, last_h = preds
+                return preds, encoded_captions, decode_lengths, sort_ind, gd_final_hidden, last_h
             return preds, encoded_captions, decode_lengths, sort_ind
         # dcnet.py:325 embeds (and drops out) all positions at once; position t is consumed by timestep t only, so its
         # mask is the (SITE_EMBED, t) stream over the rows still in the batch — as on the whole-sequence node
         raw = A.embed_relu(encoded_captions, self.embed.embedding.weight)
-        preds_t = []
+        preds_t, last_parts = [], []
         for t in range(max(decode_lengths)):
             bt = sum([l > t for l in decode_lengths])
             emb = A.philox_dropout(raw[:bt, t], p_emb, seed, rng.offset(rng.SITE_EMBED, t), training)
             h1, c1, h2, c2 = self._step_autograd(emb, final_hidden[:bt], enc[:bt], mask[:bt], h1[:bt],
                                                  c1[:bt], h2[:bt], c2[:bt], att1_c[:bt])
+            if hidden:                    # rows [bt(t + 1), bt) end at this step: their decoder_last_hidden
+                b0 = sum([l > t + 1 for l in decode_lengths])
+                if bt > b0:
+                    last_parts.append(h2[b0:bt])
             preds = A.linear(A.philox_dropout(h2, p_out, seed, rng.offset(rng.SITE_OUT, t), training),
                              self.fc.weight, self.fc.bias)
             if bt < batch_size:
                 preds = torch.cat([preds, preds.new_zeros(batch_size - bt, preds.shape[1])], 0)
             preds_t.append(preds)
+        if hidden:
+            last_parts = last_parts[::-1]             # later steps end the earlier (longer) rows of the sorted batch
+            n_live = sum([l > 0 for l in decode_lengths])
+            if n_live < batch_size:                   # decode length 0: the zero initial state
+                last_parts.append(h2.new_zeros(batch_size - n_live, self.decoder_dim))
+            return (torch.stack(preds_t, 1), encoded_captions, decode_lengths, sort_ind, gd_final_hidden,
+                    torch.cat(last_parts, 0))
         return torch.stack(preds_t, 1), encoded_captions, decode_lengths, sort_ind

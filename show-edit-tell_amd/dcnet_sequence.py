@@ -123,10 +123,16 @@ class _DcnetSequence(torch.autograd.Function):
         if uniform:
             pred_tb = _e(T, B, V, dev=dev)
             ops.linear(hout.reshape(T * B, D), P["fc_w"], P["fc_b"], pred_tb.view(T * B, V), T * B)
-            return pred_tb.transpose(0, 1)
-        out = _z(B, T, V, dev=dev)
-        for t in range(T):
-            ops.linear(hout[t], P["fc_w"], P["fc_b"], out[:, t], bts[t])
+            out = pred_tb.transpose(0, 1)
+        else:
+            out = _z(B, T, V, dev=dev)
+            for t in range(T):
+                ops.linear(hout[t], P["fc_w"], P["fc_b"], out[:, t], bts[t])
+        if getattr(cfg, "last_hidden", False):
+            # dcnet_with_mse.py:321,341: h2 of every row at its last step = slot len_b of the state log (slot 0 holds the zero
+            # initial state: a row of decode length 0), before the output dropout
+            idx = torch.tensor(lens, dtype=torch.long, device=dev)
+            return out, L["H2"][idx, torch.arange(B, device=dev)]
         return out
 
     @staticmethod
@@ -142,6 +148,9 @@ class _DcnetSequence(torch.autograd.Function):
         train = cfg.train
         pidx = {n: i for i, n in enumerate(PARAM_NAMES)}
         g = [None] * len(PARAM_NAMES)
+        dlast = None                       # d(decoder_last_hidden) (the second output in teacher-forced mode with cfg.last_hidden)
+        if cfg.rollout is None and getattr(cfg, "last_hidden", False) and dlogp is not None:
+            dlast = dlogp.contiguous()
         if cfg.rollout is not None:
             dl = dlogp.t().contiguous()
             dp = A.zero_padded_rows(T, B, V, dev)          # rows padded to 16 bytes: the fc contractions read them in place
@@ -181,6 +190,10 @@ class _DcnetSequence(torch.autograd.Function):
             bt = bts[t]
             r = lambda x: _rows(x, bt)
             h1 = L["H1"][t + 1]
+            if dlast is not None:          # rows whose last step this is, [bts[t + 1], bts[t]): d(decoder_last_hidden) joins dh2
+                b0 = bts[t + 1] if t + 1 < T else 0
+                if bt > b0:
+                    ops.pack(DH2[b0:], bt - b0, [dlast[b0:bt]], accumulate=True)
             if train and cfg.p_out > 0:    # h2 does not follow a ReLU: the mask is regenerated, not read off the zero pattern
                 check(lib.set_dropout_bwd_philox_f32(dH2D[t].data_ptr(), D, DH2.data_ptr(), D, bt, D, cfg.p_out, cfg.seed,
                                                      rng.offset(rng.SITE_OUT, t), 1, st), "set_dropout_bwd_philox_f32")

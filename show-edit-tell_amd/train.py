@@ -15,6 +15,7 @@ import torch
 import torch.nn.functional as F
 from torch.nn.utils.rnn import pack_padded_sequence
 
+from . import _lib
 from . import loss as _loss
 from .optim import clip_grad_norm_and_step
 
@@ -384,6 +385,59 @@ def dcnet_xe_train_step(dae, optimizer, caps, caplens, previous_caption, prev_ca
     loss, n_tok, _ = dcnet_xe_backward(dae, caps, caplens, previous_caption, prev_caplen, group, reduce, caplens_host)
     _refuse_non_finite(loss)
     params = [p for p in dae.parameters() if p.requires_grad]
+    clip_grad_norm_and_step(params, optimizer, GRAD_CLIP)
+    return loss, n_tok
+
+
+def _global_sums(values, device, group=None):
+    """Sums over the ranks of several host numbers in ONE collective (no-op without an active group)."""
+    import torch.distributed as dist
+    if not _dist_active(group):
+        return [float(v) for v in values]
+    t = torch.tensor([float(v) for v in values], dtype=torch.float64,
+                     device="cpu" if dist.get_backend(group) == "gloo" else device)
+    _all_reduce_sum(dist, t, group)
+    return t.tolist()
+
+
+def dcnet_mse_backward(dae_ar, caps, caplens, previous_caption, prev_caplen, group=None, reduce=True, caplens_host=None):
+    """Forward + backward + gradient exchange of the DCNet MSE stage (dcnet_with_mse.py:369-398) on this rank's shard:
+        loss = CE_sum / n_tok_global + SSE(affine_hidden(decoder_last_hidden), gd_final_hidden) / (B_global * D)
+    — with one rank exactly CrossEntropyLoss() + MSELoss() of the reference, with N ranks the same loss over the concatenated
+    batch (both normalisers are exchanged in one collective, gradients SUM-reduced).  `dae_ar`: dcnet_with_mse.DAEWithAR.
+    Returns (global loss, local tokens, reducer)."""
+    from . import autograd_ops as A
+    from .autograd_ops import deferred_param_grads
+    grp_on = reduce and _dist_active(group)
+    n_tok = _token_count(caplens, caplens_host)
+    B = int(caps.shape[0])
+    n_glob, b_glob = (int(v) for v in _global_sums((n_tok, B), caps.device, group)) if grp_on else (n_tok, B)
+    scores, caps_sorted, decode_lengths, _, gd_final_hidden, last_hidden = dae_ar(caps, caplens, previous_caption, prev_caplen)
+    ce_sum, n_chk, _, _ = xe_loss_sum(scores, caps_sorted, decode_lengths)
+    assert n_chk == n_tok, (n_chk, n_tok)
+    denom = b_glob * last_hidden.shape[1]
+    sse = A.mse_sum(last_hidden, gd_final_hidden)       # gradient to both arguments (dcnet_with_mse.py:392)
+    loss = ce_sum / n_glob + sse / denom
+    core = dae_ar.dae
+    reducer = _begin_backward(dae_ar, group, grp_on, first=(core.fc.weight, core.fc.bias))
+    with deferred_param_grads(on_ready=lambda p, eager=False: reducer.add(p.grad, flush=eager)):
+        loss.backward()
+    params = [p for p in dae_ar.parameters() if p.requires_grad]
+    allreduce_gradients(params, group, reducer=reducer)
+    sums = torch.stack([ce_sum.detach().double().reshape(()), sse.detach().double().reshape(())]).cpu().tolist()
+    if grp_on:
+        sums = _global_sums(sums, caps.device, group)
+    return sums[0] / max(n_glob, 1) + sums[1] / denom, n_tok, reducer
+
+
+def dcnet_mse_train_step(dae_ar, optimizer, caps, caplens, previous_caption, prev_caplen, group=None, reduce=True,
+                         caplens_host=None):
+    """One step of dcnet_with_mse.py:362-404 (train mode, XE + MSE, clip 0.25 over every trainable parameter of the
+    wrapper — `affine_hidden` included —, optimizer) on this rank's shard.  Returns (GLOBAL loss, local tokens)."""
+    dae_ar.train()
+    loss, n_tok, _ = dcnet_mse_backward(dae_ar, caps, caplens, previous_caption, prev_caplen, group, reduce, caplens_host)
+    _refuse_non_finite(loss)
+    params = [p for p in dae_ar.parameters() if p.requires_grad]
     clip_grad_norm_and_step(params, optimizer, GRAD_CLIP)
     return loss, n_tok
 
