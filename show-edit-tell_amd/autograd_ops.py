@@ -479,7 +479,8 @@ class _Linear(torch.autograd.Function):
         M, K, N = x2.shape[0], x2.shape[1], w.shape[0]
         y = torch.empty(M, N, dtype=torch.float32, device=x.device)
         ws = _ws(lib.set_linear_workspace_bytes, M, N, K, device=x.device)
-        check(lib.set_linear_f32(ptr(x2), K, ptr(w), K, ptr(b), ptr(y), N, M, N, K, act, ptr(ws), ws.numel(),
+        wm, ldw = _mat(w)              # a column slice of a wider weight is read in place through its row stride
+        check(lib.set_linear_f32(ptr(x2), K, ptr(wm), ldw, ptr(b), ptr(y), N, M, N, K, act, ptr(ws), ws.numel(),
                                  stream_of(x.device)), "set_linear_f32")
         ctx.act, ctx.xshape = act, x.shape
         ctx.params = (w, b)

@@ -302,6 +302,15 @@ class SelectC(nn.Module):
         return sel
 
 
+def _count_truncated(X, rmask):
+    """editnet_adaptive.py:455-456: alpha and the features are cut to the first n = max over the batch of the COUNT of
+    unmasked regions, without renormalising.  alpha reaches the context only through the features, so zeroing the feature
+    rows at index >= n IS that truncation, in the forward and in d alpha.  Nothing changes unless a valid region's
+    embedded row is entirely zero (then the last unmasked regions of the longest rows fall off, as in the reference)."""
+    n = rmask.sum(1).max()
+    return X * (torch.arange(X.shape[1], device=X.device) < n)[None, :, None].to(X.dtype)
+
+
 class VisualAttentionC(nn.Module):
     """reference editnet.py:424-447"""
 
@@ -342,6 +351,8 @@ class VisualAttentionC(nn.Module):
                 fe = fe * keep[:, :, None].to(fe.dtype)
                 rmask = (fe.detach().sum(2) != 0).float()
             att1 = A.linear(fe, self.features_att.weight, self.features_att.bias)
+            if rmask is not None:
+                X = _count_truncated(X, rmask)
             return A.visual_attention_from_att1(X, att1, _f32c(decoder_hidden), self.decoder_att.weight,
                                                 self.decoder_att.bias, self.full_att.weight, self.full_att.bias, rmask)
         lib = _lib.load()
@@ -682,13 +693,22 @@ class DecoderC(nn.Module):
             if self._adaptive:
                 cfg.adaptive = True
                 cfg.rmask = None if self.training else (Yv.detach().sum(2) != 0).float()
-            out = S.xe_sequence(cfg, X, mean, H, M, final_hidden, mask, att1_c_all, Yin, encoded_captions,
-                                S.decoder_params(self))
-            if self._adaptive:
-                out, self._last_hidden = out
-            if cfg.ss_prob > 0.0:
-                self.__dict__["_fed_tokens"] = cfg.fed_tokens       # (T, B) words the steps consumed (diagnostics / tests)
-            return out, encoded_captions, decode_lengths, sort_ind
+            try:
+                out = S.xe_sequence(cfg, X, mean, H, M, final_hidden, mask, att1_c_all, Yin, encoded_captions,
+                                    S.decoder_params(self))
+            except S.CountTruncation:
+                # adaptive only: a valid region's embedded row is entirely zero at some step and the reference's count-based
+                # truncation (editnet_adaptive.py:455-456) changes a context.  The node's kernels do not implement it: this
+                # sequence (same seed, same masks) runs on the per-operator route below, which does.
+                out = None
+            if out is not None:
+                if self._adaptive:
+                    out, self._last_hidden = out
+                if cfg.ss_prob > 0.0:
+                    self.__dict__["_fed_tokens"] = cfg.fed_tokens       # (T, B) words the steps consumed (diagnostics / tests)
+                return out, encoded_captions, decode_lengths, sort_ind
+            h1, c1 = self.init_hidden_state(batch_size)
+            h2, c2 = self.init_hidden_state(batch_size)
 
         att1_eval = rmask_eval = None
         if not self.training:            # dropout inactive: features_att(att_embed(X)) is loop invariant
@@ -730,7 +750,8 @@ class DecoderC(nn.Module):
             else:                                                                     # fresh dropout mask per step
                 fe, rmask = embed_regions(head(Y, bt), None if valid is None else head(valid, bt), t)
                 att1 = A.linear(fe, va.features_att.weight, va.features_att.bias)
-            attend_img = A.visual_attention_from_att1(head(X, bt), att1, h1, va.decoder_att.weight, va.decoder_att.bias,
+            Xt = head(X, bt) if rmask is None else _count_truncated(head(X, bt), rmask)
+            attend_img = A.visual_attention_from_att1(Xt, att1, h1, va.decoder_att.weight, va.decoder_att.bias,
                                                       va.full_att.weight, va.full_att.bias, rmask)
             sel = A.select(head(M, bt), alpha_c)
             h2, c2 = A.copy_lstm(torch.cat([h1, attend_cap, attend_img], 1), head(h2, bt), head(c2, bt), sel,

@@ -75,6 +75,30 @@ class SeqConfig:
         self.ss_prob = 0.0
 
 
+class CountTruncation(Exception):
+    """raised by the adaptive node's forward when the reference's count-based truncation would change a context (see
+    count_truncation_bites): the node's kernels sum over all unmasked regions, so the caller runs the per-operator route"""
+
+
+TRUNCATION_FALLBACKS = 0        # sequences handed back to the per-operator route (tests / diagnostics)
+
+
+def count_truncation_bites(rmask, bts):
+    """editnet_adaptive.py:455-456 truncates alpha and the features of a step to the first n = max over the live rows of
+    the COUNT of unmasked regions, without renormalising.  With the unmasked regions packed at the front (always, unless a
+    valid region's embedding row is zero: a ReLU that leaves nothing, or — in train mode, with probability 2^-D per region
+    and step — a dropout mask that drops everything) that removes only regions whose alpha is exactly zero.  rmask
+    (T, B, R) or (B, R) 0/1, bts[t] live rows of step t -> True when some live row has an unmasked region at index >= n.
+    One device->host synchronisation."""
+    T = len(bts)
+    rm = rmask if rmask.dim() == 3 else rmask.unsqueeze(0).expand(T, -1, -1)
+    B, R = rm.shape[1], rm.shape[2]
+    live = torch.arange(B, device=rm.device)[None, :] < torch.tensor(bts, device=rm.device)[:, None]
+    n = (rm.sum(2) * live).max(1).values                                        # (T,)
+    last = (rm * torch.arange(1, R + 1, device=rm.device, dtype=rm.dtype)).max(2).values * live   # (T, B): 1 + last unmasked index
+    return bool((last > n[:, None]).any().item())
+
+
 def _z(*shape, dev):
     return torch.zeros(*shape, dtype=torch.float32, device=dev)
 
@@ -374,6 +398,10 @@ class _XESequence(torch.autograd.Function):
                                               state.seq.data_ptr(), state.tokens[t + 1].data_ptr(), state.unfinished.data_ptr(),
                                               state.alive.data_ptr(), L["RAW"][t].data_ptr(), L["LSE"][t].data_ptr(),
                                               L["LOGP"][t].data_ptr(), st), "set_sample_pick_f32")
+        if adaptive and count_truncation_bites(L["RMASK"] if train else rmask_eval, bts):
+            global TRUNCATION_FALLBACKS
+            TRUNCATION_FALLBACKS += 1
+            raise CountTruncation()
         hout = L["H2D"] if (train and cfg.p_out > 0) else L["H2"][1:]
         if ro is not None:
             ctx.cfg, ctx.L, ctx.bts, ctx.uniform, ctx.hout = cfg, L, bts, True, hout

@@ -209,3 +209,28 @@ def check_sampled_paths_rows(seq_a, logp_a, seq_b, logp_b, draw_margin, draw_alt
                                                     "%.2e of the mass" % (b, n, draw_margin[n, b]))
             assert int(seq_b[b, n]) in (int(draw_alt[n, b]), 0), "row %d step %d: not the neighbouring word" % (b, n)
     return differing
+
+
+def check_grad_arrays(named_grads, ref_grads, ref_norms, what):
+    """The gradient criterion of tests/test_hip_train.py::_check_grads on FULL arrays, shared by the float64-oracle tests:
+    every parameter has a gradient, its norm within 1e-4 * |ref| + floor, every element within
+    1e-4 * max(max|ref|, 1e-6) + floor, floor = 1e-6 * the model's largest reference gradient norm.  named_grads: iterable
+    of (name, numpy gradient or None); ref_grads / ref_norms: {name: array} / {name: float}.  Returns the largest element
+    error as a fraction of its allowance."""
+    named_grads = list(named_grads)
+    assert sorted(k for k, _ in named_grads) == sorted(ref_grads), (what, sorted(set(ref_grads) ^ set(k for k, _ in named_grads)))
+    floor = 1e-6 * max(float(ref_norms[k]) for k in ref_grads)
+    worst = 0.0
+    for k, got in named_grads:
+        assert got is not None, (what, k, "no gradient")
+        ref = ref_grads[k]
+        assert ref is not None and got.shape == ref.shape, (what, k)
+        gn = float(ref_norms[k])
+        mine = float(np.sqrt((got.astype(np.float64) ** 2).sum()))
+        assert abs(mine - gn) <= 1e-4 * gn + floor, (what, k, "norm", mine, gn)
+        err = float(np.abs(got.astype(np.float64) - ref).max())
+        scale = max(float(np.abs(ref).max()), 1e-6)
+        worst = max(worst, err / (1e-4 * scale + floor))
+        assert err <= 1e-4 * scale + floor, (what, k, err, scale)
+    print(what, "largest element error: %.2f of its allowance" % worst)
+    return worst
