@@ -297,6 +297,28 @@ int set_dcnet_greedy_pick(const SetDcnetWeights* w, const SetDcnetDims* d, const
 int set_dcnet_greedy(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* prev,
                      const int64_t* prevlen, int64_t start_idx, int64_t end_idx, int max_len,
                      int64_t* seq, float* seq_logp, void* ws, size_t ws_bytes, void* stream);
+/* Beam search of ONE previous caption, the reference's own evaluate() shape (dcnet.py:405-541: batch = 1, beam k = 3), as
+ * prologue + ONE persistent launch (csrc/decode_persistent.hip, beam mode): the d->B <= 4 rows of the workspace are the k
+ * hypotheses — prev (k, T), prevlen (k) hold the caption's inputs k times, the prologue runs for all k rows — and every
+ * timestep ends with the reference's pick (dcnet.py:447-514: log-softmax, + running scores, flat top-k over k V, parent / word
+ * split with `//`, completed hypotheses leave, k shrinks) instead of the arg-max; recurrent state follows the parent map inside
+ * the launch.  The search stops when every hypothesis has ended or after max_picks picks (the reference's 50-step limit:
+ * max_picks = 51).  Outputs (device), the layout of set_editnet_beam_persistent: hist_parent / hist_word (max_picks, 4) = parent
+ * slot and appended word of every slot after every pick — the host follows them back to read a sequence; best_score /
+ * best_word [1] and result [4] = {pick index of the best completed hypothesis (-1: none), its parent slot, hypotheses still
+ * alive, picks made}.  A time-out poisons best_score with NaN and result[2..3] = -1 (SET_ERR_FAULT at the next call).
+ * SET_ERR_ARG: null pointers, max_picks < 1, start_idx outside the vocabulary — answered before any HIP call.
+ * SET_ERR_UNSUPPORTED (take set_dcnet_step + set_beam_pick_f32): no token table, k > 4, dimensions the persistent launch
+ * does not cover (D = E = 2C = 1024, A = 512, T <= 32, V <= 12288), SET_DEC_PERSISTENT=0, k V >= 2^31, another process owns the
+ * device's persistent launches — all answered BEFORE anything is touched; only a device whose LDS limit or resident-workgroup
+ * capacity turns out too small is answered after the prologue has been written into `ws` (outputs untouched).
+ * set_dcnet_workspace_bytes covers the launch's exchange region (for B <= 4 it holds B x 24 KB of candidate words at D = 1024).
+ * The ensemble's per-image search has no such launch: it runs on set_*_step + set_beam_pick_f32.
+ * Parity: tests/test_hip_dcnet_beam.py against the reference's beam goldens and the batched per-step search. */
+int set_dcnet_beam_persistent(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* prev,
+                              const int64_t* prevlen, int64_t start_idx, int64_t end_idx, int max_picks,
+                              int32_t* hist_parent, int64_t* hist_word, float* best_score, int64_t* best_word,
+                              int32_t* result, void* ws, size_t ws_bytes, void* stream);
 /* multinomial twin of set_dcnet_greedy (dcnet_rl.py:320-327); see set_editnet_sample */
 int set_dcnet_sample(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* prev,
                      const int64_t* prevlen, int64_t start_idx, int64_t end_idx, int max_len, uint64_t seed,

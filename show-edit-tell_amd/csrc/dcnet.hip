@@ -419,6 +419,25 @@ int set_dcnet_greedy(const SetDcnetWeights* w, const SetDcnetDims* d, const int6
     return dcnet_rollout(w, d, prev, prevlen, start_idx, end_idx, max_len, 0, 0, 0, seq, seq_logp, ws, ws_bytes, stream);
 }
 
+int set_dcnet_beam_persistent(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* prev, const int64_t* prevlen,
+                              int64_t start_idx, int64_t end_idx, int max_picks, int32_t* hist_parent, int64_t* hist_word,
+                              float* best_score, int64_t* best_word, int32_t* result, void* ws, size_t ws_bytes, void* stream) {
+    if (!w || !d || !prev || !prevlen || !hist_parent || !hist_word || !best_score || !best_word || !result || max_picks < 1)
+        return SET_ERR_ARG;
+    if (start_idx < 0 || start_idx >= d->V) return SET_ERR_ARG;
+    SET_TRY(check_dims(d));
+    // (nothing is touched before the checks that can answer SET_ERR_UNSUPPORTED)
+    if (!table_active(w, d)) return SET_ERR_UNSUPPORTED;
+    if (!dcnet_persistent_beam_ok(d, max_picks)) return SET_ERR_UNSUPPORTED;
+    DcnetWs W;
+    SET_TRY(prep(d, ws, ws_bytes, &W));
+    hipStream_t st = (hipStream_t)stream;
+    SET_TRY(begin_impl(w, d, prev, prevlen, W, st));              // (includes Pc = enc W_ih[:, D:]^T: dcnet_persistent_ok holds)
+    const PDecBeam beam{hist_parent, hist_word, best_score, best_word, result};
+    return dcnet_persistent_greedy(w, d, W.pre1, W.att1_c, W.mask, W.pd_pc, W.pd_x, W.it, W.unfinished, W.alive, start_idx, end_idx,
+                                   max_picks, nullptr, nullptr, st, nullptr, &beam);
+}
+
 int set_dcnet_sample(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* prev, const int64_t* prevlen,
                      int64_t start_idx, int64_t end_idx, int max_len, uint64_t seed, uint64_t offset, int64_t* seq,
                      float* seq_logp, void* ws, size_t ws_bytes, void* stream) {

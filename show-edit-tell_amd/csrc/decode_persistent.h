@@ -17,6 +17,9 @@ constexpr int PDEC_TMAX = 32;      // previous-caption positions held in registe
 constexpr int PDEC_KB = 16;        // 16-wide k-blocks per wave and gate tile: D = 1024 -> K quarter 256
 constexpr int PDEC_THREADS = 256;
 constexpr int PDEC_FC_TILES = 3;   // 16-row fc tiles per workgroup: up to 48 vocabulary rows
+// beam mode of both kernels (one image, rows = hypotheses): what a workgroup publishes per row of its vocabulary slice
+constexpr int PW_BEAM_K = 4;       // hypotheses (= rows) at most
+constexpr int PW_BEAM_W = 12;      // words per row and slice: max, sum exp, 4 x (value, index), 2 pads
 
 // diagnostic (SET_PDEC_STAMPS=1): 100-MHz time stamps of workgroup SET_PDEC_STAMP_WG, 24 per timestep
 constexpr int PD_STAMPS = 24, PD_STAMP_STEPS = 64;

@@ -68,6 +68,13 @@ struct PDecDcnetArgs {
     // (LH, teacher-forced) h2 of every row at its last step t = dlen[b] - 1 (dcnet_with_mse.py:321,341), (B, D).  Last member:
     // the offsets of the fields above, and so the instructions of the variants without it, stay as they were
     float* last_h2;
+    // beam mode (BEAM, set_dcnet_beam_persistent): the rows are the k hypotheses of ONE image.  After last_h2, for the same reason
+    void* x_fcb;                                 // (B, G, PW_BEAM_W) per-slice (max, sum exp, 4 x (score, word)) words
+    int* bm_hist_par;                            // (max_len, 4) parent slot of every slot after every pick
+    long long* bm_hist_word;                     // (max_len, 4) word appended to every slot at every pick
+    float* bm_best_score;                        // [1] best completed hypothesis (-inf: none)
+    long long* bm_best_word;                     // [1] its last word (<end>)
+    int* bm_result;                              // [4] pick index and parent slot of the best completed hypothesis, k_left, picks made
 };
 
 // RES: B <= 4 and T <= PDEC_TREG — a wave scores ONE fixed row, whose hoisted cap_features_att rows (loop-invariant, T x A
@@ -75,7 +82,19 @@ struct PDecDcnetArgs {
 // LH: teacher-forced only, also write last_h2 (set_dcnet_xe_forward_hidden).  The loop keeps computing every row until the
 // longest caption ends, so no buffer holds a row's h2 at its own last step: the owner of h2[b, u] stores it when t + 1 ==
 // dlen[b].  A template parameter, not a runtime test: the variants without it compile to the same instructions as before.
-template <bool RES, bool LH = false>
+// BEAM: free-running only; the B <= PW_BEAM_K rows are the hypotheses of ONE image and the loop is the reference's beam search
+// (dcnet.py:447-514) instead of the greedy loop: the arg-max epilogue (X4 / S6) becomes the pick of
+// editnet_persistent_wide_k<BEAM> (decode_persistent_wide.hip) — the scheme is copied, not shared: that kernel's pick is
+// written into its loop body and moving it would change its instructions.  Per pick every workgroup publishes, per row, (max,
+// sum exp, its PW_BEAM_K best (score, word) pairs) of its vocabulary slice, stages all slices and runs the same merge (value
+// descending, flat index ascending among equals): the same (parent, word) per slot everywhere, no broadcast round.
+// Recurrent state follows the parent map inside the launch: c1 / c2 of the owned units through a small LDS table, the
+// h-dependent products contracted ahead of the pick (S1') are read through the parent slot — language_lstm.W_hh h2 therefore
+// goes to LDS instead of staying in the accumulator that S2 continues.  h1 / h2 themselves are recomputed after every pick
+// and need no permutation.  The per-sequence operands (pre1, att1_c, mask, pc) are REPLICATED k times by the prologue, as
+// on the EditNet path (the rows of the workspace hold the image's previous caption k times).  A template parameter, not a
+// runtime test, like LH.
+template <bool RES, bool LH = false, bool BEAM = false>
 __global__ void __launch_bounds__(PDEC_THREADS, 1) dcnet_persistent_k(const PDecDcnetArgs P) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __shared__ long long sTok[PDEC_MAXB];
@@ -93,18 +112,38 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) dcnet_persistent_k(const PDec
     float* sF = sA2 + B * A;                             // (B, G, 4) fc triples of every workgroup
     float* sCon = sF + B * G * 4;                        // [cap_decoder_att.bias | cap_full_att.weight] (2, A): loop-invariant
     float* sPc = sCon + 2 * A;                           // (B, 16, TMAX) hoisted context products of the owned gate rows
+    // beam mode only (pdec_lds_floats): every workgroup's per-slice candidates, language_lstm.W_hh h2 of the previous timestep
+    // (added through the parent map), the cell states on their way through the parent map, the candidate lists of the pick and
+    // the pick's bookkeeping words
+    float* sFB = sPc + B * 16 * (PDEC_TMAX + 1);         // (B, G, PW_BEAM_W)
+    float* sRedP = sFB + B * G * PW_BEAM_W;              // [4 waves][16 batch rows][16 weight rows]
+    float* sCst = sRedP + 4 * 256;                       // (2, K, 4) c1 | c2 of the owned units
+    float* sCand = sCst + 2 * PW_BEAM_K * 4;             // (K, K, 2) (score, flat index) of every row's best K candidates
+    float* sScore = sCand + PW_BEAM_K * PW_BEAM_K * 2;   // (K) running scores of the slots (-inf = dead)
+    int* sPar = reinterpret_cast<int*>(sScore + PW_BEAM_K);   // (K) parent slot of every slot (identity before the first pick)
+    int* sKleft = sPar + PW_BEAM_K;                      // [0] hypotheses alive
+    float* sBest = reinterpret_cast<float*>(sKleft + 1); // [0] best completed hypothesis so far
     const LLWatch watch{P.status, P.fault, P.spin_limit};
     // exchange buffers (grid_barrier.h, flag-in-data words)
     const __amdgpu_buffer_rsrc_t h1rs = __builtin_amdgcn_make_buffer_rsrc((void*)P.x_h1, 0, B * D * 8, 0x00027000);
     const __amdgpu_buffer_rsrc_t h2rs = __builtin_amdgcn_make_buffer_rsrc((void*)P.x_h2, 0, B * D * 8, 0x00027000);
     const __amdgpu_buffer_rsrc_t a2rs = __builtin_amdgcn_make_buffer_rsrc((void*)P.x_att2, 0, B * A * 8, 0x00027000);
     const __amdgpu_buffer_rsrc_t fcrs = __builtin_amdgcn_make_buffer_rsrc((void*)P.x_fc, 0, B * G * 32, 0x00027000);
+    const __amdgpu_buffer_rsrc_t fbrs = __builtin_amdgcn_make_buffer_rsrc(BEAM ? P.x_fcb : P.x_fc, 0, BEAM ? B * G * PW_BEAM_W * 8 : 32, 0x00027000);
 
     // ---- initial state: h1 = h2 = 0, every row is fed <start>
     for (int i = tid; i < 2 * B * LDH; i += PDEC_THREADS) smem[i] = 0.f;
     for (int i = tid; i < A; i += PDEC_THREADS) { sCon[i] = P.ca_dec_b[i]; sCon[A + i] = P.ca_full_w[i]; }
     const float bf = P.ca_full_b[0];
     if (tid < B) { sTok[tid] = P.start_idx; sUnf[tid] = 1; }
+    if constexpr (BEAM) {
+        if (tid < PW_BEAM_K) { sPar[tid] = tid; sScore[tid] = tid == 0 ? 0.f : -INFINITY; }   // pick 1: all rows are identical, only row 0 counts
+        for (int i = tid; i < 4 * 256; i += PDEC_THREADS) sRedP[i] = 0.f;                     // W_hh h2 of the zero initial state
+        if (tid == 0) {
+            sKleft[0] = B; sBest[0] = -INFINITY;
+            if (wg == 0) { P.bm_best_score[0] = -INFINITY; P.bm_best_word[0] = 0; P.bm_result[0] = -1; P.bm_result[1] = -1; P.bm_result[2] = B; P.bm_result[3] = 0; }
+        }
+    }
     __syncthreads();
 
     // ---- weight tiles of this lane: gate row of output column r = gate (r >> 2) of unit u0 + (r & 3)
@@ -176,13 +215,13 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) dcnet_persistent_k(const PDec
         PD_STAMP(0);
         float tg[4] = {0.f, 0.f, 0.f, 0.f};
         int bt = B;                                              // teacher-forced: rows whose caption is still running (sorted batch)
-        if (P.caps) {
+        if (!BEAM && P.caps) {
             bt = 0;
             for (int b = 0; b < B; ++b) bt += P.dlen[b] > t ? 1 : 0;
             if (bt == 0) break;
         }
         if (pair) {
-            long long tok = P.caps ? P.caps[(long long)pb * P.caps_stride + t] : sTok[pb];
+            long long tok = (!BEAM && P.caps) ? P.caps[(long long)pb * P.caps_stride + t] : sTok[pb];
             tok = tok < 0 ? 0 : (tok >= V ? V - 1 : tok);          // same clamp as embed_relu_k
             const float* trow = P.tok_table + tok * P.ld_tab + u0 + pu;
 #pragma unroll
@@ -191,13 +230,23 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) dcnet_persistent_k(const PDec
         PD_STAMP(1);
 #pragma unroll
         for (int e = 0; e < 4; ++e) sRed[(kq * 3 + 0) * 256 + (4 * g + e) * 16 + r] = acc1[e];
+        if constexpr (BEAM) {
+            if (pair) { sCst[pb * 4 + pu] = c1; sCst[PW_BEAM_K * 4 + pb * 4 + pu] = c2; }
+        }
         __syncthreads();
+        // beam mode: slot pb continues hypothesis sPar[pb] of the previous timestep — its cell states and the gate products
+        // that were contracted before the pick (S1' of the previous timestep) are read through the parent map
+        int par = pb;
+        if constexpr (BEAM) {
+            par = sPar[pair ? pb : 0];
+            if (pair) { c1 = sCst[par * 4 + pu]; c2 = sCst[PW_BEAM_K * 4 + par * 4 + pu]; }
+        }
         ++tag;                                                   // X1: h1
         if (pair && !(P.test_stall && wg == 0)) {
             float gq[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const int o = pb * 16 + q * 4 + pu;
+                const int o = par * 16 + q * 4 + pu;
                 gq[q] = ((((sRed[o] + sRed[3 * 256 + o]) + sRed[6 * 256 + o]) + sRed[9 * 256 + o]) + pre[q]) + tg[q];
             }
             const float ai = pd_sigm(gq[0]), af = pd_sigm(gq[1]), ag = tanhf(gq[2]), ao = pd_sigm(gq[3]);
@@ -231,6 +280,10 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) dcnet_persistent_k(const PDec
                 ll_put(a2rs, cb * A + wg * apw + crr, v, tag);
             }
             g2 = ((sRed[2 * 256 + o] + sRed[5 * 256 + o]) + sRed[8 * 256 + o]) + sRed[11 * 256 + o];
+            if constexpr (BEAM) {                                // + language_lstm.W_hh h2 of the PARENT hypothesis (S1' of the previous timestep)
+                const int op = sPar[cb] * 16 + crr;
+                g2 += ((sRedP[op] + sRedP[256 + op]) + sRedP[512 + op]) + sRedP[768 + op];
+            }
         }
         PD_STAMP(6);
         ll_stage<256, 8>(a2rs, sA2, B, A, A, tag, watch, tid);
@@ -324,7 +377,7 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) dcnet_persistent_k(const PDec
             sRed[(kq * 3 + 2) * 256 + (4 * g + e) * 16 + r] = accf2[e];
         }
         __syncthreads();
-        if (P.caps) {
+        if (!BEAM && P.caps) {
             // teacher-forced: the scores themselves, rows 0 .. bt - 1 (dcnet.py:347: predictions[:batch_size_t, t, :] = preds)
             for (int b = kq; b < bt; b += 4) {
                 const int j = lane >> 4, rr = lane & 15, row = row0 + lane;
@@ -342,6 +395,188 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) dcnet_persistent_k(const PDec
                 pd_mma(acc2, wb, aH2);
             }
             __syncthreads();                                     // sRed is rewritten by the next timestep's S1
+            continue;
+        }
+        if constexpr (BEAM) {
+            // ================= beam mode (dcnet.py:447-514; the bookkeeping of csrc/beam.hip beam_pick_k for ONE image, the scheme
+            // of decode_persistent_wide.hip): X4 carries, per row and vocabulary slice, (max, sum exp) and the slice's B best
+            // (score, word) pairs — a global top-B over B x V candidates takes at most B from one slice
+            ++tag;
+            if (kq < B) {
+                const int b = kq;
+                const int j = lane >> 4, rr = lane & 15, row = row0 + lane;
+                const bool ok = lane < 16 * PDEC_FC_TILES && lane < P.rpw && row < V;
+                float x = -INFINITY;
+                if (ok) {
+                    const int o = j * 256 + b * 16 + rr;
+                    x = (((sRed[o] + sRed[3 * 256 + o]) + sRed[6 * 256 + o]) + sRed[9 * 256 + o]) + fcb_lane;
+                }
+                float cvv[PW_BEAM_K];
+                int cii[PW_BEAM_K];
+                float xx = x;
+#pragma unroll
+                for (int q = 0; q < PW_BEAM_K; ++q) {
+                    float bv = -INFINITY;
+                    int bix = 0x7fffffff;
+                    if (q < B) {
+                        if (xx > -INFINITY) { bv = xx; bix = row; }
+                        pw_wargmax(bv, bix);
+                        if (ok && row == bix) xx = -INFINITY;
+                    }
+                    cvv[q] = bv; cii[q] = bix;
+                }
+                const float mx = cvv[0];
+                float se = (ok && mx > -INFINITY) ? expf(x - mx) : 0.f;
+                se = pw_wsum(se);
+                if (lane < PW_BEAM_W) {
+                    float v = 0.f;
+                    if (lane == 0) v = mx;
+                    else if (lane == 1) v = se;
+                    else if (lane < 2 + 2 * PW_BEAM_K) {
+                        const int q = (lane - 2) >> 1;
+                        float cv_ = cvv[0]; int ci_ = cii[0];
+#pragma unroll
+                        for (int u = 1; u < PW_BEAM_K; ++u) if (q == u) { cv_ = cvv[u]; ci_ = cii[u]; }
+                        v = (lane & 1) ? __int_as_float(ci_) : cv_;
+                    }
+                    ll_put(fbrs, (b * G + wg) * PW_BEAM_W + lane, v, tag);
+                }
+            }
+            PD_STAMP(11);
+            // S1' (see the greedy path); language_lstm.W_hh h2 goes to LDS: the next timestep adds it through the parent map
+            if (more) {
+                acc1 = zero4;
+                pd_mma(acc1, wb, aH2);
+                pd_load(wb, pT2);
+                pd_mma(acc1, wa, aH1);
+                f32x4 accp = zero4;
+                pd_mma(accp, wb, aH2);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) sRedP[kq * 256 + (4 * g + e) * 16 + r] = accp[e];
+                acc2 = zero4;
+            }
+            PD_STAMP(12);
+            ll_stage<256, 8>(fbrs, sFB, B * G, PW_BEAM_W, PW_BEAM_W, tag, watch, tid);
+            __syncthreads();
+            // ---- every workgroup runs the same pick.  Wave j: log-sum-exp of row j and its B best candidates (G = 256 slices:
+            // four per lane)
+            if (kq < B) {
+                const int j = kq;
+                const float scj = sScore[j];
+                float ov[PW_BEAM_K];
+                int oi[PW_BEAM_K];
+#pragma unroll
+                for (int q = 0; q < PW_BEAM_K; ++q) { ov[q] = -INFINITY; oi[q] = 0x7fffffff; }
+                if (scj > -INFINITY) {                           // (uniform in the wave; dead slots take no part)
+                    float cv[16];
+                    int ci[16];
+                    float pm[4], ps[4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const float* e = sFB + ((j * G + lane + 64 * i) * PW_BEAM_W);
+                        pm[i] = e[0]; ps[i] = e[1];
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) { cv[4 * i + q] = e[2 + 2 * q]; ci[4 * i + q] = __float_as_int(e[3 + 2 * q]); }
+                    }
+                    const float m = pw_wmax(fmaxf(fmaxf(pm[0], pm[1]), fmaxf(pm[2], pm[3])));
+                    float ssum = 0.f;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) ssum += (pm[i] == -INFINITY) ? 0.f : ps[i] * expf(pm[i] - m);
+                    ssum = pw_wsum(ssum);
+                    const float lse = m + logf(ssum);
+#pragma unroll
+                    for (int c = 0; c < 16; ++c) {
+                        const bool have = ci[c] != 0x7fffffff;
+                        cv[c] = have ? scj + (cv[c] - lse) : -INFINITY;       // score + log-prob, as beam_pick_k forms it
+                        ci[c] = have ? j * V + ci[c] : 0x7fffffff;
+                    }
+#pragma unroll
+                    for (int q = 0; q < PW_BEAM_K; ++q) {
+                        if (q < B) {
+                            float bv = -INFINITY;
+                            int bix = 0x7fffffff;
+#pragma unroll
+                            for (int c = 0; c < 16; ++c)
+                                if (cv[c] > bv || (cv[c] == bv && ci[c] < bix)) { bv = cv[c]; bix = ci[c]; }
+                            if (!(bv > -INFINITY)) bix = 0x7fffffff;
+                            pw_wargmax(bv, bix);
+#pragma unroll
+                            for (int c = 0; c < 16; ++c) if (ci[c] == bix) cv[c] = -INFINITY;
+                            ov[q] = bv; oi[q] = bix;
+                        }
+                    }
+                }
+                if (lane == 0) {
+#pragma unroll
+                    for (int q = 0; q < PW_BEAM_K; ++q) { sCand[(j * PW_BEAM_K + q) * 2] = ov[q]; sCand[(j * PW_BEAM_K + q) * 2 + 1] = __int_as_float(oi[q]); }
+                }
+            }
+            __syncthreads();
+            if (tid == 0) {
+                // the B best of the B x B candidates (ties: lowest flat index), then beam_pick_k's bookkeeping
+                const int k = B, kl = sKleft[0];
+                float pv_[PW_BEAM_K];
+                int pi_[PW_BEAM_K];
+                unsigned taken = 0u;
+                for (int rr_ = 0; rr_ < k; ++rr_) {
+                    float bv = -INFINITY;
+                    int bix = 0x7fffffff, bc = -1;
+                    for (int c = 0; c < k * PW_BEAM_K; ++c) {
+                        if ((taken >> c) & 1u) continue;
+                        if ((c % PW_BEAM_K) >= k) continue;
+                        const float v = sCand[c * 2];
+                        const int ix = __float_as_int(sCand[c * 2 + 1]);
+                        if (ix == 0x7fffffff) continue;
+                        if (v > bv || (v == bv && ix < bix) || bc < 0) { bv = v; bix = ix; bc = c; }
+                    }
+                    if (bc >= 0) taken |= 1u << bc;
+                    pv_[rr_] = bc >= 0 ? bv : -INFINITY;
+                    pi_[rr_] = bc >= 0 ? bix : 0x7fffffff;
+                }
+                int n_end = 0, c_arg = -1, slot = 0;
+                float c_best = -INFINITY;
+                bool live[PW_BEAM_K];
+                for (int rr_ = 0; rr_ < k; ++rr_) {
+                    const int flat = pi_[rr_];
+                    const bool okp = flat != 0x7fffffff && rr_ < kl;          // only the first k_left picks count
+                    const long long word = okp ? flat % V : 0;
+                    const bool is_end = okp && word == P.end_idx;
+                    live[rr_] = okp && !is_end;
+                    if (is_end) {
+                        ++n_end;
+                        if (pv_[rr_] > c_best) { c_best = pv_[rr_]; c_arg = rr_; }   // first maximum
+                    }
+                }
+                if (c_arg >= 0 && c_best > sBest[0]) {
+                    sBest[0] = c_best;
+                    if (wg == 0) {
+                        P.bm_best_score[0] = c_best;
+                        P.bm_best_word[0] = pi_[c_arg] % V;
+                        P.bm_result[0] = t;                              // pick index of the best completed hypothesis
+                        P.bm_result[1] = pi_[c_arg] / V;                 // its parent slot (numbering before this pick)
+                    }
+                }
+                sKleft[0] = kl - n_end;
+                for (int pass = 0; pass < 2; ++pass)
+                    for (int rr_ = 0; rr_ < k; ++rr_) {
+                        if ((pass == 0) != live[rr_]) continue;
+                        const int flat = pi_[rr_];
+                        const int parent = flat != 0x7fffffff ? flat / V : 0;
+                        const long long word = flat != 0x7fffffff ? flat % V : 0;
+                        sScore[slot] = live[rr_] ? pv_[rr_] : -INFINITY;
+                        sTok[slot] = live[rr_] ? word : 0;
+                        sPar[slot] = parent;
+                        if (wg == 0) {
+                            P.bm_hist_par[t * PW_BEAM_K + slot] = parent;
+                            P.bm_hist_word[t * PW_BEAM_K + slot] = word;
+                        }
+                        ++slot;
+                    }
+                if (wg == 0) { P.bm_result[2] = kl - n_end; P.bm_result[3] = t + 1; }
+            }
+            __syncthreads();
+            PD_STAMP(13);
+            if (sKleft[0] == 0) break;                           // every hypothesis has ended (dcnet.py:507-508)
             continue;
         }
         ++tag;                                                   // X4: (max, arg-max, sum exp) of every workgroup's rows
@@ -436,7 +671,9 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) dcnet_persistent_k(const PDec
     __syncthreads();
     if (s_bad) {
         const float qnan = __builtin_nanf("");
-        if (P.caps) {
+        if constexpr (BEAM) {
+            if (wg == 0 && tid == 0) { P.bm_best_score[0] = qnan; P.bm_result[2] = -1; P.bm_result[3] = -1; }   // never a search result
+        } else if (P.caps) {
             // teacher-forced: EVERY score this workgroup wrote (its vocabulary rows, all rows and timesteps) — each workgroup
             // poisons its own region after its own loop, so no later store of another workgroup can undo it
             const int row0 = wg * P.rpw;
@@ -450,10 +687,12 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) dcnet_persistent_k(const PDec
     }
 }
 
-static int g_pdec_capacity[64][4] = {};              // [device][RES + 2 LH]
-static int g_pdec_capacity_lds[64][4] = {};
-static int pdec_lds_floats(int B, int D, int A) {
-    return 2 * B * (D + 4) + 4 * 3 * 256 + PDEC_MAXB * PDEC_TMAX + PDEC_MAXB * 16 + B * A + B * (D / 4) * 4 + 2 * A + B * 16 * (PDEC_TMAX + 1);
+static int g_pdec_capacity[64][6] = {};              // [device][RES + 2 LH], beam mode: [4 + RES]
+static int g_pdec_capacity_lds[64][6] = {};
+static int pdec_lds_floats(int B, int D, int A, bool beam = false) {
+    const int base = 2 * B * (D + 4) + 4 * 3 * 256 + PDEC_MAXB * PDEC_TMAX + PDEC_MAXB * 16 + B * A + B * (D / 4) * 4 + 2 * A + B * 16 * (PDEC_TMAX + 1);
+    // beam mode: candidates of every slice, W_hh h2 tiles, c1 | c2 table, candidate lists, scores, parents, k_left, best
+    return base + (beam ? B * (D / 4) * PW_BEAM_W + 4 * 256 + 2 * PW_BEAM_K * 4 + PW_BEAM_K * PW_BEAM_K * 2 + 2 * PW_BEAM_K + 4 : 0);
 }
 
 
@@ -468,10 +707,17 @@ bool dcnet_persistent_ok(const SetDcnetDims* d, int max_len) {
     return !persistent_disabled();
 }
 
-// exchange region of one decode: [status line | h1 | h2 | cap_decoder_att(h1) | fc triples] as 8-byte flag-in-data words
+// exchange region of one decode: [status line | h1 | h2 | cap_decoder_att(h1) | fc triples | beam candidates] as 8-byte
+// flag-in-data words.  The candidate words exist for B <= PW_BEAM_K only (B x 24 KB at D = 1024): no size for B > 4 changed
 size_t dcnet_persistent_xbytes(int B, int D, int A) {
     if (B > PDEC_MAXB) return 0;
-    return 128 + (size_t)B * D * 8 * 2 + (size_t)B * A * 8 + (size_t)B * (D / 4) * 32;
+    return 128 + (size_t)B * D * 8 * 2 + (size_t)B * A * 8 + (size_t)B * (D / 4) * 32 +
+           (B <= PW_BEAM_K ? (size_t)B * (D / 4) * PW_BEAM_W * 8 : 0);
+}
+
+// set_dcnet_beam_persistent: the k <= 4 hypotheses of one image as the rows of one launch (flat index k V must fit an int)
+bool dcnet_persistent_beam_ok(const SetDcnetDims* d, int max_picks) {
+    return d->B <= PW_BEAM_K && (long long)d->B * d->V < 0x7fffffffLL && dcnet_persistent_ok(d, max_picks);
 }
 
 // the greedy loop after set_dcnet_begin's prologue.  `pc` = the hoisted context products (B, T, 4D), `xbuf` = exchange region
@@ -479,8 +725,9 @@ size_t dcnet_persistent_xbytes(int B, int D, int A) {
 int dcnet_persistent_greedy(const SetDcnetWeights* w, const SetDcnetDims* d, const float* pre1, const float* att1_c,
                             const float* mask, const float* pc, void* xbuf, long long* it, int* unfinished, int* alive,
                             long long start_idx, long long end_idx, int max_len, long long* seq, float* seq_logp,
-                            hipStream_t s, const PDecTeacher* teach) {
+                            hipStream_t s, const PDecTeacher* teach, const PDecBeam* beam) {
     if (!dcnet_persistent_ok(d, max_len)) return SET_ERR_UNSUPPORTED;
+    if (beam && (teach || !dcnet_persistent_beam_ok(d, max_len))) return SET_ERR_UNSUPPORTED;
     const int B = d->B, D = d->D, E = d->E, C = d->C, G = D / 4;
     PDecDcnetArgs P{};
     P.al_wih_h2 = w->al_wih + E + 2 * C; P.ld_al = 3LL * E;
@@ -495,7 +742,8 @@ int dcnet_persistent_greedy(const SetDcnetWeights* w, const SetDcnetDims* d, con
         P.x_h1 = x; x += (size_t)B * D * 8;
         P.x_h2 = x; x += (size_t)B * D * 8;
         P.x_att2 = x; x += (size_t)B * d->A * 8;
-        P.x_fc = x;
+        P.x_fc = x; x += (size_t)B * G * 32;
+        P.x_fcb = x;                                 // (B <= PW_BEAM_K: dcnet_persistent_xbytes)
     }
     P.it = it; P.unfinished = unfinished; P.alive = alive; P.seq = seq; P.seq_logp = seq_logp;
     P.B = B; P.D = D; P.T = d->T; P.A = d->A; P.V = d->V; P.max_len = max_len; P.rpw = (d->V + G - 1) / G;
@@ -506,8 +754,12 @@ int dcnet_persistent_greedy(const SetDcnetWeights* w, const SetDcnetDims* d, con
         for (int b = 0; b < B; ++b) P.dlen[b] = teach->host_decode_lengths[b];
         P.last_h2 = teach->last_h2;
     }
-    const bool lh = P.caps && P.last_h2;
-    const int lds = pdec_lds_floats(B, D, d->A) * (int)sizeof(float);
+    if (beam) {
+        P.bm_hist_par = beam->hist_par; P.bm_hist_word = (long long*)beam->hist_word; P.bm_best_score = beam->best_score;
+        P.bm_best_word = (long long*)beam->best_word; P.bm_result = beam->result;
+    }
+    const bool lh = P.caps && P.last_h2, bm = beam != nullptr;
+    const int lds = pdec_lds_floats(B, D, d->A, bm) * (int)sizeof(float);
     PersistentGuard guard;
     if (guard.rc != SET_OK) return guard.rc;
     const int dev = guard.dev;
@@ -516,20 +768,24 @@ int dcnet_persistent_greedy(const SetDcnetWeights* w, const SetDcnetDims* d, con
     // residency: every workgroup must be on the chip at once (see encoder_persistent.hip penc_fits)
     // (function attributes are per device; a device whose LDS limit is below the request, e.g. a 64-KB part, is answered with
     // SET_ERR_UNSUPPORTED — the caller's per-step loop — never with a HIP error)
-    static bool configured[4][64] = {};
-    const int lds_max = pdec_lds_floats(PDEC_MAXB, D, d->A) * (int)sizeof(float);
-    // the two variants of this call's family (with / without the last_h2 output)
-    const void* k_res = lh ? reinterpret_cast<const void*>(&dcnet_persistent_k<true, true>)
+    static bool configured[6][64] = {};
+    // (beam mode: its own LDS size, at most PW_BEAM_K rows)
+    const int lds_max = pdec_lds_floats(bm ? PW_BEAM_K : PDEC_MAXB, D, d->A, bm) * (int)sizeof(float);
+    // the two variants of this call's family (with / without the last_h2 output; beam mode)
+    const void* k_res = bm ? reinterpret_cast<const void*>(&dcnet_persistent_k<true, false, true>)
+                      : lh ? reinterpret_cast<const void*>(&dcnet_persistent_k<true, true>)
                            : reinterpret_cast<const void*>(&dcnet_persistent_k<true>);
-    const void* k_gen = lh ? reinterpret_cast<const void*>(&dcnet_persistent_k<false, true>)
+    const void* k_gen = bm ? reinterpret_cast<const void*>(&dcnet_persistent_k<false, false, true>)
+                      : lh ? reinterpret_cast<const void*>(&dcnet_persistent_k<false, true>)
                            : reinterpret_cast<const void*>(&dcnet_persistent_k<false>);
-    if (guard.set_lds(k_res, lds_max, configured[lh ? 2 : 0]) != SET_OK ||
-        guard.set_lds(k_gen, lds_max, configured[lh ? 3 : 1]) != SET_OK)
+    const int fam = bm ? 4 : (lh ? 2 : 0);
+    if (guard.set_lds(k_res, lds_max, configured[fam]) != SET_OK ||
+        guard.set_lds(k_gen, lds_max, configured[fam + 1]) != SET_OK)
         return SET_ERR_UNSUPPORTED;
     const bool res = B <= 4 && d->T <= PDEC_TREG;
     // resident workgroups the device admits, asked with the LDS size of THIS batch (re-asked when a larger one comes along)
-    int& cap = g_pdec_capacity[dev][(res ? 1 : 0) + (lh ? 2 : 0)];
-    int& cap_lds = g_pdec_capacity_lds[dev][(res ? 1 : 0) + (lh ? 2 : 0)];
+    int& cap = g_pdec_capacity[dev][(res ? 1 : 0) + fam];
+    int& cap_lds = g_pdec_capacity_lds[dev][(res ? 1 : 0) + fam];
     if (cap == 0 || lds > cap_lds) {
         int per_cu = 0, cus = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, res ? k_res : k_gen, PDEC_THREADS,
@@ -546,11 +802,14 @@ int dcnet_persistent_greedy(const SetDcnetWeights* w, const SetDcnetDims* d, con
     }
     if (G > cap) return SET_ERR_UNSUPPORTED;
     const double wbytes = 4.0 * ((double)d->V * D + 4.0 * 4 * D * D + (double)d->A * D);
-    ProfScope ps("persistent_decode", s, 2.0 * B * wbytes / 4.0 * max_len, wbytes * max_len);
+    ProfScope ps(bm ? "persistent_beam" : "persistent_decode", s, 2.0 * B * wbytes / 4.0 * max_len, wbytes * max_len);
     SET_TRY(guard.serialise(s));
-    SET_HIP_TRY(hipMemsetAsync(xbuf, 0, dcnet_persistent_xbytes(B, D, d->A), s));    // no word of an earlier decode may carry a tag of this one
+    // no word of an earlier decode may carry a tag of this one (the candidate words at the end are the beam mode's alone)
+    SET_HIP_TRY(hipMemsetAsync(xbuf, 0, bm ? dcnet_persistent_xbytes(B, D, d->A) : (size_t)((char*)P.x_fcb - (char*)xbuf), s));
     SET_TRY(pd_stamps_begin(&P.stamps, &P.stamp_wg, s));
-    if (lh && res) hipLaunchKernelGGL((dcnet_persistent_k<true, true>), dim3(G), dim3(PDEC_THREADS), lds, s, P);
+    if (bm && res) hipLaunchKernelGGL((dcnet_persistent_k<true, false, true>), dim3(G), dim3(PDEC_THREADS), lds, s, P);
+    else if (bm) hipLaunchKernelGGL((dcnet_persistent_k<false, false, true>), dim3(G), dim3(PDEC_THREADS), lds, s, P);
+    else if (lh && res) hipLaunchKernelGGL((dcnet_persistent_k<true, true>), dim3(G), dim3(PDEC_THREADS), lds, s, P);
     else if (lh) hipLaunchKernelGGL((dcnet_persistent_k<false, true>), dim3(G), dim3(PDEC_THREADS), lds, s, P);
     else if (res) hipLaunchKernelGGL(dcnet_persistent_k<true>, dim3(G), dim3(PDEC_THREADS), lds, s, P);
     else hipLaunchKernelGGL(dcnet_persistent_k<false>, dim3(G), dim3(PDEC_THREADS), lds, s, P);

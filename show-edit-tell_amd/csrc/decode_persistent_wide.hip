@@ -40,8 +40,7 @@ namespace set {
 namespace {
 
 constexpr int PW_U = 16;           // 16-byte requests a lane keeps in flight while it fills LDS from an exchange buffer
-constexpr int PW_BEAM_K = 4;       // beam mode: hypotheses (= rows) at most
-constexpr int PW_BEAM_W = 12;      // ... words a workgroup publishes per row: max, sum exp, 4 x (value, index), 2 pads
+// (PW_BEAM_K, PW_BEAM_W, the candidate layout of the beam mode: decode_persistent.h — DCNet's kernel publishes the same words)
 constexpr int PW_TS = PDEC_TMAX + 1;   // row strides of the hoisted-product tables in LDS: odd (region table: RREG + 1), so that the
                                        // (thread, index) gathers of 256 threads spread over all banks
 // visual scores per row in LDS and in the exchange: 64, or the region capacity above that

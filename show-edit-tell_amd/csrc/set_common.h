@@ -276,7 +276,8 @@ bool dcnet_persistent_ok(const SetDcnetDims* d, int max_len);
 int dcnet_persistent_greedy(const SetDcnetWeights* w, const SetDcnetDims* d, const float* pre1, const float* att1_c,
                             const float* mask, const float* pc, void* xbuf, long long* it, int* unfinished, int* alive,
                             long long start_idx, long long end_idx, int max_len, long long* seq, float* seq_logp,
-                            hipStream_t s, const PDecTeacher* teach = nullptr);
+                            hipStream_t s, const PDecTeacher* teach = nullptr, const PDecBeam* beam = nullptr);
+bool dcnet_persistent_beam_ok(const SetDcnetDims* d, int max_picks);           // one image's beam search as one launch (k <= 4)
 
 size_t editnet_persistent_xbytes(int B, int D, int A, int R = 0);   // R > 64: room for R visual scores per row
 bool editnet_persistent_ok(const SetEditNetDims* d, int max_len);

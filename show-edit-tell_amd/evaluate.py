@@ -213,6 +213,48 @@ def beam_search_ensemble_batched(decoder, dae, image_features, previous_caption,
 # eval_full.py:96-109) -> (token list incl. <start>/<end>, score of the chosen hypothesis; NaN if the
 # 50-step limit was hit).  NI = 1 case of the batched on-device search above.
 # ------------------------------------------------------------------------------------------------
+class _PersistentBeamOut:
+    """Outputs of one persistent beam launch (set_editnet_beam_persistent / set_dcnet_beam_persistent), all in ONE device
+    buffer: [hist_word (picks, 4) i64 | best_word i64 | hist_parent (picks, 4) i32 | result (4) i32 | best_score f32], read
+    back with a single copy (the search's only host synchronisation)."""
+
+    def __init__(self, picks, dev):
+        self.picks = picks
+        self.n_hw, self.n_hp = picks * 4 * 8, picks * 4 * 4
+        self.buf = torch.empty(self.n_hw + 8 + self.n_hp + 16 + 8, dtype=torch.uint8, device=dev)
+        base = self.buf.data_ptr()
+        self.o_hp, self.o_res = self.n_hw + 8, self.n_hw + 8 + self.n_hp
+        self.o_bs = self.o_res + 16
+        self.hist_word, self.best_word, self.hist_parent = base, base + self.n_hw, base + self.o_hp
+        self.result, self.best_score = base + self.o_res, base + self.o_bs
+
+    def answer(self, word_map, name):
+        """(tokens, score): the best completed hypothesis, or the step-limit rule of the reference (editnet.py:702-704,711,
+        dcnet.py:503-505,512: seqs[0][:18], score NaN)."""
+        from . import _lib
+        picks, n_hw, n_hp, o_hp, o_res, o_bs = self.picks, self.n_hw, self.n_hp, self.o_hp, self.o_res, self.o_bs
+        host = self.buf.cpu().numpy()
+        hw = host[:n_hw].view("int64").reshape(picks, 4)
+        hp = host[o_hp:o_hp + n_hp].view("int32").reshape(picks, 4)
+        best_t, best_parent, k_left, made = (int(v) for v in host[o_res:o_res + 16].view("int32"))
+        best_word_h = int(host[n_hw:n_hw + 8].view("int64")[0])
+        best_score_h = float(host[o_bs:o_bs + 4].view("float32")[0])
+        if made < 0:
+            raise _lib.SetError("%s: the persistent launch timed out (result poisoned)" % name)
+
+        def trace(t_last, slot):
+            out = []
+            for t in range(t_last, -1, -1):
+                out.append(int(hw[t, slot]))
+                slot = int(hp[t, slot])
+            return out[::-1]
+
+        start = int(word_map['<start>'])
+        if k_left > 0:                                                 # ran into the step limit
+            return ([start] + trace(made - 1, 0))[:18], float("nan")
+        return [start] + trace(best_t - 1, best_parent) + [best_word_h], best_score_h
+
+
 @torch.no_grad()
 def _beam_search_editnet_persistent(decoder, image_features, previous_caption, prev_caplen, word_map, beam_size, max_steps=50,
                                     image_mean=None):
@@ -240,39 +282,15 @@ def _beam_search_editnet_persistent(decoder, image_features, previous_caption, p
     if not w.tok_table:
         return None
     ws = decoder._workspace(dims)
-    # every output of the launch in ONE device buffer: [hist_word (picks, 4) i64 | best_word i64 | hist_parent (picks, 4) i32 |
-    # result (4) i32 | best_score f32], read back with a single copy (the search's only host synchronisation)
-    n_hw, n_hp = picks * 4 * 8, picks * 4 * 4
-    buf = torch.empty(n_hw + 8 + n_hp + 16 + 8, dtype=torch.uint8, device=dev)
-    o_bw, o_hp, o_res, o_bs = n_hw, n_hw + 8, n_hw + 8 + n_hp, n_hw + 8 + n_hp + 16
-    base = buf.data_ptr()
+    out = _PersistentBeamOut(picks, dev)
     rc = lib.set_editnet_beam_persistent(C.byref(w), C.byref(dims), ptr(X), None if mean is None else ptr(mean), ptr(prev), ptr(plen),
                                          int(word_map['<start>']),
-                                         int(word_map['<end>']), picks, base + o_hp, base, base + o_bs, base + o_bw, base + o_res,
-                                         ptr(ws), ws.numel(), stream_of(dev))
+                                         int(word_map['<end>']), picks, out.hist_parent, out.hist_word, out.best_score, out.best_word,
+                                         out.result, ptr(ws), ws.numel(), stream_of(dev))
     if rc == 2:                                                    # SET_ERR_UNSUPPORTED: no output was touched (set_hip.h: answered
         return None                                                # before the prologue except on a device too small for the grid)
     check(rc, "set_editnet_beam_persistent")
-    host = buf.cpu().numpy()
-    hw = host[:n_hw].view("int64").reshape(picks, 4)
-    hp = host[o_hp:o_hp + n_hp].view("int32").reshape(picks, 4)
-    best_t, best_parent, k_left, made = (int(v) for v in host[o_res:o_res + 16].view("int32"))
-    best_word_h = int(host[o_bw:o_bw + 8].view("int64")[0])
-    best_score_h = float(host[o_bs:o_bs + 4].view("float32")[0])
-    if made < 0:
-        raise _lib.SetError("set_editnet_beam_persistent: the persistent launch timed out (result poisoned)")
-
-    def trace(t_last, slot):
-        out = []
-        for t in range(t_last, -1, -1):
-            out.append(int(hw[t, slot]))
-            slot = int(hp[t, slot])
-        return out[::-1]
-
-    start = int(word_map['<start>'])
-    if k_left > 0:                                                 # ran into the step limit (editnet.py:702-704,711)
-        return ([start] + trace(made - 1, 0))[:18], float("nan")
-    return [start] + trace(best_t - 1, best_parent) + [best_word_h], best_score_h
+    return out.answer(word_map, "set_editnet_beam_persistent")
 
 
 def beam_search_editnet(decoder, image_features, previous_caption, prev_caplen, word_map, beam_size=3):
@@ -287,7 +305,46 @@ def beam_search_editnet(decoder, image_features, previous_caption, prev_caplen, 
     return seqs[0], scores[0]
 
 
+@torch.no_grad()
+def _beam_search_dcnet_persistent(dae, previous_caption, prev_caplen, word_map, beam_size, max_steps=50):
+    """ONE previous caption, k <= 4: prologue + one persistent launch for the whole search (include/set_hip.h
+    set_dcnet_beam_persistent; the rows of the launch are the k hypotheses).  Returns None when the library answers
+    SET_ERR_UNSUPPORTED (no token table yet, k > 4, dimensions outside the persistent launch, SET_DEC_PERSISTENT=0): the
+    caller takes the per-step search.  Output buffer, read-back, trace-back and step-limit rule: _PersistentBeamOut, shared
+    with _beam_search_editnet_persistent."""
+    import ctypes as C
+    from . import _lib
+    from ._lib import check, ptr, stream_of
+    k = int(beam_size)
+    if k < 1 or k > 4 or previous_caption.shape[0] != 1:
+        return None
+    dae.eval()
+    lib = _lib.load()
+    dev = previous_caption.device
+    prev = previous_caption.long().expand(k, -1).contiguous()
+    plen = prev_caplen.reshape(-1).long().expand(k).contiguous()
+    picks = max_steps + 1
+    dims = dae._dims(k, prev.shape[1], picks)
+    w = dae._weights(dims)
+    if not w.tok_table:
+        return None
+    ws = dae._workspace(dims)
+    out = _PersistentBeamOut(picks, dev)
+    rc = lib.set_dcnet_beam_persistent(C.byref(w), C.byref(dims), ptr(prev), ptr(plen), int(word_map['<start>']),
+                                       int(word_map['<end>']), picks, out.hist_parent, out.hist_word, out.best_score, out.best_word,
+                                       out.result, ptr(ws), ws.numel(), stream_of(dev))
+    if rc == 2:                                                    # SET_ERR_UNSUPPORTED: no output was touched
+        return None
+    check(rc, "set_dcnet_beam_persistent")
+    return out.answer(word_map, "set_dcnet_beam_persistent")
+
+
 def beam_search_dcnet(dae, previous_caption, prev_caplen, word_map, beam_size=3):
+    """The reference's own calling convention, ONE previous caption per call (dcnet.py:413-423).  k <= 4 with the token table
+    active: one persistent launch (csrc/decode_persistent.hip, beam mode); otherwise the NI = 1 case of the batched search."""
+    one = _beam_search_dcnet_persistent(dae, previous_caption, prev_caplen, word_map, beam_size)
+    if one is not None:
+        return one
     seqs, scores = beam_search_dcnet_batched(dae, previous_caption, prev_caplen, word_map, beam_size, return_scores=True)
     return seqs[0], scores[0]
 
