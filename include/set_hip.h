@@ -313,12 +313,41 @@ int set_dcnet_greedy(const SetDcnetWeights* w, const SetDcnetDims* d, const int6
  * device's persistent launches — all answered BEFORE anything is touched; only a device whose LDS limit or resident-workgroup
  * capacity turns out too small is answered after the prologue has been written into `ws` (outputs untouched).
  * set_dcnet_workspace_bytes covers the launch's exchange region (for B <= 4 it holds B x 24 KB of candidate words at D = 1024).
- * The ensemble's per-image search has no such launch: it runs on set_*_step + set_beam_pick_f32.
+ * The ensemble's per-image search has a launch of its own that holds both models' state: set_ensemble_beam_persistent.
  * Parity: tests/test_hip_dcnet_beam.py against the reference's beam goldens and the batched per-step search. */
 int set_dcnet_beam_persistent(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* prev,
                               const int64_t* prevlen, int64_t start_idx, int64_t end_idx, int max_picks,
                               int32_t* hist_parent, int64_t* hist_word, float* best_score, int64_t* best_word,
                               int32_t* result, void* ws, size_t ws_bytes, void* stream);
+/* Beam search of ONE image by the EditNet + DCNet ENSEMBLE, the protocol of the reference's published scores
+ * (eval/eval xe/eval_full.py:132-202: batch = 1 image, beam k = 3; both models step on the same words, their softmax
+ * probabilities are averaged and the beam is picked from log((softmax_e + softmax_d) / 2) + running scores), as both prologues +
+ * ONE persistent launch (csrc/decode_persistent_ensemble.hip) that holds both models' state: the de->B = dd->B <= 4 rows of both
+ * workspaces are the k hypotheses — X (k, R, F), prev (k, T), prevlen (k) hold the image's inputs k times, the prologues run as in
+ * set_editnet_beam_persistent / set_dcnet_beam_persistent — and every timestep of both models ends with ONE joint pick: per-slice
+ * (max, sum exp) of both models are exchanged first, then per-slice candidates of the averaged score (flat top-k over k V, value
+ * descending, flat index ascending, parent / word split, completed hypotheses leave, k shrinks); both models' recurrent state
+ * follows the one parent map inside the launch.  Fixed features only (the image mean is the mean over all R regions).  The
+ * search stops when every hypothesis has ended or after max_picks picks (the reference's 50-step limit: max_picks = 51).
+ * Outputs (device), the layout of set_editnet_beam_persistent: hist_parent / hist_word (max_picks, 4), best_score / best_word [1],
+ * result [4] = {pick index of the best completed hypothesis (-1: none), its parent slot, hypotheses still alive, picks made}.  A
+ * time-out poisons best_score with NaN and result[2..3] = -1 (SET_ERR_FAULT at the next call).  xbuf: the launch's exchange
+ * region, 16-byte aligned, set_ensemble_beam_xbuf_bytes(de, dd) bytes (0: these dims have no such launch), zero-filled by the
+ * call; the exchange regions inside ws_e / ws_d are not used and no workspace size changed.
+ * SET_ERR_ARG: null pointers, max_picks < 1, start_idx outside the vocabulary — answered before any HIP call.
+ * SET_ERR_UNSUPPORTED (take set_*_step + set_beam_pick_f32): de->B != dd->B, T, D, A or the VOCABULARY SIZE differ between the
+ * models, an adaptive decoder, and whatever either sibling refuses (no token table, k > 4, dimensions outside its launch,
+ * SET_DEC_PERSISTENT=0, k V >= 2^31, another process owns the device's persistent launches) — all answered BEFORE anything is
+ * touched; only a device whose LDS limit or resident-workgroup capacity turns out too small is answered after the prologues have
+ * been written into ws_e / ws_d (outputs untouched).
+ * Parity: tests/test_hip_ensemble_beam.py against the reference's beam goldens and the batched per-step search. */
+int set_ensemble_beam_persistent(const SetEditNetWeights* we, const SetEditNetDims* de, const SetDcnetWeights* wd,
+                                 const SetDcnetDims* dd, const float* X, const int64_t* prev, const int64_t* prevlen,
+                                 int64_t start_idx, int64_t end_idx, int max_picks, int32_t* hist_parent,
+                                 int64_t* hist_word, float* best_score, int64_t* best_word, int32_t* result,
+                                 void* ws_e, size_t ws_e_bytes, void* ws_d, size_t ws_d_bytes, void* xbuf,
+                                 size_t xbuf_bytes, void* stream);
+size_t set_ensemble_beam_xbuf_bytes(const SetEditNetDims* de, const SetDcnetDims* dd);
 /* multinomial twin of set_dcnet_greedy (dcnet_rl.py:320-327); see set_editnet_sample */
 int set_dcnet_sample(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* prev,
                      const int64_t* prevlen, int64_t start_idx, int64_t end_idx, int max_len, uint64_t seed,

@@ -235,6 +235,9 @@ PROTOTYPES = {
     "set_dcnet_greedy": (_I, [C.POINTER(DcnetWeights), C.POINTER(DcnetDims), _P, _P, _L, _L, _I, _P, _P, _P, _Z, _P]),
     "set_dcnet_beam_persistent": (_I, [C.POINTER(DcnetWeights), C.POINTER(DcnetDims), _P, _P, _L, _L, _I, _P, _P, _P, _P, _P, _P, _Z,
                                        _P]),
+    "set_ensemble_beam_persistent": (_I, [C.POINTER(EditNetWeights), C.POINTER(EditNetDims), C.POINTER(DcnetWeights), C.POINTER(DcnetDims),
+                                          _P, _P, _P, _L, _L, _I, _P, _P, _P, _P, _P, _P, _Z, _P, _Z, _P, _Z, _P]),
+    "set_ensemble_beam_xbuf_bytes": (_Z, [C.POINTER(EditNetDims), C.POINTER(DcnetDims)]),
     "set_dcnet_sample": (_I, [C.POINTER(DcnetWeights), C.POINTER(DcnetDims), _P, _P, _L, _L, _I, _U, _U, _P, _P, _P, _Z,
                               _P]),
     "set_dcnet_xe_forward": (_I, [C.POINTER(DcnetWeights), C.POINTER(DcnetDims), _P, _L, C.POINTER(C.c_int), _P, _P,

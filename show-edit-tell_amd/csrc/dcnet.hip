@@ -553,3 +553,27 @@ void* set_dcnet_ws_tensor(const SetDcnetDims* d, void* ws, const char* name) {
 }
 
 }  // extern "C"
+
+namespace set {
+
+// DCNet's half of set_ensemble_beam_persistent (decode_persistent_ensemble.hip).  check: the answers of
+// set_dcnet_beam_persistent before anything is touched
+int dcnet_ensemble_check(const SetDcnetWeights* w, const SetDcnetDims* d, int max_picks, void* ws, size_t ws_bytes) {
+    SET_TRY(check_dims(d));
+    if (!table_active(w, d)) return SET_ERR_UNSUPPORTED;
+    if (!dcnet_persistent_beam_ok(d, max_picks)) return SET_ERR_UNSUPPORTED;
+    DcnetWs W;
+    return prep(d, ws, ws_bytes, &W);
+}
+
+// the prologue of set_dcnet_beam_persistent (k identical rows; includes Pc: dcnet_persistent_ok holds) and where it left its
+// products
+int dcnet_ensemble_prologue(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* prev, const int64_t* prevlen,
+                            void* ws, hipStream_t st, PEnsDcnetPro* out) {
+    DcnetWs W = carve(d, ws);
+    SET_TRY(begin_impl(w, d, prev, prevlen, W, st));
+    *out = PEnsDcnetPro{W.pre1, W.att1_c, W.mask, W.pd_pc};
+    return SET_OK;
+}
+
+}  // namespace set

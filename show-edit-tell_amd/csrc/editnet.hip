@@ -733,3 +733,27 @@ void* set_editnet_ws_tensor(const SetEditNetDims* d, void* ws, const char* name)
 }
 
 }  // extern "C"
+
+namespace set {
+
+// EditNet's half of set_ensemble_beam_persistent (decode_persistent_ensemble.hip).  check: the answers of
+// set_editnet_beam_persistent before anything is touched (fixed features only: the reference's ensemble has no adaptive model)
+int editnet_ensemble_check(const SetEditNetWeights* w, const SetEditNetDims* d, void* ws, size_t ws_bytes) {
+    SET_TRY(check_dims(d));
+    if (d->adaptive) return SET_ERR_UNSUPPORTED;
+    if (!(w->tok_table && (d->D % 64 == 0) && env_int("SET_NO_FUSED", 0) == 0)) return SET_ERR_UNSUPPORTED;
+    if (!editnet_persistent_beam_ok(d)) return SET_ERR_UNSUPPORTED;
+    EditNetWs W;
+    return prep(d, ws, ws_bytes, &W);
+}
+
+// the prologue of set_editnet_beam_persistent (k identical rows, Pv asked for explicitly) and where it left its products
+int editnet_ensemble_prologue(const SetEditNetWeights* w, const SetEditNetDims* d, const float* X, const int64_t* prev,
+                              const int64_t* prevlen, void* ws, hipStream_t st, PEnsEditPro* out) {
+    EditNetWs W = carve(d, ws);
+    SET_TRY(begin_impl(w, d, X, nullptr, prev, prevlen, W, st, true));
+    *out = PEnsEditPro{W.pre1, W.att1, W.att1_c, W.mask, W.cap_proj, W.mem_proj, W.Mem, W.pd_pv};
+    return SET_OK;
+}
+
+}  // namespace set

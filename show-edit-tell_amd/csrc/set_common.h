@@ -290,6 +290,18 @@ int editnet_persistent_greedy(const SetEditNetWeights* w, const SetEditNetDims* 
                               long long end_idx, int max_len, long long* seq, float* seq_logp, hipStream_t s,
                               const PDecTeacher* teach = nullptr, const PDecBeam* beam = nullptr);
 
+// decode_persistent_ensemble.hip: the EditNet + DCNet ensemble's beam search of one image as one launch.  The model halves of
+// its host side live with their models (editnet.hip / dcnet.hip): `check` answers what set_*_beam_persistent answers before
+// anything is touched, `prologue` runs the model's prologue for the k rows of `ws` and hands out its products
+struct PEnsEditPro { const float *pre1, *att1, *att1_c, *mask, *capP, *memQ, *Mem, *pv; };
+struct PEnsDcnetPro { const float *pre1, *att1_c, *mask, *pc; };
+int editnet_ensemble_check(const SetEditNetWeights* w, const SetEditNetDims* d, void* ws, size_t ws_bytes);
+int editnet_ensemble_prologue(const SetEditNetWeights* w, const SetEditNetDims* d, const float* X, const int64_t* prev,
+                              const int64_t* prevlen, void* ws, hipStream_t st, PEnsEditPro* out);
+int dcnet_ensemble_check(const SetDcnetWeights* w, const SetDcnetDims* d, int max_picks, void* ws, size_t ws_bytes);
+int dcnet_ensemble_prologue(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* prev, const int64_t* prevlen,
+                            void* ws, hipStream_t st, PEnsDcnetPro* out);
+
 // a per-row gathered addend: value(m, n) = tab[ids[m*id_stride]*ld + col0 + n]   (tab == NULL: none)
 struct RowGather {
     const float* tab = nullptr;

@@ -349,7 +349,65 @@ def beam_search_dcnet(dae, previous_caption, prev_caplen, word_map, beam_size=3)
     return seqs[0], scores[0]
 
 
+_ens_xbuf = {}                 # exchange regions of the ensemble's persistent launch, one per (bytes, device, stream)
+
+
+@torch.no_grad()
+def _beam_search_ensemble_persistent(decoder, dae, image_features, previous_caption, prev_caplen, word_map, beam_size, max_steps=50):
+    """ONE image, k <= 4, the EditNet + DCNet ensemble (eval_full.py:132-202): both prologues + one persistent launch that holds
+    both models' state for the whole search (include/set_hip.h set_ensemble_beam_persistent; the rows of the launch are the k
+    hypotheses).  Returns None when the library answers SET_ERR_UNSUPPORTED (a token table missing, k > 4, dimensions outside
+    the launch, SET_DEC_PERSISTENT=0) and on the host-side checks (more than one image, vocabularies of different size, an
+    adaptive decoder: the reference's ensemble uses fixed features): the caller takes the per-step search.  The modules' cached
+    workspaces serve the prologues; the launch's exchange region is a buffer of its own.  Output buffer, read-back, trace-back
+    and step-limit rule: _PersistentBeamOut, shared with the single-model searches."""
+    import ctypes as C
+    from . import _lib
+    from ._lib import check, ptr, stream_of
+    k = int(beam_size)
+    if (k < 1 or k > 4 or image_features.shape[0] != 1 or previous_caption.shape[0] != 1 or getattr(decoder, "_adaptive", 0)
+            or decoder.vocab_size != dae.vocab_size):
+        return None
+    decoder.eval()
+    dae.eval()
+    lib = _lib.load()
+    dev = image_features.device
+    X = image_features.float().expand(k, -1, -1).contiguous()
+    prev = previous_caption.long().expand(k, -1).contiguous()
+    plen = prev_caplen.reshape(-1).long().expand(k).contiguous()
+    picks = max_steps + 1
+    de = decoder._dims(k, prev.shape[1], X.shape[1], picks)
+    dd = dae._dims(k, prev.shape[1], picks)
+    we, wd = decoder._weights(de), dae._weights(dd)
+    if not we.tok_table or not wd.tok_table:
+        return None
+    nx = lib.set_ensemble_beam_xbuf_bytes(C.byref(de), C.byref(dd))
+    if nx == 0:
+        return None
+    ws_e, ws_d = decoder._workspace(de), dae._workspace(dd)
+    key = (nx, str(dev), torch.cuda.current_stream(dev).cuda_stream)
+    xbuf = _ens_xbuf.get(key)
+    if xbuf is None:
+        if len(_ens_xbuf) >= 8:
+            _ens_xbuf.clear()
+        xbuf = _ens_xbuf[key] = torch.empty(nx, dtype=torch.uint8, device=dev)
+    out = _PersistentBeamOut(picks, dev)
+    rc = lib.set_ensemble_beam_persistent(C.byref(we), C.byref(de), C.byref(wd), C.byref(dd), ptr(X), ptr(prev), ptr(plen),
+                                          int(word_map['<start>']), int(word_map['<end>']), picks, out.hist_parent, out.hist_word,
+                                          out.best_score, out.best_word, out.result, ptr(ws_e), ws_e.numel(), ptr(ws_d), ws_d.numel(),
+                                          ptr(xbuf), xbuf.numel(), stream_of(dev))
+    if rc == 2:                                                    # SET_ERR_UNSUPPORTED: no output was touched
+        return None
+    check(rc, "set_ensemble_beam_persistent")
+    return out.answer(word_map, "set_ensemble_beam_persistent")
+
+
 def beam_search_ensemble(decoder, dae, image_features, previous_caption, prev_caplen, word_map, beam_size=3):
+    """The reference's published protocol, ONE image per call (eval_full.py:88-237).  k <= 4 with both token tables active: one
+    persistent launch (csrc/decode_persistent_ensemble.hip); otherwise the NI = 1 case of the batched search."""
+    one = _beam_search_ensemble_persistent(decoder, dae, image_features, previous_caption, prev_caplen, word_map, beam_size)
+    if one is not None:
+        return one
     seqs, scores = beam_search_ensemble_batched(decoder, dae, image_features, previous_caption, prev_caplen, word_map,
                                                 beam_size, return_scores=True)
     return seqs[0], scores[0]

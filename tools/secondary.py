@@ -261,7 +261,7 @@ def beam(dev, images=128, k=3):
             "ensemble_one_image_per_call_mean_len": round(float(np.mean([len(o[0]) for o in out_ens])), 2),
             "ensemble_ending_captions_mean_len": round(float(np.mean([len(o[0]) for o in out_ens_short])), 2),
             "dcnet_one_image_per_call_ms": round(1e3 * t_dc, 3), "dcnet_one_image_per_call_ending_captions_ms": round(1e3 * t_dc_short, 3),
-            "one_image_per_call_paths": "editnet: persistent launch (k <= 4); ensemble, dcnet: per-step kernels, NI = 1 of the batched search",
+            "one_image_per_call_paths": "editnet, dcnet, ensemble: prologue(s) + one persistent launch (k <= 4); otherwise NI = 1 of the batched search",
             "images_per_sec_editnet": round(images / t_e, 1), "mean_caption_len": round(float(np.mean([len(s) for s in seqs])), 2)}
 
 
