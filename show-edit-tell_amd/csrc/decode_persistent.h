@@ -1,5 +1,6 @@
-// Shared pieces of the persistent small-batch decode kernels (decode_persistent.hip: DCNet, decode_persistent_wide.hip:
-// EditNet): constants, the MFMA GEMV tile helpers and the diagnostic time stamps.
+// Shared pieces of the three persistent small-batch decode kernels (decode_persistent.hip: DCNet, decode_persistent_wide.hip:
+// EditNet, decode_persistent_ensemble.hip: both models' beam search): constants, the MFMA GEMV tile helpers, EditNet's argument
+// block with its host-side fill and exchange layout, and the diagnostic time stamps.  (The beam modes' pick: beam_persistent.h.)
 #pragma once
 #include <cstdio>
 #include "set_common.h"
@@ -17,7 +18,7 @@ constexpr int PDEC_TMAX = 32;      // previous-caption positions held in registe
 constexpr int PDEC_KB = 16;        // 16-wide k-blocks per wave and gate tile: D = 1024 -> K quarter 256
 constexpr int PDEC_THREADS = 256;
 constexpr int PDEC_FC_TILES = 3;   // 16-row fc tiles per workgroup: up to 48 vocabulary rows
-// beam mode of both kernels (one image, rows = hypotheses): what a workgroup publishes per row of its vocabulary slice
+// beam mode of the three kernels (one image, rows = hypotheses): what a workgroup publishes per row of its vocabulary slice
 constexpr int PW_BEAM_K = 4;       // hypotheses (= rows) at most
 constexpr int PW_BEAM_W = 12;      // words per row and slice: max, sum exp, 4 x (value, index), 2 pads
 
@@ -202,6 +203,12 @@ struct PDecEditArgs {
 int editnet_persistent_wide_launch(PDecEditArgs& P, void* xbuf, PersistentGuard& guard, hipStream_t s, bool* unsupported, bool beam = false,
                                    bool wide_regions = false);
 size_t editnet_persistent_wide_xbytes(int B, int D, int A, int R = 0);
+// shared with the ensemble launch (decode_persistent_ensemble.hip), whose argument block embeds a PDecEditArgs: the weight /
+// dimension fields of P from (w, d, max_len); [status line | EditNet's seven exchange regions] laid out from x (returns the
+// end) and their size.  (Hidden: the library's dynamic symbol table stays as it was.)
+__attribute__((visibility("hidden"))) void pdec_edit_fill(PDecEditArgs& P, const SetEditNetWeights* w, const SetEditNetDims* d, int max_len);
+__attribute__((visibility("hidden"))) char* pdec_edit_layout(PDecEditArgs& P, char* x);
+__attribute__((visibility("hidden"))) size_t pdec_edit_xbytes(int B, int D, int A, int R);
 bool editnet_persistent_wide_ok(int B, int D, int A, int T, int R, int V, bool wide_regions);   // (default: set_common.h)
 
 // host side of the stamps: buffer for a launch (or NULL) and the report after it

@@ -29,7 +29,10 @@
 // three exchanges.
 // Same residency rule, fault word and event chain as the persistent encoder (grid_barrier.h PersistentGuard).  A poll that
 // times out poisons seq_logp with NaN; the host raises SET_ERR_FAULT at its next call.
-#include "decode_persistent.h"
+// Shared with the other two persistent decode kernels: the beam mode's pick (beam_persistent.h) and, on the host, the residency
+// check (PersistentGuard::fits).  Deliberately NOT shared: the phase code of the timestep — where a tile's loads sit between
+// the MFMAs is the schedule, and a function boundary there changes the instructions of a kernel at the register ceiling.
+#include "beam_persistent.h"
 
 namespace set {
 
@@ -83,11 +86,13 @@ struct PDecDcnetArgs {
 // longest caption ends, so no buffer holds a row's h2 at its own last step: the owner of h2[b, u] stores it when t + 1 ==
 // dlen[b].  A template parameter, not a runtime test: the variants without it compile to the same instructions as before.
 // BEAM: free-running only; the B <= PW_BEAM_K rows are the hypotheses of ONE image and the loop is the reference's beam search
-// (dcnet.py:447-514) instead of the greedy loop: the arg-max epilogue (X4 / S6) becomes the pick of
-// editnet_persistent_wide_k<BEAM> (decode_persistent_wide.hip) — the scheme is copied, not shared: that kernel's pick is
-// written into its loop body and moving it would change its instructions.  Per pick every workgroup publishes, per row, (max,
-// sum exp, its PW_BEAM_K best (score, word) pairs) of its vocabulary slice, stages all slices and runs the same merge (value
-// descending, flat index ascending among equals): the same (parent, word) per slot everywhere, no broadcast round.
+// (dcnet.py:447-514) instead of the greedy loop: the arg-max epilogue (X4 / S6) becomes the pick that
+// editnet_persistent_wide_k<BEAM> (decode_persistent_wide.hip) and the ensemble kernel run too — its slice top-k, candidate words,
+// row merge and bookkeeping are the functions of beam_persistent.h, shared by the three kernels (they run after the timestep's
+// last MFMA, no weight tile is in flight there); the phase code around them stays this kernel's own.  Per pick every workgroup
+// publishes, per row, (max, sum exp, its PW_BEAM_K best (score, word) pairs) of its vocabulary slice, stages all slices and runs
+// the same merge (value descending, flat index ascending among equals): the same (parent, word) per slot everywhere, no
+// broadcast round.
 // Recurrent state follows the parent map inside the launch: c1 / c2 of the owned units through a small LDS table, the
 // h-dependent products contracted ahead of the pick (S1') are read through the parent slot — language_lstm.W_hh h2 therefore
 // goes to LDS instead of staying in the accumulator that S2 continues.  h1 / h2 themselves are recomputed after every pick
@@ -398,9 +403,9 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) dcnet_persistent_k(const PDec
             continue;
         }
         if constexpr (BEAM) {
-            // ================= beam mode (dcnet.py:447-514; the bookkeeping of csrc/beam.hip beam_pick_k for ONE image, the scheme
-            // of decode_persistent_wide.hip): X4 carries, per row and vocabulary slice, (max, sum exp) and the slice's B best
-            // (score, word) pairs — a global top-B over B x V candidates takes at most B from one slice
+            // ================= beam mode (dcnet.py:447-514; the pick of beam_persistent.h): X4 carries, per row and vocabulary
+            // slice, (max, sum exp) and the slice's B best (score, word) pairs — a global top-B over B x V candidates takes at
+            // most B from one slice
             ++tag;
             if (kq < B) {
                 const int b = kq;
@@ -411,36 +416,13 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) dcnet_persistent_k(const PDec
                     const int o = j * 256 + b * 16 + rr;
                     x = (((sRed[o] + sRed[3 * 256 + o]) + sRed[6 * 256 + o]) + sRed[9 * 256 + o]) + fcb_lane;
                 }
-                float cvv[PW_BEAM_K];
-                int cii[PW_BEAM_K];
-                float xx = x;
-#pragma unroll
-                for (int q = 0; q < PW_BEAM_K; ++q) {
-                    float bv = -INFINITY;
-                    int bix = 0x7fffffff;
-                    if (q < B) {
-                        if (xx > -INFINITY) { bv = xx; bix = row; }
-                        pw_wargmax(bv, bix);
-                        if (ok && row == bix) xx = -INFINITY;
-                    }
-                    cvv[q] = bv; cii[q] = bix;
-                }
+                pb_vals cvv;
+                pb_idxs cii;
+                pb_slice_topk(x, row, ok, B, cvv, cii);
                 const float mx = cvv[0];
                 float se = (ok && mx > -INFINITY) ? expf(x - mx) : 0.f;
                 se = pw_wsum(se);
-                if (lane < PW_BEAM_W) {
-                    float v = 0.f;
-                    if (lane == 0) v = mx;
-                    else if (lane == 1) v = se;
-                    else if (lane < 2 + 2 * PW_BEAM_K) {
-                        const int q = (lane - 2) >> 1;
-                        float cv_ = cvv[0]; int ci_ = cii[0];
-#pragma unroll
-                        for (int u = 1; u < PW_BEAM_K; ++u) if (q == u) { cv_ = cvv[u]; ci_ = cii[u]; }
-                        v = (lane & 1) ? __int_as_float(ci_) : cv_;
-                    }
-                    ll_put(fbrs, (b * G + wg) * PW_BEAM_W + lane, v, tag);
-                }
+                pb_publish(fbrs, (b * G + wg) * PW_BEAM_W, lane, mx, se, cvv, cii, tag);
             }
             PD_STAMP(11);
             // S1' (see the greedy path); language_lstm.W_hh h2 goes to LDS: the next timestep adds it through the parent map
@@ -463,10 +445,9 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) dcnet_persistent_k(const PDec
             if (kq < B) {
                 const int j = kq;
                 const float scj = sScore[j];
-                float ov[PW_BEAM_K];
-                int oi[PW_BEAM_K];
-#pragma unroll
-                for (int q = 0; q < PW_BEAM_K; ++q) { ov[q] = -INFINITY; oi[q] = 0x7fffffff; }
+                pb_vals ov;
+                pb_idxs oi;
+                pb_none(ov, oi);
                 if (scj > -INFINITY) {                           // (uniform in the wave; dead slots take no part)
                     float cv[16];
                     int ci[16];
@@ -490,90 +471,14 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) dcnet_persistent_k(const PDec
                         cv[c] = have ? scj + (cv[c] - lse) : -INFINITY;       // score + log-prob, as beam_pick_k forms it
                         ci[c] = have ? j * V + ci[c] : 0x7fffffff;
                     }
-#pragma unroll
-                    for (int q = 0; q < PW_BEAM_K; ++q) {
-                        if (q < B) {
-                            float bv = -INFINITY;
-                            int bix = 0x7fffffff;
-#pragma unroll
-                            for (int c = 0; c < 16; ++c)
-                                if (cv[c] > bv || (cv[c] == bv && ci[c] < bix)) { bv = cv[c]; bix = ci[c]; }
-                            if (!(bv > -INFINITY)) bix = 0x7fffffff;
-                            pw_wargmax(bv, bix);
-#pragma unroll
-                            for (int c = 0; c < 16; ++c) if (ci[c] == bix) cv[c] = -INFINITY;
-                            ov[q] = bv; oi[q] = bix;
-                        }
-                    }
+                    pb_row_merge(cv, ci, B, ov, oi);
                 }
-                if (lane == 0) {
-#pragma unroll
-                    for (int q = 0; q < PW_BEAM_K; ++q) { sCand[(j * PW_BEAM_K + q) * 2] = ov[q]; sCand[(j * PW_BEAM_K + q) * 2 + 1] = __int_as_float(oi[q]); }
-                }
+                if (lane == 0) pb_row_store(sCand, j, ov, oi);
             }
             __syncthreads();
-            if (tid == 0) {
-                // the B best of the B x B candidates (ties: lowest flat index), then beam_pick_k's bookkeeping
-                const int k = B, kl = sKleft[0];
-                float pv_[PW_BEAM_K];
-                int pi_[PW_BEAM_K];
-                unsigned taken = 0u;
-                for (int rr_ = 0; rr_ < k; ++rr_) {
-                    float bv = -INFINITY;
-                    int bix = 0x7fffffff, bc = -1;
-                    for (int c = 0; c < k * PW_BEAM_K; ++c) {
-                        if ((taken >> c) & 1u) continue;
-                        if ((c % PW_BEAM_K) >= k) continue;
-                        const float v = sCand[c * 2];
-                        const int ix = __float_as_int(sCand[c * 2 + 1]);
-                        if (ix == 0x7fffffff) continue;
-                        if (v > bv || (v == bv && ix < bix) || bc < 0) { bv = v; bix = ix; bc = c; }
-                    }
-                    if (bc >= 0) taken |= 1u << bc;
-                    pv_[rr_] = bc >= 0 ? bv : -INFINITY;
-                    pi_[rr_] = bc >= 0 ? bix : 0x7fffffff;
-                }
-                int n_end = 0, c_arg = -1, slot = 0;
-                float c_best = -INFINITY;
-                bool live[PW_BEAM_K];
-                for (int rr_ = 0; rr_ < k; ++rr_) {
-                    const int flat = pi_[rr_];
-                    const bool okp = flat != 0x7fffffff && rr_ < kl;          // only the first k_left picks count
-                    const long long word = okp ? flat % V : 0;
-                    const bool is_end = okp && word == P.end_idx;
-                    live[rr_] = okp && !is_end;
-                    if (is_end) {
-                        ++n_end;
-                        if (pv_[rr_] > c_best) { c_best = pv_[rr_]; c_arg = rr_; }   // first maximum
-                    }
-                }
-                if (c_arg >= 0 && c_best > sBest[0]) {
-                    sBest[0] = c_best;
-                    if (wg == 0) {
-                        P.bm_best_score[0] = c_best;
-                        P.bm_best_word[0] = pi_[c_arg] % V;
-                        P.bm_result[0] = t;                              // pick index of the best completed hypothesis
-                        P.bm_result[1] = pi_[c_arg] / V;                 // its parent slot (numbering before this pick)
-                    }
-                }
-                sKleft[0] = kl - n_end;
-                for (int pass = 0; pass < 2; ++pass)
-                    for (int rr_ = 0; rr_ < k; ++rr_) {
-                        if ((pass == 0) != live[rr_]) continue;
-                        const int flat = pi_[rr_];
-                        const int parent = flat != 0x7fffffff ? flat / V : 0;
-                        const long long word = flat != 0x7fffffff ? flat % V : 0;
-                        sScore[slot] = live[rr_] ? pv_[rr_] : -INFINITY;
-                        sTok[slot] = live[rr_] ? word : 0;
-                        sPar[slot] = parent;
-                        if (wg == 0) {
-                            P.bm_hist_par[t * PW_BEAM_K + slot] = parent;
-                            P.bm_hist_word[t * PW_BEAM_K + slot] = word;
-                        }
-                        ++slot;
-                    }
-                if (wg == 0) { P.bm_result[2] = kl - n_end; P.bm_result[3] = t + 1; }
-            }
+            if (tid == 0)                                        // the pick itself and its bookkeeping (beam_persistent.h)
+                pb_pick(sCand, sScore, sTok, sPar, &sKleft[0], &sBest[0], P.bm_hist_par, P.bm_hist_word, P.bm_best_score, P.bm_best_word,
+                        P.bm_result, V, P.end_idx, t, B, wg == 0);
             __syncthreads();
             PD_STAMP(13);
             if (sKleft[0] == 0) break;                           // every hypothesis has ended (dcnet.py:507-508)
@@ -672,7 +577,7 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) dcnet_persistent_k(const PDec
     if (s_bad) {
         const float qnan = __builtin_nanf("");
         if constexpr (BEAM) {
-            if (wg == 0 && tid == 0) { P.bm_best_score[0] = qnan; P.bm_result[2] = -1; P.bm_result[3] = -1; }   // never a search result
+            if (wg == 0 && tid == 0) pb_poison(P.bm_best_score, P.bm_result);
         } else if (P.caps) {
             // teacher-forced: EVERY score this workgroup wrote (its vocabulary rows, all rows and timesteps) — each workgroup
             // poisons its own region after its own loop, so no later store of another workgroup can undo it
@@ -765,7 +670,7 @@ int dcnet_persistent_greedy(const SetDcnetWeights* w, const SetDcnetDims* d, con
     const int dev = guard.dev;
     P.spin_limit = guard.spin_limit();              // bound of one wait, ticks of the 100-MHz counter
     P.test_stall = guard.test_stall(); P.fault = guard.fault;
-    // residency: every workgroup must be on the chip at once (see encoder_persistent.hip penc_fits)
+    // residency: every workgroup must be on the chip at once (grid_barrier.h PersistentGuard::fits)
     // (function attributes are per device; a device whose LDS limit is below the request, e.g. a 64-KB part, is answered with
     // SET_ERR_UNSUPPORTED — the caller's per-step loop — never with a HIP error)
     static bool configured[6][64] = {};
@@ -783,24 +688,10 @@ int dcnet_persistent_greedy(const SetDcnetWeights* w, const SetDcnetDims* d, con
         guard.set_lds(k_gen, lds_max, configured[fam + 1]) != SET_OK)
         return SET_ERR_UNSUPPORTED;
     const bool res = B <= 4 && d->T <= PDEC_TREG;
-    // resident workgroups the device admits, asked with the LDS size of THIS batch (re-asked when a larger one comes along)
-    int& cap = g_pdec_capacity[dev][(res ? 1 : 0) + fam];
-    int& cap_lds = g_pdec_capacity_lds[dev][(res ? 1 : 0) + fam];
-    if (cap == 0 || lds > cap_lds) {
-        int per_cu = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, res ? k_res : k_gen, PDEC_THREADS,
-                                                         (size_t)lds) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) {
-            (void)hipGetLastError();
-            return SET_ERR_UNSUPPORTED;
-        }
-        cap = per_cu * cus;
-        cap_lds = lds;
-        if (cap <= 0) cap = -1;
-        const int forced = env_int("SET_PENC_TEST_CAPACITY", 0);
-        if (forced > 0) cap = forced;
-    }
-    if (G > cap) return SET_ERR_UNSUPPORTED;
+    // resident workgroups the device admits, asked with the LDS size of THIS batch
+    if (guard.fits(res ? k_res : k_gen, PDEC_THREADS, lds, G, g_pdec_capacity[dev][(res ? 1 : 0) + fam],
+                   g_pdec_capacity_lds[dev][(res ? 1 : 0) + fam]) != PersistentGuard::Fit::yes)
+        return SET_ERR_UNSUPPORTED;
     const double wbytes = 4.0 * ((double)d->V * D + 4.0 * 4 * D * D + (double)d->A * D);
     ProfScope ps(bm ? "persistent_beam" : "persistent_decode", s, 2.0 * B * wbytes / 4.0 * max_len, wbytes * max_len);
     SET_TRY(guard.serialise(s));

@@ -4,9 +4,12 @@
 // BOTH models' state: a workgroup owns four hidden units of EditNet's two cells and of DCNet's two cells, and the SAME
 // vocabulary rows [v0, v1) of both fc layers — both models' logits of a slice meet in one workgroup and no logits travel.
 // The phase code is copied from editnet_persistent_wide_k<BEAM, 36> (decode_persistent_wide.hip) and from the general BEAM
-// instantiation of dcnet_persistent_k (decode_persistent.hip), which stay untouched (copying is this project's practice: moving
-// code out of those loop bodies changes their instructions).  The rows are the k <= PW_BEAM_K hypotheses, fixed features
-// (R <= 36), both token tables active.
+// instantiation of dcnet_persistent_k (decode_persistent.hip), which stay untouched: in the phase code the order of the loads and
+// the rotating weight buffers are the schedule, and moving it out of those loop bodies changes their instructions.  What does
+// not carry a schedule is shared with those two kernels: the tail of the pick (slice top-k, candidate words, row merge,
+// bookkeeping, poison: beam_persistent.h) and, on the host, the residency check (PersistentGuard::fits), the fill of EditNet's
+// argument block and the layout of its exchange regions (pdec_edit_fill / pdec_edit_layout, decode_persistent_wide.hip).  The
+// rows are the k <= PW_BEAM_K hypotheses, fixed features (R <= 36), both token tables active.
 // Per pick:
 //   S1    both attention_lstm cells from the products contracted ahead of the previous pick, read through the parent map
 //                                                                                       -> h1 of EditNet X1e, h1 of DCNet X1d
@@ -20,14 +23,14 @@
 //   P2    per live row and word of the slice lp = logf((expf(le - lse_e) + expf(ld - lse_d)) * 0.5f) and score[j] + lp — the float
 //         operations of beam_pick_k (beam.hip) in that form: the two routes differ only by the summation order inside the
 //         normalisers — and the slice's 4 best (value, flat index j V + v) per row        -> XC (B, G, PW_BEAM_W)
-//   P3    the merge of the two single-model launches (value descending, flat index ascending, parent = index / V), completed
-//         hypotheses leave, k shrinks, the (parent, word) history is written by workgroup 0
+//   P3    the merge and the bookkeeping of the two single-model launches (beam_persistent.h: value descending, flat index
+//         ascending, parent = index / V), completed hypotheses leave, k shrinks, the (parent, word) history is written by workgroup 0
 // A single round of per-slice candidates is not enough here: the order of the candidates INSIDE a slice depends on both
 // models' global normalisers, hence P1 before P2.  Ten exchanges per pick, all flag-in-data words with vector stores
 // (grid_barrier.h); every wait is wall-clock bounded by the same spin_limit / fault machinery (a time-out poisons best_score with
 // NaN and sets result[2..3] = -1; the host answers SET_ERR_FAULT at its next call); the launch is serialised with the other
 // persistent launches by PersistentGuard.
-#include "decode_persistent.h"
+#include "beam_persistent.h"
 
 namespace set {
 
@@ -633,10 +636,9 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) ensemble_persistent_k(const P
         if (kq < B) {
             const int j = kq;
             const float scj = sScore[j];
-            float cvv[PE_K];
-            int cii[PE_K];
-#pragma unroll
-            for (int q = 0; q < PE_K; ++q) { cvv[q] = -INFINITY; cii[q] = 0x7fffffff; }
+            pb_vals cvv;
+            pb_idxs cii;
+            pb_none(cvv, cii);
             if (scj > -INFINITY) {                               // (uniform in the wave; dead slots publish empty lists)
                 float pme[4], pse[4], pmd[4], psd[4];
 #pragma unroll
@@ -659,30 +661,9 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) ensemble_persistent_k(const P
                     const float lp = logf((expf(xe - lse_e) + expf(xd - lse_d)) * 0.5f);   // as beam_pick_k forms it
                     xx = scj + lp;
                 }
-                const int flat = j * V + row0 + lane;
-#pragma unroll
-                for (int q = 0; q < PE_K; ++q) {
-                    float bv = -INFINITY;
-                    int bix = 0x7fffffff;
-                    if (q < B) {
-                        if (xx > -INFINITY) { bv = xx; bix = flat; }
-                        pw_wargmax(bv, bix);
-                        if (fc_ok && flat == bix) xx = -INFINITY;
-                    }
-                    cvv[q] = bv; cii[q] = bix;
-                }
+                pb_slice_topk(xx, j * V + row0 + lane, fc_ok, B, cvv, cii);
             }
-            if (lane < PW_BEAM_W) {
-                float v = 0.f;
-                if (lane >= 2 && lane < 2 + 2 * PE_K) {
-                    const int q = (lane - 2) >> 1;
-                    float cv_ = cvv[0]; int ci_ = cii[0];
-#pragma unroll
-                    for (int u = 1; u < PE_K; ++u) if (q == u) { cv_ = cvv[u]; ci_ = cii[u]; }
-                    v = (lane & 1) ? __int_as_float(ci_) : cv_;
-                }
-                ll_put(fbrs, (j * G + wg) * PW_BEAM_W + lane, v, tag);
-            }
+            pb_publish(fbrs, (j * G + wg) * PW_BEAM_W, lane, 0.f, 0.f, cvv, cii, tag);   // (the normalisers travelled in P1)
         }
         PE_STAMP(18);
         PE_STAGE(fbrs, sFB, B * G, PW_BEAM_W, PW_BEAM_W, tag);
@@ -692,10 +673,9 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) ensemble_persistent_k(const P
         // per lane)
         if (kq < B) {
             const int j = kq;
-            float ov[PE_K];
-            int oi[PE_K];
-#pragma unroll
-            for (int q = 0; q < PE_K; ++q) { ov[q] = -INFINITY; oi[q] = 0x7fffffff; }
+            pb_vals ov;
+            pb_idxs oi;
+            pb_none(ov, oi);
             if (sScore[j] > -INFINITY) {
                 float cv[16];
                 int ci[16];
@@ -708,90 +688,14 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) ensemble_persistent_k(const P
                         cv[4 * i + q] = ci[4 * i + q] != 0x7fffffff ? e[2 + 2 * q] : -INFINITY;
                     }
                 }
-#pragma unroll
-                for (int q = 0; q < PE_K; ++q) {
-                    if (q < B) {
-                        float bv = -INFINITY;
-                        int bix = 0x7fffffff;
-#pragma unroll
-                        for (int c = 0; c < 16; ++c)
-                            if (cv[c] > bv || (cv[c] == bv && ci[c] < bix)) { bv = cv[c]; bix = ci[c]; }
-                        if (!(bv > -INFINITY)) bix = 0x7fffffff;
-                        pw_wargmax(bv, bix);
-#pragma unroll
-                        for (int c = 0; c < 16; ++c) if (ci[c] == bix) cv[c] = -INFINITY;
-                        ov[q] = bv; oi[q] = bix;
-                    }
-                }
+                pb_row_merge(cv, ci, B, ov, oi);
             }
-            if (lane == 0) {
-#pragma unroll
-                for (int q = 0; q < PE_K; ++q) { sCand[(j * PE_K + q) * 2] = ov[q]; sCand[(j * PE_K + q) * 2 + 1] = __int_as_float(oi[q]); }
-            }
+            if (lane == 0) pb_row_store(sCand, j, ov, oi);
         }
         PE_SYNC();
-        if (tid == 0) {
-            // the B best of the B x B candidates (ties: lowest flat index), then beam_pick_k's bookkeeping
-            const int k = B, kl = sKleft;
-            float pv_[PE_K];
-            int pi_[PE_K];
-            unsigned taken = 0u;
-            for (int rr_ = 0; rr_ < k; ++rr_) {
-                float bv = -INFINITY;
-                int bix = 0x7fffffff, bc = -1;
-                for (int c = 0; c < k * PE_K; ++c) {
-                    if ((taken >> c) & 1u) continue;
-                    if ((c % PE_K) >= k) continue;
-                    const float v = sCand[c * 2];
-                    const int ix = __float_as_int(sCand[c * 2 + 1]);
-                    if (ix == 0x7fffffff) continue;
-                    if (v > bv || (v == bv && ix < bix) || bc < 0) { bv = v; bix = ix; bc = c; }
-                }
-                if (bc >= 0) taken |= 1u << bc;
-                pv_[rr_] = bc >= 0 ? bv : -INFINITY;
-                pi_[rr_] = bc >= 0 ? bix : 0x7fffffff;
-            }
-            int n_end = 0, c_arg = -1, slot = 0;
-            float c_best = -INFINITY;
-            bool live[PE_K];
-            for (int rr_ = 0; rr_ < k; ++rr_) {
-                const int flat = pi_[rr_];
-                const bool okp = flat != 0x7fffffff && rr_ < kl;          // only the first k_left picks count
-                const long long word = okp ? flat % V : 0;
-                const bool is_end = okp && word == P.e.end_idx;
-                live[rr_] = okp && !is_end;
-                if (is_end) {
-                    ++n_end;
-                    if (pv_[rr_] > c_best) { c_best = pv_[rr_]; c_arg = rr_; }   // first maximum
-                }
-            }
-            if (c_arg >= 0 && c_best > sBest) {
-                sBest = c_best;
-                if (wg == 0) {
-                    P.e.bm_best_score[0] = c_best;
-                    P.e.bm_best_word[0] = pi_[c_arg] % V;
-                    P.e.bm_result[0] = t;                            // pick index of the best completed hypothesis
-                    P.e.bm_result[1] = pi_[c_arg] / V;               // its parent slot (numbering before this pick)
-                }
-            }
-            sKleft = kl - n_end;
-            for (int pass = 0; pass < 2; ++pass)
-                for (int rr_ = 0; rr_ < k; ++rr_) {
-                    if ((pass == 0) != live[rr_]) continue;
-                    const int flat = pi_[rr_];
-                    const int parent = flat != 0x7fffffff ? flat / V : 0;
-                    const long long word = flat != 0x7fffffff ? flat % V : 0;
-                    sScore[slot] = live[rr_] ? pv_[rr_] : -INFINITY;
-                    sTok[slot] = live[rr_] ? word : 0;
-                    sPar[slot] = parent;
-                    if (wg == 0) {
-                        P.e.bm_hist_par[t * PW_BEAM_K + slot] = parent;
-                        P.e.bm_hist_word[t * PW_BEAM_K + slot] = word;
-                    }
-                    ++slot;
-                }
-            if (wg == 0) { P.e.bm_result[2] = sKleft; P.e.bm_result[3] = t + 1; }
-        }
+        if (tid == 0)                                            // the pick itself and its bookkeeping (beam_persistent.h)
+            pb_pick(sCand, sScore, sTok, sPar, &sKleft, &sBest, P.e.bm_hist_par, P.e.bm_hist_word, P.e.bm_best_score, P.e.bm_best_word,
+                    P.e.bm_result, V, P.e.end_idx, t, B, wg == 0);
         PE_SYNC();
         PE_STAMP(20);
         if (sKleft == 0) break;                                  // every hypothesis has ended (eval_full.py:197-198)
@@ -802,7 +706,7 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) ensemble_persistent_k(const P
     __shared__ unsigned s_bad;
     if (tid == 0) s_bad = __hip_atomic_load(P.e.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();
-    if (s_bad && wg == 0 && tid == 0) { P.e.bm_best_score[0] = __builtin_nanf(""); P.e.bm_result[2] = -1; P.e.bm_result[3] = -1; }
+    if (s_bad && wg == 0 && tid == 0) pb_poison(P.e.bm_best_score, P.e.bm_result);
 }
 
 namespace {
@@ -819,8 +723,7 @@ int pens_lds_floats(int B, int D, int A) {
 //  normaliser words | candidate words] as flag-in-data words of 8 bytes
 size_t pens_xbytes(int B, int D, int A) {
     const size_t G = D / 4;
-    return 128 + 8 * ((size_t)B * D * 6 + (size_t)B * 2 * A + (size_t)B * PDEC_TMAX + (size_t)B * 64 + (size_t)B * A + (size_t)B * G * 4 +
-                      (size_t)B * G * PW_BEAM_W);
+    return pdec_edit_xbytes(B, D, A, 0) + 8 * ((size_t)B * D * 2 + (size_t)B * A + (size_t)B * G * 4 + (size_t)B * G * PW_BEAM_W);
 }
 
 bool pens_dims_ok(const SetEditNetDims* de, const SetDcnetDims* dd) {
@@ -872,18 +775,9 @@ int set_ensemble_beam_persistent(const SetEditNetWeights* we, const SetEditNetDi
     PDecEnsArgs P{};
     {
         PDecEditArgs& E = P.e;
-        const SetEditNetWeights* w = we;
-        const int F = de->F;
-        E.al_wih = w->al_wih; E.ld_ih = 3LL * D + F; E.al_whh = w->al_whh; E.cl_h2h_w = w->cl_h2h_w;
-        E.cl_x2h_w = w->cl_x2h_w; E.ld_x2h = 2LL * D + F; E.cl_x2h_b = w->cl_x2h_b; E.cl_h2h_b = w->cl_h2h_b;
-        E.ca_gate_w = w->ca_gate_w; E.ca_gate_b = w->ca_gate_b; E.ca_tc_w = w->ca_tc_w; E.ca_tc_b = w->ca_tc_b; E.ca_sc_b = w->ca_sc_b;
-        E.ca_dec_w = w->ca_dec_w; E.ca_dec_b = w->ca_dec_b; E.ca_full_w = w->ca_full_w; E.ca_full_b = w->ca_full_b;
-        E.va_dec_w = w->va_dec_w; E.va_dec_b = w->va_dec_b; E.va_full_w = w->va_full_w; E.va_full_b = w->va_full_b;
-        E.cl_cnew_w = w->cl_cnew_w; E.cl_cnew_b = w->cl_cnew_b; E.cl_cmem_b = w->cl_cmem_b;
-        E.fc_w = w->fc_w; E.fc_b = w->fc_b; E.tok_table = w->tok_table; E.ld_tab = 10LL * D;
+        pdec_edit_fill(E, we, de, max_picks);
         E.pre1 = pe.pre1; E.att1 = pe.att1; E.att1_c = pe.att1_c; E.mask = pe.mask; E.capP = pe.capP; E.memQ = pe.memQ; E.Mem = pe.Mem;
         E.pv = pe.pv;
-        E.B = B; E.D = D; E.T = de->T; E.R = de->R; E.A = A; E.V = de->V; E.max_len = max_picks; E.rpw = (de->V + G - 1) / G;
         E.start_idx = start_idx; E.end_idx = end_idx;
         E.bm_hist_par = hist_parent; E.bm_hist_word = (long long*)hist_word; E.bm_best_score = best_score;
         E.bm_best_word = (long long*)best_word; E.bm_result = result;
@@ -898,15 +792,7 @@ int set_ensemble_beam_persistent(const SetEditNetWeights* we, const SetEditNetDi
         P.d.pre1 = pd.pre1; P.d.att1_c = pd.att1_c; P.d.mask = pd.mask; P.d.pc = pd.pc;
     }
     {
-        char* x = (char*)xbuf;
-        P.e.status = (unsigned*)x; x += 128;
-        P.e.x_h1 = x; x += (size_t)B * D * 8;
-        P.e.x_gt = x; x += (size_t)B * D * 8;
-        P.e.x_cn = x; x += (size_t)B * D * 8;
-        P.e.x_h2 = x; x += (size_t)B * D * 8;
-        P.e.x_a2 = x; x += (size_t)B * 2 * A * 8;
-        P.e.x_cs = x; x += (size_t)B * PDEC_TMAX * 8;
-        P.e.x_vs = x; x += (size_t)B * 64 * 8;
+        char* x = pdec_edit_layout(P.e, (char*)xbuf);        // (R <= 36 here: 64 visual scores per row, as the kernel reads them)
         P.d.x_h1 = x; x += (size_t)B * D * 8;
         P.d.x_h2 = x; x += (size_t)B * D * 8;
         P.d.x_att2 = x; x += (size_t)B * A * 8;
@@ -917,27 +803,13 @@ int set_ensemble_beam_persistent(const SetEditNetWeights* we, const SetEditNetDi
     if (guard.rc != SET_OK) return guard.rc;
     P.e.spin_limit = guard.spin_limit();
     P.e.test_stall = guard.test_stall(); P.e.fault = guard.fault;
-    // residency: every workgroup must be on the chip at once (see encoder_persistent.hip penc_fits); a device whose LDS limit or
+    // residency: every workgroup must be on the chip at once (grid_barrier.h PersistentGuard::fits); a device whose LDS limit or
     // capacity is too small is answered with SET_ERR_UNSUPPORTED, never with a HIP error
     const void* kern = reinterpret_cast<const void*>(&ensemble_persistent_k);
     static bool configured[64] = {};
     if (guard.set_lds(kern, lds_max, configured) != SET_OK) return SET_ERR_UNSUPPORTED;
-    int& cap = g_pens_capacity[guard.dev];
-    int& cap_lds = g_pens_capacity_lds[guard.dev];
-    if (cap == 0 || lds > cap_lds) {
-        int per_cu = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, PDEC_THREADS, (size_t)lds) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, guard.dev) != hipSuccess) {
-            (void)hipGetLastError();
-            return SET_ERR_UNSUPPORTED;
-        }
-        cap = per_cu * cus;
-        cap_lds = lds;
-        if (cap <= 0) cap = -1;
-        const int forced = env_int("SET_PENC_TEST_CAPACITY", 0);
-        if (forced > 0) cap = forced;
-    }
-    if (G > cap) return SET_ERR_UNSUPPORTED;
+    if (guard.fits(kern, PDEC_THREADS, lds, G, g_pens_capacity[guard.dev], g_pens_capacity_lds[guard.dev]) != PersistentGuard::Fit::yes)
+        return SET_ERR_UNSUPPORTED;
     const double wbytes = 4.0 * (2.0 * (double)de->V * D + 9.0 * 4 * D * D + 3.0 * D * D + 3.0 * A * D);
     ProfScope ps("persistent_beam_ensemble", st, 2.0 * B * wbytes / 4.0 * max_picks, wbytes * max_picks);
     SET_TRY(guard.serialise(st));

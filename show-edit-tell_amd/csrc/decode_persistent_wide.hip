@@ -33,7 +33,12 @@
 // Buffer reuse without a barrier (grid_barrier.h): every workgroup contributes to X1 and consumes exchanges in order, so a
 // word of any exchange of timestep t is overwritten (timestep t + 1) only after every workgroup consumed it.
 // Teacher-forced mode (set_editnet_xe_forward): words from the captions, scores written by the owners of the vocabulary rows.
-#include "decode_persistent.h"
+// Beam mode (BEAM): the pick — slice top-k, candidate words, row merge, bookkeeping, poison — is beam_persistent.h, shared with
+// DCNet's kernel and the ensemble's.  On the host the residency check (PersistentGuard::fits) and, with the ensemble launch,
+// the fill of PDecEditArgs and the layout of its seven exchange regions (pdec_edit_fill / pdec_edit_layout below) are shared
+// too.  The phase code is deliberately this kernel's own (the ensemble kernel carries a copy): the order of its loads and the
+// three rotating weight buffers are its schedule.
+#include "beam_persistent.h"
 
 namespace set {
 
@@ -474,7 +479,7 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) editnet_persistent_wide_k(con
             continue;
         }
         if constexpr (BEAM) {
-            // ================= beam mode (editnet.py:654-699; the bookkeeping of csrc/beam.hip beam_pick_k for ONE image):
+            // ================= beam mode (editnet.py:654-699; the pick of beam_persistent.h):
             // X6 carries, per row and vocabulary slice, (max, sum exp) and the slice's B best (score, word) pairs — a global
             // top-B over B x V candidates takes at most B from one slice
             ++tag;
@@ -487,36 +492,13 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) editnet_persistent_wide_k(con
                     const int o = j * 256 + b * 16 + rr;
                     x = (((sRed[o] + sRed[3 * 256 + o]) + sRed[6 * 256 + o]) + sRed[9 * 256 + o]) + fcb_lane;
                 }
-                float cvv[PW_BEAM_K];
-                int cii[PW_BEAM_K];
-                float xx = x;
-#pragma unroll
-                for (int q = 0; q < PW_BEAM_K; ++q) {
-                    float bv = -INFINITY;
-                    int bix = 0x7fffffff;
-                    if (q < B) {
-                        if (xx > -INFINITY) { bv = xx; bix = row; }
-                        pw_wargmax(bv, bix);
-                        if (ok && row == bix) xx = -INFINITY;
-                    }
-                    cvv[q] = bv; cii[q] = bix;
-                }
+                pb_vals cvv;
+                pb_idxs cii;
+                pb_slice_topk(x, row, ok, B, cvv, cii);
                 const float mx = cvv[0];
                 float se = (ok && mx > -INFINITY) ? expf(x - mx) : 0.f;
                 se = pw_wsum(se);
-                if (lane < PW_BEAM_W) {
-                    float v = 0.f;
-                    if (lane == 0) v = mx;
-                    else if (lane == 1) v = se;
-                    else if (lane < 2 + 2 * PW_BEAM_K) {
-                        const int q = (lane - 2) >> 1;
-                        float cv_ = cvv[0]; int ci_ = cii[0];
-#pragma unroll
-                        for (int u = 1; u < PW_BEAM_K; ++u) if (q == u) { cv_ = cvv[u]; ci_ = cii[u]; }
-                        v = (lane & 1) ? __int_as_float(ci_) : cv_;
-                    }
-                    ll_put(fbrs, (b * G + wg) * PW_BEAM_W + lane, v, tag);
-                }
+                pb_publish(fbrs, (b * G + wg) * PW_BEAM_W, lane, mx, se, cvv, cii, tag);
             }
             // S1' (see the greedy path); copy_lstm.h2h h2 goes to LDS: the next timestep adds it through the parent map
             if (more) {
@@ -535,10 +517,9 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) editnet_persistent_wide_k(con
             if (kq < B) {
                 const int j = kq;
                 const float scj = sScore[j];
-                float ov[PW_BEAM_K];
-                int oi[PW_BEAM_K];
-#pragma unroll
-                for (int q = 0; q < PW_BEAM_K; ++q) { ov[q] = -INFINITY; oi[q] = 0x7fffffff; }
+                pb_vals ov;
+                pb_idxs oi;
+                pb_none(ov, oi);
                 if (scj > -INFINITY) {                           // (uniform in the wave; dead slots take no part)
                     float cv[16];
                     int ci[16];
@@ -562,90 +543,14 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) editnet_persistent_wide_k(con
                         cv[c] = have ? scj + (cv[c] - lse) : -INFINITY;       // score + log-prob, as beam_pick_k forms it
                         ci[c] = have ? j * V + ci[c] : 0x7fffffff;
                     }
-#pragma unroll
-                    for (int q = 0; q < PW_BEAM_K; ++q) {
-                        if (q < B) {
-                            float bv = -INFINITY;
-                            int bix = 0x7fffffff;
-#pragma unroll
-                            for (int c = 0; c < 16; ++c)
-                                if (cv[c] > bv || (cv[c] == bv && ci[c] < bix)) { bv = cv[c]; bix = ci[c]; }
-                            if (!(bv > -INFINITY)) bix = 0x7fffffff;
-                            pw_wargmax(bv, bix);
-#pragma unroll
-                            for (int c = 0; c < 16; ++c) if (ci[c] == bix) cv[c] = -INFINITY;
-                            ov[q] = bv; oi[q] = bix;
-                        }
-                    }
+                    pb_row_merge(cv, ci, B, ov, oi);
                 }
-                if (lane == 0) {
-#pragma unroll
-                    for (int q = 0; q < PW_BEAM_K; ++q) { sCand[(j * PW_BEAM_K + q) * 2] = ov[q]; sCand[(j * PW_BEAM_K + q) * 2 + 1] = __int_as_float(oi[q]); }
-                }
+                if (lane == 0) pb_row_store(sCand, j, ov, oi);
             }
             PW_SYNC();
-            if (tid == 0) {
-                // the B best of the B x B candidates (ties: lowest flat index), then beam_pick_k's bookkeeping
-                const int k = B, kl = sKleft;
-                float pv_[PW_BEAM_K];
-                int pi_[PW_BEAM_K];
-                unsigned taken = 0u;
-                for (int rr_ = 0; rr_ < k; ++rr_) {
-                    float bv = -INFINITY;
-                    int bix = 0x7fffffff, bc = -1;
-                    for (int c = 0; c < k * PW_BEAM_K; ++c) {
-                        if ((taken >> c) & 1u) continue;
-                        if ((c % PW_BEAM_K) >= k) continue;
-                        const float v = sCand[c * 2];
-                        const int ix = __float_as_int(sCand[c * 2 + 1]);
-                        if (ix == 0x7fffffff) continue;
-                        if (v > bv || (v == bv && ix < bix) || bc < 0) { bv = v; bix = ix; bc = c; }
-                    }
-                    if (bc >= 0) taken |= 1u << bc;
-                    pv_[rr_] = bc >= 0 ? bv : -INFINITY;
-                    pi_[rr_] = bc >= 0 ? bix : 0x7fffffff;
-                }
-                int n_end = 0, c_arg = -1, slot = 0;
-                float c_best = -INFINITY;
-                bool live[PW_BEAM_K];
-                for (int rr_ = 0; rr_ < k; ++rr_) {
-                    const int flat = pi_[rr_];
-                    const bool okp = flat != 0x7fffffff && rr_ < kl;          // only the first k_left picks count
-                    const long long word = okp ? flat % V : 0;
-                    const bool is_end = okp && word == P.end_idx;
-                    live[rr_] = okp && !is_end;
-                    if (is_end) {
-                        ++n_end;
-                        if (pv_[rr_] > c_best) { c_best = pv_[rr_]; c_arg = rr_; }   // first maximum
-                    }
-                }
-                if (c_arg >= 0 && c_best > sBest) {
-                    sBest = c_best;
-                    if (wg == 0) {
-                        P.bm_best_score[0] = c_best;
-                        P.bm_best_word[0] = pi_[c_arg] % V;
-                        P.bm_result[0] = t;                              // pick index of the best completed hypothesis
-                        P.bm_result[1] = pi_[c_arg] / V;                 // its parent slot (numbering before this pick)
-                    }
-                }
-                sKleft = kl - n_end;
-                for (int pass = 0; pass < 2; ++pass)
-                    for (int rr_ = 0; rr_ < k; ++rr_) {
-                        if ((pass == 0) != live[rr_]) continue;
-                        const int flat = pi_[rr_];
-                        const int parent = flat != 0x7fffffff ? flat / V : 0;
-                        const long long word = flat != 0x7fffffff ? flat % V : 0;
-                        sScore[slot] = live[rr_] ? pv_[rr_] : -INFINITY;
-                        sTok[slot] = live[rr_] ? word : 0;
-                        sPar[slot] = parent;
-                        if (wg == 0) {
-                            P.bm_hist_par[t * PW_BEAM_K + slot] = parent;
-                            P.bm_hist_word[t * PW_BEAM_K + slot] = word;
-                        }
-                        ++slot;
-                    }
-                if (wg == 0) { P.bm_result[2] = sKleft; P.bm_result[3] = t + 1; }
-            }
+            if (tid == 0)                                        // the pick itself and its bookkeeping (beam_persistent.h)
+                pb_pick(sCand, sScore, sTok, sPar, &sKleft, &sBest, P.bm_hist_par, P.bm_hist_word, P.bm_best_score, P.bm_best_word,
+                        P.bm_result, V, P.end_idx, t, B, wg == 0);
             PW_SYNC();
             PD_STAMP(16);
             if (sKleft == 0) break;                              // every hypothesis has ended (editnet.py:700-701)
@@ -748,7 +653,7 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) editnet_persistent_wide_k(con
                 if (row < V) P.predictions[(long long)(bt_ / P.max_len) * P.ld_pred_b + (long long)(bt_ % P.max_len) * V + row] = qnan;
             }
         } else if (BEAM) {
-            if (wg == 0 && tid == 0) { P.bm_best_score[0] = qnan; P.bm_result[2] = -1; P.bm_result[3] = -1; }   // never a search result
+            if (wg == 0 && tid == 0) pb_poison(P.bm_best_score, P.bm_result);
         } else if (wg == 0) {
             for (int i = tid; i < B * P.max_len; i += PDEC_THREADS) { P.seq_logp[i] = qnan; P.seq[i] = 0; }
         }
@@ -760,12 +665,42 @@ static int pwide_lds_floats(int B, int D, int A, bool beam = false, int rreg = P
     return base + (beam ? B * (D / 4) * PW_BEAM_W + 4 * 256 + 2 * PW_BEAM_K * 4 + PW_BEAM_K * PW_BEAM_K * 2 : 0);
 }
 
-// [status line | h1 | attend_cap | c_new | h2 | projections | caption scores | visual scores | fc triples] as flag-in-data words
-// (visual scores: 64 per row, R per row above 64 regions)
+// EditNet's part of an exchange region, the same in this file's launches and in the ensemble's: [status line | h1 | attend_cap |
+// c_new | h2 | projections | caption scores | visual scores] as flag-in-data words of 8 bytes (visual scores: 64 per row, R per
+// row above 64 regions).  P.B / D / A / R must be set; returns the end.  pdec_edit_xbytes = its size.
+char* pdec_edit_layout(PDecEditArgs& P, char* x) {
+    const size_t B = P.B;
+    P.status = (unsigned*)x; x += 128;
+    P.x_h1 = x; x += B * P.D * 8;
+    P.x_gt = x; x += B * P.D * 8;
+    P.x_cn = x; x += B * P.D * 8;
+    P.x_h2 = x; x += B * P.D * 8;
+    P.x_a2 = x; x += B * 2 * P.A * 8;
+    P.x_cs = x; x += B * PDEC_TMAX * 8;
+    P.x_vs = x; x += B * pw_vcols(P.R) * 8;
+    return x;
+}
+size_t pdec_edit_xbytes(int B, int D, int A, int R) {
+    return 128 + 8 * ((size_t)B * D * 4 + (size_t)B * 2 * A + (size_t)B * PDEC_TMAX + (size_t)B * pw_vcols(R));
+}
+
+// ... | fc triples | the beam mode's candidate words]
 size_t editnet_persistent_wide_xbytes(int B, int D, int A, int R) {
     if (B > PDW_MAXB) return 0;
-    return 128 + (size_t)B * D * 8 * 4 + (size_t)B * 2 * A * 8 + (size_t)B * PDEC_TMAX * 8 + (size_t)B * pw_vcols(R) * 8 + (size_t)B * (D / 4) * 32 +
-           (B <= PW_BEAM_K ? (size_t)B * (D / 4) * PW_BEAM_W * 8 : 0);       // + the beam mode's candidate words
+    return pdec_edit_xbytes(B, D, A, R) + (size_t)B * (D / 4) * 32 + (B <= PW_BEAM_K ? (size_t)B * (D / 4) * PW_BEAM_W * 8 : 0);
+}
+
+// the weights in place, their leading dimensions, the dimensions and the vocabulary rows per workgroup of one EditNet launch
+void pdec_edit_fill(PDecEditArgs& P, const SetEditNetWeights* w, const SetEditNetDims* d, int max_len) {
+    const int D = d->D, F = d->F, G = D / 4;
+    P.al_wih = w->al_wih; P.ld_ih = 3LL * D + F; P.al_whh = w->al_whh; P.cl_h2h_w = w->cl_h2h_w;
+    P.cl_x2h_w = w->cl_x2h_w; P.ld_x2h = 2LL * D + F; P.cl_x2h_b = w->cl_x2h_b; P.cl_h2h_b = w->cl_h2h_b;
+    P.ca_gate_w = w->ca_gate_w; P.ca_gate_b = w->ca_gate_b; P.ca_tc_w = w->ca_tc_w; P.ca_tc_b = w->ca_tc_b; P.ca_sc_b = w->ca_sc_b;
+    P.ca_dec_w = w->ca_dec_w; P.ca_dec_b = w->ca_dec_b; P.ca_full_w = w->ca_full_w; P.ca_full_b = w->ca_full_b;
+    P.va_dec_w = w->va_dec_w; P.va_dec_b = w->va_dec_b; P.va_full_w = w->va_full_w; P.va_full_b = w->va_full_b;
+    P.cl_cnew_w = w->cl_cnew_w; P.cl_cnew_b = w->cl_cnew_b; P.cl_cmem_b = w->cl_cmem_b;
+    P.fc_w = w->fc_w; P.fc_b = w->fc_b; P.tok_table = w->tok_table; P.ld_tab = 10LL * D;
+    P.B = d->B; P.D = D; P.T = d->T; P.R = d->R; P.A = d->A; P.V = d->V; P.max_len = max_len; P.rpw = (d->V + G - 1) / G;
 }
 
 // wide_regions: the PDEC_RREG_WIDE instantiation (adaptive beam search), otherwise the PDEC_RREG one
@@ -794,15 +729,7 @@ int editnet_persistent_wide_launch(PDecEditArgs& P, void* xbuf, PersistentGuard&
     if (!editnet_persistent_wide_ok(B, D, A, P.T, P.R, P.V, wide_regions)) return SET_OK;
     if (beam && (B > PW_BEAM_K || P.caps || (long long)B * P.V >= 0x7fffffffLL)) return SET_OK;
     {
-        char* x = (char*)xbuf;
-        P.status = (unsigned*)x; x += 128;
-        P.x_h1 = x; x += (size_t)B * D * 8;
-        P.x_gt = x; x += (size_t)B * D * 8;
-        P.x_cn = x; x += (size_t)B * D * 8;
-        P.x_h2 = x; x += (size_t)B * D * 8;
-        P.x_a2 = x; x += (size_t)B * 2 * A * 8;
-        P.x_cs = x; x += (size_t)B * PDEC_TMAX * 8;
-        P.x_vs = x; x += (size_t)B * pw_vcols(P.R) * 8;
+        char* x = pdec_edit_layout(P, (char*)xbuf);
         P.x_fc = x; x += (size_t)B * G * 32;
         P.x_fcb = x;
     }
@@ -815,22 +742,9 @@ int editnet_persistent_wide_launch(PDecEditArgs& P, void* xbuf, PersistentGuard&
     int lds_max = pwide_lds_floats(beam ? PW_BEAM_K : PDW_MAXB, D, A, beam, rreg) * (int)sizeof(float);
     if (lds_max > 156 * 1024) lds_max = 156 * 1024;
     if (lds > lds_max || guard.set_lds(kern, lds_max, configured[inst]) != SET_OK) return SET_OK;
-    int& cap = g_pwide_capacity[inst][guard.dev];
-    int& cap_lds = g_pwide_capacity_lds[inst][guard.dev];
-    if (cap == 0 || lds > cap_lds) {
-        int per_cu = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, PDEC_THREADS, (size_t)lds) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, guard.dev) != hipSuccess) {
-            (void)hipGetLastError();
-            return SET_OK;
-        }
-        cap = per_cu * cus;
-        cap_lds = lds;
-        if (cap <= 0) cap = -1;
-        const int forced = env_int("SET_PENC_TEST_CAPACITY", 0);
-        if (forced > 0) cap = forced;
-    }
-    if (G > cap) return SET_OK;
+    if (guard.fits(kern, PDEC_THREADS, lds, G, g_pwide_capacity[inst][guard.dev], g_pwide_capacity_lds[inst][guard.dev]) !=
+        PersistentGuard::Fit::yes)
+        return SET_OK;
     *unsupported = false;
     const double wbytes = 4.0 * ((double)P.V * D + 5.0 * 4 * D * D + 3.0 * D * D + 2.0 * A * D);
     ProfScope ps(beam ? "persistent_beam" : "persistent_decode", s, 2.0 * B * wbytes / 4.0 * P.max_len, wbytes * P.max_len);
@@ -884,18 +798,11 @@ int editnet_persistent_greedy(const SetEditNetWeights* w, const SetEditNetDims* 
         if (!env_int("SET_DEC_PERSISTENT", 1) || max_len < 1 || (d->adaptive && !beam->rmask) || persistent_disabled() ||
             !editnet_persistent_wide_ok(d->B, d->D, d->A, d->T, d->R, d->V, wide)) return SET_ERR_UNSUPPORTED;
     } else if (!editnet_persistent_ok(d, max_len)) return SET_ERR_UNSUPPORTED;
-    const int B = d->B, D = d->D, A = d->A, F = d->F, G = D / 4;
+    const int B = d->B;
     PDecEditArgs P{};
-    P.al_wih = w->al_wih; P.ld_ih = 3LL * D + F; P.al_whh = w->al_whh; P.cl_h2h_w = w->cl_h2h_w;
-    P.cl_x2h_w = w->cl_x2h_w; P.ld_x2h = 2LL * D + F; P.cl_x2h_b = w->cl_x2h_b; P.cl_h2h_b = w->cl_h2h_b;
-    P.ca_gate_w = w->ca_gate_w; P.ca_gate_b = w->ca_gate_b; P.ca_tc_w = w->ca_tc_w; P.ca_tc_b = w->ca_tc_b; P.ca_sc_b = w->ca_sc_b;
-    P.ca_dec_w = w->ca_dec_w; P.ca_dec_b = w->ca_dec_b; P.ca_full_w = w->ca_full_w; P.ca_full_b = w->ca_full_b;
-    P.va_dec_w = w->va_dec_w; P.va_dec_b = w->va_dec_b; P.va_full_w = w->va_full_w; P.va_full_b = w->va_full_b;
-    P.cl_cnew_w = w->cl_cnew_w; P.cl_cnew_b = w->cl_cnew_b; P.cl_cmem_b = w->cl_cmem_b;
-    P.fc_w = w->fc_w; P.fc_b = w->fc_b; P.tok_table = w->tok_table; P.ld_tab = 10LL * D;
+    pdec_edit_fill(P, w, d, max_len);
     P.pre1 = pre1; P.att1 = att1; P.att1_c = att1_c; P.mask = mask; P.capP = capP; P.memQ = memQ; P.Mem = Mem; P.pv = pv;
     P.it = it; P.unfinished = unfinished; P.alive = alive; P.seq = seq; P.seq_logp = seq_logp;
-    P.B = B; P.D = D; P.T = d->T; P.R = d->R; P.A = A; P.V = d->V; P.max_len = max_len; P.rpw = (d->V + G - 1) / G;
     P.start_idx = start_idx; P.end_idx = end_idx;
     if (teach) {
         P.caps = (const long long*)teach->caps; P.caps_stride = teach->caps_stride;

@@ -342,6 +342,22 @@ int PersistentGuard::set_lds(const void* kernel, int bytes, bool (&done)[64]) {
     done[dev] = true;
     return SET_OK;
 }
+PersistentGuard::Fit PersistentGuard::fits(const void* kernel, int threads, int lds, int grid, int& cap, int& cap_lds) {
+    if (cap == 0 || lds > cap_lds) {
+        int per_cu = 0, cus = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, (size_t)lds) != hipSuccess ||
+            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) {
+            (void)hipGetLastError();
+            return Fit::unknown;
+        }
+        cap = per_cu * cus;
+        cap_lds = lds;
+        if (cap <= 0) cap = -1;
+        const int forced = env_int("SET_PENC_TEST_CAPACITY", 0);
+        if (forced > 0) cap = forced;
+    }
+    return grid <= cap ? Fit::yes : Fit::no;
+}
 int PersistentGuard::test_stall() const { static const int v = env_int("SET_PENC_TEST_STALL", 0); return v; }
 // persistent launches are not to be tried on the current device: a barrier timed out earlier in this process, or another
 // process owns them (penc_process_owns; asked again at every call, so a device whose owner exited is taken over).  Callers ask
@@ -378,6 +394,8 @@ template <int NT, int KB> constexpr int penc_slot() { return (NT == 2 ? 0 : NT =
 // (registers, LDS) and how many CUs the device has (a partitioned or smaller part reports fewer); when the grid does not fit
 // the caller takes the per-step kernels.  (MI355X_MICROARCH.md: the API can be one high per CU only at >= 7 workgroups per
 // CU; these kernels sit at 1-2 by their register budget.)
+// (Not PersistentGuard::fits, the decode launches' form of this check: here the per-CU count is capped at 8 and a failed query is
+// a HIP error with the runtime's code (SET_HIP_TRY), not "unsupported".)
 template <int NT, int KB>
 static int penc_fits(PersistentGuard& guard, int grid, int dev, bool* fits) {
     const int lds = 4 * NT * 256 * (int)sizeof(float);

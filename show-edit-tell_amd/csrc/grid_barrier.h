@@ -164,6 +164,14 @@ struct PersistentGuard {
     // per-device flags).  SET_ERR_UNSUPPORTED when the device's LDS limit is below `bytes` or the runtime refuses: the caller
     // takes the per-step kernels, no HIP error leaves the library
     int set_lds(const void* kernel, int bytes, bool (&done)[64]);
+    // residency: a persistent grid needs every workgroup on the chip at once.  Does THIS device admit `grid` workgroups of
+    // `kernel` (`threads` threads, `lds` bytes of dynamic LDS)?  cap / cap_lds = the caller's cache slots of this kernel on
+    // this device (0 = not asked yet): workgroups per CU from the occupancy query x the device's CUs, asked again when a larger
+    // LDS size comes along; SET_PENC_TEST_CAPACITY (test hook) pretends the device admits that many.  unknown = a query failed
+    // (no HIP error is left behind): the decode launches answer it like `no`, with the per-step kernels.  (Hidden: the library's
+    // dynamic symbol table stays as it was.)
+    enum class Fit { yes, no, unknown };
+    __attribute__((visibility("hidden"))) Fit fits(const void* kernel, int threads, int lds, int grid, int& cap, int& cap_lds);
   private:
     bool locked;
 };
