@@ -139,12 +139,14 @@ static int begin_impl(const SetDcnetWeights* w, const SetDcnetDims* d, const int
         else return rc;
     }
     for (int t = 0; t < T && !persistent; ++t) {
+        const bool h_zero = t == 0 && !dead_work();           // hf / hb were zeroed above: the steps skip their contraction
         if (fused && tab) {                   // x W_ih^T + b_ih of every word is a row of the token table
             SET_TRY(fused_encoder_step(hf_cur, hf_nxt, ws.cf, w->enc_whh_f, w->tok_table + 4 * D, ldt, 0, w->enc_bhh_f,
-                                       prevlen, t, 0, ws.enc, nullptr, (long long)T * 2 * C, 2 * C, 0, B, C, st, prev, T, d->V));
+                                       prevlen, t, 0, ws.enc, nullptr, (long long)T * 2 * C, 2 * C, 0, B, C, st, prev, T, d->V, nullptr,
+                                       nullptr, h_zero));
             SET_TRY(fused_encoder_step(hb_cur, hb_nxt, ws.cb, w->enc_whh_b, w->tok_table + 4 * D + 4 * C, ldt, 0,
                                        w->enc_bhh_b, prevlen, t, 1, ws.enc, nullptr, (long long)T * 2 * C, 2 * C, C, B, C, st,
-                                       prev, T, d->V));
+                                       prev, T, d->V, nullptr, nullptr, h_zero));
             float* tmp = hf_cur; hf_cur = hf_nxt; hf_nxt = tmp;
             tmp = hb_cur; hb_cur = hb_nxt; hb_nxt = tmp;
             continue;
@@ -152,10 +154,10 @@ static int begin_impl(const SetDcnetWeights* w, const SetDcnetDims* d, const int
         if (fused) {
             SET_TRY(fused_encoder_step(hf_cur, hf_nxt, ws.cf, w->enc_whh_f, ws.xg_f, (long long)T * 4 * C, 4 * C,
                                        w->enc_bhh_f, prevlen, t, 0, ws.enc, nullptr, (long long)T * 2 * C, 2 * C, 0, B, C,
-                                       st));
+                                       st, nullptr, 0, 0, nullptr, nullptr, h_zero));
             SET_TRY(fused_encoder_step(hb_cur, hb_nxt, ws.cb, w->enc_whh_b, ws.xg_b, (long long)T * 4 * C, 4 * C,
                                        w->enc_bhh_b, prevlen, t, 1, ws.enc, nullptr, (long long)T * 2 * C, 2 * C, C, B, C,
-                                       st));
+                                       st, nullptr, 0, 0, nullptr, nullptr, h_zero));
             float* tmp = hf_cur; hf_cur = hf_nxt; hf_nxt = tmp;
             tmp = hb_cur; hb_cur = hb_nxt; hb_nxt = tmp;
             continue;
@@ -226,11 +228,11 @@ static void build_phase_a(const SetDcnetWeights* w, const SetDcnetDims* d, Dcnet
 }
 
 // tok_ids / tok_stride: the tokens of THIS timestep (table gather).  a_pre / a_next / bt_next / logits_biased: the F/A
-// merge, exactly as in csrc/editnet.hip step_impl.
+// merge, exactly as in csrc/editnet.hip step_impl; zero_state / fc_alone likewise.
 static int step_impl(const SetDcnetWeights* w, const SetDcnetDims* d, int bt, DcnetWs& ws, float* dst, long long ld_dst,
                      Slabs* logits_out, hipStream_t st, const long long* tok_ids = nullptr, long long tok_stride = 1,
                      const GemmProb* a_pre = nullptr, GemmProb* a_next = nullptr, bool* logits_biased = nullptr,
-                     int bt_next = -1, bool a_done = false) {
+                     int bt_next = -1, bool a_done = false, bool zero_state = false, bool fc_alone = false) {
     const int B = d->B, T = d->T, D = d->D, A = d->A, C = d->C, E = d->E, V = d->V;
     const int tgt = gemm_target_wgs();
     const Slabs none{nullptr, 0, 0, 0};
@@ -238,15 +240,17 @@ static int step_impl(const SetDcnetWeights* w, const SetDcnetDims* d, int bt, Dc
     RowGather g_gates;
     if (tab) g_gates = RowGather{w->tok_table, tok_ids, tok_stride, 4LL * D + 8LL * C, 0, V};
     GemmProb a[2];
+    const bool a_zero = zero_state && tab && !a_pre;     // h1 == h2 == 0 and no emb segment: the products are exactly zero
     if (a_pre) {
         a[0] = a_pre[0]; a[1] = a_pre[1];
-    } else {
+    } else if (!a_zero) {
         build_phase_a(w, d, ws, bt, tab, a);
         plan_ksplit(a, 2, tgt);
         SET_TRY(gemm_group(a, 2, st, "gemm:A gates1+h2h"));
     }
+    const Slabs a0 = a_zero ? none : slabs_of(a[0]), a1 = a_zero ? none : slabs_of(a[1]);
     if (!(a_done && a_pre && tab))       // a_done: the previous pick finished this cell (LstmTail, as in csrc/editnet.hip)
-        SET_TRY(lstm_pointwise(slabs_of(a[0]), none, none, ws.pre1, 4 * D, nullptr, nullptr, ws.c1, ws.c1, ws.h1, nullptr,
+        SET_TRY(lstm_pointwise(a0, none, none, ws.pre1, 4 * D, nullptr, nullptr, ws.c1, ws.c1, ws.h1, nullptr,
                                bt, D, st, g_gates));
     GemmProb b[2];
     b[0] = slab_prob(ws.sB0, bt, A, B);
@@ -261,7 +265,7 @@ static int step_impl(const SetDcnetWeights* w, const SetDcnetDims* d, int bt, Dc
     c.add(ws.attend_cap, 2 * C, w->ll_wih + D, 2 * E, 2 * C);
     plan_ksplit(&c, 1, tgt);
     SET_TRY(gemm_group(&c, 1, st, "gemm:C ll_ctx"));
-    SET_TRY(lstm_pointwise(slabs_of(a[1]), slabs_of(b[1]), slabs_of(c), nullptr, 0, w->ll_bih, w->ll_bhh, ws.c2, ws.c2,
+    SET_TRY(lstm_pointwise(a1, slabs_of(b[1]), slabs_of(c), nullptr, 0, w->ll_bih, w->ll_bhh, ws.c2, ws.c2,
                            ws.h2, nullptr, bt, D, st));
     const long long Vp = (long long)round_up((size_t)V, 64);
     GemmProb f = slab_prob(ws.sF0, bt, V, B);
@@ -279,7 +283,12 @@ static int step_impl(const SetDcnetWeights* w, const SetDcnetDims* d, int bt, Dc
             fa[0].ldc = dst ? ld_dst : Vp;
             if (logits_biased) *logits_biased = true;
         }
-        SET_TRY(gemm_group(fa, 3, st, "gemm:F fc + next A"));
+        if (fc_alone) {                      // no next phase A: fc alone, on the merged launch's K plan and row tile
+            const int bm = gemm_launch_rows(fa, 3);
+            if (bm == 64 || bm == 128) fa[0].bm_hint = bm;
+            SET_TRY(gemm_group(fa, 1, st, "gemm:F fc"));
+        } else
+            SET_TRY(gemm_group(fa, 3, st, "gemm:F fc + next A"));
         if (dst && fa[0].ksplit > 1)
             SET_TRY(reduce_bias_act(slabs_of(fa[0]), w->fc_b, nullptr, dst, ld_dst, bt, V, SET_ACT_NONE, st));
         a_next[0] = fa[1]; a_next[1] = fa[2];
@@ -381,15 +390,19 @@ static int dcnet_rollout(const SetDcnetWeights* w, const SetDcnetDims* d, const 
                                                start_idx, end_idx, max_len, (long long*)seq, seq_logp, st);
         if (rc != SET_ERR_UNSUPPORTED) return rc;
     }
-    for (int t = 0; t <= max_len; ++t) {                                 // dcnet_rl.py:305,315-316
+    // the reference runs max_len + 1 timesteps and discards the last one (dcnet_rl.py:305,315-316); the loop ends with the
+    // pick of timestep max_len - 1 unless SET_DEAD_WORK=1 (as in editnet.hip rollout)
+    const int last_t = dead_work() ? max_len : max_len - 1;
+    for (int t = 0; t <= last_t; ++t) {
         Slabs lg;
         bool biased = false;
-        const bool next_a = merge && t < max_len;
+        const bool next_a = merge && t < last_t;
+        const bool fc_alone = merge && !next_a && t < max_len;
         RowGate gate;
         if (loop_gate && t > 0) gate.alive_prev = W.alive + (t - 1);
         RowGateScope gate_scope(gate);
-        SET_TRY(step_impl(w, d, B, W, nullptr, 0, &lg, st, W.it, 1, have_a ? a_cur : nullptr, next_a ? a_nxt : nullptr,
-                          &biased, -1, a_done));
+        SET_TRY(step_impl(w, d, B, W, nullptr, 0, &lg, st, W.it, 1, have_a ? a_cur : nullptr,
+                          next_a || fc_alone ? a_nxt : nullptr, &biased, -1, a_done, t == 0 && !dead_work(), fc_alone));
         have_a = next_a;
         if (next_a) { a_cur[0] = a_nxt[0]; a_cur[1] = a_nxt[1]; }
         if (t == max_len) break;

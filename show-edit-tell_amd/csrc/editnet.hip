@@ -30,6 +30,10 @@ int gemm_target_wgs() {
     static int v = env_int("SET_GEMM_TARGET_WGS", 512);
     return v;
 }
+int dead_work() {
+    static int v = env_int("SET_DEAD_WORK", 0);
+    return v;
+}
 
 struct EditNetWs {
     // per-sequence invariants (prologue)
@@ -211,13 +215,15 @@ int editnet_encoder(const SetEditNetWeights* w, const int64_t* seq, const int64_
     }
     for (int t = 0; t < T && !persistent; ++t) {
         if (fused) {
+            const bool h_zero = t == 0 && !dead_work();       // enc_h was zeroed above: the step skips its contraction
             if (tab)
                 SET_TRY(fused_encoder_step(h_cur, h_nxt, enc_c, w->enc_h2h_w, w->tok_table + 6 * D, 10LL * D, 0,
-                                           w->enc_h2h_b, lens, t, 0, H, Mem, (long long)T * D, D, 0, B, D, st, seq, T, V, perm, nactive));
+                                           w->enc_h2h_b, lens, t, 0, H, Mem, (long long)T * D, D, 0, B, D, st, seq, T, V, perm, nactive,
+                                           h_zero));
             else
                 SET_TRY(fused_encoder_step(h_cur, h_nxt, enc_c, w->enc_h2h_w, xg, (long long)T * 4 * D, 4 * D,
                                            w->enc_h2h_b, lens, t, 0, H, Mem, (long long)T * D, D, 0, B, D, st, nullptr, 0, 0,
-                                           perm, nactive));
+                                           perm, nactive, h_zero));
             float* tmp = h_cur; h_cur = h_nxt; h_nxt = tmp;
             continue;
         }
@@ -333,10 +339,16 @@ static void build_phase_a(const SetEditNetWeights* w, const SetEditNetDims* d, E
 //   a_next != NULL: launch the NEXT timestep's phase A together with this timestep's fc and return its problems here
 //   *logits_biased: set when the returned logits already include fc.bias (unsplit fc)
 //   a_done: the attention-LSTM cell of this timestep was finished by the previous pick (LstmTail): h1 / c1 are current
+//   zero_state: h1 == h2 == 0 (first timestep after begin_impl).  With the token table every phase-A operand is then a zero
+//     row and the products are exactly zero: no phase-A launch, the two LSTM cells get empty slab sets instead
+//   fc_alone (with a_next): the loop ends after this timestep, so there is no next phase A to launch — but fc keeps the
+//     split-K plan and the row tile it has inside the merged launch, so its logits have the summation order of every
+//     other timestep's (a launch planned on its own could split K where the merged one does not)
 static int step_impl(const SetEditNetWeights* w, const SetEditNetDims* d, const float* X, int bt, EditNetWs& ws,
                      const long long* tok_ids, long long tok_stride, float* dst,
                      long long ld_dst, Slabs* logits_out, hipStream_t st, const GemmProb* a_pre = nullptr,
-                     GemmProb* a_next = nullptr, bool* logits_biased = nullptr, int bt_next = -1, bool a_done = false) {
+                     GemmProb* a_next = nullptr, bool* logits_biased = nullptr, int bt_next = -1, bool a_done = false,
+                     bool zero_state = false, bool fc_alone = false) {
     const int B = d->B, T = d->T, R = d->R, F = d->F, D = d->D, A = d->A, V = d->V;
     const int tgt = gemm_target_wgs();
     const long long ld_x2h = 2LL * D + F;
@@ -352,16 +364,18 @@ static int step_impl(const SetEditNetWeights* w, const SetEditNetDims* d, const 
         g_cg = RowGather{w->tok_table, tok_ids, tok_stride, 10LL * D, 5 * D, V};
     }
     GemmProb a[2];
+    const bool a_zero = zero_state && tab && !a_pre;
     if (a_pre) {
         a[0] = a_pre[0]; a[1] = a_pre[1];
-    } else {
+    } else if (!a_zero) {
         build_phase_a(w, d, ws, bt, tab, a);
         plan_ksplit(a, 2, tgt);
         SET_TRY(gemm_group(a, 2, st, "gemm:A gates1+h2h"));
     }
     const Slabs none{nullptr, 0, 0, 0};
+    const Slabs a0 = a_zero ? none : slabs_of(a[0]), a1 = a_zero ? none : slabs_of(a[1]);
     if (!(a_done && a_pre && tab))
-        SET_TRY(lstm_pointwise(slabs_of(a[0]), none, none, ws.pre1, 4 * D, nullptr, nullptr, ws.c1, ws.c1, ws.h1, nullptr,
+        SET_TRY(lstm_pointwise(a0, none, none, ws.pre1, 4 * D, nullptr, nullptr, ws.c1, ws.c1, ws.h1, nullptr,
                                bt, D, st, g_gates));
     // ---- B
     GemmProb b[5];
@@ -403,7 +417,7 @@ static int step_impl(const SetEditNetWeights* w, const SetEditNetDims* d, const 
     dd.add(ws.attend_img, F, w->cl_x2h_w + 2 * D, ld_x2h, F);
     plan_ksplit(&dd, 1, tgt);
     SET_TRY(gemm_group(&dd, 1, st, "gemm:D x2h_ctx"));
-    SET_TRY(lstm_pointwise(slabs_of(a[1]), slabs_of(b[4]), slabs_of(dd), nullptr, 0, w->cl_x2h_b, w->cl_h2h_b, ws.c2,
+    SET_TRY(lstm_pointwise(a1, slabs_of(b[4]), slabs_of(dd), nullptr, 0, w->cl_x2h_b, w->cl_h2h_b, ws.c2,
                            ws.c_new, nullptr, ws.ogate, bt, D, st));
     // ---- E (+ copy gate): gate_cnew(c_new) is the only contraction left here
     if (fused) {
@@ -437,7 +451,12 @@ static int step_impl(const SetEditNetWeights* w, const SetEditNetDims* d, const 
             if (dst) fa[0].ldc = ld_dst;
             if (logits_biased) *logits_biased = true;
         }
-        SET_TRY(gemm_group(fa, 3, st, "gemm:F fc + next A"));
+        if (fc_alone) {
+            const int bm = gemm_launch_rows(fa, 3);
+            if (bm == 64 || bm == 128) fa[0].bm_hint = bm;   // (16 / 32: the class follows from the rows, same for fc alone)
+            SET_TRY(gemm_group(fa, 1, st, "gemm:F fc"));
+        } else
+            SET_TRY(gemm_group(fa, 3, st, "gemm:F fc + next A"));
         if (dst && fa[0].ksplit > 1)
             SET_TRY(reduce_bias_act(slabs_of(fa[0]), w->fc_b, nullptr, dst, ld_dst, bt, V, SET_ACT_NONE, st));
         a_next[0] = fa[1]; a_next[1] = fa[2];
@@ -532,7 +551,9 @@ static int rollout(const SetEditNetWeights* w, const SetEditNetDims* d, const fl
     // so neither the loop's first timestep nor the epilogue gathers the embedding
     const bool emb_needed = !(w->tok_table && (d->D % 64 == 0) && env_int("SET_NO_FUSED", 0) == 0);
     if (emb_needed) SET_TRY(embed_relu(w->embed, (const int64_t*)W.it, 1, W.emb, d->D, B, d->D, d->V, st));
-    // the reference runs max_len + 1 timesteps and discards the last one (editnet_rl.py:503,517-518)
+    // the reference runs max_len + 1 timesteps and discards the last one (editnet_rl.py:503,517-518): seq / seq_logp do not
+    // depend on it, so the loop ends with the pick of timestep max_len - 1 (SET_DEAD_WORK=1 runs it as the reference does)
+    const int last_t = dead_work() ? max_len : max_len - 1;
     static const int fa_merge = env_int("SET_FA_MERGE", 1);
     const bool merge = fa_merge && !emb_needed;      // the token table is active: phase A does not see the token
     // the pick finishes the next timestep's attention-LSTM cell (LstmTail): its gate products ride this timestep's fc
@@ -557,15 +578,17 @@ static int rollout(const SetEditNetWeights* w, const SetEditNetDims* d, const fl
                                                  seq_logp, st);
         if (rc != SET_ERR_UNSUPPORTED) return rc;
     }
-    for (int t = 0; t <= max_len; ++t) {
+    for (int t = 0; t <= last_t; ++t) {
         Slabs lg;
         bool biased = false;
-        const bool next_a = merge && t < max_len;     // there is a next timestep to pre-launch phase A for
+        const bool next_a = merge && t < last_t;      // there is a next timestep to pre-launch phase A for
+        const bool fc_alone = merge && !next_a && t < max_len;     // last kept timestep: fc as in the merged launch
         RowGate gate;
         if (loop_gate && t > 0) gate.alive_prev = W.alive + (t - 1);
         RowGateScope gate_scope(gate);
-        SET_TRY(step_impl(w, d, X, B, W, W.it, 1, nullptr, 0, &lg, st, have_a ? a_cur : nullptr, next_a ? a_nxt : nullptr,
-                          &biased, -1, a_done));
+        // t == 0: begin_impl left h1 = c1 = h2 = c2 = 0
+        SET_TRY(step_impl(w, d, X, B, W, W.it, 1, nullptr, 0, &lg, st, have_a ? a_cur : nullptr,
+                          next_a || fc_alone ? a_nxt : nullptr, &biased, -1, a_done, t == 0 && !dead_work(), fc_alone));
         have_a = next_a;
         if (next_a) { a_cur[0] = a_nxt[0]; a_cur[1] = a_nxt[1]; }
         if (t == max_len) break;

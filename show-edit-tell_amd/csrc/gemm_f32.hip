@@ -701,6 +701,7 @@ static int launch_tile_m(const GemmProb* probs, int n) {
     const double c128 = (double)((t128 + 255) / 256) * 1.08, c64 = (double)((t64 + 255) / 256) * 0.57;
     return c64 < 0.97 * c128 ? 64 : 128;
 }
+int gemm_launch_rows(const GemmProb* probs, int n) { return n > 0 ? launch_tile_m(probs, n) : 0; }
 static int launch_tile_n(const GemmProb* probs, int n) {
     if (use_bn32(probs, n)) return 32;
     const int bm = launch_tile_m(probs, n);

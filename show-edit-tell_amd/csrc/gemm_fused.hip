@@ -146,8 +146,11 @@ __global__ void __launch_bounds__(64 * NW) gemm_fused_k(const FusedArgs P) {
 #else
     const int nkt = P.K / BK;
 #endif
+    // ENCLSTM with K == 0 (the host knows h_in is all zero: first step of a recurrence): no tile is loaded or contracted, the
+    // epilogue runs on the zero accumulators
+    const bool kloop = (EPI != EPI_ENCLSTM) || nkt > 0;
     const int frow = lane & 31, fk = (lane >> 5) * 4;
-    FS_GLOAD(ra0, rw0);                                  // tile 0
+    if (kloop) FS_GLOAD(ra0, rw0);                       // tile 0
     if (nkt > 1) FS_GLOAD(ra1, rw1);                     // tile 1
     if constexpr (ST == 4) {
         if (nkt > 2) FS_GLOAD(ra2, rw2);                 // tile 2
@@ -228,7 +231,7 @@ __global__ void __launch_bounds__(64 * NW) gemm_fused_k(const FusedArgs P) {
         }                                                                                               \
     }
 
-    FS_LSTORE(0, ra0, rw0);
+    if (kloop) FS_LSTORE(0, ra0, rw0);
     if constexpr (ST == 4) { if (nkt > 4) FS_GLOAD(ra0, rw0); }          // tile 4
     else { if (nkt > 2) FS_GLOAD(ra0, rw0); }                            // tile 2
     __syncthreads();
@@ -275,6 +278,7 @@ __global__ void __launch_bounds__(64 * NW) gemm_fused_k(const FusedArgs P) {
             if (kt == 0 && nkt >= 2) { ENC_STAGE2(); }
         }
     }
+    if (!kloop) { ENC_STAGE1(); ENC_STAGE2(); }
 #undef ENC_STAGE1
 #undef ENC_STAGE2
 #undef FS_ITER
@@ -467,11 +471,13 @@ int encoder_order(const int64_t* lens, int B, int T, int* perm, int* nactive, hi
 int fused_encoder_step(const float* h_in, float* h_out, float* c, const float* w_hh, const float* xg,
                        long long ld_xg_row, long long ld_xg_t, const float* b_extra, const int64_t* lens, int t,
                        int reverse, float* H, float* Mem, long long ld_out_b, long long ld_out_t, int out_col0, int B,
-                       int D, hipStream_t s, const int64_t* seq, int seq_T, int seq_V, const int* perm, const int* nactive) {
+                       int D, hipStream_t s, const int64_t* seq, int seq_T, int seq_V, const int* perm, const int* nactive,
+                       bool h_zero) {
     if (D % 128) return SET_ERR_UNSUPPORTED;
     FusedArgs P{};
     P.A[0] = h_in; P.lda[0] = D; P.W[0] = w_hh; P.ldw[0] = D;
-    P.K = D; P.M = B; P.N = D; P.gate_stride = D;
+    // h_zero: h_in is all zero, so h_in W_hh^T is exactly zero whatever W_hh holds: an empty contraction gives the same gates
+    P.K = h_zero ? 0 : D; P.M = B; P.N = D; P.gate_stride = D;
     P.b0 = b_extra; P.e0 = xg; P.e1 = h_in; P.o0 = h_out; P.o1 = c; P.o2 = H; P.o3 = Mem; P.lens = lens;
     P.ld_xg_row = ld_xg_row; P.ld_xg_t = ld_xg_t; P.ld_out_b = ld_out_b; P.ld_out_t = ld_out_t;
     P.t = t; P.reverse = reverse; P.out_col0 = out_col0; P.seq = seq; P.seq_T = seq_T; P.seq_V = seq_V > 0 ? seq_V : 1;

@@ -93,6 +93,8 @@ struct GemmProb {
 // similar length; problems with max_ksplit == 1 keep a fused bias/activation epilogue
 void plan_ksplit(GemmProb* probs, int n, int target_wgs);
 int gemm_group(const GemmProb* probs, int n, hipStream_t stream, const char* tag = nullptr);
+// the row-tile class (16 / 32 / 64 / 128) a grouped launch of these problems runs on
+int gemm_launch_rows(const GemmProb* probs, int n);
 // gemm_gen.hip: C (+)= a . b^T with either operand stored k-major or k-minor (training backward)
 int gemm_gen(const float* A, long long lda, int a_kminor, const float* B, long long ldb, int b_kminor, float* C,
              long long ldc, int M, int N, int K, int accumulate, void* ws, size_t ws_bytes, hipStream_t s);
@@ -244,6 +246,9 @@ struct ProfScope {
 // editnet.hip (shared host helpers)
 int env_int(const char* name, int dflt);
 int gemm_target_wgs();
+// SET_DEAD_WORK=1: the free-running loops run the reference's discarded last timestep and the all-zero products of the
+// first one again (decode loops of editnet.hip / dcnet.hip, encoder step at t == 0), as they did before; outputs are the same
+int dead_work();
 GemmProb slab_prob(float* slab, int M, int N, int Bmax);
 GemmProb direct_prob(float* out, long long ldo, int M, int N, const float* bias, int act);
 int editnet_encoder(const SetEditNetWeights* w, const int64_t* seq, const int64_t* lens, float* H, float* Mem,
@@ -380,7 +385,7 @@ int fused_encoder_step(const float* h_in, float* h_out, float* c, const float* w
                        long long ld_xg_row, long long ld_xg_t, const float* b_extra, const int64_t* lens, int t,
                        int reverse, float* H, float* Mem, long long ld_out_b, long long ld_out_t, int out_col0, int B,
                        int D, hipStream_t s, const int64_t* seq = nullptr, int seq_T = 0, int seq_V = 0, const int* perm = nullptr,
-                       const int* nactive = nullptr);
+                       const int* nactive = nullptr, bool h_zero = false);
 int encoder_order(const int64_t* lens, int B, int T, int* perm, int* nactive, hipStream_t s);
 
 // epilogue.hip
