@@ -238,6 +238,36 @@ int set_editnet_xe_forward(const SetEditNetWeights* w, const SetEditNetDims* d, 
                            const int64_t* prevlen, float* predictions, void* ws, size_t ws_bytes,
                            void* stream);
 
+/* Edit trace: the per-word record behind the reference's headline figure (demo.png) — the attention over the existing caption,
+ * the one position SelectC's hard choice took (editnet.py:403-421) and how far the Copy-LSTM copied the selected memory instead
+ * of editing it (editnet.py:281-283) — of a teacher-forced, no-grad decode of GIVEN token sequences.  The recurrent state depends
+ * on the token prefix only, so the forced decode of the tokens a search returned (greedy, sampled, beam, ensemble) or of a
+ * ground-truth caption repeats the steps that produced them; the persistent launches are not tapped.
+ * Step t (0 <= t < S) feeds tokens[b, t] (tokens[b, 0] = <start>; row stride ld_tokens >= S + 1); its record describes how
+ * tokens[b, t+1] was produced.  Row b is recorded for t < n_steps[b] (device, B int32, clamped to [0, S]); steps at or beyond
+ * n_steps[b] hold 0, with select = -1.  All B rows step together (no sorting, no shrinking batch) on the per-step kernels:
+ * set_editnet_begin, then S times set_editnet_step's kernels (token table when attached, region mask when adaptive) followed by
+ * gate_cnew(c_new) as one grouped GEMM and ONE record launch (csrc/edit_trace.hip); no host synchronisation, fixed reduction
+ * orders.  S <= d->maxT.  Outputs (device, fully overwritten): */
+typedef struct {
+  float*   alpha_c;    /* (B, S, T)  caption-attention weights; columns >= max prev length of the batch are 0 */
+  int32_t* select;     /* (B, S)     arg-max position of alpha_c (first index on ties) = SelectC's hard choice */
+  float*   copy_gate;  /* (B, S)     mean over D of sigmoid(gate_cnew(c_new) + gate_cmem(selected memory)) */
+  float*   gate_full;  /* (B, S, D)  the gate itself; may be NULL */
+  float*   alpha_v;    /* (B, S, R)  visual attention weights; masked / truncated regions 0 (adaptive); may be NULL */
+  float*   logp;       /* (B, S)     log_softmax(logits of step t)[tokens[b, t+1]] */
+} SetEditTrace;
+/* `ws`: set_editnet_workspace_bytes(d) as for every decode (unchanged); `trace_ws`: the trace's own scratch (the gate product's
+ * split-K partials), set_editnet_edit_trace_workspace_bytes(d, S) bytes (0: dims / S not admitted), 16-byte aligned.
+ * SET_ERR_ARG (null pointers, S < 1, S > d->maxT, ld_tokens < S + 1), SET_ERR_UNSUPPORTED (dimensions the step does not admit)
+ * and SET_ERR_WORKSPACE are answered before anything is touched.  Parity: tests/test_hip_edit_trace.py against the oracle's
+ * per-step trace. */
+size_t set_editnet_edit_trace_workspace_bytes(const SetEditNetDims* d, int S);
+int set_editnet_edit_trace(const SetEditNetWeights* w, const SetEditNetDims* d, const float* X, const float* image_mean,
+                           const int64_t* prev, const int64_t* prevlen, const int64_t* tokens, int64_t ld_tokens,
+                           const int32_t* n_steps, int S, const SetEditTrace* out, void* ws, size_t ws_bytes,
+                           void* trace_ws, size_t trace_ws_bytes, void* stream);
+
 /* Debug / module-API accessor: device pointer of a named workspace tensor (NULL if unknown).
  * names: "H" (B,T,D) "M" (B,T,D) "final_hidden" (B,D) "mask" (B,T) "att1" (B,R,A) "att1_c" (B,T,A)
  * "image_mean" (B,F) "h1" "c1" "h2" "c2" "emb" "ctx_cap" "attend_cap" "sel" (B,D) "attend_img" (B,F)

@@ -80,6 +80,11 @@ class EditNetWeights(C.Structure):
     _fields_ = [(f, C.c_void_p) for f, _ in EDITNET_WEIGHT_FIELDS] + [("tok_table", C.c_void_p)]
 
 
+class EditTrace(C.Structure):
+    """include/set_hip.h SetEditTrace: output pointers of set_editnet_edit_trace (gate_full / alpha_v may be NULL)"""
+    _fields_ = [(n, C.c_void_p) for n in ("alpha_c", "select", "copy_gate", "gate_full", "alpha_v", "logp")]
+
+
 class ProfileEntry(C.Structure):
     _fields_ = [("tag", C.c_char * 32), ("launches", C.c_int), ("ms", C.c_double), ("flops", C.c_double),
                 ("bytes", C.c_double)]
@@ -223,6 +228,9 @@ PROTOTYPES = {
                                 _P, _P, _Z, _P]),
     "set_editnet_xe_forward": (_I, [C.POINTER(EditNetWeights), C.POINTER(EditNetDims), _P, _P, _P, _L,
                                     C.POINTER(C.c_int), _P, _P, _P, _P, _Z, _P]),
+    "set_editnet_edit_trace_workspace_bytes": (_Z, [C.POINTER(EditNetDims), _I]),
+    "set_editnet_edit_trace": (_I, [C.POINTER(EditNetWeights), C.POINTER(EditNetDims), _P, _P, _P, _P, _P, _L, _P, _I,
+                                    C.POINTER(EditTrace), _P, _Z, _P, _Z, _P]),
     "set_editnet_ws_tensor": (_P, [C.POINTER(EditNetDims), _P, C.c_char_p]),
     "set_dcnet_workspace_bytes": (_Z, [C.POINTER(DcnetDims)]),
     "set_dcnet_token_table_bytes": (_Z, [C.POINTER(DcnetDims)]),

@@ -704,6 +704,69 @@ int set_editnet_xe_forward(const SetEditNetWeights* w, const SetEditNetDims* d, 
     return SET_OK;
 }
 
+// Edit trace: forced decode of given tokens that records every step (kernel: edit_trace.hip).  The trace's only scratch is the
+// split-K slab region of gate_cnew(c_new); it lives in the caller's trace_ws so that set_editnet_workspace_bytes stays as it is.
+static size_t edit_trace_ws_bytes(const SetEditNetDims* d) {
+    return round_up(sizeof(float) * (size_t)GEMM_MAX_KSPLIT * d->B * d->D, 256);
+}
+
+size_t set_editnet_edit_trace_workspace_bytes(const SetEditNetDims* d, int S) {
+    if (check_dims(d) != SET_OK || S < 1 || S > d->maxT) return 0;
+    return edit_trace_ws_bytes(d) + 256;
+}
+
+int set_editnet_edit_trace(const SetEditNetWeights* w, const SetEditNetDims* d, const float* X, const float* image_mean,
+                           const int64_t* prev, const int64_t* prevlen, const int64_t* tokens, int64_t ld_tokens,
+                           const int32_t* n_steps, int S, const SetEditTrace* out, void* ws, size_t ws_bytes,
+                           void* trace_ws, size_t trace_ws_bytes, void* stream) {
+    if (!w || !d || !X || !prev || !prevlen || !tokens || !n_steps || !out) return SET_ERR_ARG;
+    if (!out->alpha_c || !out->select || !out->copy_gate || !out->logp) return SET_ERR_ARG;
+    if (S < 1 || S > d->maxT || ld_tokens < (int64_t)S + 1) return SET_ERR_ARG;
+    EditNetWs W;
+    SET_TRY(prep(d, ws, ws_bytes, &W));
+    if (!trace_ws || !aligned16(trace_ws)) return SET_ERR_ARG;
+    if (trace_ws_bytes < edit_trace_ws_bytes(d)) return SET_ERR_WORKSPACE;
+    // (nothing has been touched up to here)
+    hipStream_t st = (hipStream_t)stream;
+    const int B = d->B, D = d->D, V = d->V;
+    const int tgt = gemm_target_wgs();
+    float* sG = static_cast<float*>(trace_ws);
+    SET_TRY(begin_impl(w, d, X, image_mean, prev, prevlen, W, st));
+    // the loop of the free-running decode on the per-step kernels (rollout above) with the forced token in place of the pick:
+    // with the token table fc(h2_t) and the phase-A products of t + 1 ride one launch, the last step's fc keeps that launch's plan
+    const bool emb_needed = !(w->tok_table && (D % 64 == 0) && env_int("SET_NO_FUSED", 0) == 0);
+    static const int fa_merge = env_int("SET_FA_MERGE", 1);
+    const bool merge = fa_merge && !emb_needed;
+    GemmProb a_cur[2], a_nxt[2];
+    bool have_a = false;
+    for (int t = 0; t < S; ++t) {
+        const int64_t* tok_t = tokens + t;
+        if (emb_needed) SET_TRY(embed_relu(w->embed, tok_t, ld_tokens, W.emb, D, B, D, V, st));
+        const bool next_a = merge && t + 1 < S;
+        const bool fc_alone = merge && !next_a;
+        Slabs lg;
+        bool biased = false;
+        SET_TRY(step_impl(w, d, X, B, W, (const long long*)tok_t, ld_tokens, nullptr, 0, &lg, st, have_a ? a_cur : nullptr,
+                          next_a || fc_alone ? a_nxt : nullptr, &biased, -1, false, t == 0 && !dead_work(), fc_alone));
+        have_a = next_a;
+        if (next_a) { a_cur[0] = a_nxt[0]; a_cur[1] = a_nxt[1]; }
+        // the gate's only missing contraction (from 17 rows the step computes it inside fused_copy_gate_pre and keeps nothing)
+        GemmProb e = slab_prob(sG, B, D, B);
+        e.add(W.c_new, D, w->cl_cnew_w, D, D);
+        plan_ksplit(&e, 1, tgt);
+        SET_TRY(gemm_group(&e, 1, st, "gemm:trace cnew"));
+        EditTraceStep r;
+        r.alpha_c = W.alpha_c; r.alpha_v = W.alpha;
+        r.gn = slabs_of(e); r.bn = w->cl_cnew_b; r.cmem_pre = W.cmem_pre; r.bm = w->cl_cmem_b;
+        r.logits = lg; r.fc_bias = biased ? nullptr : w->fc_b;
+        r.tokens = (const long long*)tokens; r.ld_tokens = ld_tokens; r.n_steps = n_steps;
+        r.t = t; r.S = S; r.T = d->T; r.R = d->R; r.D = D; r.V = V;
+        r.out = *out;
+        SET_TRY(edit_trace_record(r, B, st));
+    }
+    return SET_OK;
+}
+
 size_t set_editnet_token_table_bytes(const SetEditNetDims* d) {
     if (check_dims(d) != SET_OK) return 0;
     return sizeof(float) * (size_t)d->V * 10 * d->D;

@@ -415,6 +415,26 @@ int sample_pick(Slabs logits, const float* bias, int V, int t, int max_len, long
                 float* step_logp, hipStream_t s, const LstmTail* tail = nullptr);
 int sample_logp_bwd(const float* logits, long long ld, const float* lse, const long long* ids, const float* g,
                     float* dlogits, long long ldd, int B, int V, hipStream_t s);
+// edit_trace.hip: the record of ONE forced timestep (set_editnet_edit_trace), taken from what the step left in the workspace.
+// One workgroup per row: copies the two attention rows, first-index arg-max of alpha_c, the copy gate
+// sigmoid((gn + bn) + (cmem_pre + bm)) with its mean over D, log-sum-exp of the logits (slabs in index order, + bias) and the
+// forced token's log-probability.  Rows with t >= n_steps[b] get zeros and select = -1.
+struct EditTraceStep {
+    const float* alpha_c;       // (B, T) this step's caption-attention weights
+    const float* alpha_v;       // (B, R) this step's visual attention weights
+    Slabs gn;                   // gate_cnew(c_new) partials (B, D), bias bn not added
+    const float* bn;
+    const float* cmem_pre;      // (B, D) gate_cmem(sel) without its bias bm
+    const float* bm;
+    Slabs logits;               // (B, V) partials; fc_bias == NULL: already included
+    const float* fc_bias;
+    const long long* tokens;    // (B, ld_tokens) forced tokens; the step's target is column t + 1
+    long long ld_tokens;
+    const int* n_steps;         // (B)
+    int t, S, T, R, D, V;
+    SetEditTrace out;
+};
+int edit_trace_record(const EditTraceStep& a, int B, hipStream_t s);
 int philox_fill(uint32_t* out, int n, unsigned long long seed, unsigned long long offset, hipStream_t s);
 int iota_i64(long long* p, int n, hipStream_t s);
 int set_tokens(long long* it, long long value, int* unfinished, int* alive, int n_alive, int B,

@@ -166,19 +166,30 @@ def _fused_beam(models, NI, k, V, word_map, dev, max_steps, poll=4, return_score
     return (out, out_scores) if return_scores else out
 
 
+def _with_trace(result, batched, return_scores, decoder, X, prev, plen, word_map, image_mean=None):
+    """return_trace=True: the search's result + the EditTrace of the returned sequences (one forced decode of NI rows after
+    the search; evaluate.edit_trace).  result: (tokens, score) of a per-image entry, the token lists (or (lists, scores)) of
+    a batched one."""
+    seqs = (result[0] if return_scores else result) if batched else [result[0]]
+    tr = edit_trace(decoder, X, prev, plen, word_map, seqs, image_mean=image_mean)
+    return (tuple(result) + (tr,)) if (not batched or return_scores) else (result, tr)
+
+
 @torch.no_grad()
 def beam_search_editnet_batched(decoder, image_features, previous_caption, prev_caplen, word_map, beam_size=3,
-                                max_steps=50, return_scores=False):
+                                max_steps=50, return_scores=False, return_trace=False):
     """image_features (NI,R,F), previous_caption (NI,T), prev_caplen (NI,1) -> list of NI token lists
     (with return_scores: also the list of their scores; NaN where the step limit was hit).  The attention LSTM sees the mean
-    over all R regions; adaptive features (zero-padded regions, an image mean per image): beam_search_adaptive_batched."""
+    over all R regions; adaptive features (zero-padded regions, an image mean per image): beam_search_adaptive_batched.
+    return_trace: the result gains the EditTrace of the returned sequences as its last element."""
     decoder.eval()
     X = image_features.float().contiguous()
     prev = previous_caption.long().contiguous()
     plen = prev_caplen.reshape(-1).long().contiguous()
     m = _FusedEditNet(decoder, X, prev, plen, beam_size, max_steps)
-    return _fused_beam([m], X.shape[0], beam_size, decoder.vocab_size, word_map, X.device, max_steps,
-                       return_scores=return_scores)
+    res = _fused_beam([m], X.shape[0], beam_size, decoder.vocab_size, word_map, X.device, max_steps,
+                      return_scores=return_scores)
+    return _with_trace(res, True, return_scores, decoder, X, prev, plen, word_map) if return_trace else res
 
 
 @torch.no_grad()
@@ -194,9 +205,10 @@ def beam_search_dcnet_batched(dae, previous_caption, prev_caplen, word_map, beam
 
 @torch.no_grad()
 def beam_search_ensemble_batched(decoder, dae, image_features, previous_caption, prev_caplen, word_map, beam_size=3,
-                                 max_steps=50, return_scores=False):
+                                 max_steps=50, return_scores=False, return_trace=False):
     """eval_full.py:88-218 for NI images at once: both models step on the same words, the epilogue averages
-    their softmax probabilities.  Fixed features (image mean over all R regions); adaptive features: beam_search_adaptive*."""
+    their softmax probabilities.  Fixed features (image mean over all R regions); adaptive features: beam_search_adaptive*.
+    return_trace: the result gains, as its last element, EditNet's view of the jointly chosen words (their EditTrace)."""
     decoder.eval()
     dae.eval()
     X = image_features.float().contiguous()
@@ -204,8 +216,9 @@ def beam_search_ensemble_batched(decoder, dae, image_features, previous_caption,
     plen = prev_caplen.reshape(-1).long().contiguous()
     e = _FusedEditNet(decoder, X, prev, plen, beam_size, max_steps)
     d = _FusedDcnet(dae, prev, plen, beam_size, max_steps)
-    return _fused_beam([e, d], X.shape[0], beam_size, decoder.vocab_size, word_map, X.device, max_steps,
-                       return_scores=return_scores)
+    res = _fused_beam([e, d], X.shape[0], beam_size, decoder.vocab_size, word_map, X.device, max_steps,
+                      return_scores=return_scores)
+    return _with_trace(res, True, return_scores, decoder, X, prev, plen, word_map) if return_trace else res
 
 
 # ------------------------------------------------------------------------------------------------
@@ -293,16 +306,19 @@ def _beam_search_editnet_persistent(decoder, image_features, previous_caption, p
     return out.answer(word_map, "set_editnet_beam_persistent")
 
 
-def beam_search_editnet(decoder, image_features, previous_caption, prev_caplen, word_map, beam_size=3):
+def beam_search_editnet(decoder, image_features, previous_caption, prev_caplen, word_map, beam_size=3, return_trace=False):
     """The reference's own calling convention, ONE image per call (editnet.py:601-613).  k <= 4 with the token table
     active: one persistent launch (csrc/decode_persistent_wide.hip, beam mode); otherwise the NI = 1 case of the batched
-    search.  Adaptive features (an image mean per image, zero-padded regions): beam_search_adaptive."""
+    search.  Adaptive features (an image mean per image, zero-padded regions): beam_search_adaptive.
+    return_trace: (tokens, score, EditTrace of the returned tokens)."""
     one = _beam_search_editnet_persistent(decoder, image_features, previous_caption, prev_caplen, word_map, beam_size)
-    if one is not None:
-        return one
-    seqs, scores = beam_search_editnet_batched(decoder, image_features, previous_caption, prev_caplen, word_map,
-                                               beam_size, return_scores=True)
-    return seqs[0], scores[0]
+    if one is None:
+        seqs, scores = beam_search_editnet_batched(decoder, image_features, previous_caption, prev_caplen, word_map,
+                                                   beam_size, return_scores=True)
+        one = seqs[0], scores[0]
+    if return_trace:
+        return _with_trace(one, False, True, decoder, image_features, previous_caption, prev_caplen, word_map)
+    return one
 
 
 @torch.no_grad()
@@ -402,15 +418,19 @@ def _beam_search_ensemble_persistent(decoder, dae, image_features, previous_capt
     return out.answer(word_map, "set_ensemble_beam_persistent")
 
 
-def beam_search_ensemble(decoder, dae, image_features, previous_caption, prev_caplen, word_map, beam_size=3):
+def beam_search_ensemble(decoder, dae, image_features, previous_caption, prev_caplen, word_map, beam_size=3,
+                         return_trace=False):
     """The reference's published protocol, ONE image per call (eval_full.py:88-237).  k <= 4 with both token tables active: one
-    persistent launch (csrc/decode_persistent_ensemble.hip); otherwise the NI = 1 case of the batched search."""
+    persistent launch (csrc/decode_persistent_ensemble.hip); otherwise the NI = 1 case of the batched search.
+    return_trace: (tokens, score, EditNet's EditTrace of the jointly chosen tokens)."""
     one = _beam_search_ensemble_persistent(decoder, dae, image_features, previous_caption, prev_caplen, word_map, beam_size)
-    if one is not None:
-        return one
-    seqs, scores = beam_search_ensemble_batched(decoder, dae, image_features, previous_caption, prev_caplen, word_map,
-                                                beam_size, return_scores=True)
-    return seqs[0], scores[0]
+    if one is None:
+        seqs, scores = beam_search_ensemble_batched(decoder, dae, image_features, previous_caption, prev_caplen, word_map,
+                                                    beam_size, return_scores=True)
+        one = seqs[0], scores[0]
+    if return_trace:
+        return _with_trace(one, False, True, decoder, image_features, previous_caption, prev_caplen, word_map)
+    return one
 
 
 # ------------------------------------------------------------------------------------------------
@@ -432,7 +452,7 @@ def _adaptive_args(decoder, image_features, image_mean):
 
 @torch.no_grad()
 def beam_search_adaptive_batched(decoder, image_features, image_mean, previous_caption, prev_caplen, word_map, beam_size=3,
-                                 max_steps=50, return_scores=False):
+                                 max_steps=50, return_scores=False, return_trace=False):
     """image_features (NI,R,F) zero-padded regions, image_mean (NI,F), previous_caption (NI,T), prev_caplen (NI,1) ->
     list of NI token lists (with return_scores: also their scores; NaN where the step limit was hit).  NI images at once
     on the per-step fused kernels."""
@@ -441,18 +461,142 @@ def beam_search_adaptive_batched(decoder, image_features, image_mean, previous_c
     prev = previous_caption.long().contiguous()
     plen = prev_caplen.reshape(-1).long().contiguous()
     m = _FusedEditNet(decoder, X, prev, plen, beam_size, max_steps, image_mean=mean)
-    return _fused_beam([m], X.shape[0], beam_size, decoder.vocab_size, word_map, X.device, max_steps,
-                       return_scores=return_scores)
+    res = _fused_beam([m], X.shape[0], beam_size, decoder.vocab_size, word_map, X.device, max_steps,
+                      return_scores=return_scores)
+    return _with_trace(res, True, return_scores, decoder, X, prev, plen, word_map, image_mean=mean) if return_trace else res
 
 
-def beam_search_adaptive(decoder, image_features, image_mean, previous_caption, prev_caplen, word_map, beam_size=3):
+def beam_search_adaptive(decoder, image_features, image_mean, previous_caption, prev_caplen, word_map, beam_size=3,
+                         return_trace=False):
     """The reference's adaptive evaluate(), ONE image per call (editnet_adaptive.py:620-735) -> (tokens, score).  k <= 4
     with the token table active: one persistent launch (beam mode over up to 128 masked regions, even R); otherwise the
     NI = 1 case of beam_search_adaptive_batched."""
     X, mean = _adaptive_args(decoder, image_features, image_mean)
     one = _beam_search_editnet_persistent(decoder, X, previous_caption, prev_caplen, word_map, beam_size, image_mean=mean)
-    if one is not None:
-        return one
-    seqs, scores = beam_search_adaptive_batched(decoder, X, mean, previous_caption, prev_caplen, word_map, beam_size,
-                                                return_scores=True)
-    return seqs[0], scores[0]
+    if one is None:
+        seqs, scores = beam_search_adaptive_batched(decoder, X, mean, previous_caption, prev_caplen, word_map, beam_size,
+                                                    return_scores=True)
+        one = seqs[0], scores[0]
+    if return_trace:
+        return _with_trace(one, False, True, decoder, X, previous_caption, prev_caplen, word_map, image_mean=mean)
+    return one
+
+
+# ------------------------------------------------------------------------------------------------
+# Edit trace: the per-word record behind the reference's demo figure — attention over the existing caption, the position the
+# hard selection took, and whether the Copy-LSTM copied the selected memory or edited it.  The recurrent state depends on
+# the token prefix only, so the trace of ANY decoder output (greedy, sampled, beam, ensemble, a ground-truth caption) is the
+# teacher-forced, no-grad decode of those tokens (include/set_hip.h set_editnet_edit_trace; per-step kernels, the
+# persistent launches are not tapped).  EditNet only: DCNet has neither a selection nor a copy gate.
+# ------------------------------------------------------------------------------------------------
+class EditTrace:
+    """Record of a forced decode of `tokens` (B, S + 1; `<start>` first): step t describes how tokens[b, t + 1] was produced.
+    alpha_c (B, S, T) caption-attention weights, select (B, S) int32 its arg-max position (-1 where t >= n_steps[b]),
+    copy_gate (B, S) mean over D of the Copy-LSTM's gate, gate_full (B, S, D) the gate, alpha_v (B, S, R) visual attention
+    weights, logp (B, S) log-probability of the forced word; everything at t >= n_steps[b] is 0."""
+
+    def __init__(self, alpha_c, select, copy_gate, gate_full, alpha_v, logp, n_steps, tokens, previous_caption):
+        self.alpha_c, self.select, self.copy_gate, self.gate_full = alpha_c, select, copy_gate, gate_full
+        self.alpha_v, self.logp, self.n_steps, self.tokens = alpha_v, logp, n_steps, tokens
+        self.previous_caption = previous_caption
+
+    @property
+    def copied(self):
+        """(B, S) bool: the produced word IS the selected word of the previous caption (the figure's copy / edit label)."""
+        sel = self.select.long()
+        live = sel >= 0
+        picked = self.previous_caption.long().gather(1, sel.clamp(min=0))
+        return live & (self.tokens[:, 1:sel.shape[1] + 1] == picked)
+
+    def rows(self, word_map):
+        """per image: [(word, selected previous word, copy_gate, copied)] for its n_steps recorded steps"""
+        rev = {v: k for k, v in word_map.items()}
+        tok, prev = self.tokens.cpu().tolist(), self.previous_caption.cpu().tolist()
+        sel, gate, cop = self.select.cpu().tolist(), self.copy_gate.cpu().tolist(), self.copied.cpu().tolist()
+        out = []
+        for b, n in enumerate(self.n_steps.cpu().tolist()):
+            out.append([(rev[tok[b][t + 1]], rev[prev[b][sel[b][t]]], float(gate[b][t]), bool(cop[b][t])) for t in range(n)])
+        return out
+
+
+def tokens_from_greedy(seq, word_map):
+    """(B, max_len) greedy / sampled output -> forced token lists: `<start>` in front and, for rows that ended before
+    max_len, `<end>` behind (the decode loops store `<end>` as 0, editnet_rl.py:531)."""
+    start, end = int(word_map['<start>']), int(word_map['<end>'])
+    rows = seq.cpu().tolist() if torch.is_tensor(seq) else [list(map(int, r)) for r in seq]
+    out = []
+    for r in rows:
+        n = r.index(0) if 0 in r else len(r)
+        out.append([start] + [int(x) for x in r[:n]] + ([end] if n < len(r) else []))
+    return out
+
+
+def _forced_tokens(tokens, lengths, dev):
+    """token lists | (B, L) tensor + lengths -> (tokens (B, S + 1) int64 zero-padded, n_steps (B) int32, S) with
+    n_steps[b] = len(tokens[b]) - 1 and S = the largest of them (at least 1)"""
+    if torch.is_tensor(tokens):
+        if lengths is None:
+            raise ValueError("edit_trace: a token tensor needs `lengths` (tokens per row, <start> included)")
+        lens = torch.as_tensor(lengths).reshape(-1).cpu().long()
+        if lens.numel() != tokens.shape[0] or int(lens.min()) < 1 or int(lens.max()) > tokens.shape[1]:
+            raise ValueError("edit_trace: lengths must be B values in [1, %d]" % tokens.shape[1])
+        S = max(1, int(lens.max()) - 1)
+        tok = torch.zeros(tokens.shape[0], S + 1, dtype=torch.long)
+        src = tokens.cpu().long()
+        keep = torch.arange(S + 1)[None, :] < lens[:, None]
+        w = min(S + 1, src.shape[1])
+        tok[:, :w] = src[:, :w] * keep[:, :w]
+    else:
+        rows = [[int(x) for x in r] for r in tokens]
+        if not rows or min(len(r) for r in rows) < 1:
+            raise ValueError("edit_trace: every token list starts with <start>")
+        lens = torch.tensor([len(r) for r in rows], dtype=torch.long)
+        S = max(1, int(lens.max()) - 1)
+        tok = torch.zeros(len(rows), S + 1, dtype=torch.long)
+        for b, r in enumerate(rows):
+            tok[b, :len(r)] = torch.tensor(r, dtype=torch.long)
+    return tok.to(dev), (lens - 1).to(torch.int32).to(dev), S
+
+
+@torch.no_grad()
+def edit_trace(decoder, image_features, previous_caption, prev_caplen, word_map, tokens, image_mean=None, lengths=None):
+    """Forced, no-grad decode of `tokens` that records every step -> EditTrace.  tokens: a list of B token lists as the beam
+    searches return them (`<start>` ... `<end>`, or cut at the step limit; see tokens_from_greedy for greedy output), or a
+    (B, L) tensor with `lengths` (B) tokens per row.  image_mean (B, F) selects the adaptive model's image input exactly as
+    beam_search_adaptive* takes it (None: the mean over all R regions)."""
+    import ctypes as C
+    from . import _lib
+    from ._lib import check, ptr, stream_of
+    decoder.eval()
+    lib = _lib.load()
+    X = image_features.float().contiguous()
+    dev = X.device
+    prev = previous_caption.long().contiguous()
+    plen = prev_caplen.reshape(-1).long().contiguous()
+    if getattr(decoder, "_adaptive", 0):
+        X, mean = _adaptive_args(decoder, X, image_mean)
+    else:
+        mean = None if image_mean is None else image_mean.to(dev).float().contiguous()
+    tok, n_steps, S = _forced_tokens(tokens, lengths, dev)
+    B, R = X.shape[0], X.shape[1]
+    if tok.shape[0] != B or prev.shape[0] != B or plen.shape[0] != B:
+        raise ValueError("edit_trace: %d token rows for %d images / %d previous captions" % (tok.shape[0], B, prev.shape[0]))
+    if int(tok.min()) < 0 or int(tok.max()) >= decoder.vocab_size:
+        raise ValueError("edit_trace: token outside the vocabulary")
+    T, D = prev.shape[1], decoder.decoder_dim
+    dims = decoder._dims(B, T, R, S)
+    w = decoder._weights(dims)
+    ws = decoder._workspace(dims)
+    n = lib.set_editnet_edit_trace_workspace_bytes(C.byref(dims), S)
+    if n == 0:
+        raise _lib.SetError("edit_trace: unsupported dims")
+    tws = torch.empty(n, dtype=torch.uint8, device=dev)
+    f32 = dict(dtype=torch.float32, device=dev)
+    tr = EditTrace(torch.empty(B, S, T, **f32), torch.empty(B, S, dtype=torch.int32, device=dev), torch.empty(B, S, **f32),
+                   torch.empty(B, S, D, **f32), torch.empty(B, S, R, **f32), torch.empty(B, S, **f32), n_steps, tok, prev)
+    out = _lib.EditTrace(alpha_c=tr.alpha_c.data_ptr(), select=tr.select.data_ptr(), copy_gate=tr.copy_gate.data_ptr(),
+                         gate_full=tr.gate_full.data_ptr(), alpha_v=tr.alpha_v.data_ptr(), logp=tr.logp.data_ptr())
+    check(lib.set_editnet_edit_trace(C.byref(w), C.byref(dims), ptr(X), None if mean is None else ptr(mean), ptr(prev), ptr(plen),
+                                     ptr(tok), tok.shape[1], ptr(n_steps), S, C.byref(out), ptr(ws), ws.numel(), ptr(tws),
+                                     tws.numel(), stream_of(dev)), "set_editnet_edit_trace")
+    return tr
