@@ -49,6 +49,7 @@ struct EditNetWs {
     // prologue scratch
     float *enc_h, *enc_c, *xg, *emb_seq, *fe, *s_enc, *s_aff, *s_pre;
     int* enc_order;                   // [perm (B) | nactive (T)] of the length-ordered encoder
+    int *pro_rows, *pro_count;        // valid caption rows b*T + t (t < len[b]) of the hoisted projections, and how many (inside sF0)
     char* enc_bar;                    // barrier words of the persistent encoder
     float* pd_pv;                     // persistent small-batch decode (decode_persistent_wide.hip): X x2h[:, 2D:]^T (B, R, 4D) ...
     char* pd_x;                       // ... and its exchange region
@@ -70,8 +71,15 @@ static EditNetWs carve(const SetEditNetDims* d, void* base) {
     const size_t B = d->B, T = d->T, R = d->R, F = d->F, D = d->D, A = d->A, V = d->V;
     const size_t KS = GEMM_MAX_KSPLIT;
     const size_t Vp = round_up(V, 64);
+    // (what begin_impl clears, back to back: one fill)
     w.H = c.take<float>(B * T * D);
     w.Mem = c.take<float>(B * T * D);
+    w.enc_h = c.take<float>(B * D);
+    w.enc_c = c.take<float>(B * D);
+    w.h1 = c.take<float>(B * D);
+    w.c1 = c.take<float>(B * D);
+    w.h2 = c.take<float>(B * D);
+    w.c2 = c.take<float>(B * D);
     w.final_hidden = c.take<float>(B * D);
     w.mask = c.take<float>(B * T);
     w.att1 = c.take<float>(B * R * A);
@@ -81,10 +89,6 @@ static EditNetWs carve(const SetEditNetDims* d, void* base) {
     w.rmask = c.take<float>(B * R);
     w.cap_proj = c.take<float>(B * T * 2 * D);
     w.mem_proj = c.take<float>(B * T * D);
-    w.h1 = c.take<float>(B * D);
-    w.c1 = c.take<float>(B * D);
-    w.h2 = c.take<float>(B * D);
-    w.c2 = c.take<float>(B * D);
     w.emb = c.take<float>(B * D);
     w.ctx_cap = c.take<float>(B * D);
     w.attend_cap = c.take<float>(B * D);
@@ -112,8 +116,6 @@ static EditNetWs carve(const SetEditNetDims* d, void* base) {
     w.sD0 = c.take<float>(KS * B * 4 * D);
     w.sE0 = c.take<float>(KS * B * D);
     w.sF0 = c.take<float>(KS * B * Vp);
-    w.enc_h = c.take<float>(B * D);
-    w.enc_c = c.take<float>(B * D);
     w.xg = c.take<float>(B * T * 4 * D);
     const size_t seq_rows = B * (T > (size_t)d->maxT ? T : (size_t)d->maxT);
     w.emb_seq = c.take<float>(seq_rows * D);
@@ -122,6 +124,11 @@ static EditNetWs carve(const SetEditNetDims* d, void* base) {
     w.s_aff = c.take<float>(KS * B * D);
     w.s_pre = c.take<float>(KS * B * 4 * D);
     w.enc_order = c.take<int>(B + T);
+    // the row list lives only from the encoder's row-ranking launch to the cap projections launch of the same prologue: it
+    // borrows the head of fc's slab region, which nothing touches before the first timestep's fc ((B*T + 1) ints <=
+    // KS * B * Vp floats: T <= 256, Vp >= 64), so the workspace keeps its size
+    w.pro_rows = reinterpret_cast<int*>(w.sF0);
+    w.pro_count = w.pro_rows + B * T;
     w.enc_bar = c.take<char>(persistent_encoder_bar_bytes());
     {
         const size_t pb = B <= (size_t)PDW_MAXB ? B : 0;             // only small batches take the persistent decode
@@ -176,7 +183,8 @@ int zero_runs(float* const* p, const size_t* n, int cnt, hipStream_t st) {
 // t < len[b]; H / Mem rows beyond a caption's length stay zero; mask = (Mem.sum(2) != 0).
 int editnet_encoder(const SetEditNetWeights* w, const int64_t* seq, const int64_t* lens, float* H, float* Mem,
                     float* final_hidden, float* mask, int B, int T, int D, int V, float* emb_seq, float* xg,
-                    float* enc_h, float* enc_c, float* s_enc, float* s_aff, hipStream_t st, int* order, void* enc_bar) {
+                    float* enc_h, float* enc_c, float* s_enc, float* s_aff, hipStream_t st, int* order, void* enc_bar,
+                    ProRows* pro, bool zeroed) {
     const int tgt = gemm_target_wgs();
     const bool fused = (D % 128 == 0) && env_int("SET_NO_FUSED", 0) == 0;
     // with the token table the hoisted input projection x W_xh^T + b_xh is a row gather done by the step kernel
@@ -187,7 +195,7 @@ int editnet_encoder(const SetEditNetWeights* w, const int64_t* seq, const int64_
         p.add(emb_seq, D, w->enc_x2h_w, D, D);
         SET_TRY(gemm_group(&p, 1, st, "gemm:enc x2h"));
     }
-    {
+    if (!zeroed) {
         float* zp[4] = {H, Mem, enc_h, enc_c};
         const size_t zn[4] = {(size_t)B * T * D, (size_t)B * T * D, (size_t)B * D, (size_t)B * D};
         SET_TRY(zero_runs(zp, zn, 4, st));
@@ -200,7 +208,8 @@ int editnet_encoder(const SetEditNetWeights* w, const int64_t* seq, const int64_
     int *perm = nullptr, *nactive = nullptr;
     if (fused && order && skip && B <= 4096) {
         perm = order; nactive = order + B;
-        SET_TRY(encoder_order(lens, B, T, perm, nactive, st));
+        SET_TRY(encoder_order(lens, B, T, perm, nactive, st, pro));       // (+ the prologue's row list, in the same launch)
+        if (pro) pro->built = true;
     }
     // the whole recurrence as ONE weights-stationary launch (encoder_persistent.hip) when the shape allows it
     bool persistent = fused && perm && enc_bar && persistent_encoder_ok(B, D, T);
@@ -254,16 +263,27 @@ static int begin_impl(const SetEditNetWeights* w, const SetEditNetDims* d, const
                       const int64_t* prev, const int64_t* prevlen, EditNetWs& ws, hipStream_t st, bool beam_pv = false) {
     const int B = d->B, T = d->T, R = d->R, F = d->F, D = d->D, A = d->A;
     const int tgt = gemm_target_wgs();
-    // ---- caption encoder (editnet.py:319-348)
-    SET_TRY(editnet_encoder(w, prev, prevlen, ws.H, ws.Mem, ws.final_hidden, ws.mask, B, T, D, d->V, ws.emb_seq, ws.xg,
-                            ws.enc_h, ws.enc_c, ws.s_enc, ws.s_aff, st, ws.enc_order, ws.enc_bar));
-    // ---- hoisted, loop-invariant projections (eval mode)
     {
-        // one grouped launch over the encoder outputs: att1_c (editnet.py:370) and the contractions that are linear in
-        // the attention context / the selected memory row, hoisted out of the timestep (see CapAttArgs in attention.hip):
-        //   cap_proj[b,t] = [context_gate.W[:, 2D:3D] H_t | sc_affine.W H_t]   (editnet.py:378-379, no bias here)
-        //   mem_proj[b,t] = gate_cmem.W Mem_t                                   (editnet.py:281)
-        GemmProb p[4];
+        // everything the prologue needs cleared, in one fill (carved back to back): the encoder's outputs and state, and the
+        // decoder's initial state (nothing reads or writes h1 .. c2 before the first timestep)
+        float* zp[8] = {ws.H, ws.Mem, ws.enc_h, ws.enc_c, ws.h1, ws.c1, ws.h2, ws.c2};
+        const size_t BD = (size_t)B * D;
+        const size_t zn[8] = {BD * T, BD * T, BD, BD, BD, BD, BD, BD};
+        SET_TRY(zero_runs(zp, zn, 8, st));
+    }
+    // ---- hoisted, loop-invariant projections (eval mode)
+    // one grouped launch over the encoder outputs: att1_c (editnet.py:370) and the contractions that are linear in
+    // the attention context / the selected memory row, hoisted out of the timestep (see CapAttArgs in attention.hip):
+    //   cap_proj[b,t] = [context_gate.W[:, 2D:3D] H_t | sc_affine.W H_t]   (editnet.py:378-379, no bias here)
+    //   mem_proj[b,t] = gate_cmem.W Mem_t                                   (editnet.py:281)
+    // Rows of H / Mem beyond a caption's length are exactly zero, their products exactly 0 + bias or +0, and the caption
+    // attention masks them out: the launch contracts the valid rows only, through a row list that the encoder's
+    // row-ranking launch writes (it also stores the padded rows' values), so no host read and no extra launch
+    // (SET_PRO_ROWLIST=0: all B*T rows as before; also where that launch does not run, at <= 16 rows, adaptive features)
+    GemmProb p[4];
+    ProRows pro;
+    static const int pro_rowlist = env_int("SET_PRO_ROWLIST", 1);
+    {
         p[0] = direct_prob(ws.att1_c, A, B * T, A, w->ca_feat_b, SET_ACT_NONE);
         p[0].add(ws.H, D, w->ca_feat_w, D, D);
         p[1] = direct_prob(ws.cap_proj, 2LL * D, B * T, D, nullptr, SET_ACT_NONE);
@@ -272,20 +292,31 @@ static int begin_impl(const SetEditNetWeights* w, const SetEditNetDims* d, const
         p[2].add(ws.H, D, w->ca_sc_w, D, D);
         p[3] = direct_prob(ws.mem_proj, D, B * T, D, nullptr, SET_ACT_NONE);
         p[3].add(ws.Mem, D, w->cl_cmem_w, D, D);
-        SET_TRY(gemm_group(p, 4, st, "gemm:pro cap projections"));
+        pro.list = ws.pro_rows; pro.count = ws.pro_count;
+        pro.bias_out = ws.att1_c; pro.bias = w->ca_feat_b; pro.nbias = A;
+        pro.zero_out[0] = ws.cap_proj; pro.nzero[0] = 2 * D;
+        pro.zero_out[1] = ws.mem_proj; pro.nzero[1] = D;
     }
+    const bool want_rows = pro_rowlist && !d->adaptive && gemm_row_list_ok(p, 4);
+    // ---- caption encoder (editnet.py:319-348)
+    SET_TRY(editnet_encoder(w, prev, prevlen, ws.H, ws.Mem, ws.final_hidden, ws.mask, B, T, D, d->V, ws.emb_seq, ws.xg,
+                            ws.enc_h, ws.enc_c, ws.s_enc, ws.s_aff, st, ws.enc_order, ws.enc_bar, want_rows ? &pro : nullptr,
+                            true));
+    if (pro.built)
+        for (int i = 0; i < 4; ++i) { p[i].row_list = pro.list; p[i].row_count = pro.count; }
+    SET_TRY(gemm_group(p, 4, st, "gemm:pro cap projections"));
     {
         // small batches (persistent decode, decode_persistent_wide.hip): the region half of copy_lstm.x2h is linear in the
         // visual attention weights — Pv = X x2h[:, 2D:]^T (B, R, 4D) rides the att_embed launch (same operand X)
-        GemmProb p[2];
-        p[0] = direct_prob(ws.fe, D, B * R, D, w->va_emb_b, SET_ACT_RELU);                // editnet.py:441
-        p[0].add(X, F, w->va_emb_w, F, F);
+        GemmProb e[2];
+        e[0] = direct_prob(ws.fe, D, B * R, D, w->va_emb_b, SET_ACT_RELU);                // editnet.py:441
+        e[0].add(X, F, w->va_emb_w, F, F);
         const bool pv = beam_pv || editnet_persistent_ok(d, 1);
         if (pv) {
-            p[1] = direct_prob(ws.pd_pv, 4LL * D, B * R, 4 * D, nullptr, SET_ACT_NONE);
-            p[1].add(X, F, w->cl_x2h_w + 2 * D, 2LL * D + F, F);
+            e[1] = direct_prob(ws.pd_pv, 4LL * D, B * R, 4 * D, nullptr, SET_ACT_NONE);
+            e[1].add(X, F, w->cl_x2h_w + 2 * D, 2LL * D + F, F);
         }
-        SET_TRY(gemm_group(p, pv ? 2 : 1, st, "gemm:pro att_embed"));
+        SET_TRY(gemm_group(e, pv ? 2 : 1, st, "gemm:pro att_embed"));
         GemmProb q = direct_prob(ws.att1, A, B * R, A, w->va_feat_b, SET_ACT_NONE);       // editnet.py:442
         q.add(ws.fe, D, w->va_feat_w, D, D);
         SET_TRY(gemm_group(&q, 1, st, "gemm:pro features_att"));
@@ -298,17 +329,12 @@ static int begin_impl(const SetEditNetWeights* w, const SetEditNetDims* d, const
     {
         // attention_lstm input columns [D,2D) (final_hidden) and [3D,3D+F) (image_mean) + both biases
         const long long ldw = 3LL * D + F;
-        GemmProb p = slab_prob(ws.s_pre, B, 4 * D, B);
-        p.add(ws.final_hidden, D, w->al_wih + D, ldw, D);
-        p.add(ws.image_mean, F, w->al_wih + 3 * D, ldw, F);
-        plan_ksplit(&p, 1, tgt);
-        SET_TRY(gemm_group(&p, 1, st));
-        SET_TRY(reduce_bias_act(slabs_of(p), w->al_bih, w->al_bhh, ws.pre1, 4 * D, B, 4 * D, SET_ACT_NONE, st));
-    }
-    {
-        float* zp[4] = {ws.h1, ws.c1, ws.h2, ws.c2};
-        const size_t zn[4] = {(size_t)B * D, (size_t)B * D, (size_t)B * D, (size_t)B * D};
-        SET_TRY(zero_runs(zp, zn, 4, st));
+        GemmProb g = slab_prob(ws.s_pre, B, 4 * D, B);
+        g.add(ws.final_hidden, D, w->al_wih + D, ldw, D);
+        g.add(ws.image_mean, F, w->al_wih + 3 * D, ldw, F);
+        plan_ksplit(&g, 1, tgt);
+        SET_TRY(gemm_group(&g, 1, st));
+        SET_TRY(reduce_bias_act(slabs_of(g), w->al_bih, w->al_bhh, ws.pre1, 4 * D, B, 4 * D, SET_ACT_NONE, st));
     }
     return SET_OK;
 }
@@ -812,6 +838,7 @@ void* set_editnet_ws_tensor(const SetEditNetDims* d, void* ws, const char* name)
         {"attend_cap", W.attend_cap}, {"attend_img", W.attend_img}, {"sel", W.sel}, {"c_new", W.c_new},
         {"alpha_c", W.alpha_c}, {"alpha", W.alpha}, {"logits", W.logits}, {"it", W.it},
         {"cap_proj", W.cap_proj}, {"mem_proj", W.mem_proj}, {"enc_bar", W.enc_bar},
+        {"pro_rows", W.pro_rows}, {"pro_count", W.pro_count},
         {"unfinished", W.unfinished}, {"alive", W.alive}};
     for (auto& e : tab)
         if (!strcmp(e.n, name)) return e.p;

@@ -55,7 +55,8 @@ struct GemmTask {
 struct GemmLaunch {
     GemmTask t[GEMM_MAX_TASKS];
     int ntasks;
-    RowGate gate;                    // set_common.h: loop-left test and the compacted row list of the decode loops
+    RowGate gate;                    // set_common.h: loop-left test of the decode loops
+    const int* row_list;             // GATE == 2: the launch's compacted row list (GemmProb::row_list), else unused
 #ifdef SET_EXP_STAMPS
     unsigned long long* stamps;      // debug: 8 wall-clock stamps (10 ns units) per workgroup
 #endif
@@ -84,6 +85,11 @@ __device__ __forceinline__ float apply_act(float v, int act) {
 // GATE (row gate of the decode loops, set_common.h): 0 = none (prologue, training, every other caller: no gate code at all),
 // 1 = loop-left test.  Separate instantiations: the ungated kernel keeps the round-3 instruction stream (the gate's branch
 // costs 0.4-0.5 us per launch when compiled in).
+// GATE = 2: compacted row list (GemmProb::row_list).  The grid is still sized for all M rows; row tile m0 covers the list
+// entries [m0, m0 + BM) and a tile at or beyond the count (gate_nrows, a preloaded scalar argument) returns at once.  The
+// indirection sits in the pointer set-up (A rows) and in the epilogue (C rows) only: tile shape, K order and the k-loop of
+// every computed element are those of the full launch.  Every index read from the list is clamped to [0, M) before it
+// forms an address and the count to [0, M]: a wrong list gives a wrong result, never an access outside the operands.
 template <int BM, int BN, int WAVES_M, int WAVES_N, int KG = 1, int GATE = 0>
 __global__ void __launch_bounds__(256 * KG) gemm_nt_f32(const int ntasks, const int wb1, const int wb2, const int wb3,
                                                         const int wb4, const int wb5, const int* const gate_alive,
@@ -135,18 +141,27 @@ __global__ void __launch_bounds__(256 * KG) gemm_nt_f32(const int ntasks, const 
     // ---- row gate of the decode loops (set_common.h): nothing to do once the reference has left its loop
     // (gate_alive repeats L.gate.alive_prev as a leading, SGPR-preloaded argument: its value is requested with the wave's
     // first instructions, next to the task descriptor, not behind it; gate_nrows is an unused slot of the preloaded block)
-    const int epi_m = T.M;
-    if constexpr (GATE >= 1) {
+    int epi_m = T.M;
+    if constexpr (GATE == 1) {
         if (gate_alive && *gate_alive == 0) return;
     }
-    auto epi_row = [&](int row) { return row; };
+    const int* const rlist = L.row_list;
+    if constexpr (GATE == 2) {
+        const int cnt = *gate_nrows;
+        epi_m = cnt < 0 ? 0 : (cnt < T.M ? cnt : T.M);
+        if (m0 >= epi_m) return;                      // (uniform over the workgroup, before its first barrier)
+    }
+    auto epi_row = [&](int row) {                     // tile row (< epi_m) -> row of A and of C
+        if constexpr (GATE == 2) { const int i = rlist[row]; return i < 0 ? 0 : (i < T.M ? i : T.M - 1); }
+        else return row;
+    };
 
     // ---- staging assignment: thread -> (row = tid/8 + RP*i, 16-byte column = tid%8)
     const int srow = tid >> 3, scol = (tid & 7) * 4;
     const int sswz = ((tid & 7) ^ ((srow >> 1) & 7)) * 4;          // swizzled chunk (rows srow+RP*i share (r>>1)&7)
     int arow[LA], wrow[LW];
 #pragma unroll
-    for (int i = 0; i < LA; ++i) { int r = m0 + srow + RP * i; r = r < epi_m ? r : epi_m - 1; arow[i] = r; }
+    for (int i = 0; i < LA; ++i) { int r = m0 + srow + RP * i; r = r < epi_m ? r : epi_m - 1; arow[i] = epi_row(r); }
 #pragma unroll
     for (int i = 0; i < LW; ++i) { int r = n0 + srow + RP * i; wrow[i] = r < T.N ? r : T.N - 1; }
 #ifdef SET_EXP_SAMEW
@@ -405,17 +420,25 @@ __global__ void __launch_bounds__(256) gemm_nt_f32_asm(const int ntasks, const i
     const int tm = local / T.tm_stride;
     const int rem0 = local - tm * T.tm_stride;
     if (rem0 >= T.tiles_n * T.ksplit) return;          // padding slot
-    if constexpr (GATE >= 1) {
+    if constexpr (GATE == 1) {
         if (gate_alive && *gate_alive == 0) return;
     }
-    (void)gate_nrows;
     const int ks = rem0 % T.ksplit;
     const int tn = rem0 / T.ksplit;
     const int m0 = tm * BM, n0 = tn * BN;
     const int kt0 = (int)(((long long)ks * T.ktiles) / T.ksplit);
     const int kt1 = (int)(((long long)(ks + 1) * T.ktiles) / T.ksplit);
-    const int epi_m = T.M;
-    auto epi_row = [](int row) { return row; };
+    int epi_m = T.M;
+    const int* const rlist = L.row_list;
+    if constexpr (GATE == 2) {                        // compacted row list: see gemm_nt_f32
+        const int cnt = *gate_nrows;
+        epi_m = cnt < 0 ? 0 : (cnt < T.M ? cnt : T.M);
+        if (m0 >= epi_m) return;
+    }
+    auto epi_row = [&](int row) {
+        if constexpr (GATE == 2) { const int i = rlist[row]; return i < 0 ? 0 : (i < T.M ? i : T.M - 1); }
+        else return row;
+    };
 
     // the slice's segment (the launcher guarantees [kt0, kt1) lies inside one)
     int sg = 0, kbase = 0;
@@ -437,7 +460,8 @@ __global__ void __launch_bounds__(256) gemm_nt_f32_asm(const int ntasks, const i
     unsigned oA0, oA1, oW0, oW1;                  // byte offsets of this thread's pieces from the scalar bases
     {
         int r0 = m0 + srow, r1 = m0 + srow + 32;
-        r0 = r0 < T.M ? r0 : T.M - 1; r1 = r1 < T.M ? r1 : T.M - 1;
+        r0 = r0 < epi_m ? r0 : epi_m - 1; r1 = r1 < epi_m ? r1 : epi_m - 1;
+        r0 = epi_row(r0); r1 = epi_row(r1);
         oA0 = (unsigned)((r0 * lda + scol) * 4); oA1 = (unsigned)((r1 * lda + scol) * 4);
         int c0 = n0 + srow, c1 = n0 + srow + 32;
         c0 = c0 < T.N ? c0 : T.N - 1; c1 = c1 < T.N ? c1 : T.N - 1;
@@ -702,6 +726,13 @@ static int launch_tile_m(const GemmProb* probs, int n) {
     return c64 < 0.97 * c128 ? 64 : 128;
 }
 int gemm_launch_rows(const GemmProb* probs, int n) { return n > 0 ? launch_tile_m(probs, n) : 0; }
+static int launch_tile_n(const GemmProb* probs, int n);
+// the LDS-staged tile classes of the shipped library take a row list; the <= 16-row class (no tile rows to skip) does not
+bool gemm_row_list_ok(const GemmProb* probs, int n) {
+    if (n <= 0 || gemm_split_mode() || gemm_dma() || gemm_wreg() || gemm_kgroups() != 1) return false;
+    const int bm = launch_tile_m(probs, n), bn = launch_tile_n(probs, n);
+    return (bm == 128 && bn == 64) || (bm == 64 && bn == 64) || (bm == 32 && bn == 128);
+}
 static int launch_tile_n(const GemmProb* probs, int n) {
     if (use_bn32(probs, n)) return 32;
     const int bm = launch_tile_m(probs, n);
@@ -789,11 +820,18 @@ int gemm_group(const GemmProb* probs, int n, hipStream_t stream, const char* tag
     GemmLaunch L;
     L.ntasks = n;
     L.gate = g_row_gate;
+    L.row_list = probs[0].row_list;
+    const int* const row_count = probs[0].row_count;
+    if ((L.row_list != nullptr) != (row_count != nullptr)) return SET_ERR_ARG;
+    for (int i = 1; i < n; ++i)          // one list per launch: every problem contracts the same rows
+        if (probs[i].row_list != L.row_list || probs[i].row_count != row_count) return SET_ERR_ARG;
+    if (L.row_list && L.gate.alive_prev) return SET_ERR_ARG;
 #ifdef SET_EXP_STAMPS
     L.stamps = g_gemm_stamps;
 #endif
     int wg = 0;
     const int bm = launch_tile_m(probs, n), bn = launch_tile_n(probs, n);
+    if (L.row_list && !gemm_row_list_ok(probs, n)) return SET_ERR_UNSUPPORTED;
     for (int i = 0; i < n; ++i) {
         const GemmProb& p = probs[i];
         GemmTask& t = L.t[i];
@@ -859,9 +897,18 @@ int gemm_group(const GemmProb* probs, int n, hipStream_t stream, const char* tag
         const int nt = L.ntasks, w1 = L.t[1].wg_begin, w2 = L.t[2].wg_begin, w3 = L.t[3].wg_begin, w4 = L.t[4].wg_begin,
                   w5 = L.t[5].wg_begin;
         const int* ga = L.gate.alive_prev;
-        const int* gn = nullptr;                 // (unused slot of the preloaded argument block)
-        const int gate_mode = ga ? 1 : 0;
-        if (bm == 16)
+        const int* gn = row_count;               // GATE == 2: the length of the row list (else an unused slot)
+        const int gate_mode = L.row_list ? 2 : (ga ? 1 : 0);
+        if (gate_mode == 2) {                    // (gemm_row_list_ok: one of these three classes)
+            if (bm == 128)
+                hipLaunchKernelGGL((gemm_nt_f32<128, 64, 2, 2, 1, 2>), grid, block, 0, stream, nt, w1, w2, w3, w4, w5, ga, gn, L);
+            else if (bm == 64 && gemm_asm() && slices_in_one_segment(L))
+                hipLaunchKernelGGL((gemm_nt_f32_asm<2>), grid, block, 0, stream, nt, w1, w2, w3, w4, w5, ga, gn, L);
+            else if (bm == 64)
+                hipLaunchKernelGGL((gemm_nt_f32<64, 64, 2, 2, 1, 2>), grid, block, 0, stream, nt, w1, w2, w3, w4, w5, ga, gn, L);
+            else
+                hipLaunchKernelGGL((gemm_nt_f32<32, 128, 1, 4, 1, 2>), grid, block, 0, stream, nt, w1, w2, w3, w4, w5, ga, gn, L);
+        } else if (bm == 16)
             hipLaunchKernelGGL(gemv_nt_f32, grid, block, 0, stream, nt, w1, w2, w3, w4, w5, ga, gn, L);
 #ifdef SET_EXPERIMENTAL_GEMMS
         else if (bm == 128 && bn == 32)

@@ -440,9 +440,33 @@ int fused_copy_gate_pre(const float* c_new, const float* sel, const float* cmem_
     return launch_fused<1, true, 64, EPI_COPYGATE1>(P, grid, s);
 }
 
-// perm[p] = row with the p-th longest sequence (stable: ties keep row order); nactive[t] = #rows with len > t
-__global__ void __launch_bounds__(1024) encoder_order_k(const int64_t* lens, int B, int T, int* perm, int* nactive) {
+// perm[p] = row with the p-th longest sequence (stable: ties keep row order); nactive[t] = #rows with len > t.
+// ROWS (decode prologue, set_common.h ProRows): workgroup 0 also writes the list of valid rows b*T + t (t < len[b], row-major
+// order) and its length; workgroups 1.. store what the full hoisted projections leave in the padded rows (t >= len[b]): 0 + bias
+// and +0, with plain vector stores.  They need the lengths only, not the list.
+template <bool ROWS>
+__global__ void __launch_bounds__(1024) encoder_order_k(const int64_t* lens, int B, int T, int* perm, int* nactive,
+                                                        const ProRows R) {
     __shared__ int sl[4096];                              // B <= 4096 (host check): the lengths once, then LDS only
+    if (ROWS && blockIdx.x > 0) {
+        const int rows = B * T, q0 = R.nbias >> 2, q1 = q0 + (R.nzero[0] >> 2), q2 = q1 + (R.nzero[1] >> 2);   // (columns % 4 == 0)
+        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+        for (int r = (int)blockIdx.x - 1; r < rows; r += (int)gridDim.x - 1) {
+            const int b = r / T, t = r - b * T;
+            if ((long long)t < lens[b]) continue;
+            for (int q = threadIdx.x; q < q2; q += blockDim.x) {
+                if (q < q0) {
+                    const float* bp = R.bias + 4 * q;
+                    const f32x4 v = {0.f + bp[0], 0.f + bp[1], 0.f + bp[2], 0.f + bp[3]};     // (what acc + bias gives: -0 -> +0)
+                    *reinterpret_cast<f32x4*>(R.bias_out + (long long)r * R.nbias + 4 * q) = v;
+                } else if (q < q1)
+                    *reinterpret_cast<f32x4*>(R.zero_out[0] + (long long)r * R.nzero[0] + 4 * (q - q0)) = z;
+                else
+                    *reinterpret_cast<f32x4*>(R.zero_out[1] + (long long)r * R.nzero[1] + 4 * (q - q1)) = z;
+            }
+        }
+        return;
+    }
     for (int b = threadIdx.x; b < B; b += blockDim.x) sl[b] = (int)lens[b];
     __syncthreads();
     for (int b = threadIdx.x; b < B; b += blockDim.x) {
@@ -459,10 +483,29 @@ __global__ void __launch_bounds__(1024) encoder_order_k(const int64_t* lens, int
         for (int j = 0; j < B; ++j) n += sl[j] > t;
         nactive[t] = n;
     }
+    if (ROWS) {
+        for (int b = threadIdx.x; b < B; b += blockDim.x) {
+            int off = 0;                                  // valid rows before row b's: off + lb <= B*T, the size of the list
+            for (int j = 0; j < b; ++j) { const int lj = sl[j]; off += lj < 0 ? 0 : (lj < T ? lj : T); }
+            int lb = sl[b];
+            lb = lb < 0 ? 0 : (lb < T ? lb : T);
+            for (int t = 0; t < lb; ++t) R.list[off + t] = b * T + t;
+            if (b == B - 1) *R.count = off + lb;
+        }
+    }
 }
 
-int encoder_order(const int64_t* lens, int B, int T, int* perm, int* nactive, hipStream_t s) {
-    hipLaunchKernelGGL(encoder_order_k, dim3(1), dim3(1024), 0, s, lens, B, T, perm, nactive);
+int encoder_order(const int64_t* lens, int B, int T, int* perm, int* nactive, hipStream_t s, const ProRows* pro) {
+    if (B > 4096) return SET_ERR_UNSUPPORTED;
+    if (pro) {
+        if (!pro->list || !pro->count || !pro->bias_out || !pro->bias || !pro->zero_out[0] || !pro->zero_out[1]) return SET_ERR_ARG;
+        if ((pro->nbias & 3) || (pro->nzero[0] & 3) || (pro->nzero[1] & 3)) return SET_ERR_ARG;
+        if (!aligned16(pro->bias_out) || !aligned16(pro->zero_out[0]) || !aligned16(pro->zero_out[1])) return SET_ERR_ARG;
+        const long long rows = (long long)B * T;
+        const int fill = (int)(rows < 1024 ? rows : 1024);     // workgroups that write the padded rows (one row per turn)
+        hipLaunchKernelGGL(encoder_order_k<true>, dim3(1 + fill), dim3(1024), 0, s, lens, B, T, perm, nactive, *pro);
+    } else
+        hipLaunchKernelGGL(encoder_order_k<false>, dim3(1), dim3(1024), 0, s, lens, B, T, perm, nactive, ProRows());
     SET_LAUNCH_CHECK();
     return SET_OK;
 }

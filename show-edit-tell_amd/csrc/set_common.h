@@ -83,6 +83,11 @@ struct GemmProb {
     int ksplit = 1;              // filled by plan_ksplit or by the caller
     int max_ksplit = GEMM_MAX_KSPLIT;
     int bm_hint = 0;             // 0: row tile chosen from M (gemm_tile_m); 64 / 128: forced for the whole launch (probs[0] decides)
+    // optional compacted row list (device memory, the same for every problem of a launch): only rows row_list[0 .. *row_count)
+    // of A are contracted and only those rows of C are written, by the tiles and in the K order of the full launch; the
+    // other rows of C are left as they are.  Indices are clamped to [0, M), the count to [0, M].  Unsplit problems only.
+    const int* row_list = nullptr;
+    const int* row_count = nullptr;
     void add(const float* A, long long lda, const float* W, long long ldw, int K) {
         seg[nseg++] = GemmSeg{A, W, lda, ldw, K};
     }
@@ -95,6 +100,8 @@ void plan_ksplit(GemmProb* probs, int n, int target_wgs);
 int gemm_group(const GemmProb* probs, int n, hipStream_t stream, const char* tag = nullptr);
 // the row-tile class (16 / 32 / 64 / 128) a grouped launch of these problems runs on
 int gemm_launch_rows(const GemmProb* probs, int n);
+// whether a grouped launch of these problems can take GemmProb::row_list (every tile class but the <= 16-row one)
+bool gemm_row_list_ok(const GemmProb* probs, int n);
 // gemm_gen.hip: C (+)= a . b^T with either operand stored k-major or k-minor (training backward)
 int gemm_gen(const float* A, long long lda, int a_kminor, const float* B, long long ldb, int b_kminor, float* C,
              long long ldc, int M, int N, int K, int accumulate, void* ws, size_t ws_bytes, hipStream_t s);
@@ -251,10 +258,21 @@ int gemm_target_wgs();
 int dead_work();
 GemmProb slab_prob(float* slab, int M, int N, int Bmax);
 GemmProb direct_prob(float* out, long long ldo, int M, int N, const float* bias, int act);
+// Valid caption rows of the decode prologue (editnet.hip begin_impl).  The launch that ranks the rows for the encoder also
+// writes list = the rows b*T + t with t < len[b] in row-major order and *count = how many (the row list of the hoisted
+// caption projections), and stores into the other, padded rows what the full products leave there: 0 + bias[n] in
+// bias_out (B*T, nbias) and +0 in zero_out[i] (B*T, nzero[i]).  built: set by editnet_encoder when that launch was enqueued.
+struct ProRows {
+    int* list = nullptr; int* count = nullptr;
+    float* bias_out = nullptr; const float* bias = nullptr; int nbias = 0;
+    float* zero_out[2] = {nullptr, nullptr}; int nzero[2] = {0, 0};
+    bool built = false;
+};
+// zeroed: the caller has cleared H, Mem, enc_h and enc_c on this stream already
 int editnet_encoder(const SetEditNetWeights* w, const int64_t* seq, const int64_t* lens, float* H, float* Mem,
                     float* final_hidden, float* mask, int B, int T, int D, int V, float* emb_seq, float* xg,
                     float* enc_h, float* enc_c, float* s_enc, float* s_aff, hipStream_t st, int* order = nullptr,
-                    void* enc_bar = nullptr);
+                    void* enc_bar = nullptr, ProRows* pro = nullptr, bool zeroed = false);
 // encoder_persistent.hip: the whole encoder recurrence in one weights-stationary launch with grid barriers
 size_t persistent_encoder_bar_bytes();
 bool persistent_encoder_ok(int B, int D, int T);
@@ -386,7 +404,7 @@ int fused_encoder_step(const float* h_in, float* h_out, float* c, const float* w
                        int reverse, float* H, float* Mem, long long ld_out_b, long long ld_out_t, int out_col0, int B,
                        int D, hipStream_t s, const int64_t* seq = nullptr, int seq_T = 0, int seq_V = 0, const int* perm = nullptr,
                        const int* nactive = nullptr, bool h_zero = false);
-int encoder_order(const int64_t* lens, int B, int T, int* perm, int* nactive, hipStream_t s);
+int encoder_order(const int64_t* lens, int B, int T, int* perm, int* nactive, hipStream_t s, const ProRows* pro = nullptr);
 
 // epilogue.hip
 // Optional tail of the pick kernels (free-running loops with the token table): the NEXT timestep's attention-LSTM cell
