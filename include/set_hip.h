@@ -406,6 +406,55 @@ size_t set_linear_workspace_bytes(int M, int N, int K);
 int set_linear_f32(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias,
                    float* y, int64_t ldy, int M, int N, int K, int act, void* ws, size_t ws_bytes,
                    void* stream);
+/* The grouped NT GEMM under every forward contraction (csrc/gemm_f32.hip), as its launcher takes it: up to 6 problems
+ *     C_i[M_i, N_i] = act_i(sum over segments s of A_is[M_i, K_is] W_is[N_i, K_is]^T + bias_i)
+ * in ONE launch, each contraction a concatenation of up to 3 (A, W) column segments that stay where they lie (every K a
+ * multiple of 32; A, W 16-byte aligned, lda / ldw multiples of 4 floats and >= K).  For direct tests and measurements of the
+ * kernel family: tile class, split, segment layout, row gate and k-loop are the caller's to choose.
+ *   ksplit   0: the launcher's planner decides.  >= 1: that many K slices, clamped to the problem's k-tiles (K_total / 32).
+ *            A problem that ends up split writes its partials into `ws` and is reduced into C with bias and activation by a
+ *            second launch (as set_linear_f32 does); an unsplit one runs the fused epilogue straight into C.
+ *   bm_hint  0: row-tile class from the largest M (<= 16 rows: 16, <= 32: 32, <= 512: 64, beyond: 128 or 64 by the tile
+ *            model).  64 / 128: forced for the whole launch.
+ *   row_list, row_count   both or neither; device memory.  Only rows row_list[0 .. *row_count) of every A are contracted and
+ *            only those rows of every C written; indices are clamped to [0, M), the count to [0, M].  Unsplit problems only
+ *            (SET_ERR_ARG with ksplit > 1; with ksplit = 0 the problems stay unsplit), not with `alive`, and not on the
+ *            <= 16-row class (SET_ERR_UNSUPPORTED).
+ *   alive    device int or NULL: *alive == 0 when the kernels start -> the launch writes nothing, neither C nor partials —
+ *            the loop-left gate of the free-running decode loops.  The reduction launches carry no gate (the decode loops
+ *            hand gated partials to gated consumers), so a split problem takes `alive` only with SET_GEMM_NT_KEEP_SLABS
+ *            (SET_ERR_ARG otherwise; with ksplit = 0 the problems stay unsplit).
+ *   flags    SET_GEMM_NT_NO_ASM: take the compiler-scheduled k-loop where the hand-written 64x64 one is eligible.  Flips a
+ *            process-wide switch around the call: NOT thread-safe, diagnostic only.
+ *            SET_GEMM_NT_KEEP_SLABS: no reduction launches; each problem goes to the launcher with its own bias and
+ *            activation, so a split one with either is refused (SET_ERR_ARG) and otherwise leaves its partials in `ws`:
+ *            problem i's slab s at ws + slab_offset_i + s * M_i * N_i floats, slab_offset_i = the 256-byte-rounded sizes
+ *            (ksplit_j * M_j * N_j * 4 bytes) of the split problems j < i.
+ *   ksplit_out  NULL or n ints: the split each problem ran with.   rows_out  NULL or one int: the row-tile class.
+ * Every refusal is answered before any HIP call. */
+#define SET_GEMM_NT_NO_ASM 1
+#define SET_GEMM_NT_KEEP_SLABS 2
+typedef struct SetGemmNtSeg {
+    const float* A; int64_t lda;
+    const float* W; int64_t ldw;
+    int32_t K, pad_;
+} SetGemmNtSeg;
+typedef struct SetGemmNtProb {
+    SetGemmNtSeg seg[3];
+    float* C; int64_t ldc;
+    const float* bias;               /* N floats or NULL */
+    int32_t nseg, M, N, act, ksplit, pad_;
+} SetGemmNtProb;
+typedef struct SetGemmNtLaunch {
+    const int32_t* row_list; const int32_t* row_count;
+    const int32_t* alive;
+    int32_t* ksplit_out; int32_t* rows_out;      /* HOST memory */
+    int32_t bm_hint, flags;
+} SetGemmNtLaunch;
+/* upper bound for `ws` of the call below (0 when nothing can be split or an argument is out of range) */
+size_t set_gemm_nt_group_workspace_bytes(const SetGemmNtProb* probs, int n);
+int set_gemm_nt_group_f32(const SetGemmNtProb* probs, int n, const SetGemmNtLaunch* launch /* NULL: all defaults */,
+                          void* ws, size_t ws_bytes, void* stream);
 /* EmbeddingC.forward (editnet.py:300-304), eval: out[i] = relu(table[ids[i]]) */
 int set_embed_relu_f32(const float* table, const int64_t* ids, int64_t ids_stride, float* out,
                        int64_t ldo, int n, int D, int V, void* stream);

@@ -146,6 +146,27 @@ class GemmDesc(C.Structure):
                 ("accumulate", C.c_int)]
 
 
+class GemmNtSeg(C.Structure):
+    """include/set_hip.h SetGemmNtSeg: one (A, W) column segment of a grouped NT GEMM problem"""
+    _fields_ = [("A", C.c_void_p), ("lda", C.c_int64), ("W", C.c_void_p), ("ldw", C.c_int64), ("K", C.c_int32),
+                ("pad_", C.c_int32)]
+
+
+class GemmNtProb(C.Structure):
+    """include/set_hip.h SetGemmNtProb"""
+    _fields_ = [("seg", GemmNtSeg * 3), ("C", C.c_void_p), ("ldc", C.c_int64), ("bias", C.c_void_p), ("nseg", C.c_int32),
+                ("M", C.c_int32), ("N", C.c_int32), ("act", C.c_int32), ("ksplit", C.c_int32), ("pad_", C.c_int32)]
+
+
+class GemmNtLaunch(C.Structure):
+    """include/set_hip.h SetGemmNtLaunch (ksplit_out / rows_out are HOST pointers)"""
+    _fields_ = [("row_list", C.c_void_p), ("row_count", C.c_void_p), ("alive", C.c_void_p), ("ksplit_out", C.c_void_p),
+                ("rows_out", C.c_void_p), ("bm_hint", C.c_int32), ("flags", C.c_int32)]
+
+
+GEMM_NT_NO_ASM, GEMM_NT_KEEP_SLABS = 1, 2
+
+
 class SlabSrc(C.Structure):
     """include/set_hip.h SetSlabSrc: one addend of a gradient that is still split-K partials"""
     _fields_ = [("p", C.c_void_p), ("slab_stride", C.c_int64), ("ld", C.c_int64), ("nslab", C.c_int32), ("rows", C.c_int32)]
@@ -255,6 +276,8 @@ PROTOTYPES = {
     "set_dcnet_ws_tensor": (_P, [C.POINTER(DcnetDims), _P, C.c_char_p]),
     "set_linear_workspace_bytes": (_Z, [_I, _I, _I]),
     "set_linear_f32": (_I, [_P, _L, _P, _L, _P, _P, _L, _I, _I, _I, _I, _P, _Z, _P]),
+    "set_gemm_nt_group_workspace_bytes": (_Z, [C.POINTER(GemmNtProb), _I]),
+    "set_gemm_nt_group_f32": (_I, [C.POINTER(GemmNtProb), _I, C.POINTER(GemmNtLaunch), _P, _Z, _P]),
     "set_embed_relu_f32": (_I, [_P, _P, _L, _P, _L, _I, _I, _I, _P]),
     "set_lstm_cell_workspace_bytes": (_Z, [_I, _I, _I]),
     "set_lstm_cell_f32": (_I, [_P, _L, _I, _P, _P, _P, _L, _P, _P, _P, _P, _P, _I, _I, _P, _Z, _P]),

@@ -95,6 +95,41 @@ def gemm_group(items, a_kminor, b_kminor):
     return outs
 
 
+def gemm_nt_group(problems, bm_hint=0, row_list=None, row_count=None, alive=None, no_asm=False, keep_slabs=False, ws=None,
+                  code=False):
+    """The grouped NT GEMM of csrc/gemm_f32.hip in ONE launch (set_gemm_nt_group_f32; no autograd node): problem i is
+    dict(segs=[(A, W), ...], C=out view, bias=None, act=ACT_NONE, ksplit=0) with C = act(sum_s A_s W_s^T + bias).  Operands are
+    read and written IN PLACE through their row strides (2-D views with unit inner stride; nothing is copied, a layout the
+    kernels cannot take is the library's refusal).  `ws`: uint8 scratch for split problems (allocated when None).
+    -> (split used per problem, row-tile class); with code=True the library's return code comes first and nothing raises."""
+    lib = _lib.load()
+    n = len(problems)
+    descs = (_lib.GemmNtProb * max(n, 1))()
+    dev = problems[0]["C"].device
+    for d, p in zip(descs, problems):
+        for s, (a, w) in enumerate(p["segs"][:3]):
+            if a.stride(1) != 1 or w.stride(1) != 1 or a.shape[1] != w.shape[1]:
+                raise ValueError("segment %d: operands need unit inner stride and the same K" % s)
+            d.seg[s] = _lib.GemmNtSeg(a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), a.shape[1], 0)
+        c = p["C"]
+        if c.stride(1) != 1:
+            raise ValueError("C needs unit inner stride")
+        b = p.get("bias")
+        d.C, d.ldc, d.bias = c.data_ptr(), c.stride(0), (None if b is None else b.data_ptr())
+        d.nseg, d.M, d.N, d.act, d.ksplit = len(p["segs"]), c.shape[0], c.shape[1], p.get("act", _lib.ACT_NONE), p.get("ksplit", 0)
+    if ws is None:
+        ws = torch.empty(max(16, lib.set_gemm_nt_group_workspace_bytes(descs, n)), dtype=torch.uint8, device=dev)
+    ks_out, rows_out = (C.c_int32 * max(n, 1))(), C.c_int32(0)
+    dp = lambda t: None if t is None else t.data_ptr()
+    launch = _lib.GemmNtLaunch(dp(row_list), dp(row_count), dp(alive), C.addressof(ks_out), C.addressof(rows_out), bm_hint,
+                               (_lib.GEMM_NT_NO_ASM if no_asm else 0) | (_lib.GEMM_NT_KEEP_SLABS if keep_slabs else 0))
+    rc = lib.set_gemm_nt_group_f32(descs, n, C.byref(launch), ptr(ws), ws.numel(), stream_of(dev))
+    if code:
+        return rc, list(ks_out)[:n], rows_out.value
+    check(rc, "set_gemm_nt_group_f32")
+    return list(ks_out)[:n], rows_out.value
+
+
 def _dgrad_group(pairs):
     """[(dy, w, out or None)] -> [dX (+)= dy . w], grouped into one launch when the kernel can take them all"""
     ok = all(_native_ok(dy, w) and not (dy.shape[1] & 3) and not (w.shape[1] & 3) and w.shape[1] >= 4 and

@@ -856,6 +856,7 @@ int gemm_group(const GemmProb* probs, int n, hipStream_t stream, const char* tag
         t.ksplit = p.ksplit < 1 ? 1 : p.ksplit;
         if (t.ksplit > kt) t.ksplit = kt;
         if (t.ksplit > 1 && (p.act != SET_ACT_NONE)) return SET_ERR_ARG;
+        if (t.ksplit > 1 && L.row_list) return SET_ERR_ARG;       // (GemmProb::row_list: unsplit problems only)
         t.tiles_m = cdiv(p.M, bm); t.tiles_n = cdiv(p.N, bn);
         static const int vec_epi = env_int("SET_GEMM_VEC_EPILOGUE", 1);
         t.vec_store = vec_epi && !(p.N & 3) && !(p.ldc & 3) && !(p.slab_stride & 3) && aligned16(p.C);

@@ -6,9 +6,67 @@
 
 using namespace set;
 
+namespace set {
+extern int g_gemm_asm_force;      // gemm_f32.hip: 0 = compiler-scheduled 64x64 k-loop, -1 = the environment decides
+}
+
 namespace {
 constexpr size_t KS = GEMM_MAX_KSPLIT;
 size_t fbytes(size_t n) { return round_up(n * sizeof(float), 256); }
+
+// set_gemm_nt_group_f32: the launcher's problems of a validated call (split ones with their slabs at ws + off)
+struct NtPlan {
+    GemmProb p[GEMM_MAX_TASKS];
+    size_t off[GEMM_MAX_TASKS];
+    size_t bytes = 0;
+};
+int nt_check_prob(const SetGemmNtProb& d) {
+    if (d.nseg < 1 || d.nseg > GEMM_MAX_SEG || !d.C || d.M <= 0 || d.N <= 0 || d.ldc < d.N) return SET_ERR_ARG;
+    if (d.act < SET_ACT_NONE || d.act > SET_ACT_SIGMOID || d.ksplit < 0) return SET_ERR_ARG;
+    for (int s = 0; s < d.nseg; ++s) {
+        const SetGemmNtSeg& g = d.seg[s];
+        if (!g.A || !g.W || g.K <= 0) return SET_ERR_ARG;
+        if (g.K % GEMM_BK) return SET_ERR_UNSUPPORTED;
+        if (!aligned16(g.A) || !aligned16(g.W) || (g.lda & 3) || (g.ldw & 3) || g.lda < g.K || g.ldw < g.K) return SET_ERR_ARG;
+    }
+    return SET_OK;
+}
+int nt_plan(const SetGemmNtProb* d, int n, const SetGemmNtLaunch& l, NtPlan* out) {
+    if (!d || n < 0 || n > GEMM_MAX_TASKS) return SET_ERR_ARG;
+    if ((l.bm_hint != 0 && l.bm_hint != 64 && l.bm_hint != 128) || (l.flags & ~(SET_GEMM_NT_NO_ASM | SET_GEMM_NT_KEEP_SLABS)))
+        return SET_ERR_ARG;
+    if ((l.row_list != nullptr) != (l.row_count != nullptr) || (l.row_list && l.alive)) return SET_ERR_ARG;
+    for (int i = 0; i < n; ++i) SET_TRY(nt_check_prob(d[i]));
+    const bool keep = (l.flags & SET_GEMM_NT_KEEP_SLABS) != 0;
+    const bool unsplit_only = l.row_list || (l.alive && !keep);
+    GemmProb* p = out->p;
+    for (int i = 0; i < n; ++i) {
+        p[i] = slab_prob(nullptr, d[i].M, d[i].N, d[i].M);
+        for (int s = 0; s < d[i].nseg; ++s) p[i].add(d[i].seg[s].A, d[i].seg[s].lda, d[i].seg[s].W, d[i].seg[s].ldw, d[i].seg[s].K);
+        p[i].bm_hint = l.bm_hint;
+        if (unsplit_only) p[i].max_ksplit = 1;
+    }
+    plan_ksplit(p, n, gemm_target_wgs());                        // the planner's word for the problems that ask for it
+    for (int i = 0; i < n; ++i) {
+        const int kt = p[i].ktiles();
+        int ks = d[i].ksplit == 0 ? p[i].ksplit : d[i].ksplit;
+        ks = ks > kt ? kt : ks;
+        ks = ks < 1 ? 1 : ks;
+        if (ks > 1 && unsplit_only) return SET_ERR_ARG;
+        if (ks > 1 && keep && d[i].bias) return SET_ERR_ARG;     // (the launcher drops the bias of a split problem)
+        out->off[i] = out->bytes;
+        if (ks == 1) {
+            p[i].C = d[i].C; p[i].ldc = d[i].ldc; p[i].slab_stride = 0;
+            p[i].bias = d[i].bias; p[i].act = d[i].act;
+        } else {
+            out->bytes += fbytes((size_t)ks * d[i].M * d[i].N);
+            if (keep) p[i].act = d[i].act;
+        }
+        p[i].ksplit = ks;
+        p[i].row_list = (const int*)l.row_list; p[i].row_count = (const int*)l.row_count;
+    }
+    return SET_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -35,6 +93,56 @@ int set_linear_f32(const float* x, int64_t ldx, const float* w, int64_t ldw, con
     if (!ws || !aligned16(ws) || ws_bytes < fbytes((size_t)p.ksplit * M * N)) return SET_ERR_WORKSPACE;
     SET_TRY(gemm_group(&p, 1, st));
     return reduce_bias_act(slabs_of(p), bias, nullptr, y, ldy, M, N, act, st);
+}
+
+// ------------------------------------------------------------------------------- the grouped NT GEMM itself
+size_t set_gemm_nt_group_workspace_bytes(const SetGemmNtProb* probs, int n) {
+    if (!probs || n <= 0 || n > GEMM_MAX_TASKS) return 0;
+    size_t bytes = 0;
+    for (int i = 0; i < n; ++i) {
+        const SetGemmNtProb& d = probs[i];
+        if (nt_check_prob(d) != SET_OK) return 0;
+        int kt = 0;
+        for (int s = 0; s < d.nseg; ++s) kt += d.seg[s].K / GEMM_BK;
+        int ks = d.ksplit == 0 ? (int)KS : d.ksplit;
+        ks = ks > kt ? kt : ks;
+        if (ks > 1) bytes += fbytes((size_t)ks * d.M * d.N);
+    }
+    return bytes ? bytes + 256 : 0;
+}
+
+int set_gemm_nt_group_f32(const SetGemmNtProb* probs, int n, const SetGemmNtLaunch* launch, void* ws, size_t ws_bytes,
+                          void* stream) {
+    const SetGemmNtLaunch dflt = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
+    const SetGemmNtLaunch& l = launch ? *launch : dflt;
+    NtPlan plan;
+    SET_TRY(nt_plan(probs, n, l, &plan));
+    if (n == 0) return SET_OK;
+    if (plan.bytes && (!ws || !aligned16(ws) || ws_bytes < plan.bytes)) return SET_ERR_WORKSPACE;
+    for (int i = 0; i < n; ++i)
+        if (plan.p[i].ksplit > 1) plan.p[i].C = reinterpret_cast<float*>(static_cast<char*>(ws) + plan.off[i]);
+    if (l.row_list && !gemm_row_list_ok(plan.p, n)) return SET_ERR_UNSUPPORTED;
+    if (l.ksplit_out)
+        for (int i = 0; i < n; ++i) l.ksplit_out[i] = plan.p[i].ksplit;
+    if (l.rows_out) *l.rows_out = gemm_launch_rows(plan.p, n);
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    {
+        RowGate gate = g_row_gate;
+        if (l.alive) gate.alive_prev = (const int*)l.alive;
+        RowGateScope scope(gate);
+        const int asm_was = g_gemm_asm_force;                    // process-wide: see the header (diagnostic, not thread-safe)
+        if (l.flags & SET_GEMM_NT_NO_ASM) g_gemm_asm_force = 0;
+        rc = gemm_group(plan.p, n, st, "gemm:nt group");
+        g_gemm_asm_force = asm_was;
+    }
+    SET_TRY(rc);
+    if (l.flags & SET_GEMM_NT_KEEP_SLABS) return SET_OK;
+    for (int i = 0; i < n; ++i)
+        if (plan.p[i].ksplit > 1)
+            SET_TRY(reduce_bias_act(slabs_of(plan.p[i]), probs[i].bias, nullptr, probs[i].C, probs[i].ldc, probs[i].M,
+                                    probs[i].N, probs[i].act, st));
+    return SET_OK;
 }
 
 // ------------------------------------------------------------------------------- EmbeddingC
