@@ -219,6 +219,22 @@ int set_editnet_beam_persistent(const SetEditNetWeights* w, const SetEditNetDims
                                 int64_t start_idx, int64_t end_idx, int max_picks, int32_t* hist_parent,
                                 int64_t* hist_word, float* best_score, int64_t* best_word, int32_t* result,
                                 void* ws, size_t ws_bytes, void* stream);
+/* The same search, the same launch and the same bytes in every output above, plus the N-BEST list: hist_score (max_picks, 4)
+ * float, laid out like hist_word.  hist_score[t][s] = the value (sum of log-probabilities) of the pick behind slot s after pick t
+ * if that pick COUNTED (it was among the first k_left of the pick: the hypothesis stays alive or has just completed), -inf
+ * otherwise.  The hypotheses completed by pick t are therefore the slots with hist_word[t][s] == end_idx and hist_score[t][s] >
+ * -inf (a slot whose word is <end> but whose pick did not count looks the same in hist_word alone); their score is
+ * hist_score[t][s] and their words are read by following hist_parent back from (t, s), as for the best hypothesis.  COMPLETION
+ * ORDER: by pick t ascending and, within a pick, by slot ascending — completed slots keep their pick-rank order (value
+ * descending, flat index ascending among equals).  A search completes at most k hypotheses; one that stops at max_picks has
+ * fewer, possibly none.  Rows of picks that were not made (t >= result[3]) and slots s >= k are not written, as in hist_word.  SET_ERR_ARG also for a NULL
+ * hist_score; every other refusal is that of set_editnet_beam_persistent, answered at the same point.
+ * Parity: tests/test_hip_nbest_beam.py. */
+int set_editnet_beam_persistent_nbest(const SetEditNetWeights* w, const SetEditNetDims* d, const float* X,
+                                      const float* image_mean, const int64_t* prev, const int64_t* prevlen,
+                                      int64_t start_idx, int64_t end_idx, int max_picks, int32_t* hist_parent,
+                                      int64_t* hist_word, float* best_score, int64_t* best_word, int32_t* result,
+                                      void* ws, size_t ws_bytes, void* stream, float* hist_score);
 
 /* The same loop with multinomial sampling (editnet_rl.py:521-528, sample_rl=True, eval mode, no gradients):
  * it ~ Categorical(softmax(logits)) drawn on the device with Philox4x32-10 (counter = (row, timestep, offset),
@@ -349,6 +365,12 @@ int set_dcnet_beam_persistent(const SetDcnetWeights* w, const SetDcnetDims* d, c
                               const int64_t* prevlen, int64_t start_idx, int64_t end_idx, int max_picks,
                               int32_t* hist_parent, int64_t* hist_word, float* best_score, int64_t* best_word,
                               int32_t* result, void* ws, size_t ws_bytes, void* stream);
+/* set_dcnet_beam_persistent plus the n-best list: hist_score (max_picks, 4), the convention and completion order of
+ * set_editnet_beam_persistent_nbest (-inf = the slot's pick did not count).  Every other output holds the same bytes. */
+int set_dcnet_beam_persistent_nbest(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* prev,
+                                    const int64_t* prevlen, int64_t start_idx, int64_t end_idx, int max_picks,
+                                    int32_t* hist_parent, int64_t* hist_word, float* best_score, int64_t* best_word,
+                                    int32_t* result, void* ws, size_t ws_bytes, void* stream, float* hist_score);
 /* Beam search of ONE image by the EditNet + DCNet ENSEMBLE, the protocol of the reference's published scores
  * (eval/eval xe/eval_full.py:132-202: batch = 1 image, beam k = 3; both models step on the same words, their softmax
  * probabilities are averaged and the beam is picked from log((softmax_e + softmax_d) / 2) + running scores), as both prologues +
@@ -377,6 +399,14 @@ int set_ensemble_beam_persistent(const SetEditNetWeights* we, const SetEditNetDi
                                  int64_t* hist_word, float* best_score, int64_t* best_word, int32_t* result,
                                  void* ws_e, size_t ws_e_bytes, void* ws_d, size_t ws_d_bytes, void* xbuf,
                                  size_t xbuf_bytes, void* stream);
+/* set_ensemble_beam_persistent plus the n-best list: hist_score (max_picks, 4), the convention and completion order of
+ * set_editnet_beam_persistent_nbest; the scores are those of the joint pick.  Every other output holds the same bytes. */
+int set_ensemble_beam_persistent_nbest(const SetEditNetWeights* we, const SetEditNetDims* de, const SetDcnetWeights* wd,
+                                       const SetDcnetDims* dd, const float* X, const int64_t* prev,
+                                       const int64_t* prevlen, int64_t start_idx, int64_t end_idx, int max_picks,
+                                       int32_t* hist_parent, int64_t* hist_word, float* best_score, int64_t* best_word,
+                                       int32_t* result, void* ws_e, size_t ws_e_bytes, void* ws_d, size_t ws_d_bytes,
+                                       void* xbuf, size_t xbuf_bytes, void* stream, float* hist_score);
 size_t set_ensemble_beam_xbuf_bytes(const SetEditNetDims* de, const SetDcnetDims* dd);
 /* multinomial twin of set_dcnet_greedy (dcnet_rl.py:320-327); see set_editnet_sample */
 int set_dcnet_sample(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* prev,
@@ -739,6 +769,18 @@ int set_beam_pick_f32(const float* logits, const float* logits2, int64_t ld, int
                       int cur_len, int Lmax, float* scores, int32_t* k_left, const int64_t* seqs_in,
                       int64_t* seqs_out, float* best_score, int64_t* best_seq, int32_t* best_len, int64_t* words,
                       int32_t* rows, void* stream);
+/* set_beam_pick_f32 plus the N-BEST list of every image: done_score (NI, k), done_seq (NI, k, Lmax), done_len (NI, k) and
+ * n_done (NI), which the caller zero-fills before step 1 (n_done) and hands to every step.  Every COUNTED <end> pick (one among
+ * the first k_left picks of its image) appends one entry at index n_done[i]: its value, its cur_len + 1 tokens and that length.
+ * COMPLETION ORDER: by step and, within a step, by pick rank (value descending, flat index ascending among equals).  An image
+ * completes at most k hypotheses, so the arrays have room for all of them; entries past n_done[i] are never written.  Images
+ * with k_left == 0 are left untouched.  Every other output holds the same bytes as after set_beam_pick_f32.  SET_ERR_ARG also
+ * for a NULL done_* array; the other refusals are those of set_beam_pick_f32. */
+int set_beam_pick_nbest_f32(const float* logits, const float* logits2, int64_t ld, int NI, int k, int V, int64_t end_idx,
+                            int cur_len, int Lmax, float* scores, int32_t* k_left, const int64_t* seqs_in,
+                            int64_t* seqs_out, float* best_score, int64_t* best_seq, int32_t* best_len, int64_t* words,
+                            int32_t* rows, float* done_score, int64_t* done_seq, int32_t* done_len, int32_t* n_done,
+                            void* stream);
 /* In-place re-index of up to four (NI*k, D) recurrent-state tensors by `rows` (editnet.py:687-696). */
 int set_beam_gather_f32(float* s0, float* s1, float* s2, float* s3, const int32_t* rows, int NI, int k, int D,
                         void* stream);

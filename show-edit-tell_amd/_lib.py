@@ -245,6 +245,8 @@ PROTOTYPES = {
     "set_editnet_greedy_begun": (_I, [C.POINTER(EditNetWeights), C.POINTER(EditNetDims), _P, _L, _L, _I, _P, _P, _P, _Z, _P]),
     "set_editnet_beam_persistent": (_I, [C.POINTER(EditNetWeights), C.POINTER(EditNetDims), _P, _P, _P, _P, _L, _L, _I, _P, _P, _P, _P, _P,
                                          _P, _Z, _P]),
+    "set_editnet_beam_persistent_nbest": (_I, [C.POINTER(EditNetWeights), C.POINTER(EditNetDims), _P, _P, _P, _P, _L, _L, _I, _P, _P, _P,
+                                               _P, _P, _P, _Z, _P, _P]),
     "set_editnet_sample": (_I, [C.POINTER(EditNetWeights), C.POINTER(EditNetDims), _P, _P, _P, _P, _L, _L, _I, _U, _U, _P,
                                 _P, _P, _Z, _P]),
     "set_editnet_xe_forward": (_I, [C.POINTER(EditNetWeights), C.POINTER(EditNetDims), _P, _P, _P, _L,
@@ -264,8 +266,13 @@ PROTOTYPES = {
     "set_dcnet_greedy": (_I, [C.POINTER(DcnetWeights), C.POINTER(DcnetDims), _P, _P, _L, _L, _I, _P, _P, _P, _Z, _P]),
     "set_dcnet_beam_persistent": (_I, [C.POINTER(DcnetWeights), C.POINTER(DcnetDims), _P, _P, _L, _L, _I, _P, _P, _P, _P, _P, _P, _Z,
                                        _P]),
+    "set_dcnet_beam_persistent_nbest": (_I, [C.POINTER(DcnetWeights), C.POINTER(DcnetDims), _P, _P, _L, _L, _I, _P, _P, _P, _P, _P, _P,
+                                             _Z, _P, _P]),
     "set_ensemble_beam_persistent": (_I, [C.POINTER(EditNetWeights), C.POINTER(EditNetDims), C.POINTER(DcnetWeights), C.POINTER(DcnetDims),
                                           _P, _P, _P, _L, _L, _I, _P, _P, _P, _P, _P, _P, _Z, _P, _Z, _P, _Z, _P]),
+    "set_ensemble_beam_persistent_nbest": (_I, [C.POINTER(EditNetWeights), C.POINTER(EditNetDims), C.POINTER(DcnetWeights),
+                                                C.POINTER(DcnetDims), _P, _P, _P, _L, _L, _I, _P, _P, _P, _P, _P, _P, _Z, _P, _Z, _P, _Z,
+                                                _P, _P]),
     "set_ensemble_beam_xbuf_bytes": (_Z, [C.POINTER(EditNetDims), C.POINTER(DcnetDims)]),
     "set_dcnet_sample": (_I, [C.POINTER(DcnetWeights), C.POINTER(DcnetDims), _P, _P, _L, _L, _I, _U, _U, _P, _P, _P, _Z,
                               _P]),
@@ -342,6 +349,7 @@ PROTOTYPES = {
     "set_sample_logp_bwd_f32": (_I, [_P, _L, _P, _P, _P, _P, _L, _I, _I, _P]),
     "set_philox4x32": (_I, [_P, _I, _U, _U, _P]),
     "set_beam_pick_f32": (_I, [_P, _P, _L, _I, _I, _I, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "set_beam_pick_nbest_f32": (_I, [_P, _P, _L, _I, _I, _I, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "set_beam_gather_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "set_gemm_group_f32": (_I, [C.POINTER(GemmDesc), _I, _I, _I, _P, _Z, _P]),
     "set_gemm_group_slabs_f32": (_I, [C.POINTER(GemmDesc), _I, _I, _I, _P, _Z, C.POINTER(SlabSrc), _P]),

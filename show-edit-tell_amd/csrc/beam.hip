@@ -32,6 +32,12 @@ struct BeamArgs {
     int* best_len;               // (NI)
     long long* words;            // (NI*k) next input token per hypothesis row
     int* rows;                   // (NI*k) source row of each hypothesis row's recurrent state
+    // n-best (set_beam_pick_nbest_f32; all four nullptr otherwise): every counted <end> pick appends one entry, in completion
+    // order (by pick, within a pick by pick rank).  An image completes at most k hypotheses
+    float* done_score;           // (NI, k)
+    long long* done_seq;         // (NI, k, Lmax)
+    int* done_len;               // (NI, k)
+    int* n_done;                 // (NI) entries so far
 };
 
 __device__ __forceinline__ bool beam_better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
@@ -47,6 +53,9 @@ __global__ void __launch_bounds__(256) beam_pick_k(const BeamArgs a) {
     __shared__ long long s_word[BEAM_KMAX];     // per output slot: appended word
     __shared__ int s_best_parent;
     __shared__ long long s_best_word;
+    __shared__ int s_done_par[BEAM_KMAX];       // per completion of this pick: parent hypothesis
+    __shared__ long long s_done_word[BEAM_KMAX];
+    __shared__ int s_done_at, s_done_n;         // first entry of this pick in the image's list, entries of this pick
     const int img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int k = a.k, V = a.V;
     const int kl = a.k_left[img];
@@ -167,6 +176,22 @@ __global__ void __launch_bounds__(256) beam_pick_k(const BeamArgs a) {
             s_best_word = s_pick_i[c_arg] % V;
         }
         a.k_left[img] = kl - n_end;
+        s_done_n = 0;
+        if (a.n_done) {                          // the completions of this pick, in pick-rank order
+            const int at = max(a.n_done[img], 0);
+            int nd = 0;
+            for (int r = 0; r < k; ++r) {
+                const int flat = s_pick_i[r];
+                if (!(flat != 0x7fffffff && r < kl && flat % V == a.end_idx) || at + nd >= k) continue;
+                a.done_score[img * k + at + nd] = s_pick_v[r];
+                a.done_len[img * k + at + nd] = a.cur_len + 1;
+                s_done_par[nd] = flat / V;
+                s_done_word[nd] = flat % V;
+                ++nd;
+            }
+            a.n_done[img] = at + nd;
+            s_done_at = at; s_done_n = nd;
+        }
         // live picks first, in pick order; the other slots die
         for (int pass = 0; pass < 2; ++pass)
             for (int r = 0; r < k; ++r) {
@@ -193,6 +218,13 @@ __global__ void __launch_bounds__(256) beam_pick_k(const BeamArgs a) {
     if (s_best_parent >= 0)
         for (int p = tid; p <= L; p += 256)
             a.best_seq[(long long)img * a.Lmax + p] = p < L ? sin[(long long)s_best_parent * a.Lmax + p] : s_best_word;
+    if (s_done_n > 0) {
+        long long* dout = a.done_seq + ((long long)img * k + s_done_at) * a.Lmax;
+        for (int e = tid; e < s_done_n * (L + 1); e += 256) {
+            const int j = e / (L + 1), p = e - j * (L + 1);
+            dout[(long long)j * a.Lmax + p] = p < L ? sin[(long long)s_done_par[j] * a.Lmax + p] : s_done_word[j];
+        }
+    }
 }
 
 // state[s][r] <- state[s][rows[r]] for the k rows of one image, in place (all parents are rows of the same image)
@@ -221,10 +253,11 @@ using namespace set;
 
 extern "C" {
 
-int set_beam_pick_f32(const float* logits, const float* logits2, int64_t ld, int NI, int k, int V, int64_t end_idx,
-                      int cur_len, int Lmax, float* scores, int32_t* k_left, const int64_t* seqs_in, int64_t* seqs_out,
-                      float* best_score, int64_t* best_seq, int32_t* best_len, int64_t* words, int32_t* rows,
-                      void* stream) {
+// done_*: all four NULL for set_beam_pick_f32 (nothing written), the n-best entry's arrays otherwise
+static int beam_pick(const float* logits, const float* logits2, int64_t ld, int NI, int k, int V, int64_t end_idx,
+                     int cur_len, int Lmax, float* scores, int32_t* k_left, const int64_t* seqs_in, int64_t* seqs_out,
+                     float* best_score, int64_t* best_seq, int32_t* best_len, int64_t* words, int32_t* rows,
+                     float* done_score, int64_t* done_seq, int32_t* done_len, int32_t* n_done, void* stream) {
     if (!logits || !scores || !k_left || !seqs_in || !seqs_out || !best_score || !best_seq || !best_len || !words || !rows)
         return SET_ERR_ARG;
     if (NI <= 0 || k <= 0 || V <= 0 || cur_len < 1 || cur_len + 1 > Lmax || ld < V) return SET_ERR_ARG;
@@ -235,10 +268,28 @@ int set_beam_pick_f32(const float* logits, const float* logits2, int64_t ld, int
     a.seqs_in = (const long long*)seqs_in; a.seqs_out = (long long*)seqs_out;
     a.best_score = best_score; a.best_seq = (long long*)best_seq; a.best_len = best_len;
     a.words = (long long*)words; a.rows = rows;
+    a.done_score = done_score; a.done_seq = (long long*)done_seq; a.done_len = done_len; a.n_done = n_done;
     ProfScope ps("beam_pick", (hipStream_t)stream, 0.0, 8.0 * NI * k * V * (logits2 ? 2.0 : 1.0));
     hipLaunchKernelGGL(beam_pick_k, dim3(NI), dim3(256), 0, (hipStream_t)stream, a);
     SET_LAUNCH_CHECK();
     return SET_OK;
+}
+
+int set_beam_pick_f32(const float* logits, const float* logits2, int64_t ld, int NI, int k, int V, int64_t end_idx,
+                      int cur_len, int Lmax, float* scores, int32_t* k_left, const int64_t* seqs_in, int64_t* seqs_out,
+                      float* best_score, int64_t* best_seq, int32_t* best_len, int64_t* words, int32_t* rows,
+                      void* stream) {
+    return beam_pick(logits, logits2, ld, NI, k, V, end_idx, cur_len, Lmax, scores, k_left, seqs_in, seqs_out, best_score,
+                     best_seq, best_len, words, rows, nullptr, nullptr, nullptr, nullptr, stream);
+}
+
+int set_beam_pick_nbest_f32(const float* logits, const float* logits2, int64_t ld, int NI, int k, int V, int64_t end_idx,
+                            int cur_len, int Lmax, float* scores, int32_t* k_left, const int64_t* seqs_in, int64_t* seqs_out,
+                            float* best_score, int64_t* best_seq, int32_t* best_len, int64_t* words, int32_t* rows,
+                            float* done_score, int64_t* done_seq, int32_t* done_len, int32_t* n_done, void* stream) {
+    if (!done_score || !done_seq || !done_len || !n_done) return SET_ERR_ARG;
+    return beam_pick(logits, logits2, ld, NI, k, V, end_idx, cur_len, Lmax, scores, k_left, seqs_in, seqs_out, best_score,
+                     best_seq, best_len, words, rows, done_score, done_seq, done_len, n_done, stream);
 }
 
 int set_beam_gather_f32(float* s0, float* s1, float* s2, float* s3, const int32_t* rows, int NI, int k, int D,

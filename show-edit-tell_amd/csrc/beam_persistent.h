@@ -89,10 +89,13 @@ __device__ __forceinline__ void pb_row_store(float* sCand, const int j, const pb
 // the B best of the B x B candidates (ties: lowest flat index), then the bookkeeping the reference does on the host
 // (editnet.py:666-699).  sScore / sTok / sPar: running score, next word and parent slot of every slot; *k_left: hypotheses alive;
 // *best: best completed hypothesis so far; t = pick index, k = rows of the launch.
+// bm_hist_score (optional, laid out like bm_hist_word): the value of the pick behind slot s after pick t if that pick counted
+// (alive or just completed), -inf otherwise — a slot with word == <end> and a score above -inf IS a completion of pick t, and
+// the completions of one pick stand in pick-rank order (the n-best list of the search).  NULL: nothing is written.
 __device__ __forceinline__ void pb_pick(const float* sCand, float* sScore, long long* sTok, int* sPar, int* k_left, float* best,
                                         int* bm_hist_par, long long* bm_hist_word, float* bm_best_score, long long* bm_best_word,
                                         int* bm_result, const int V, const long long end_idx, const int t, const int k,
-                                        const bool wg0) {
+                                        const bool wg0, float* bm_hist_score = nullptr) {
     const int kl = *k_left;
     float pv_[PW_BEAM_K];
     int pi_[PW_BEAM_K];
@@ -148,6 +151,7 @@ __device__ __forceinline__ void pb_pick(const float* sCand, float* sScore, long 
             if (wg0) {
                 bm_hist_par[t * PW_BEAM_K + slot] = parent;
                 bm_hist_word[t * PW_BEAM_K + slot] = word;
+                if (bm_hist_score) bm_hist_score[t * PW_BEAM_K + slot] = (flat != 0x7fffffff && rr_ < kl) ? pv_[rr_] : -INFINITY;
             }
             ++slot;
         }

@@ -432,9 +432,11 @@ int set_dcnet_greedy(const SetDcnetWeights* w, const SetDcnetDims* d, const int6
     return dcnet_rollout(w, d, prev, prevlen, start_idx, end_idx, max_len, 0, 0, 0, seq, seq_logp, ws, ws_bytes, stream);
 }
 
-int set_dcnet_beam_persistent(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* prev, const int64_t* prevlen,
-                              int64_t start_idx, int64_t end_idx, int max_picks, int32_t* hist_parent, int64_t* hist_word,
-                              float* best_score, int64_t* best_word, int32_t* result, void* ws, size_t ws_bytes, void* stream) {
+// hist_score: NULL for set_dcnet_beam_persistent (nothing written), the n-best entry's array otherwise
+static int dcnet_beam_persistent(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* prev, const int64_t* prevlen,
+                                 int64_t start_idx, int64_t end_idx, int max_picks, int32_t* hist_parent, int64_t* hist_word,
+                                 float* hist_score, float* best_score, int64_t* best_word, int32_t* result, void* ws, size_t ws_bytes,
+                                 void* stream) {
     if (!w || !d || !prev || !prevlen || !hist_parent || !hist_word || !best_score || !best_word || !result || max_picks < 1)
         return SET_ERR_ARG;
     if (start_idx < 0 || start_idx >= d->V) return SET_ERR_ARG;
@@ -446,9 +448,25 @@ int set_dcnet_beam_persistent(const SetDcnetWeights* w, const SetDcnetDims* d, c
     SET_TRY(prep(d, ws, ws_bytes, &W));
     hipStream_t st = (hipStream_t)stream;
     SET_TRY(begin_impl(w, d, prev, prevlen, W, st));              // (includes Pc = enc W_ih[:, D:]^T: dcnet_persistent_ok holds)
-    const PDecBeam beam{hist_parent, hist_word, best_score, best_word, result};
+    const PDecBeam beam{hist_parent, hist_word, best_score, best_word, result, nullptr, hist_score};
     return dcnet_persistent_greedy(w, d, W.pre1, W.att1_c, W.mask, W.pd_pc, W.pd_x, W.it, W.unfinished, W.alive, start_idx, end_idx,
                                    max_picks, nullptr, nullptr, st, nullptr, &beam);
+}
+
+int set_dcnet_beam_persistent(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* prev, const int64_t* prevlen,
+                              int64_t start_idx, int64_t end_idx, int max_picks, int32_t* hist_parent, int64_t* hist_word,
+                              float* best_score, int64_t* best_word, int32_t* result, void* ws, size_t ws_bytes, void* stream) {
+    return dcnet_beam_persistent(w, d, prev, prevlen, start_idx, end_idx, max_picks, hist_parent, hist_word, nullptr, best_score,
+                                 best_word, result, ws, ws_bytes, stream);
+}
+
+int set_dcnet_beam_persistent_nbest(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* prev, const int64_t* prevlen,
+                                    int64_t start_idx, int64_t end_idx, int max_picks, int32_t* hist_parent, int64_t* hist_word,
+                                    float* best_score, int64_t* best_word, int32_t* result, void* ws, size_t ws_bytes, void* stream,
+                                    float* hist_score) {
+    if (!hist_score) return SET_ERR_ARG;
+    return dcnet_beam_persistent(w, d, prev, prevlen, start_idx, end_idx, max_picks, hist_parent, hist_word, hist_score, best_score,
+                                 best_word, result, ws, ws_bytes, stream);
 }
 
 int set_dcnet_sample(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* prev, const int64_t* prevlen,

@@ -197,6 +197,7 @@ struct PDecEditArgs {
     float* bm_best_score;                        // [1] best completed hypothesis (-inf: none)
     long long* bm_best_word;                     // [1] its last word (<end>)
     int* bm_result;                              // [4] pick index and parent slot of the best completed hypothesis, k_left, picks made
+    float* bm_hist_score;                        // (max_len, 4) or NULL: value of every counted pick, -inf elsewhere (n-best).  Last member
 };
 
 // the wide variant's launch (decode_persistent_wide.hip); P is complete except for the exchange pointers it lays out itself

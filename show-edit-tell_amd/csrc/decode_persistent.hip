@@ -78,6 +78,7 @@ struct PDecDcnetArgs {
     float* bm_best_score;                        // [1] best completed hypothesis (-inf: none)
     long long* bm_best_word;                     // [1] its last word (<end>)
     int* bm_result;                              // [4] pick index and parent slot of the best completed hypothesis, k_left, picks made
+    float* bm_hist_score;                        // (max_len, 4) or NULL: value of every counted pick, -inf elsewhere (n-best).  Last member
 };
 
 // RES: B <= 4 and T <= PDEC_TREG — a wave scores ONE fixed row, whose hoisted cap_features_att rows (loop-invariant, T x A
@@ -478,7 +479,7 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) dcnet_persistent_k(const PDec
             __syncthreads();
             if (tid == 0)                                        // the pick itself and its bookkeeping (beam_persistent.h)
                 pb_pick(sCand, sScore, sTok, sPar, &sKleft[0], &sBest[0], P.bm_hist_par, P.bm_hist_word, P.bm_best_score, P.bm_best_word,
-                        P.bm_result, V, P.end_idx, t, B, wg == 0);
+                        P.bm_result, V, P.end_idx, t, B, wg == 0, P.bm_hist_score);
             __syncthreads();
             PD_STAMP(13);
             if (sKleft[0] == 0) break;                           // every hypothesis has ended (dcnet.py:507-508)
@@ -661,7 +662,7 @@ int dcnet_persistent_greedy(const SetDcnetWeights* w, const SetDcnetDims* d, con
     }
     if (beam) {
         P.bm_hist_par = beam->hist_par; P.bm_hist_word = (long long*)beam->hist_word; P.bm_best_score = beam->best_score;
-        P.bm_best_word = (long long*)beam->best_word; P.bm_result = beam->result;
+        P.bm_best_word = (long long*)beam->best_word; P.bm_result = beam->result; P.bm_hist_score = beam->hist_score;
     }
     const bool lh = P.caps && P.last_h2, bm = beam != nullptr;
     const int lds = pdec_lds_floats(B, D, d->A, bm) * (int)sizeof(float);

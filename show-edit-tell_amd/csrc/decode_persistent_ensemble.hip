@@ -695,7 +695,7 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) ensemble_persistent_k(const P
         PE_SYNC();
         if (tid == 0)                                            // the pick itself and its bookkeeping (beam_persistent.h)
             pb_pick(sCand, sScore, sTok, sPar, &sKleft, &sBest, P.e.bm_hist_par, P.e.bm_hist_word, P.e.bm_best_score, P.e.bm_best_word,
-                    P.e.bm_result, V, P.e.end_idx, t, B, wg == 0);
+                    P.e.bm_result, V, P.e.end_idx, t, B, wg == 0, P.e.bm_hist_score);
         PE_SYNC();
         PE_STAMP(20);
         if (sKleft == 0) break;                                  // every hypothesis has ended (eval_full.py:197-198)
@@ -747,11 +747,12 @@ size_t set_ensemble_beam_xbuf_bytes(const SetEditNetDims* de, const SetDcnetDims
     return pens_xbytes(de->B, de->D, de->A);
 }
 
-int set_ensemble_beam_persistent(const SetEditNetWeights* we, const SetEditNetDims* de, const SetDcnetWeights* wd,
-                                 const SetDcnetDims* dd, const float* X, const int64_t* prev, const int64_t* prevlen,
-                                 int64_t start_idx, int64_t end_idx, int max_picks, int32_t* hist_parent, int64_t* hist_word,
-                                 float* best_score, int64_t* best_word, int32_t* result, void* ws_e, size_t ws_e_bytes, void* ws_d,
-                                 size_t ws_d_bytes, void* xbuf, size_t xbuf_bytes, void* stream) {
+// hist_score: NULL for set_ensemble_beam_persistent (nothing written), the n-best entry's array otherwise
+static int ensemble_beam_persistent(const SetEditNetWeights* we, const SetEditNetDims* de, const SetDcnetWeights* wd,
+                                    const SetDcnetDims* dd, const float* X, const int64_t* prev, const int64_t* prevlen,
+                                    int64_t start_idx, int64_t end_idx, int max_picks, int32_t* hist_parent, int64_t* hist_word,
+                                    float* hist_score, float* best_score, int64_t* best_word, int32_t* result, void* ws_e,
+                                    size_t ws_e_bytes, void* ws_d, size_t ws_d_bytes, void* xbuf, size_t xbuf_bytes, void* stream) {
     if (!we || !de || !wd || !dd || !X || !prev || !prevlen || !hist_parent || !hist_word || !best_score || !best_word || !result ||
         !ws_e || !ws_d || !xbuf || max_picks < 1)
         return SET_ERR_ARG;
@@ -780,7 +781,7 @@ int set_ensemble_beam_persistent(const SetEditNetWeights* we, const SetEditNetDi
         E.pv = pe.pv;
         E.start_idx = start_idx; E.end_idx = end_idx;
         E.bm_hist_par = hist_parent; E.bm_hist_word = (long long*)hist_word; E.bm_best_score = best_score;
-        E.bm_best_word = (long long*)best_word; E.bm_result = result;
+        E.bm_best_word = (long long*)best_word; E.bm_result = result; E.bm_hist_score = hist_score;
     }
     {
         const int E_ = dd->E, C = dd->C;
@@ -820,6 +821,26 @@ int set_ensemble_beam_persistent(const SetEditNetWeights* we, const SetEditNetDi
     SET_TRY(guard.launched(st));
     SET_TRY(pd_stamps_report(P.e.stamps, P.e.stamp_wg, 20, max_picks, st));
     return SET_OK;
+}
+
+int set_ensemble_beam_persistent(const SetEditNetWeights* we, const SetEditNetDims* de, const SetDcnetWeights* wd,
+                                 const SetDcnetDims* dd, const float* X, const int64_t* prev, const int64_t* prevlen,
+                                 int64_t start_idx, int64_t end_idx, int max_picks, int32_t* hist_parent, int64_t* hist_word,
+                                 float* best_score, int64_t* best_word, int32_t* result, void* ws_e, size_t ws_e_bytes, void* ws_d,
+                                 size_t ws_d_bytes, void* xbuf, size_t xbuf_bytes, void* stream) {
+    return ensemble_beam_persistent(we, de, wd, dd, X, prev, prevlen, start_idx, end_idx, max_picks, hist_parent, hist_word, nullptr,
+                                    best_score, best_word, result, ws_e, ws_e_bytes, ws_d, ws_d_bytes, xbuf, xbuf_bytes, stream);
+}
+
+int set_ensemble_beam_persistent_nbest(const SetEditNetWeights* we, const SetEditNetDims* de, const SetDcnetWeights* wd,
+                                       const SetDcnetDims* dd, const float* X, const int64_t* prev, const int64_t* prevlen,
+                                       int64_t start_idx, int64_t end_idx, int max_picks, int32_t* hist_parent, int64_t* hist_word,
+                                       float* best_score, int64_t* best_word, int32_t* result, void* ws_e, size_t ws_e_bytes,
+                                       void* ws_d, size_t ws_d_bytes, void* xbuf, size_t xbuf_bytes, void* stream,
+                                       float* hist_score) {
+    if (!hist_score) return SET_ERR_ARG;
+    return ensemble_beam_persistent(we, de, wd, dd, X, prev, prevlen, start_idx, end_idx, max_picks, hist_parent, hist_word, hist_score,
+                                    best_score, best_word, result, ws_e, ws_e_bytes, ws_d, ws_d_bytes, xbuf, xbuf_bytes, stream);
 }
 
 }  // extern "C"

@@ -550,7 +550,7 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) editnet_persistent_wide_k(con
             PW_SYNC();
             if (tid == 0)                                        // the pick itself and its bookkeeping (beam_persistent.h)
                 pb_pick(sCand, sScore, sTok, sPar, &sKleft, &sBest, P.bm_hist_par, P.bm_hist_word, P.bm_best_score, P.bm_best_word,
-                        P.bm_result, V, P.end_idx, t, B, wg == 0);
+                        P.bm_result, V, P.end_idx, t, B, wg == 0, P.bm_hist_score);
             PW_SYNC();
             PD_STAMP(16);
             if (sKleft == 0) break;                              // every hypothesis has ended (editnet.py:700-701)
@@ -815,7 +815,7 @@ int editnet_persistent_greedy(const SetEditNetWeights* w, const SetEditNetDims* 
     P.test_stall = guard.test_stall(); P.fault = guard.fault;
     if (beam) {
         P.bm_hist_par = beam->hist_par; P.bm_hist_word = (long long*)beam->hist_word; P.bm_best_score = beam->best_score;
-        P.bm_best_word = (long long*)beam->best_word; P.bm_result = beam->result;
+        P.bm_best_word = (long long*)beam->best_word; P.bm_result = beam->result; P.bm_hist_score = beam->hist_score;
         if (wide) P.rmask = beam->rmask;
     }
     bool unsupported = true;

@@ -657,10 +657,11 @@ int set_editnet_greedy_begun(const SetEditNetWeights* w, const SetEditNetDims* d
                    stream, true);
 }
 
-int set_editnet_beam_persistent(const SetEditNetWeights* w, const SetEditNetDims* d, const float* X, const float* image_mean,
-                                const int64_t* prev, const int64_t* prevlen, int64_t start_idx, int64_t end_idx, int max_picks,
-                                int32_t* hist_parent, int64_t* hist_word, float* best_score, int64_t* best_word,
-                                int32_t* result, void* ws, size_t ws_bytes, void* stream) {
+// hist_score: NULL for set_editnet_beam_persistent (nothing written), the n-best entry's array otherwise
+static int editnet_beam_persistent(const SetEditNetWeights* w, const SetEditNetDims* d, const float* X, const float* image_mean,
+                                   const int64_t* prev, const int64_t* prevlen, int64_t start_idx, int64_t end_idx, int max_picks,
+                                   int32_t* hist_parent, int64_t* hist_word, float* hist_score, float* best_score, int64_t* best_word,
+                                   int32_t* result, void* ws, size_t ws_bytes, void* stream) {
     if (!w || !d || !X || !prev || !prevlen || !hist_parent || !hist_word || !best_score || !best_word || !result || max_picks < 1)
         return SET_ERR_ARG;
     if (start_idx < 0 || start_idx >= d->V) return SET_ERR_ARG;
@@ -671,9 +672,26 @@ int set_editnet_beam_persistent(const SetEditNetWeights* w, const SetEditNetDims
     SET_TRY(prep(d, ws, ws_bytes, &W));
     hipStream_t st = (hipStream_t)stream;
     SET_TRY(begin_impl(w, d, X, image_mean, prev, prevlen, W, st, true));      // (includes Pv = X x2h[:, 2D:]^T and the region mask)
-    const PDecBeam beam{hist_parent, hist_word, best_score, best_word, result, d->adaptive ? W.rmask : nullptr};
+    const PDecBeam beam{hist_parent, hist_word, best_score, best_word, result, d->adaptive ? W.rmask : nullptr, hist_score};
     return editnet_persistent_greedy(w, d, W.pre1, W.att1, W.att1_c, W.mask, W.cap_proj, W.mem_proj, W.Mem, W.pd_pv, W.pd_x, W.it,
                                      W.unfinished, W.alive, start_idx, end_idx, max_picks, nullptr, nullptr, st, nullptr, &beam);
+}
+
+int set_editnet_beam_persistent(const SetEditNetWeights* w, const SetEditNetDims* d, const float* X, const float* image_mean,
+                                const int64_t* prev, const int64_t* prevlen, int64_t start_idx, int64_t end_idx, int max_picks,
+                                int32_t* hist_parent, int64_t* hist_word, float* best_score, int64_t* best_word,
+                                int32_t* result, void* ws, size_t ws_bytes, void* stream) {
+    return editnet_beam_persistent(w, d, X, image_mean, prev, prevlen, start_idx, end_idx, max_picks, hist_parent, hist_word, nullptr,
+                                   best_score, best_word, result, ws, ws_bytes, stream);
+}
+
+int set_editnet_beam_persistent_nbest(const SetEditNetWeights* w, const SetEditNetDims* d, const float* X, const float* image_mean,
+                                      const int64_t* prev, const int64_t* prevlen, int64_t start_idx, int64_t end_idx, int max_picks,
+                                      int32_t* hist_parent, int64_t* hist_word, float* best_score, int64_t* best_word,
+                                      int32_t* result, void* ws, size_t ws_bytes, void* stream, float* hist_score) {
+    if (!hist_score) return SET_ERR_ARG;
+    return editnet_beam_persistent(w, d, X, image_mean, prev, prevlen, start_idx, end_idx, max_picks, hist_parent, hist_word, hist_score,
+                                   best_score, best_word, result, ws, ws_bytes, stream);
 }
 
 int set_editnet_sample(const SetEditNetWeights* w, const SetEditNetDims* d, const float* X, const float* image_mean,

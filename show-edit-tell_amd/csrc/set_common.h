@@ -290,7 +290,7 @@ int persistent_encoder(const float* w_hh, const float* xg, long long ld_xg_row, 
 struct PDecTeacher { const int64_t* caps; long long caps_stride; float* predictions; const int* host_decode_lengths;
                      float* last_h2 = nullptr; };
 // beam mode (one image, rows = hypotheses); rmask != NULL: adaptive features (region mask (B, R), up to PDEC_RREG_WIDE regions)
-struct PDecBeam { int* hist_par; int64_t* hist_word; float* best_score; int64_t* best_word; int* result; const float* rmask = nullptr; };
+struct PDecBeam { int* hist_par; int64_t* hist_word; float* best_score; int64_t* best_word; int* result; const float* rmask = nullptr; float* hist_score = nullptr; };
 // decode_persistent.hip: the greedy loop of a small batch as one launch with grid barriers
 constexpr int PDEC_MAXB = 8;          // rows of the <= 8-row persistent decode kernels
 constexpr int PDW_MAXB = 16;          // rows of the wide EditNet variant (decode_persistent_wide.hip): one full 16-row MFMA tile

@@ -119,7 +119,22 @@ class _FusedDcnet(_FusedModel):
                                       logits.shape[1], ptr(self.ws), self.ws.numel(), self.st), "set_dcnet_step")
 
 
-def _fused_beam(models, NI, k, V, word_map, dev, max_steps, poll=4, return_scores=False):
+def _check_n_best(n_best, beam_size):
+    """n_best=None: off.  Otherwise an integer in 1 .. beam_size (a search completes at most beam_size hypotheses)."""
+    if n_best is None:
+        return None
+    m = int(n_best)
+    if m != n_best or m < 1 or m > int(beam_size):
+        raise ValueError("n_best must be an integer in 1 .. beam_size = %d, got %r" % (int(beam_size), n_best))
+    return m
+
+
+def _n_best_sorted(done, m):
+    """[(tokens, score)] in completion order -> the m best: score descending, equal scores in completion order."""
+    return sorted(done, key=lambda e: -e[1])[:m]
+
+
+def _fused_beam(models, NI, k, V, word_map, dev, max_steps, poll=4, return_scores=False, n_best=None):
     from . import _lib
     from ._lib import check, ptr, stream_of
     lib = _lib.load()
@@ -137,13 +152,22 @@ def _fused_beam(models, NI, k, V, word_map, dev, max_steps, poll=4, return_score
     best_seq = torch.zeros(NI, Lmax, dtype=torch.long, device=dev)
     best_len = torch.zeros(NI, dtype=torch.int32, device=dev)
     logits = [torch.empty(B, V, dtype=torch.float32, device=dev) for _ in models]
+    if n_best is not None:                               # every counted <end> pick appends (score, tokens, length), set_hip.h
+        done_score = torch.full((NI, k), neg, device=dev)
+        done_seq = torch.zeros(NI, k, Lmax, dtype=torch.long, device=dev)
+        done_len = torch.zeros(NI, k, dtype=torch.int32, device=dev)
+        n_done = torch.zeros(NI, dtype=torch.int32, device=dev)
     step = 1
     while True:
         for m, lg in zip(models, logits):
             m.step(words, lg)
-        check(lib.set_beam_pick_f32(ptr(logits[0]), ptr(logits[1]) if len(models) > 1 else None, V, NI, k, V, end, step,
-                                    Lmax, ptr(scores), ptr(k_left), ptr(seqs[0]), ptr(seqs[1]), ptr(best_score),
-                                    ptr(best_seq), ptr(best_len), ptr(words), ptr(rows), st), "set_beam_pick_f32")
+        pick = (ptr(logits[0]), ptr(logits[1]) if len(models) > 1 else None, V, NI, k, V, end, step, Lmax, ptr(scores), ptr(k_left),
+                ptr(seqs[0]), ptr(seqs[1]), ptr(best_score), ptr(best_seq), ptr(best_len), ptr(words), ptr(rows))
+        if n_best is None:
+            check(lib.set_beam_pick_f32(*pick, st), "set_beam_pick_f32")
+        else:
+            check(lib.set_beam_pick_nbest_f32(*pick, ptr(done_score), ptr(done_seq), ptr(done_len), ptr(n_done), st),
+                  "set_beam_pick_nbest_f32")
         seqs.reverse()
         for m in models:
             s0, s1, s2, s3 = m.states
@@ -163,52 +187,71 @@ def _fused_beam(models, NI, k, V, word_map, dev, max_steps, poll=4, return_score
         else:
             out.append(best_c[i, :int(len_c[i])].tolist())
             out_scores.append(float(score_c[i]))
-    return (out, out_scores) if return_scores else out
+    if n_best is None:
+        return (out, out_scores) if return_scores else out
+    ds_c, dq_c, dl_c, nd_c = done_score.cpu(), done_seq.cpu(), done_len.cpu(), n_done.cpu()
+    nbest = [_n_best_sorted([(dq_c[i, j, :int(dl_c[i, j])].tolist(), float(ds_c[i, j])) for j in range(int(nd_c[i]))], n_best)
+             for i in range(NI)]
+    return (out, out_scores, nbest) if return_scores else (out, nbest)
 
 
-def _with_trace(result, batched, return_scores, decoder, X, prev, plen, word_map, image_mean=None):
+def _with_trace(result, batched, return_scores, decoder, X, prev, plen, word_map, image_mean=None, n_best=None):
     """return_trace=True: the search's result + the EditTrace of the returned sequences (one forced decode of NI rows after
-    the search; evaluate.edit_trace).  result: (tokens, score) of a per-image entry, the token lists (or (lists, scores)) of
-    a batched one."""
-    seqs = (result[0] if return_scores else result) if batched else [result[0]]
+    the search; evaluate.edit_trace).  result: (tokens, score[, n-best]) of a per-image entry, the token lists (or (lists[,
+    scores][, n-best])) of a batched one.  The trace is that of the PRIMARY result, with n_best too."""
+    multi = return_scores or n_best is not None
+    seqs = (result[0] if multi else result) if batched else [result[0]]
     tr = edit_trace(decoder, X, prev, plen, word_map, seqs, image_mean=image_mean)
-    return (tuple(result) + (tr,)) if (not batched or return_scores) else (result, tr)
+    return (tuple(result) + (tr,)) if (not batched or multi) else (result, tr)
 
 
 @torch.no_grad()
 def beam_search_editnet_batched(decoder, image_features, previous_caption, prev_caplen, word_map, beam_size=3,
-                                max_steps=50, return_scores=False, return_trace=False):
+                                max_steps=50, return_scores=False, return_trace=False, n_best=None):
     """image_features (NI,R,F), previous_caption (NI,T), prev_caplen (NI,1) -> list of NI token lists
     (with return_scores: also the list of their scores; NaN where the step limit was hit).  The attention LSTM sees the mean
     over all R regions; adaptive features (zero-padded regions, an image mean per image): beam_search_adaptive_batched.
-    return_trace: the result gains the EditTrace of the returned sequences as its last element."""
+    n_best=m (1 <= m <= beam_size, all eight beam_search_* entries): the result gains, after the elements above, the N-BEST
+    lists — per image up to m (tokens, score) pairs of its COMPLETED hypotheses, tokens with <start> and <end>, score descending
+    and equal scores in completion order (by pick, within a pick by pick rank).  When the search finished, entry 0 is the
+    primary result; a search that hit the step limit keeps the reference's primary answer (seqs[0][:18], NaN) and lists what
+    had completed by then, possibly nothing.  The trace of an alternative is one more forced decode:
+        seqs, nbest = beam_search_editnet_batched(dec, X, prev, plen, wm, 3, n_best=3)
+        runner_up = nbest[i][1][0]                      # tokens of image i's second-best completed hypothesis
+        tr = edit_trace(dec, X[i:i + 1], prev[i:i + 1], plen[i:i + 1], wm, [runner_up])
+    return_trace: the result gains the EditTrace of the returned (primary) sequences as its last element."""
+    n_best = _check_n_best(n_best, beam_size)
     decoder.eval()
     X = image_features.float().contiguous()
     prev = previous_caption.long().contiguous()
     plen = prev_caplen.reshape(-1).long().contiguous()
     m = _FusedEditNet(decoder, X, prev, plen, beam_size, max_steps)
     res = _fused_beam([m], X.shape[0], beam_size, decoder.vocab_size, word_map, X.device, max_steps,
-                      return_scores=return_scores)
-    return _with_trace(res, True, return_scores, decoder, X, prev, plen, word_map) if return_trace else res
+                      return_scores=return_scores, n_best=n_best)
+    return _with_trace(res, True, return_scores, decoder, X, prev, plen, word_map, n_best=n_best) if return_trace else res
 
 
 @torch.no_grad()
 def beam_search_dcnet_batched(dae, previous_caption, prev_caplen, word_map, beam_size=3, max_steps=50,
-                              return_scores=False):
+                              return_scores=False, n_best=None):
+    """n_best: see beam_search_editnet_batched."""
+    n_best = _check_n_best(n_best, beam_size)
     dae.eval()
     prev = previous_caption.long().contiguous()
     plen = prev_caplen.reshape(-1).long().contiguous()
     m = _FusedDcnet(dae, prev, plen, beam_size, max_steps)
     return _fused_beam([m], prev.shape[0], beam_size, dae.vocab_size, word_map, prev.device, max_steps,
-                       return_scores=return_scores)
+                       return_scores=return_scores, n_best=n_best)
 
 
 @torch.no_grad()
 def beam_search_ensemble_batched(decoder, dae, image_features, previous_caption, prev_caplen, word_map, beam_size=3,
-                                 max_steps=50, return_scores=False, return_trace=False):
+                                 max_steps=50, return_scores=False, return_trace=False, n_best=None):
     """eval_full.py:88-218 for NI images at once: both models step on the same words, the epilogue averages
     their softmax probabilities.  Fixed features (image mean over all R regions); adaptive features: beam_search_adaptive*.
+    n_best: see beam_search_editnet_batched (the scores are those of the joint pick).
     return_trace: the result gains, as its last element, EditNet's view of the jointly chosen words (their EditTrace)."""
+    n_best = _check_n_best(n_best, beam_size)
     decoder.eval()
     dae.eval()
     X = image_features.float().contiguous()
@@ -217,8 +260,8 @@ def beam_search_ensemble_batched(decoder, dae, image_features, previous_caption,
     e = _FusedEditNet(decoder, X, prev, plen, beam_size, max_steps)
     d = _FusedDcnet(dae, prev, plen, beam_size, max_steps)
     res = _fused_beam([e, d], X.shape[0], beam_size, decoder.vocab_size, word_map, X.device, max_steps,
-                      return_scores=return_scores)
-    return _with_trace(res, True, return_scores, decoder, X, prev, plen, word_map) if return_trace else res
+                      return_scores=return_scores, n_best=n_best)
+    return _with_trace(res, True, return_scores, decoder, X, prev, plen, word_map, n_best=n_best) if return_trace else res
 
 
 # ------------------------------------------------------------------------------------------------
@@ -228,22 +271,27 @@ def beam_search_ensemble_batched(decoder, dae, image_features, previous_caption,
 # ------------------------------------------------------------------------------------------------
 class _PersistentBeamOut:
     """Outputs of one persistent beam launch (set_editnet_beam_persistent / set_dcnet_beam_persistent), all in ONE device
-    buffer: [hist_word (picks, 4) i64 | best_word i64 | hist_parent (picks, 4) i32 | result (4) i32 | best_score f32], read
-    back with a single copy (the search's only host synchronisation)."""
+    buffer: [hist_word (picks, 4) i64 | best_word i64 | hist_parent (picks, 4) i32 | result (4) i32 | best_score f32 | pad],
+    with n_best=True followed by [hist_score (picks, 4) f32] (the *_nbest entries), read back with a single copy (the search's
+    only host synchronisation)."""
 
-    def __init__(self, picks, dev):
+    def __init__(self, picks, dev, n_best=False):
         self.picks = picks
         self.n_hw, self.n_hp = picks * 4 * 8, picks * 4 * 4
-        self.buf = torch.empty(self.n_hw + 8 + self.n_hp + 16 + 8, dtype=torch.uint8, device=dev)
+        self.o_hs = self.n_hw + 8 + self.n_hp + 16 + 8
+        self.buf = torch.empty(self.o_hs + (picks * 4 * 4 if n_best else 0), dtype=torch.uint8, device=dev)
         base = self.buf.data_ptr()
         self.o_hp, self.o_res = self.n_hw + 8, self.n_hw + 8 + self.n_hp
         self.o_bs = self.o_res + 16
         self.hist_word, self.best_word, self.hist_parent = base, base + self.n_hw, base + self.o_hp
         self.result, self.best_score = base + self.o_res, base + self.o_bs
+        self.hist_score = base + self.o_hs if n_best else None
 
-    def answer(self, word_map, name):
+    def answer(self, word_map, name, n_best=None, k=4):
         """(tokens, score): the best completed hypothesis, or the step-limit rule of the reference (editnet.py:702-704,711,
-        dcnet.py:503-505,512: seqs[0][:18], score NaN)."""
+        dcnet.py:503-505,512: seqs[0][:18], score NaN).  n_best=m: (tokens, score, the m best completed hypotheses) — the
+        completions of pick t are the slots s < k (the others are never written) with hist_word == <end> and hist_score > -inf, in
+        slot order (set_hip.h)."""
         from . import _lib
         picks, n_hw, n_hp, o_hp, o_res, o_bs = self.picks, self.n_hw, self.n_hp, self.o_hp, self.o_res, self.o_bs
         host = self.buf.cpu().numpy()
@@ -264,13 +312,21 @@ class _PersistentBeamOut:
 
         start = int(word_map['<start>'])
         if k_left > 0:                                                 # ran into the step limit
-            return ([start] + trace(made - 1, 0))[:18], float("nan")
-        return [start] + trace(best_t - 1, best_parent) + [best_word_h], best_score_h
+            one = ([start] + trace(made - 1, 0))[:18], float("nan")
+        else:
+            one = [start] + trace(best_t - 1, best_parent) + [best_word_h], best_score_h
+        if n_best is None:
+            return one
+        hs = host[self.o_hs:self.o_hs + n_hp].view("float32").reshape(picks, 4)
+        end = int(word_map['<end>'])
+        done = [([start] + trace(t, s), float(hs[t, s])) for t in range(made) for s in range(k)
+                if int(hw[t, s]) == end and hs[t, s] > float("-inf")]
+        return one + (_n_best_sorted(done, n_best),)
 
 
 @torch.no_grad()
 def _beam_search_editnet_persistent(decoder, image_features, previous_caption, prev_caplen, word_map, beam_size, max_steps=50,
-                                    image_mean=None):
+                                    image_mean=None, n_best=None):
     """ONE image, k <= 4: prologue + one persistent launch for the whole search (include/set_hip.h
     set_editnet_beam_persistent; the rows of the launch are the k hypotheses).  Returns None when the library answers
     SET_ERR_UNSUPPORTED (no token table yet, k > 4, dimensions outside the persistent launch): the caller takes the
@@ -295,34 +351,47 @@ def _beam_search_editnet_persistent(decoder, image_features, previous_caption, p
     if not w.tok_table:
         return None
     ws = decoder._workspace(dims)
-    out = _PersistentBeamOut(picks, dev)
-    rc = lib.set_editnet_beam_persistent(C.byref(w), C.byref(dims), ptr(X), None if mean is None else ptr(mean), ptr(prev), ptr(plen),
-                                         int(word_map['<start>']),
-                                         int(word_map['<end>']), picks, out.hist_parent, out.hist_word, out.best_score, out.best_word,
-                                         out.result, ptr(ws), ws.numel(), stream_of(dev))
+    out = _PersistentBeamOut(picks, dev, n_best is not None)
+    args = (C.byref(w), C.byref(dims), ptr(X), None if mean is None else ptr(mean), ptr(prev), ptr(plen), int(word_map['<start>']),
+            int(word_map['<end>']), picks, out.hist_parent, out.hist_word, out.best_score, out.best_word, out.result, ptr(ws),
+            ws.numel(), stream_of(dev))
+    if n_best is None:
+        rc = lib.set_editnet_beam_persistent(*args)
+    else:                                                          # the same launch, plus the score of every counted pick
+        rc = lib.set_editnet_beam_persistent_nbest(*args, out.hist_score)
     if rc == 2:                                                    # SET_ERR_UNSUPPORTED: no output was touched (set_hip.h: answered
         return None                                                # before the prologue except on a device too small for the grid)
     check(rc, "set_editnet_beam_persistent")
-    return out.answer(word_map, "set_editnet_beam_persistent")
+    return out.answer(word_map, "set_editnet_beam_persistent", n_best, k)
 
 
-def beam_search_editnet(decoder, image_features, previous_caption, prev_caplen, word_map, beam_size=3, return_trace=False):
+def _first(res):
+    """the NI = 1 batched result (lists, scores[, n-best lists]) as a per-image one"""
+    return tuple(r[0] for r in res)
+
+
+def beam_search_editnet(decoder, image_features, previous_caption, prev_caplen, word_map, beam_size=3, return_trace=False,
+                        n_best=None):
     """The reference's own calling convention, ONE image per call (editnet.py:601-613).  k <= 4 with the token table
     active: one persistent launch (csrc/decode_persistent_wide.hip, beam mode); otherwise the NI = 1 case of the batched
     search.  Adaptive features (an image mean per image, zero-padded regions): beam_search_adaptive.
-    return_trace: (tokens, score, EditTrace of the returned tokens)."""
-    one = _beam_search_editnet_persistent(decoder, image_features, previous_caption, prev_caplen, word_map, beam_size)
+    n_best=m: (tokens, score, [(tokens, score)] of up to m completed hypotheses, best first) — see
+    beam_search_editnet_batched; the routing is the same, and an entry's tokens go to edit_trace as they are:
+        tokens, score, nbest = beam_search_editnet(dec, X, prev, plen, wm, 3, n_best=3)
+        tr = edit_trace(dec, X, prev, plen, wm, [nbest[1][0]])         # the runner-up's trace
+    return_trace: (tokens, score[, n-best], EditTrace of the returned tokens)."""
+    n_best = _check_n_best(n_best, beam_size)
+    one = _beam_search_editnet_persistent(decoder, image_features, previous_caption, prev_caplen, word_map, beam_size, n_best=n_best)
     if one is None:
-        seqs, scores = beam_search_editnet_batched(decoder, image_features, previous_caption, prev_caplen, word_map,
-                                                   beam_size, return_scores=True)
-        one = seqs[0], scores[0]
+        one = _first(beam_search_editnet_batched(decoder, image_features, previous_caption, prev_caplen, word_map, beam_size,
+                                                 return_scores=True, n_best=n_best))
     if return_trace:
         return _with_trace(one, False, True, decoder, image_features, previous_caption, prev_caplen, word_map)
     return one
 
 
 @torch.no_grad()
-def _beam_search_dcnet_persistent(dae, previous_caption, prev_caplen, word_map, beam_size, max_steps=50):
+def _beam_search_dcnet_persistent(dae, previous_caption, prev_caplen, word_map, beam_size, max_steps=50, n_best=None):
     """ONE previous caption, k <= 4: prologue + one persistent launch for the whole search (include/set_hip.h
     set_dcnet_beam_persistent; the rows of the launch are the k hypotheses).  Returns None when the library answers
     SET_ERR_UNSUPPORTED (no token table yet, k > 4, dimensions outside the persistent launch, SET_DEC_PERSISTENT=0): the
@@ -345,31 +414,34 @@ def _beam_search_dcnet_persistent(dae, previous_caption, prev_caplen, word_map, 
     if not w.tok_table:
         return None
     ws = dae._workspace(dims)
-    out = _PersistentBeamOut(picks, dev)
-    rc = lib.set_dcnet_beam_persistent(C.byref(w), C.byref(dims), ptr(prev), ptr(plen), int(word_map['<start>']),
-                                       int(word_map['<end>']), picks, out.hist_parent, out.hist_word, out.best_score, out.best_word,
-                                       out.result, ptr(ws), ws.numel(), stream_of(dev))
+    out = _PersistentBeamOut(picks, dev, n_best is not None)
+    args = (C.byref(w), C.byref(dims), ptr(prev), ptr(plen), int(word_map['<start>']), int(word_map['<end>']), picks, out.hist_parent,
+            out.hist_word, out.best_score, out.best_word, out.result, ptr(ws), ws.numel(), stream_of(dev))
+    rc = lib.set_dcnet_beam_persistent(*args) if n_best is None else lib.set_dcnet_beam_persistent_nbest(*args, out.hist_score)
     if rc == 2:                                                    # SET_ERR_UNSUPPORTED: no output was touched
         return None
     check(rc, "set_dcnet_beam_persistent")
-    return out.answer(word_map, "set_dcnet_beam_persistent")
+    return out.answer(word_map, "set_dcnet_beam_persistent", n_best, k)
 
 
-def beam_search_dcnet(dae, previous_caption, prev_caplen, word_map, beam_size=3):
+def beam_search_dcnet(dae, previous_caption, prev_caplen, word_map, beam_size=3, n_best=None):
     """The reference's own calling convention, ONE previous caption per call (dcnet.py:413-423).  k <= 4 with the token table
-    active: one persistent launch (csrc/decode_persistent.hip, beam mode); otherwise the NI = 1 case of the batched search."""
-    one = _beam_search_dcnet_persistent(dae, previous_caption, prev_caplen, word_map, beam_size)
+    active: one persistent launch (csrc/decode_persistent.hip, beam mode); otherwise the NI = 1 case of the batched search.
+    n_best=m: (tokens, score, [(tokens, score)] of up to m completed hypotheses, best first), see beam_search_editnet_batched."""
+    n_best = _check_n_best(n_best, beam_size)
+    one = _beam_search_dcnet_persistent(dae, previous_caption, prev_caplen, word_map, beam_size, n_best=n_best)
     if one is not None:
         return one
-    seqs, scores = beam_search_dcnet_batched(dae, previous_caption, prev_caplen, word_map, beam_size, return_scores=True)
-    return seqs[0], scores[0]
+    return _first(beam_search_dcnet_batched(dae, previous_caption, prev_caplen, word_map, beam_size, return_scores=True,
+                                            n_best=n_best))
 
 
 _ens_xbuf = {}                 # exchange regions of the ensemble's persistent launch, one per (bytes, device, stream)
 
 
 @torch.no_grad()
-def _beam_search_ensemble_persistent(decoder, dae, image_features, previous_caption, prev_caplen, word_map, beam_size, max_steps=50):
+def _beam_search_ensemble_persistent(decoder, dae, image_features, previous_caption, prev_caplen, word_map, beam_size, max_steps=50,
+                                     n_best=None):
     """ONE image, k <= 4, the EditNet + DCNet ensemble (eval_full.py:132-202): both prologues + one persistent launch that holds
     both models' state for the whole search (include/set_hip.h set_ensemble_beam_persistent; the rows of the launch are the k
     hypotheses).  Returns None when the library answers SET_ERR_UNSUPPORTED (a token table missing, k > 4, dimensions outside
@@ -407,27 +479,29 @@ def _beam_search_ensemble_persistent(decoder, dae, image_features, previous_capt
         if len(_ens_xbuf) >= 8:
             _ens_xbuf.clear()
         xbuf = _ens_xbuf[key] = torch.empty(nx, dtype=torch.uint8, device=dev)
-    out = _PersistentBeamOut(picks, dev)
-    rc = lib.set_ensemble_beam_persistent(C.byref(we), C.byref(de), C.byref(wd), C.byref(dd), ptr(X), ptr(prev), ptr(plen),
-                                          int(word_map['<start>']), int(word_map['<end>']), picks, out.hist_parent, out.hist_word,
-                                          out.best_score, out.best_word, out.result, ptr(ws_e), ws_e.numel(), ptr(ws_d), ws_d.numel(),
-                                          ptr(xbuf), xbuf.numel(), stream_of(dev))
+    out = _PersistentBeamOut(picks, dev, n_best is not None)
+    args = (C.byref(we), C.byref(de), C.byref(wd), C.byref(dd), ptr(X), ptr(prev), ptr(plen), int(word_map['<start>']),
+            int(word_map['<end>']), picks, out.hist_parent, out.hist_word, out.best_score, out.best_word, out.result, ptr(ws_e),
+            ws_e.numel(), ptr(ws_d), ws_d.numel(), ptr(xbuf), xbuf.numel(), stream_of(dev))
+    rc = lib.set_ensemble_beam_persistent(*args) if n_best is None else lib.set_ensemble_beam_persistent_nbest(*args, out.hist_score)
     if rc == 2:                                                    # SET_ERR_UNSUPPORTED: no output was touched
         return None
     check(rc, "set_ensemble_beam_persistent")
-    return out.answer(word_map, "set_ensemble_beam_persistent")
+    return out.answer(word_map, "set_ensemble_beam_persistent", n_best, k)
 
 
 def beam_search_ensemble(decoder, dae, image_features, previous_caption, prev_caplen, word_map, beam_size=3,
-                         return_trace=False):
+                         return_trace=False, n_best=None):
     """The reference's published protocol, ONE image per call (eval_full.py:88-237).  k <= 4 with both token tables active: one
     persistent launch (csrc/decode_persistent_ensemble.hip); otherwise the NI = 1 case of the batched search.
-    return_trace: (tokens, score, EditNet's EditTrace of the jointly chosen tokens)."""
-    one = _beam_search_ensemble_persistent(decoder, dae, image_features, previous_caption, prev_caplen, word_map, beam_size)
+    n_best=m: (tokens, score, [(tokens, score)] of up to m completed hypotheses, best first), see beam_search_editnet_batched.
+    return_trace: (tokens, score[, n-best], EditNet's EditTrace of the jointly chosen tokens)."""
+    n_best = _check_n_best(n_best, beam_size)
+    one = _beam_search_ensemble_persistent(decoder, dae, image_features, previous_caption, prev_caplen, word_map, beam_size,
+                                           n_best=n_best)
     if one is None:
-        seqs, scores = beam_search_ensemble_batched(decoder, dae, image_features, previous_caption, prev_caplen, word_map,
-                                                    beam_size, return_scores=True)
-        one = seqs[0], scores[0]
+        one = _first(beam_search_ensemble_batched(decoder, dae, image_features, previous_caption, prev_caplen, word_map, beam_size,
+                                                  return_scores=True, n_best=n_best))
     if return_trace:
         return _with_trace(one, False, True, decoder, image_features, previous_caption, prev_caplen, word_map)
     return one
@@ -452,31 +526,35 @@ def _adaptive_args(decoder, image_features, image_mean):
 
 @torch.no_grad()
 def beam_search_adaptive_batched(decoder, image_features, image_mean, previous_caption, prev_caplen, word_map, beam_size=3,
-                                 max_steps=50, return_scores=False, return_trace=False):
+                                 max_steps=50, return_scores=False, return_trace=False, n_best=None):
     """image_features (NI,R,F) zero-padded regions, image_mean (NI,F), previous_caption (NI,T), prev_caplen (NI,1) ->
     list of NI token lists (with return_scores: also their scores; NaN where the step limit was hit).  NI images at once
-    on the per-step fused kernels."""
+    on the per-step fused kernels.  n_best: see beam_search_editnet_batched."""
+    n_best = _check_n_best(n_best, beam_size)
     X, mean = _adaptive_args(decoder, image_features, image_mean)
     decoder.eval()
     prev = previous_caption.long().contiguous()
     plen = prev_caplen.reshape(-1).long().contiguous()
     m = _FusedEditNet(decoder, X, prev, plen, beam_size, max_steps, image_mean=mean)
     res = _fused_beam([m], X.shape[0], beam_size, decoder.vocab_size, word_map, X.device, max_steps,
-                      return_scores=return_scores)
-    return _with_trace(res, True, return_scores, decoder, X, prev, plen, word_map, image_mean=mean) if return_trace else res
+                      return_scores=return_scores, n_best=n_best)
+    return (_with_trace(res, True, return_scores, decoder, X, prev, plen, word_map, image_mean=mean, n_best=n_best)
+            if return_trace else res)
 
 
 def beam_search_adaptive(decoder, image_features, image_mean, previous_caption, prev_caplen, word_map, beam_size=3,
-                         return_trace=False):
+                         return_trace=False, n_best=None):
     """The reference's adaptive evaluate(), ONE image per call (editnet_adaptive.py:620-735) -> (tokens, score).  k <= 4
     with the token table active: one persistent launch (beam mode over up to 128 masked regions, even R); otherwise the
-    NI = 1 case of beam_search_adaptive_batched."""
+    NI = 1 case of beam_search_adaptive_batched.  n_best=m: (tokens, score, [(tokens, score)] of up to m completed hypotheses,
+    best first), see beam_search_editnet_batched."""
+    n_best = _check_n_best(n_best, beam_size)
     X, mean = _adaptive_args(decoder, image_features, image_mean)
-    one = _beam_search_editnet_persistent(decoder, X, previous_caption, prev_caplen, word_map, beam_size, image_mean=mean)
+    one = _beam_search_editnet_persistent(decoder, X, previous_caption, prev_caplen, word_map, beam_size, image_mean=mean,
+                                          n_best=n_best)
     if one is None:
-        seqs, scores = beam_search_adaptive_batched(decoder, X, mean, previous_caption, prev_caplen, word_map, beam_size,
-                                                    return_scores=True)
-        one = seqs[0], scores[0]
+        one = _first(beam_search_adaptive_batched(decoder, X, mean, previous_caption, prev_caplen, word_map, beam_size,
+                                                  return_scores=True, n_best=n_best))
     if return_trace:
         return _with_trace(one, False, True, decoder, X, previous_caption, prev_caplen, word_map, image_mean=mean)
     return one

@@ -7,7 +7,7 @@ dimensions, k=3, on one MI355X:
   * for reference, the fixed-feature persistent one-image search (R=36) from the same run.
 One JSON line.  Kernel statistics: run it under `rocprofv3 --kernel-trace --stats -d <dir> -o run --` in a separate run.
 
-    python tools/bench_adaptive_beam.py [--images 64] [--per-image 16] [--rounds 3] [--boost 2.0]
+    python tools/bench_adaptive_beam.py [--images 64] [--per-image 16] [--rounds 3] [--boost 2.0] [--n-best N]
 """
 import argparse, json, os, statistics, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -19,6 +19,7 @@ def main():
     ap.add_argument("--images", type=int, default=64); ap.add_argument("--per-image", type=int, default=16)
     ap.add_argument("--rounds", type=int, default=3); ap.add_argument("--beam", type=int, default=3)
     ap.add_argument("--boost", type=float, default=2.0, help="fc.bias[<end>] raise: multi-word searches")
+    ap.add_argument("--n-best", type=int, default=0, help="time the adaptive searches with n_best=N (0: off, the default)")
     a = ap.parse_args()
     from show_edit_tell_amd import editnet, editnet_adaptive, evaluate, synth
     dev = torch.device("cuda", 0)
@@ -35,13 +36,15 @@ def main():
     prev, plen = (torch.from_numpy(x).to(dev) for x in synth.prev_captions(35, NI, T, V, 5))
     X36 = torch.from_numpy(synth.features(35, NI, 36, F)).to(dev)
 
+    kw = {"n_best": a.n_best} if a.n_best else {}              # (the results gain the n-best lists as one more element)
+
     def timed(fn):
         torch.cuda.synchronize(); t = time.perf_counter(); out = fn(); torch.cuda.synchronize()
         return time.perf_counter() - t, out
 
     # ---- batched search over NI images
     evaluate.beam_search_adaptive_batched(dec, X, mean, prev, plen, wm, k)                         # warm-up
-    t_b = [timed(lambda: evaluate.beam_search_adaptive_batched(dec, X, mean, prev, plen, wm, k, return_scores=True))
+    t_b = [timed(lambda: evaluate.beam_search_adaptive_batched(dec, X, mean, prev, plen, wm, k, return_scores=True, **kw))
            for _ in range(a.rounds)]
     seqs_b = t_b[0][1][0]
 
@@ -61,9 +64,9 @@ def main():
         for _ in range(a.rounds):
             for b in range(n1):
                 os.environ["SET_DEC_PERSISTENT"] = "1"
-                tp, (sp, _) = timed(lambda: evaluate.beam_search_adaptive(dec, *one(b), wm, k))
+                tp, (sp, *_) = timed(lambda: evaluate.beam_search_adaptive(dec, *one(b), wm, k, **kw))
                 os.environ["SET_DEC_PERSISTENT"] = "0"
-                ts, (ss, _) = timed(lambda: evaluate.beam_search_adaptive(dec, *one(b), wm, k))
+                ts, (ss, *_) = timed(lambda: evaluate.beam_search_adaptive(dec, *one(b), wm, k, **kw))
                 os.environ["SET_DEC_PERSISTENT"] = "1"
                 tf, _ = timed(lambda: evaluate.beam_search_editnet(fixed, X36[b:b + 1], prev[b:b + 1], plen[b:b + 1], wm, k))
                 per["persistent"].append(tp); per["per_step"].append(ts); per["fixed_persistent"].append(tf)
@@ -78,6 +81,7 @@ def main():
     print(json.dumps({
         "config": "adaptive features R=%d (valid %d..%d), D=%d, V=%d, k=%d, <end> boost %.1f" % (
             R, int(nvalid.min()), int(nvalid.max()), D, V, k, a.boost),
+        "n_best": a.n_best,
         "batched_images": NI, "batched_ms": round(1e3 * min(t for t, _ in t_b), 2),
         "batched_ms_per_image": round(1e3 * min(t for t, _ in t_b) / NI, 3),
         "batched_mean_tokens": round(sum(len(s) for s in seqs_b) / NI, 2),

@@ -12,7 +12,7 @@ published scores) at full dimensions (D = 1024, A = 512, V = 10000, R = 36, T = 
 One JSON line, also written to --out.  Kernel statistics: run it under `rocprofv3 --kernel-trace --stats -d <dir> -o run --`
 in a separate run (no counters in that run); per-pick phases inside the launch: SET_PDEC_STAMPS=1 in a separate run.
 
-    python tools/bench_ensemble_beam.py [--images 16] [--rounds 3] [--boost 4.0] [--out profiles/ensemble_beam_bench.json]
+    python tools/bench_ensemble_beam.py [--images 16] [--rounds 3] [--boost 4.0] [--n-best N] [--out profiles/ensemble_beam_bench.json]
 """
 import argparse, json, math, os, statistics, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -24,6 +24,7 @@ def main():
     ap.add_argument("--images", type=int, default=16); ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--beam", type=int, default=3)
     ap.add_argument("--boost", type=float, default=4.0, help="fc.bias[<end>] raise of the ending workload")
+    ap.add_argument("--n-best", type=int, default=0, help="time the searches with n_best=N (0: off, the default)")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     from show_edit_tell_amd import dcnet, editnet, evaluate, synth
@@ -48,9 +49,11 @@ def main():
         torch.cuda.synchronize(); t = time.perf_counter(); out = fn(); torch.cuda.synchronize()
         return time.perf_counter() - t, out
 
+    kw = {"n_best": a.n_best} if a.n_best else {}              # (the result gains the n-best list as a third element)
     one = lambda b: (X[b:b + 1], prev[b:b + 1], plen[b:b + 1])
     env0 = os.environ.get("SET_DEC_PERSISTENT")
-    result = {"config": "EditNet + DCNet ensemble D=%d A=%d V=%d R=%d T=%d, k=%d, %d images, %d rounds, arms alternated image by image" % (D, A, V, R, T, k, NI, a.rounds)}
+    result = {"config": "EditNet + DCNet ensemble D=%d A=%d V=%d R=%d T=%d, k=%d, %d images, %d rounds, arms alternated image by image" % (D, A, V, R, T, k, NI, a.rounds),
+              "n_best": a.n_best}
     try:
         for name, boost in (("step_limit", 0.0), ("ending", a.boost)):
             xe, dae = models(boost)
@@ -66,9 +69,9 @@ def main():
                 tp, ts = [], []
                 for b in range(NI):
                     os.environ["SET_DEC_PERSISTENT"] = "1"
-                    t1, (sp, scp) = timed(lambda: evaluate.beam_search_ensemble(xe, dae, *one(b), wm, k))
+                    t1, (sp, scp, *_) = timed(lambda: evaluate.beam_search_ensemble(xe, dae, *one(b), wm, k, **kw))
                     os.environ["SET_DEC_PERSISTENT"] = "0"
-                    t0, (ss, scs) = timed(lambda: evaluate.beam_search_ensemble(xe, dae, *one(b), wm, k))
+                    t0, (ss, scs, *_) = timed(lambda: evaluate.beam_search_ensemble(xe, dae, *one(b), wm, k, **kw))
                     tp.append(t1); ts.append(t0)
                     lens.append(len(sp)); same += int(sp == ss); limit += int(math.isnan(scp))
                 rounds["persistent"].append(1e3 * statistics.median(tp)); rounds["per_step"].append(1e3 * statistics.median(ts))
