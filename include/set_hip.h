@@ -757,6 +757,50 @@ int set_sample_logp_bwd_f32(const float* logits, int64_t ld_logits, const float*
 /* the device RNG itself (tests: known-answer vectors): out (n,4) uint32 = Philox4x32-10(counter (i,0,offset), key seed) */
 int set_philox4x32(uint32_t* out, int n, uint64_t seed, uint64_t offset, void* stream);
 
+/* The vocabulary-row epilogue of one free-running timestep (csrc/epilogue.hip greedy_pick_k / sample_pick_k) with every
+ * argument the decode loops give it, for direct tests: one workgroup per row turns
+ *     logit[b, v] = sum over slabs s < n of logits[s * stride + b * ld + v]  (+ bias[v]),  v < V
+ * into the row's word (greedy: first index of the maximum; sample: inverse CDF of one Philox uniform per (seed, offset, b, t)),
+ * does the bookkeeping of editnet_rl.py:529-547 (<end> -> 0, `unfinished` latch, seq / seq_logp[:, t] while t < max_len and
+ * alive[t - 1] != 0, alive[t] += rows still unfinished, it = next input word), gathers emb_out[b] = relu(table[it[b]])
+ * (table (>= V, D), emb_out (B, D); skipped when either is NULL) and, with `tail`, finishes the NEXT timestep's LSTM cell of
+ * the row: gates = g0 slabs (in index order) + pre + tab[it, col0 .. col0 + 4D), order i, f, g, o; c_out = f c_in + i g,
+ * h_out = o tanh(c_out); c_in may be c_out.
+ * The caller owns the state: it, unfinished (B), alive (> t entries, alive[t] zero before the call) are NOT initialised here.
+ * The row-limit override of set_decode_row_limits applies to the greedy mode as it does inside the decode loops; the sample
+ * mode has no row limit (sample_pick takes none, in the rollout neither).  `stride` is taken as given: with n > 1 the caller
+ * keeps the slabs apart (stride >= B * ld); it is not checked.
+ *   SET_ERR_ARG          a NULL args / logits / seq / it / unfinished / alive (greedy: seq_logp too), mode not 0 / 1, B, V,
+ *                        n, max_len <= 0, t < 0, ld < V, and a tail that is not laid out as the kernels read it (tail D <= 0
+ *                        or not a multiple of 4, a NULL or not 16-byte-aligned g0 / tab / c_in / c_out / h_out, g0_n < 1,
+ *                        g0_ld / g0_stride / ld_tab / col0 / ldpre not multiples of 4, nrows <= 0, misaligned pre)
+ *   SET_ERR_UNSUPPORTED  D not a multiple of 4
+ * Every refusal is answered before any HIP call and nothing is written.  Rows of up to 12288 words whose ld and stride are
+ * multiples of 4 floats on a 16-byte-aligned base are read once as float4 into registers; any other row takes the
+ * scalar kernels.  raw_ids / lse / step_logp (sample mode; each may be NULL) as set_sample_pick_f32. */
+#define SET_PICK_GREEDY 0
+#define SET_PICK_SAMPLE 1
+typedef struct SetPickTail {
+    const float* g0; int64_t g0_stride, g0_ld;   /* gate pre-activation partials (rows, 4 D), g0_n slabs */
+    const float* pre; int64_t ldpre;             /* (rows, ldpre) or NULL */
+    const float* tab; int64_t ld_tab;            /* token table (nrows, ld_tab) */
+    const float* c_in; float* c_out; float* h_out;   /* (rows, D) */
+    int32_t g0_n, col0, nrows, D;
+} SetPickTail;
+typedef struct SetPickArgs {
+    const float* logits; int64_t ld, stride;
+    const float* bias;                           /* V floats or NULL */
+    int64_t end_idx;
+    int64_t* seq; float* seq_logp;               /* (B, max_len) */
+    int64_t* it; int32_t* unfinished; int32_t* alive;
+    const float* table; float* emb_out;
+    uint64_t seed, offset;                       /* sample mode */
+    int64_t* raw_ids; float* lse; float* step_logp;
+    const SetPickTail* tail;                     /* or NULL */
+    int32_t n, B, V, t, max_len, D, mode, pad_;
+} SetPickArgs;
+int set_pick_slabs_f32(const SetPickArgs* args, void* stream);
+
 /* Beam-search step epilogue for NI images x k hypotheses (rows i*k+j), replacing the host bookkeeping of
  * editnet.py:654-699 / dcnet.py:450-500 / eval_full.py:150-200: log_softmax (or, with logits2, the ensemble
  * log((softmax(logits)+softmax(logits2))/2)), + running scores, flat top-k over k*V per image (ties: lowest

@@ -167,6 +167,26 @@ class GemmNtLaunch(C.Structure):
 GEMM_NT_NO_ASM, GEMM_NT_KEEP_SLABS = 1, 2
 
 
+class PickTail(C.Structure):
+    """include/set_hip.h SetPickTail: the LSTM-cell tail of the pick kernels"""
+    _fields_ = [("g0", C.c_void_p), ("g0_stride", C.c_int64), ("g0_ld", C.c_int64), ("pre", C.c_void_p), ("ldpre", C.c_int64),
+                ("tab", C.c_void_p), ("ld_tab", C.c_int64), ("c_in", C.c_void_p), ("c_out", C.c_void_p), ("h_out", C.c_void_p),
+                ("g0_n", C.c_int32), ("col0", C.c_int32), ("nrows", C.c_int32), ("D", C.c_int32)]
+
+
+class PickArgs(C.Structure):
+    """include/set_hip.h SetPickArgs (set_pick_slabs_f32)"""
+    _fields_ = [("logits", C.c_void_p), ("ld", C.c_int64), ("stride", C.c_int64), ("bias", C.c_void_p), ("end_idx", C.c_int64),
+                ("seq", C.c_void_p), ("seq_logp", C.c_void_p), ("it", C.c_void_p), ("unfinished", C.c_void_p),
+                ("alive", C.c_void_p), ("table", C.c_void_p), ("emb_out", C.c_void_p), ("seed", C.c_uint64),
+                ("offset", C.c_uint64), ("raw_ids", C.c_void_p), ("lse", C.c_void_p), ("step_logp", C.c_void_p),
+                ("tail", C.POINTER(PickTail)), ("n", C.c_int32), ("B", C.c_int32), ("V", C.c_int32), ("t", C.c_int32),
+                ("max_len", C.c_int32), ("D", C.c_int32), ("mode", C.c_int32), ("pad_", C.c_int32)]
+
+
+PICK_GREEDY, PICK_SAMPLE = 0, 1
+
+
 class SlabSrc(C.Structure):
     """include/set_hip.h SetSlabSrc: one addend of a gradient that is still split-K partials"""
     _fields_ = [("p", C.c_void_p), ("slab_stride", C.c_int64), ("ld", C.c_int64), ("nslab", C.c_int32), ("rows", C.c_int32)]
@@ -348,6 +368,7 @@ PROTOTYPES = {
     "set_sample_pick_f32": (_I, [_P, _L, _I, _I, _I, _I, _L, _U, _U, _P, _P, _P, _P, _P, _P, _P, _P]),
     "set_sample_logp_bwd_f32": (_I, [_P, _L, _P, _P, _P, _P, _L, _I, _I, _P]),
     "set_philox4x32": (_I, [_P, _I, _U, _U, _P]),
+    "set_pick_slabs_f32": (_I, [C.POINTER(PickArgs), _P]),
     "set_beam_pick_f32": (_I, [_P, _P, _L, _I, _I, _I, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "set_beam_pick_nbest_f32": (_I, [_P, _P, _L, _I, _I, _I, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "set_beam_gather_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),

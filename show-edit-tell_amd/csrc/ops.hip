@@ -555,4 +555,27 @@ int set_philox4x32(uint32_t* out, int n, uint64_t seed, uint64_t offset, void* s
     return philox_fill(out, n, seed, offset, (hipStream_t)stream);
 }
 
+// the pick kernels with every argument of the decode loops (tests/test_hip_pick_epilogues.py); no state is initialised here
+int set_pick_slabs_f32(const SetPickArgs* a, void* stream) {
+    if (!a || !a->logits || !a->seq || !a->it || !a->unfinished || !a->alive) return SET_ERR_ARG;
+    if (a->mode != SET_PICK_GREEDY && a->mode != SET_PICK_SAMPLE) return SET_ERR_ARG;
+    if (a->mode == SET_PICK_GREEDY && !a->seq_logp) return SET_ERR_ARG;
+    if (a->B <= 0 || a->V <= 0 || a->n <= 0 || a->t < 0 || a->max_len <= 0 || a->ld < a->V) return SET_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    Slabs lg{a->logits, a->stride, a->ld, a->n};
+    LstmTail tl;
+    if (const SetPickTail* T = a->tail) {
+        tl.g0 = Slabs{T->g0, T->g0_stride, T->g0_ld, T->g0_n};
+        tl.pre = T->pre; tl.ldpre = T->ldpre;
+        tl.tab = T->tab; tl.ld_tab = T->ld_tab; tl.col0 = T->col0; tl.nrows = T->nrows;
+        tl.c_in = T->c_in; tl.c_out = T->c_out; tl.h_out = T->h_out; tl.D = T->D;
+    }
+    if (a->mode == SET_PICK_SAMPLE)
+        return sample_pick(lg, a->bias, a->V, a->t, a->max_len, a->end_idx, (long long*)a->seq, a->seq_logp, (long long*)a->it,
+                           a->unfinished, a->alive, a->table, a->emb_out, a->D, a->B, a->seed, a->offset, (long long*)a->raw_ids,
+                           a->lse, a->step_logp, st, a->tail ? &tl : nullptr);
+    return greedy_pick(lg, a->bias, a->V, a->t, a->max_len, a->end_idx, (long long*)a->seq, a->seq_logp, (long long*)a->it,
+                       a->unfinished, a->alive, a->table, a->emb_out, a->D, a->B, st, a->tail ? &tl : nullptr);
+}
+
 }  // extern "C"

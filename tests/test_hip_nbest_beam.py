@@ -14,6 +14,7 @@ import torch
 
 import beam_parity
 import nbest_oracle as NO
+import pick_oracle
 from hip_adapter import load_numpy_state, to_dev
 from oracle import cases
 
@@ -227,56 +228,11 @@ K8, V16, END, START, LMAX = 8, 16, 15, 14, 8
 
 
 def _np_pick(logits, scores, k_left, seqs, best_score, best_seq, best_len, done_score, done_seq, done_len, n_done, cur_len, flags):
-    """csrc/beam.hip beam_pick_k in float32 numpy, in place.  Every row's largest logit stands >= 32 above the others, so that
-    its log-sum-exp IS that logit in float32 (1 + 15 e^-32 rounds to 1) and every candidate value is exact."""
-    NI, k, V = scores.shape[0], K8, V16
-    words, rows = np.zeros(NI * k, np.int64), np.zeros(NI * k, np.int32)
-    out = seqs.copy()
-    for i in range(NI):
-        kl = int(k_left[i])
-        if kl <= 0:
-            rows[i * k:(i + 1) * k] = np.arange(i * k, (i + 1) * k)
-            flags["noop"] += 1
-            continue
-        cand = []
-        for j in range(k):
-            if scores[i, j] == -np.inf:
-                continue
-            row = logits[i * k + j]
-            lp = (row - row.max()).astype(np.float32)
-            cand += [(-float(np.float32(scores[i, j] + lp[v])), j * V + v) for v in range(V)]
-        cand.sort()
-        picks = [(np.float32(-nv), flat) for nv, flat in cand[:k]]
-        ends = [(r, v) for r, (v, flat) in enumerate(picks) if r < kl and flat % V == END]
-        flags["uncounted_end"] += sum(1 for r, (v, flat) in enumerate(picks) if r >= kl and flat % V == END)
-        flags["tie"] += sum(1 for a, b in zip(ends, ends[1:]) if a[1] == b[1])
-        if ends:
-            r0 = max(ends, key=lambda e: (e[1], -e[0]))[0]              # first maximum
-            if picks[r0][0] > best_score[i]:
-                best_score[i], best_len[i] = picks[r0][0], cur_len + 1
-                best_seq[i, :cur_len] = seqs[i, picks[r0][1] // V, :cur_len]
-                best_seq[i, cur_len] = END
-        for r, v in ends:
-            at = int(n_done[i])
-            done_score[i, at], done_len[i, at] = v, cur_len + 1
-            done_seq[i, at, :cur_len] = seqs[i, picks[r][1] // V, :cur_len]
-            done_seq[i, at, cur_len] = END
-            n_done[i] += 1
-        k_left[i] = kl - len(ends)
-        live = [r for r, (v, flat) in enumerate(picks) if r < kl and flat % V != END]
-        order = live + [r for r in range(k) if r not in live]
-        new_scores = np.full(k, -np.inf, np.float32)
-        for slot, r in enumerate(order):
-            v, flat = picks[r]
-            is_live = r in live
-            new_scores[slot] = v if is_live else -np.inf
-            words[i * k + slot] = flat % V if is_live else 0
-            rows[i * k + slot] = i * k + flat // V
-            out[i, slot, :cur_len] = seqs[i, flat // V, :cur_len]
-            out[i, slot, cur_len] = flat % V
-        scores[i] = new_scores
-        flags["zero"] += int(k_left[i] == 0)
-    return out, words, rows
+    """csrc/beam.hip beam_pick_k in float32 numpy, in place (tests/pick_oracle.beam_pick at this test's sizes).  Every row's
+    largest logit stands >= 32 above the others, so that its log-sum-exp IS that logit in float32 (1 + 15 e^-32 rounds to 1) and
+    every candidate value is exact."""
+    return pick_oracle.beam_pick(logits, scores, k_left, seqs, best_score, best_seq, best_len, done_score, done_seq, done_len,
+                                 n_done, cur_len, flags, K8, V16, END)
 
 
 def _made_up_logits(rng, NI, p_end):

@@ -54,7 +54,7 @@ def test_device_philox_matches_oracle():
 def test_sampling_distribution_chi_square(V, pad):
     """>= 1e5 draws from one logit row: chi-square of the observed counts against softmax(logits) (bins merged to
     an expected count >= 8), p-value > 1e-4; covers the register path (V % 4 == 0, <= 12288 words) and the generic
-    path (odd leading stride / long rows).  Also the exact inverse-CDF identity against the oracle's uniforms."""
+    path (odd leading stride / long rows)."""
     from scipy import stats
     rng = np.random.default_rng(V)
     row = (rng.standard_normal(V) * 2.0).astype(np.float32)
