@@ -1,6 +1,9 @@
 // Shared pieces of the three persistent small-batch decode kernels (decode_persistent.hip: DCNet, decode_persistent_wide.hip:
 // EditNet, decode_persistent_ensemble.hip: both models' beam search): constants, the MFMA GEMV tile helpers, EditNet's argument
 // block with its host-side fill and exchange layout, and the diagnostic time stamps.  (The beam modes' pick: beam_persistent.h.)
+// On the host (end of this file) the three launches share everything that carries no schedule: the record of one kernel
+// instantiation (PersistentKernel), the launch sequence from the LDS cap to the stamp report (pdec_launch) and the fills of the
+// argument blocks' common fields (pdec_dcnet_fill / pdec_dcnet_layout, pdec_beam_fill, pdec_teacher_fill, pdec_guard_fill).
 #pragma once
 #include <cstdio>
 #include "set_common.h"
@@ -248,6 +251,74 @@ inline int pd_stamps_report(const unsigned long long* d_stamps, int wg, int last
         fprintf(stderr, "  step %.2f  (step-to-step %.2f)\n", tot / n, n > 1 ? (double)(h[n * PD_STAMPS] - h[PD_STAMPS]) * 0.01 / (n - 1) : 0.0);
     }
     return SET_OK;
+}
+
+// ---- host side of the three launches.  Everything here is `static inline`: no symbol leaves the library.
+// One kernel instantiation: its entry point and, per device, whether its LDS cap has been raised and the residency answer
+// (workgroups the device admits, asked with `cap_lds` bytes: PersistentGuard::set_lds / fits).  Each file keeps a static table
+// of its instantiations and picks an entry by its mode flags.
+struct PersistentKernel { const void* fn; bool configured[64]; int cap[64]; int cap_lds[64]; };
+struct PDecProf { const char* tag; double flops, bytes; };
+// the argument block's stamps / stamp_wg fields, the last stamp index of a timestep and the number of timesteps
+struct PDecStamps { unsigned long long** buf; int* wg; int last, steps; };
+
+// One persistent launch of `k` under `guard` (taken and checked by the caller): G workgroups with `lds` bytes of dynamic LDS
+// (`lds_max` = the cap of this instantiation, set once per device); P = the kernel's single by-value argument block; the first
+// `xzero` bytes of the exchange region are cleared so that no word of an earlier launch carries a tag of this one.
+// SET_ERR_UNSUPPORTED (the device's LDS limit is below lds_max, or it does not admit the whole grid): answered before anything
+// is written, the caller runs the per-step kernels.
+static inline int pdec_launch(PersistentKernel& k, PersistentGuard& guard, int G, int lds, int lds_max, void* P, void* xbuf, size_t xzero,
+                              hipStream_t s, const PDecProf& prof, const PDecStamps& st) {
+    if (guard.set_lds(k.fn, lds_max, k.configured) != SET_OK ||
+        guard.fits(k.fn, PDEC_THREADS, lds, G, k.cap[guard.dev], k.cap_lds[guard.dev]) != PersistentGuard::Fit::yes)
+        return SET_ERR_UNSUPPORTED;
+    ProfScope ps(prof.tag, s, prof.flops, prof.bytes);
+    SET_TRY(guard.serialise(s));
+    SET_HIP_TRY(hipMemsetAsync(xbuf, 0, xzero, s));
+    SET_TRY(pd_stamps_begin(st.buf, st.wg, s));
+    void* args[] = {P};
+    (void)hipLaunchKernel(k.fn, dim3(G), dim3(PDEC_THREADS), args, lds, s);      // (its answer is the runtime's last error)
+    SET_LAUNCH_CHECK();
+    SET_TRY(guard.launched(s));
+    return pd_stamps_report(*st.buf, *st.wg, st.last, st.steps, s);
+}
+
+// the fields every argument block takes from the guard: bound of one wait, the stall test hook, the device's fault word
+template <class Args>
+static inline void pdec_guard_fill(Args& P, const PersistentGuard& guard) {
+    P.spin_limit = guard.spin_limit(); P.test_stall = guard.test_stall(); P.fault = guard.fault;
+}
+// DCNet's weights in place and their leading dimensions: PDecDcnetArgs (decode_persistent.hip) and PDecEnsArgs::d (the ensemble's
+// block) carry the same field names.  pdec_dcnet_layout: the [h1 | h2 | cap_decoder_att(h1)] run of both exchange regions, as
+// flag-in-data words of 8 bytes; returns the end.
+template <class Args>
+static inline void pdec_dcnet_fill(Args& P, const SetDcnetWeights* w, const SetDcnetDims* d) {
+    const long long E = d->E, C = d->C;
+    P.al_wih_h2 = w->al_wih + E + 2 * C; P.ld_al = 3 * E;
+    P.al_whh = w->al_whh; P.ll_whh = w->ll_whh; P.ll_wih = w->ll_wih; P.ld_ll = 2 * E;
+    P.ll_bih = w->ll_bih; P.ll_bhh = w->ll_bhh;
+    P.ca_dec_w = w->ca_dec_w; P.ca_dec_b = w->ca_dec_b; P.ca_full_w = w->ca_full_w; P.ca_full_b = w->ca_full_b;
+    P.fc_w = w->fc_w; P.fc_b = w->fc_b; P.tok_table = w->tok_table; P.ld_tab = 4LL * d->D + 8 * C;
+}
+template <class Args>
+static inline char* pdec_dcnet_layout(Args& P, char* x, size_t B, size_t D, size_t A) {
+    P.x_h1 = x; x += B * D * 8;
+    P.x_h2 = x; x += B * D * 8;
+    P.x_att2 = x; x += B * A * 8;
+    return x;
+}
+// beam mode: the outputs of the pick (PDecEditArgs and PDecDcnetArgs name them alike)
+template <class Args>
+static inline void pdec_beam_fill(Args& P, const PDecBeam& b) {
+    P.bm_hist_par = b.hist_par; P.bm_hist_word = (long long*)b.hist_word; P.bm_best_score = b.best_score;
+    P.bm_best_word = (long long*)b.best_word; P.bm_result = b.result; P.bm_hist_score = b.hist_score;
+}
+// teacher-forced mode: the captions, the scores' destination (B, max_len, V) and the decode lengths of the P.B rows
+template <class Args>
+static inline void pdec_teacher_fill(Args& P, const PDecTeacher& t) {
+    P.caps = (const long long*)t.caps; P.caps_stride = t.caps_stride;
+    P.predictions = t.predictions; P.ld_pred_b = (long long)P.max_len * P.V;
+    for (int b = 0; b < P.B; ++b) P.dlen[b] = t.host_decode_lengths[b];
 }
 
 }  // namespace set

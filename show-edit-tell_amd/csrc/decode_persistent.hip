@@ -29,8 +29,10 @@
 // three exchanges.
 // Same residency rule, fault word and event chain as the persistent encoder (grid_barrier.h PersistentGuard).  A poll that
 // times out poisons seq_logp with NaN; the host raises SET_ERR_FAULT at its next call.
-// Shared with the other two persistent decode kernels: the beam mode's pick (beam_persistent.h) and, on the host, the residency
-// check (PersistentGuard::fits).  Deliberately NOT shared: the phase code of the timestep — where a tile's loads sit between
+// Shared with the other two persistent decode kernels: the beam mode's pick (beam_persistent.h) and, on the host, the launch
+// itself (decode_persistent.h: the per-instantiation record PersistentKernel, pdec_launch from the LDS cap and the residency
+// check to the stamp report, and the fills of the argument block; pdec_dcnet_fill / pdec_dcnet_layout also serve the ensemble's
+// DCNet half).  Deliberately NOT shared: the phase code of the timestep — where a tile's loads sit between
 // the MFMAs is the schedule, and a function boundary there changes the instructions of a kernel at the register ceiling.
 #include "beam_persistent.h"
 
@@ -593,8 +595,6 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) dcnet_persistent_k(const PDec
     }
 }
 
-static int g_pdec_capacity[64][6] = {};              // [device][RES + 2 LH], beam mode: [4 + RES]
-static int g_pdec_capacity_lds[64][6] = {};
 static int pdec_lds_floats(int B, int D, int A, bool beam = false) {
     const int base = 2 * B * (D + 4) + 4 * 3 * 256 + PDEC_MAXB * PDEC_TMAX + PDEC_MAXB * 16 + B * A + B * (D / 4) * 4 + 2 * A + B * 16 * (PDEC_TMAX + 1);
     // beam mode: candidates of every slice, W_hh h2 tiles, c1 | c2 table, candidate lists, scores, parents, k_left, best
@@ -626,6 +626,13 @@ bool dcnet_persistent_beam_ok(const SetDcnetDims* d, int max_picks) {
     return d->B <= PW_BEAM_K && (long long)d->B * d->V < 0x7fffffffLL && dcnet_persistent_ok(d, max_picks);
 }
 
+// the six instantiations: [resident (B <= 4 and T <= PDEC_TREG), general][beam, teacher-forced with last_h2, every other launch].
+// (Listed in the order in which the kernels have always been instantiated: the device code object stays byte for byte the same.)
+#define PDEC_K(...) {reinterpret_cast<const void*>(&dcnet_persistent_k<__VA_ARGS__>)}
+static PersistentKernel g_pdec_k[2][3] = {{PDEC_K(true, false, true), PDEC_K(true, true), PDEC_K(true)},
+                                          {PDEC_K(false, false, true), PDEC_K(false, true), PDEC_K(false)}};
+#undef PDEC_K
+
 // the greedy loop after set_dcnet_begin's prologue.  `pc` = the hoisted context products (B, T, 4D), `xbuf` = exchange region
 // (dcnet_persistent_xbytes).  SET_ERR_UNSUPPORTED: nothing was touched, the caller runs the per-step loop.
 int dcnet_persistent_greedy(const SetDcnetWeights* w, const SetDcnetDims* d, const float* pre1, const float* att1_c,
@@ -634,81 +641,32 @@ int dcnet_persistent_greedy(const SetDcnetWeights* w, const SetDcnetDims* d, con
                             hipStream_t s, const PDecTeacher* teach, const PDecBeam* beam) {
     if (!dcnet_persistent_ok(d, max_len)) return SET_ERR_UNSUPPORTED;
     if (beam && (teach || !dcnet_persistent_beam_ok(d, max_len))) return SET_ERR_UNSUPPORTED;
-    const int B = d->B, D = d->D, E = d->E, C = d->C, G = D / 4;
+    const int B = d->B, D = d->D, G = D / 4;
     PDecDcnetArgs P{};
-    P.al_wih_h2 = w->al_wih + E + 2 * C; P.ld_al = 3LL * E;
-    P.al_whh = w->al_whh; P.ll_whh = w->ll_whh; P.ll_wih = w->ll_wih; P.ld_ll = 2LL * E;
-    P.ll_bih = w->ll_bih; P.ll_bhh = w->ll_bhh;
-    P.ca_dec_w = w->ca_dec_w; P.ca_dec_b = w->ca_dec_b; P.ca_full_w = w->ca_full_w; P.ca_full_b = w->ca_full_b;
-    P.fc_w = w->fc_w; P.fc_b = w->fc_b; P.tok_table = w->tok_table; P.ld_tab = 4LL * D + 8LL * C;
+    pdec_dcnet_fill(P, w, d);
     P.pre1 = pre1; P.att1_c = att1_c; P.mask = mask; P.pc = pc;
-    {
-        char* x = (char*)xbuf;
-        P.status = (unsigned*)x; x += 128;
-        P.x_h1 = x; x += (size_t)B * D * 8;
-        P.x_h2 = x; x += (size_t)B * D * 8;
-        P.x_att2 = x; x += (size_t)B * d->A * 8;
-        P.x_fc = x; x += (size_t)B * G * 32;
-        P.x_fcb = x;                                 // (B <= PW_BEAM_K: dcnet_persistent_xbytes)
-    }
+    P.status = (unsigned*)xbuf;
+    char* x = pdec_dcnet_layout(P, (char*)xbuf + 128, B, D, d->A);
+    P.x_fc = x; x += (size_t)B * G * 32;
+    P.x_fcb = x;                                     // (B <= PW_BEAM_K: dcnet_persistent_xbytes)
     P.it = it; P.unfinished = unfinished; P.alive = alive; P.seq = seq; P.seq_logp = seq_logp;
     P.B = B; P.D = D; P.T = d->T; P.A = d->A; P.V = d->V; P.max_len = max_len; P.rpw = (d->V + G - 1) / G;
     P.start_idx = start_idx; P.end_idx = end_idx;
-    if (teach) {
-        P.caps = (const long long*)teach->caps; P.caps_stride = teach->caps_stride;
-        P.predictions = teach->predictions; P.ld_pred_b = (long long)max_len * d->V;
-        for (int b = 0; b < B; ++b) P.dlen[b] = teach->host_decode_lengths[b];
-        P.last_h2 = teach->last_h2;
-    }
-    if (beam) {
-        P.bm_hist_par = beam->hist_par; P.bm_hist_word = (long long*)beam->hist_word; P.bm_best_score = beam->best_score;
-        P.bm_best_word = (long long*)beam->best_word; P.bm_result = beam->result; P.bm_hist_score = beam->hist_score;
-    }
-    const bool lh = P.caps && P.last_h2, bm = beam != nullptr;
-    const int lds = pdec_lds_floats(B, D, d->A, bm) * (int)sizeof(float);
+    if (teach) { pdec_teacher_fill(P, *teach); P.last_h2 = teach->last_h2; }
+    if (beam) pdec_beam_fill(P, *beam);
+    const bool lh = P.caps && P.last_h2, bm = beam != nullptr, res = B <= 4 && d->T <= PDEC_TREG;
     PersistentGuard guard;
     if (guard.rc != SET_OK) return guard.rc;
-    const int dev = guard.dev;
-    P.spin_limit = guard.spin_limit();              // bound of one wait, ticks of the 100-MHz counter
-    P.test_stall = guard.test_stall(); P.fault = guard.fault;
-    // residency: every workgroup must be on the chip at once (grid_barrier.h PersistentGuard::fits)
-    // (function attributes are per device; a device whose LDS limit is below the request, e.g. a 64-KB part, is answered with
-    // SET_ERR_UNSUPPORTED — the caller's per-step loop — never with a HIP error)
-    static bool configured[6][64] = {};
+    pdec_guard_fill(P, guard);
     // (beam mode: its own LDS size, at most PW_BEAM_K rows)
+    const int lds = pdec_lds_floats(B, D, d->A, bm) * (int)sizeof(float);
     const int lds_max = pdec_lds_floats(bm ? PW_BEAM_K : PDEC_MAXB, D, d->A, bm) * (int)sizeof(float);
-    // the two variants of this call's family (with / without the last_h2 output; beam mode)
-    const void* k_res = bm ? reinterpret_cast<const void*>(&dcnet_persistent_k<true, false, true>)
-                      : lh ? reinterpret_cast<const void*>(&dcnet_persistent_k<true, true>)
-                           : reinterpret_cast<const void*>(&dcnet_persistent_k<true>);
-    const void* k_gen = bm ? reinterpret_cast<const void*>(&dcnet_persistent_k<false, false, true>)
-                      : lh ? reinterpret_cast<const void*>(&dcnet_persistent_k<false, true>)
-                           : reinterpret_cast<const void*>(&dcnet_persistent_k<false>);
-    const int fam = bm ? 4 : (lh ? 2 : 0);
-    if (guard.set_lds(k_res, lds_max, configured[fam]) != SET_OK ||
-        guard.set_lds(k_gen, lds_max, configured[fam + 1]) != SET_OK)
-        return SET_ERR_UNSUPPORTED;
-    const bool res = B <= 4 && d->T <= PDEC_TREG;
-    // resident workgroups the device admits, asked with the LDS size of THIS batch
-    if (guard.fits(res ? k_res : k_gen, PDEC_THREADS, lds, G, g_pdec_capacity[dev][(res ? 1 : 0) + fam],
-                   g_pdec_capacity_lds[dev][(res ? 1 : 0) + fam]) != PersistentGuard::Fit::yes)
-        return SET_ERR_UNSUPPORTED;
     const double wbytes = 4.0 * ((double)d->V * D + 4.0 * 4 * D * D + (double)d->A * D);
-    ProfScope ps(bm ? "persistent_beam" : "persistent_decode", s, 2.0 * B * wbytes / 4.0 * max_len, wbytes * max_len);
-    SET_TRY(guard.serialise(s));
     // no word of an earlier decode may carry a tag of this one (the candidate words at the end are the beam mode's alone)
-    SET_HIP_TRY(hipMemsetAsync(xbuf, 0, bm ? dcnet_persistent_xbytes(B, D, d->A) : (size_t)((char*)P.x_fcb - (char*)xbuf), s));
-    SET_TRY(pd_stamps_begin(&P.stamps, &P.stamp_wg, s));
-    if (bm && res) hipLaunchKernelGGL((dcnet_persistent_k<true, false, true>), dim3(G), dim3(PDEC_THREADS), lds, s, P);
-    else if (bm) hipLaunchKernelGGL((dcnet_persistent_k<false, false, true>), dim3(G), dim3(PDEC_THREADS), lds, s, P);
-    else if (lh && res) hipLaunchKernelGGL((dcnet_persistent_k<true, true>), dim3(G), dim3(PDEC_THREADS), lds, s, P);
-    else if (lh) hipLaunchKernelGGL((dcnet_persistent_k<false, true>), dim3(G), dim3(PDEC_THREADS), lds, s, P);
-    else if (res) hipLaunchKernelGGL(dcnet_persistent_k<true>, dim3(G), dim3(PDEC_THREADS), lds, s, P);
-    else hipLaunchKernelGGL(dcnet_persistent_k<false>, dim3(G), dim3(PDEC_THREADS), lds, s, P);
-    SET_LAUNCH_CHECK();
-    SET_TRY(guard.launched(s));
-    SET_TRY(pd_stamps_report(P.stamps, P.stamp_wg, 13, max_len, s));
-    return SET_OK;
+    return pdec_launch(g_pdec_k[res ? 0 : 1][bm ? 0 : lh ? 1 : 2], guard, G, lds, lds_max, &P, xbuf,
+                       bm ? dcnet_persistent_xbytes(B, D, d->A) : (size_t)((char*)P.x_fcb - (char*)xbuf), s,
+                       {bm ? "persistent_beam" : "persistent_decode", 2.0 * B * wbytes / 4.0 * max_len, wbytes * max_len},
+                       {&P.stamps, &P.stamp_wg, 13, max_len});
 }
 
 }  // namespace set

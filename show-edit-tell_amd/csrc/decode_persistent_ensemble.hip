@@ -7,9 +7,10 @@
 // instantiation of dcnet_persistent_k (decode_persistent.hip), which stay untouched: in the phase code the order of the loads and
 // the rotating weight buffers are the schedule, and moving it out of those loop bodies changes their instructions.  What does
 // not carry a schedule is shared with those two kernels: the tail of the pick (slice top-k, candidate words, row merge,
-// bookkeeping, poison: beam_persistent.h) and, on the host, the residency check (PersistentGuard::fits), the fill of EditNet's
-// argument block and the layout of its exchange regions (pdec_edit_fill / pdec_edit_layout, decode_persistent_wide.hip).  The
-// rows are the k <= PW_BEAM_K hypotheses, fixed features (R <= 36), both token tables active.
+// bookkeeping, poison: beam_persistent.h) and, on the host, the launch itself (PersistentKernel / pdec_launch,
+// decode_persistent.h) and the fills and exchange layouts of both models' argument blocks (pdec_edit_fill / pdec_edit_layout,
+// decode_persistent_wide.hip; pdec_dcnet_fill / pdec_dcnet_layout, pdec_beam_fill, decode_persistent.h).  The rows are the
+// k <= PW_BEAM_K hypotheses, fixed features (R <= 36), both token tables active.
 // Per pick:
 //   S1    both attention_lstm cells from the products contracted ahead of the previous pick, read through the parent map
 //                                                                                       -> h1 of EditNet X1e, h1 of DCNet X1d
@@ -731,9 +732,6 @@ bool pens_dims_ok(const SetEditNetDims* de, const SetDcnetDims* dd) {
            de->B <= PE_K;
 }
 
-int g_pens_capacity[64] = {};
-int g_pens_capacity_lds[64] = {};
-
 }  // namespace
 
 }  // namespace set
@@ -774,53 +772,25 @@ static int ensemble_beam_persistent(const SetEditNetWeights* we, const SetEditNe
     SET_TRY(dcnet_ensemble_prologue(wd, dd, prev, prevlen, ws_d, st, &pd));
 
     PDecEnsArgs P{};
-    {
-        PDecEditArgs& E = P.e;
-        pdec_edit_fill(E, we, de, max_picks);
-        E.pre1 = pe.pre1; E.att1 = pe.att1; E.att1_c = pe.att1_c; E.mask = pe.mask; E.capP = pe.capP; E.memQ = pe.memQ; E.Mem = pe.Mem;
-        E.pv = pe.pv;
-        E.start_idx = start_idx; E.end_idx = end_idx;
-        E.bm_hist_par = hist_parent; E.bm_hist_word = (long long*)hist_word; E.bm_best_score = best_score;
-        E.bm_best_word = (long long*)best_word; E.bm_result = result; E.bm_hist_score = hist_score;
-    }
-    {
-        const int E_ = dd->E, C = dd->C;
-        P.d.al_wih_h2 = wd->al_wih + E_ + 2 * C; P.d.ld_al = 3LL * E_;
-        P.d.al_whh = wd->al_whh; P.d.ll_whh = wd->ll_whh; P.d.ll_wih = wd->ll_wih; P.d.ld_ll = 2LL * E_;
-        P.d.ll_bih = wd->ll_bih; P.d.ll_bhh = wd->ll_bhh;
-        P.d.ca_dec_w = wd->ca_dec_w; P.d.ca_dec_b = wd->ca_dec_b; P.d.ca_full_w = wd->ca_full_w; P.d.ca_full_b = wd->ca_full_b;
-        P.d.fc_w = wd->fc_w; P.d.fc_b = wd->fc_b; P.d.tok_table = wd->tok_table; P.d.ld_tab = 4LL * D + 8LL * C;
-        P.d.pre1 = pd.pre1; P.d.att1_c = pd.att1_c; P.d.mask = pd.mask; P.d.pc = pd.pc;
-    }
-    {
-        char* x = pdec_edit_layout(P.e, (char*)xbuf);        // (R <= 36 here: 64 visual scores per row, as the kernel reads them)
-        P.d.x_h1 = x; x += (size_t)B * D * 8;
-        P.d.x_h2 = x; x += (size_t)B * D * 8;
-        P.d.x_att2 = x; x += (size_t)B * A * 8;
-        P.x_lse = x; x += (size_t)B * G * 4 * 8;
-        P.x_cand = x;
-    }
+    pdec_edit_fill(P.e, we, de, max_picks);
+    P.e.pre1 = pe.pre1; P.e.att1 = pe.att1; P.e.att1_c = pe.att1_c; P.e.mask = pe.mask; P.e.capP = pe.capP; P.e.memQ = pe.memQ;
+    P.e.Mem = pe.Mem; P.e.pv = pe.pv;
+    P.e.start_idx = start_idx; P.e.end_idx = end_idx;
+    pdec_beam_fill(P.e, PDecBeam{hist_parent, hist_word, best_score, best_word, result, nullptr, hist_score});
+    pdec_dcnet_fill(P.d, wd, dd);
+    P.d.pre1 = pd.pre1; P.d.att1_c = pd.att1_c; P.d.mask = pd.mask; P.d.pc = pd.pc;
+    char* x = pdec_edit_layout(P.e, (char*)xbuf);            // (R <= 36 here: 64 visual scores per row, as the kernel reads them)
+    x = pdec_dcnet_layout(P.d, x, B, D, A);
+    P.x_lse = x; x += (size_t)B * G * 4 * 8;
+    P.x_cand = x;
     PersistentGuard guard;
     if (guard.rc != SET_OK) return guard.rc;
-    P.e.spin_limit = guard.spin_limit();
-    P.e.test_stall = guard.test_stall(); P.e.fault = guard.fault;
-    // residency: every workgroup must be on the chip at once (grid_barrier.h PersistentGuard::fits); a device whose LDS limit or
-    // capacity is too small is answered with SET_ERR_UNSUPPORTED, never with a HIP error
-    const void* kern = reinterpret_cast<const void*>(&ensemble_persistent_k);
-    static bool configured[64] = {};
-    if (guard.set_lds(kern, lds_max, configured) != SET_OK) return SET_ERR_UNSUPPORTED;
-    if (guard.fits(kern, PDEC_THREADS, lds, G, g_pens_capacity[guard.dev], g_pens_capacity_lds[guard.dev]) != PersistentGuard::Fit::yes)
-        return SET_ERR_UNSUPPORTED;
+    pdec_guard_fill(P.e, guard);
+    static PersistentKernel kern = {reinterpret_cast<const void*>(&ensemble_persistent_k)};
     const double wbytes = 4.0 * (2.0 * (double)de->V * D + 9.0 * 4 * D * D + 3.0 * D * D + 3.0 * A * D);
-    ProfScope ps("persistent_beam_ensemble", st, 2.0 * B * wbytes / 4.0 * max_picks, wbytes * max_picks);
-    SET_TRY(guard.serialise(st));
-    SET_HIP_TRY(hipMemsetAsync(xbuf, 0, pens_xbytes(B, D, A), st));      // no word of an earlier search may carry a tag of this one
-    SET_TRY(pd_stamps_begin(&P.e.stamps, &P.e.stamp_wg, st));
-    hipLaunchKernelGGL(ensemble_persistent_k, dim3(G), dim3(PDEC_THREADS), lds, st, P);
-    SET_LAUNCH_CHECK();
-    SET_TRY(guard.launched(st));
-    SET_TRY(pd_stamps_report(P.e.stamps, P.e.stamp_wg, 20, max_picks, st));
-    return SET_OK;
+    return pdec_launch(kern, guard, G, lds, lds_max, &P, xbuf, pens_xbytes(B, D, A), st,
+                       {"persistent_beam_ensemble", 2.0 * B * wbytes / 4.0 * max_picks, wbytes * max_picks},
+                       {&P.e.stamps, &P.e.stamp_wg, 20, max_picks});
 }
 
 int set_ensemble_beam_persistent(const SetEditNetWeights* we, const SetEditNetDims* de, const SetDcnetWeights* wd,

@@ -34,10 +34,11 @@
 // word of any exchange of timestep t is overwritten (timestep t + 1) only after every workgroup consumed it.
 // Teacher-forced mode (set_editnet_xe_forward): words from the captions, scores written by the owners of the vocabulary rows.
 // Beam mode (BEAM): the pick — slice top-k, candidate words, row merge, bookkeeping, poison — is beam_persistent.h, shared with
-// DCNet's kernel and the ensemble's.  On the host the residency check (PersistentGuard::fits) and, with the ensemble launch,
-// the fill of PDecEditArgs and the layout of its seven exchange regions (pdec_edit_fill / pdec_edit_layout below) are shared
-// too.  The phase code is deliberately this kernel's own (the ensemble kernel carries a copy): the order of its loads and the
-// three rotating weight buffers are its schedule.
+// DCNet's kernel and the ensemble's.  On the host the launch itself (decode_persistent.h: PersistentKernel, pdec_launch, the
+// fills of the beam / teacher-forced / guard fields) and, with the ensemble launch, the fill of PDecEditArgs and the layout of
+// its seven exchange regions (pdec_edit_fill / pdec_edit_layout below) are shared too.  The phase code is deliberately this
+// kernel's own (the ensemble kernel carries a copy): the order of its loads and the three rotating weight buffers are its
+// schedule.
 #include "beam_persistent.h"
 
 namespace set {
@@ -717,9 +718,11 @@ bool editnet_persistent_wide_ok(int B, int D, int A, int T, int R, int V, bool w
     return true;
 }
 
-// residency and LDS configuration per instantiation: [0] greedy / teacher-forced, [1] beam, [2] beam over up to 128 masked regions
-static int g_pwide_capacity[3][64] = {};
-static int g_pwide_capacity_lds[3][64] = {};
+// the three instantiations: [0] beam over up to 128 masked regions, [1] beam, [2] greedy / teacher-forced.  (Listed in the order in
+// which the kernels have always been instantiated: the device code object stays byte for byte the same.)
+#define PWIDE_K(...) {reinterpret_cast<const void*>(&editnet_persistent_wide_k<__VA_ARGS__>)}
+static PersistentKernel g_pwide_k[3] = {PWIDE_K(true, PDEC_RREG_WIDE), PWIDE_K(true, PDEC_RREG), PWIDE_K(false, PDEC_RREG)};
+#undef PWIDE_K
 
 int editnet_persistent_wide_launch(PDecEditArgs& P, void* xbuf, PersistentGuard& guard, hipStream_t s, bool* unsupported, bool beam,
                                    bool wide_regions) {
@@ -733,31 +736,17 @@ int editnet_persistent_wide_launch(PDecEditArgs& P, void* xbuf, PersistentGuard&
         P.x_fc = x; x += (size_t)B * G * 32;
         P.x_fcb = x;
     }
-    const int inst = wide_regions ? 2 : (beam ? 1 : 0), rreg = wide_regions ? PDEC_RREG_WIDE : PDEC_RREG;
-    const void* kern = inst == 2 ? reinterpret_cast<const void*>(&editnet_persistent_wide_k<true, PDEC_RREG_WIDE>)
-                     : inst == 1 ? reinterpret_cast<const void*>(&editnet_persistent_wide_k<true, PDEC_RREG>)
-                                 : reinterpret_cast<const void*>(&editnet_persistent_wide_k<false, PDEC_RREG>);
+    const int rreg = wide_regions ? PDEC_RREG_WIDE : PDEC_RREG;
     const int lds = pwide_lds_floats(B, D, A, beam, rreg) * (int)sizeof(float);
-    static bool configured[3][64] = {};
     int lds_max = pwide_lds_floats(beam ? PW_BEAM_K : PDW_MAXB, D, A, beam, rreg) * (int)sizeof(float);
     if (lds_max > 156 * 1024) lds_max = 156 * 1024;
-    if (lds > lds_max || guard.set_lds(kern, lds_max, configured[inst]) != SET_OK) return SET_OK;
-    if (guard.fits(kern, PDEC_THREADS, lds, G, g_pwide_capacity[inst][guard.dev], g_pwide_capacity_lds[inst][guard.dev]) !=
-        PersistentGuard::Fit::yes)
-        return SET_OK;
-    *unsupported = false;
+    if (lds > lds_max) return SET_OK;
     const double wbytes = 4.0 * ((double)P.V * D + 5.0 * 4 * D * D + 3.0 * D * D + 2.0 * A * D);
-    ProfScope ps(beam ? "persistent_beam" : "persistent_decode", s, 2.0 * B * wbytes / 4.0 * P.max_len, wbytes * P.max_len);
-    SET_TRY(guard.serialise(s));
-    SET_HIP_TRY(hipMemsetAsync(xbuf, 0, editnet_persistent_wide_xbytes(B, D, A, P.R), s));    // no word of an earlier decode may carry a tag of this one
-    SET_TRY(pd_stamps_begin(&P.stamps, &P.stamp_wg, s));
-    if (inst == 2) hipLaunchKernelGGL((editnet_persistent_wide_k<true, PDEC_RREG_WIDE>), dim3(G), dim3(PDEC_THREADS), lds, s, P);
-    else if (inst == 1) hipLaunchKernelGGL((editnet_persistent_wide_k<true, PDEC_RREG>), dim3(G), dim3(PDEC_THREADS), lds, s, P);
-    else hipLaunchKernelGGL((editnet_persistent_wide_k<false, PDEC_RREG>), dim3(G), dim3(PDEC_THREADS), lds, s, P);
-    SET_LAUNCH_CHECK();
-    SET_TRY(guard.launched(s));
-    SET_TRY(pd_stamps_report(P.stamps, P.stamp_wg, 16, P.max_len, s));
-    return SET_OK;
+    const int rc = pdec_launch(g_pwide_k[wide_regions ? 0 : beam ? 1 : 2], guard, G, lds, lds_max, &P, xbuf, editnet_persistent_wide_xbytes(B, D, A, P.R),
+                               s, {beam ? "persistent_beam" : "persistent_decode", 2.0 * B * wbytes / 4.0 * P.max_len, wbytes * P.max_len},
+                               {&P.stamps, &P.stamp_wg, 16, P.max_len});
+    *unsupported = rc == SET_ERR_UNSUPPORTED;
+    return *unsupported ? SET_OK : rc;
 }
 
 
@@ -798,26 +787,16 @@ int editnet_persistent_greedy(const SetEditNetWeights* w, const SetEditNetDims* 
         if (!env_int("SET_DEC_PERSISTENT", 1) || max_len < 1 || (d->adaptive && !beam->rmask) || persistent_disabled() ||
             !editnet_persistent_wide_ok(d->B, d->D, d->A, d->T, d->R, d->V, wide)) return SET_ERR_UNSUPPORTED;
     } else if (!editnet_persistent_ok(d, max_len)) return SET_ERR_UNSUPPORTED;
-    const int B = d->B;
     PDecEditArgs P{};
     pdec_edit_fill(P, w, d, max_len);
     P.pre1 = pre1; P.att1 = att1; P.att1_c = att1_c; P.mask = mask; P.capP = capP; P.memQ = memQ; P.Mem = Mem; P.pv = pv;
     P.it = it; P.unfinished = unfinished; P.alive = alive; P.seq = seq; P.seq_logp = seq_logp;
     P.start_idx = start_idx; P.end_idx = end_idx;
-    if (teach) {
-        P.caps = (const long long*)teach->caps; P.caps_stride = teach->caps_stride;
-        P.predictions = teach->predictions; P.ld_pred_b = (long long)max_len * d->V;
-        for (int b = 0; b < B; ++b) P.dlen[b] = teach->host_decode_lengths[b];
-    }
+    if (teach) pdec_teacher_fill(P, *teach);
+    if (beam) { pdec_beam_fill(P, *beam); if (wide) P.rmask = beam->rmask; }
     PersistentGuard guard;
     if (guard.rc != SET_OK) return guard.rc;
-    P.spin_limit = guard.spin_limit();
-    P.test_stall = guard.test_stall(); P.fault = guard.fault;
-    if (beam) {
-        P.bm_hist_par = beam->hist_par; P.bm_hist_word = (long long*)beam->hist_word; P.bm_best_score = beam->best_score;
-        P.bm_best_word = (long long*)beam->best_word; P.bm_result = beam->result; P.bm_hist_score = beam->hist_score;
-        if (wide) P.rmask = beam->rmask;
-    }
+    pdec_guard_fill(P, guard);
     bool unsupported = true;
     const int rc = editnet_persistent_wide_launch(P, xbuf, guard, s, &unsupported, beam != nullptr, wide);      // (lays out the exchange region)
     return rc != SET_OK ? rc : (unsupported ? SET_ERR_UNSUPPORTED : SET_OK);

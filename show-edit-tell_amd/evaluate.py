@@ -324,6 +324,24 @@ class _PersistentBeamOut:
         return one + (_n_best_sorted(done, n_best),)
 
 
+def _persistent_beam(name, head, tail, word_map, k, picks, dev, n_best):
+    """What the three persistent searches share once their own guards have passed: the output buffer, the C entry's argument
+    list (the caller's leading arguments `head`, then <start>, <end>, picks and the five output pointers, then the caller's
+    workspaces `tail` and the stream), the choice of `name` or `name`_nbest (the same launch, plus the score of every counted
+    pick), and the answer.  None on SET_ERR_UNSUPPORTED: no output was touched (set_hip.h: answered before the prologue except
+    on a device too small for the grid)."""
+    from . import _lib
+    lib = _lib.load()
+    out = _PersistentBeamOut(picks, dev, n_best is not None)
+    args = head + (int(word_map['<start>']), int(word_map['<end>']), picks, out.hist_parent, out.hist_word, out.best_score,
+                   out.best_word, out.result) + tail + (_lib.stream_of(dev),)
+    rc = getattr(lib, name)(*args) if n_best is None else getattr(lib, name + "_nbest")(*args, out.hist_score)
+    if rc == 2:
+        return None
+    _lib.check(rc, name)
+    return out.answer(word_map, name, n_best, k)
+
+
 @torch.no_grad()
 def _beam_search_editnet_persistent(decoder, image_features, previous_caption, prev_caplen, word_map, beam_size, max_steps=50,
                                     image_mean=None, n_best=None):
@@ -333,14 +351,11 @@ def _beam_search_editnet_persistent(decoder, image_features, previous_caption, p
     per-step search.  image_mean (1, F): the adaptive model's image input (beam_search_adaptive); an adaptive decoder
     without one is refused here (the fixed-feature entries keep their routing)."""
     import ctypes as C
-    from . import _lib
-    from ._lib import check, ptr, stream_of
+    from ._lib import ptr
     k = int(beam_size)
     if k < 1 or k > 4 or image_features.shape[0] != 1 or (getattr(decoder, "_adaptive", 0) and image_mean is None):
         return None
     decoder.eval()
-    lib = _lib.load()
-    dev = image_features.device
     X = image_features.float().expand(k, -1, -1).contiguous()
     prev = previous_caption.long().expand(k, -1).contiguous()
     plen = prev_caplen.reshape(-1).long().expand(k).contiguous()
@@ -351,18 +366,9 @@ def _beam_search_editnet_persistent(decoder, image_features, previous_caption, p
     if not w.tok_table:
         return None
     ws = decoder._workspace(dims)
-    out = _PersistentBeamOut(picks, dev, n_best is not None)
-    args = (C.byref(w), C.byref(dims), ptr(X), None if mean is None else ptr(mean), ptr(prev), ptr(plen), int(word_map['<start>']),
-            int(word_map['<end>']), picks, out.hist_parent, out.hist_word, out.best_score, out.best_word, out.result, ptr(ws),
-            ws.numel(), stream_of(dev))
-    if n_best is None:
-        rc = lib.set_editnet_beam_persistent(*args)
-    else:                                                          # the same launch, plus the score of every counted pick
-        rc = lib.set_editnet_beam_persistent_nbest(*args, out.hist_score)
-    if rc == 2:                                                    # SET_ERR_UNSUPPORTED: no output was touched (set_hip.h: answered
-        return None                                                # before the prologue except on a device too small for the grid)
-    check(rc, "set_editnet_beam_persistent")
-    return out.answer(word_map, "set_editnet_beam_persistent", n_best, k)
+    return _persistent_beam("set_editnet_beam_persistent",
+                            (C.byref(w), C.byref(dims), ptr(X), None if mean is None else ptr(mean), ptr(prev), ptr(plen)),
+                            (ptr(ws), ws.numel()), word_map, k, picks, X.device, n_best)
 
 
 def _first(res):
@@ -398,14 +404,11 @@ def _beam_search_dcnet_persistent(dae, previous_caption, prev_caplen, word_map, 
     caller takes the per-step search.  Output buffer, read-back, trace-back and step-limit rule: _PersistentBeamOut, shared
     with _beam_search_editnet_persistent."""
     import ctypes as C
-    from . import _lib
-    from ._lib import check, ptr, stream_of
+    from ._lib import ptr
     k = int(beam_size)
     if k < 1 or k > 4 or previous_caption.shape[0] != 1:
         return None
     dae.eval()
-    lib = _lib.load()
-    dev = previous_caption.device
     prev = previous_caption.long().expand(k, -1).contiguous()
     plen = prev_caplen.reshape(-1).long().expand(k).contiguous()
     picks = max_steps + 1
@@ -414,14 +417,8 @@ def _beam_search_dcnet_persistent(dae, previous_caption, prev_caplen, word_map, 
     if not w.tok_table:
         return None
     ws = dae._workspace(dims)
-    out = _PersistentBeamOut(picks, dev, n_best is not None)
-    args = (C.byref(w), C.byref(dims), ptr(prev), ptr(plen), int(word_map['<start>']), int(word_map['<end>']), picks, out.hist_parent,
-            out.hist_word, out.best_score, out.best_word, out.result, ptr(ws), ws.numel(), stream_of(dev))
-    rc = lib.set_dcnet_beam_persistent(*args) if n_best is None else lib.set_dcnet_beam_persistent_nbest(*args, out.hist_score)
-    if rc == 2:                                                    # SET_ERR_UNSUPPORTED: no output was touched
-        return None
-    check(rc, "set_dcnet_beam_persistent")
-    return out.answer(word_map, "set_dcnet_beam_persistent", n_best, k)
+    return _persistent_beam("set_dcnet_beam_persistent", (C.byref(w), C.byref(dims), ptr(prev), ptr(plen)), (ptr(ws), ws.numel()),
+                            word_map, k, picks, prev.device, n_best)
 
 
 def beam_search_dcnet(dae, previous_caption, prev_caplen, word_map, beam_size=3, n_best=None):
@@ -451,14 +448,13 @@ def _beam_search_ensemble_persistent(decoder, dae, image_features, previous_capt
     and step-limit rule: _PersistentBeamOut, shared with the single-model searches."""
     import ctypes as C
     from . import _lib
-    from ._lib import check, ptr, stream_of
+    from ._lib import ptr
     k = int(beam_size)
     if (k < 1 or k > 4 or image_features.shape[0] != 1 or previous_caption.shape[0] != 1 or getattr(decoder, "_adaptive", 0)
             or decoder.vocab_size != dae.vocab_size):
         return None
     decoder.eval()
     dae.eval()
-    lib = _lib.load()
     dev = image_features.device
     X = image_features.float().expand(k, -1, -1).contiguous()
     prev = previous_caption.long().expand(k, -1).contiguous()
@@ -469,7 +465,7 @@ def _beam_search_ensemble_persistent(decoder, dae, image_features, previous_capt
     we, wd = decoder._weights(de), dae._weights(dd)
     if not we.tok_table or not wd.tok_table:
         return None
-    nx = lib.set_ensemble_beam_xbuf_bytes(C.byref(de), C.byref(dd))
+    nx = _lib.load().set_ensemble_beam_xbuf_bytes(C.byref(de), C.byref(dd))
     if nx == 0:
         return None
     ws_e, ws_d = decoder._workspace(de), dae._workspace(dd)
@@ -479,15 +475,9 @@ def _beam_search_ensemble_persistent(decoder, dae, image_features, previous_capt
         if len(_ens_xbuf) >= 8:
             _ens_xbuf.clear()
         xbuf = _ens_xbuf[key] = torch.empty(nx, dtype=torch.uint8, device=dev)
-    out = _PersistentBeamOut(picks, dev, n_best is not None)
-    args = (C.byref(we), C.byref(de), C.byref(wd), C.byref(dd), ptr(X), ptr(prev), ptr(plen), int(word_map['<start>']),
-            int(word_map['<end>']), picks, out.hist_parent, out.hist_word, out.best_score, out.best_word, out.result, ptr(ws_e),
-            ws_e.numel(), ptr(ws_d), ws_d.numel(), ptr(xbuf), xbuf.numel(), stream_of(dev))
-    rc = lib.set_ensemble_beam_persistent(*args) if n_best is None else lib.set_ensemble_beam_persistent_nbest(*args, out.hist_score)
-    if rc == 2:                                                    # SET_ERR_UNSUPPORTED: no output was touched
-        return None
-    check(rc, "set_ensemble_beam_persistent")
-    return out.answer(word_map, "set_ensemble_beam_persistent", n_best, k)
+    return _persistent_beam("set_ensemble_beam_persistent",
+                            (C.byref(we), C.byref(de), C.byref(wd), C.byref(dd), ptr(X), ptr(prev), ptr(plen)),
+                            (ptr(ws_e), ws_e.numel(), ptr(ws_d), ws_d.numel(), ptr(xbuf), xbuf.numel()), word_map, k, picks, dev, n_best)
 
 
 def beam_search_ensemble(decoder, dae, image_features, previous_caption, prev_caplen, word_map, beam_size=3,

@@ -181,6 +181,57 @@ def test_dcnet_persistent_xe_forward_matches_golden_and_per_step():
     assert float((pred - ref[0]).abs().max()) < 2e-5 * max(1.0, float(ref[0].abs().max()))
 
 
+def test_dcnet_persistent_instantiations_interleaved_in_one_process():
+    """The six instantiations of DCNet's kernel keep their LDS cap and their residency answer in one record each
+    (csrc/decode_persistent.h PersistentKernel).  One process, in this order: greedy at B = 2 (resident), greedy at B = 6
+    (general), the teacher-forced forward with last_hidden at B = 2 (resident, last_h2), a beam search at k = 3, the B = 2
+    greedy again.  Every call takes the persistent launch (profile tags) — a record read for another instantiation would leave
+    a kernel without its LDS cap or refuse it — and equals the per-step loop (SET_DEC_PERSISTENT=0, computed first; those calls
+    also build the token tables): ids exact, log-probs within 1e-5, teacher-forced scores and last_hidden (|h2| < 1, the
+    operand of those scores) within 2e-5 with the same zero pattern, beam tokens exact and score within beam_parity.SCORE_TOL."""
+    import beam_parity
+    from oracle import cases
+    from show_edit_tell_amd import evaluate
+    from test_hip_dcnet_beam import _dae
+    from test_hip_dcnet_mse import mse_module
+    d, xe, rl = dcnet_modules("dcnet_full_b4")
+    wm = d["wm"]
+    _, ar = mse_module("dcnet_full_b4")
+    db = cases.build_beam("beam_full_b4")
+    dae = _dae(db)
+    rows6 = [0, 1, 2, 3, 2, 1]
+    g2 = (wm, to_dev(d["prev"][:2]), to_dev(d["plen"][:2]), True, False)
+    g6 = (wm, to_dev(d["prev"][rows6]), to_dev(d["plen"][rows6]), True, False)
+    tf = tuple(to_dev(d[k][:2]) for k in ("caps", "clen", "prev", "plen"))
+    bm = (to_dev(db["prev"][:1]), to_dev(db["plen"][:1]), db["wm"], 3)
+
+    def per_step():
+        for _ in range(2):
+            ref = rl(*g2), rl(*g6), ar(*tf), evaluate.beam_search_dcnet(dae, *bm)
+        torch.cuda.synchronize()
+        return ref
+
+    with torch.no_grad():
+        ref2, ref6, ref_tf, ref_bm = _with_env("SET_DEC_PERSISTENT", "0", per_step)
+        got = []
+        for fn, tag in ((lambda: rl(*g2), "persistent_decode"), (lambda: rl(*g6), "persistent_decode"),
+                        (lambda: ar(*tf), "persistent_decode"),
+                        (lambda: evaluate._beam_search_dcnet_persistent(dae, *bm), "persistent_beam"),
+                        (lambda: rl(*g2), "persistent_decode")):
+            names = _tags(lambda: got.append(fn()))
+            assert tag in names, (len(got), names)
+    for (seq, logp), ref in ((got[0], ref2), (got[1], ref6), (got[4], ref2)):
+        assert torch.equal(seq, ref[0])
+        assert float((logp - ref[1]).abs().max()) < 1e-5
+    pred, _, dl, sort_ind, _, last_h = got[2]
+    assert dl == ref_tf[2] and torch.equal(sort_ind, ref_tf[3])
+    assert torch.equal(pred == 0, ref_tf[0] == 0)
+    assert float((pred - ref_tf[0]).abs().max()) < 2e-5 * max(1.0, float(ref_tf[0].abs().max()))
+    assert float((last_h - ref_tf[5]).abs().max()) < 2e-5
+    assert got[3] is not None and not np.isnan(ref_bm[1]), (got[3], ref_bm)
+    assert got[3][0] == ref_bm[0] and abs(got[3][1] - ref_bm[1]) < beam_parity.SCORE_TOL, (got[3], ref_bm)
+
+
 @pytest.mark.parametrize("name", ["editnet_full_b4", "editnet_full_v9490"])
 def test_editnet_persistent_decode_matches_golden_and_per_step(name):
     """EditNet greedy at full dimensions (csrc/decode_persistent_wide.hip): B = 4 (one row per wave, its attention rows
