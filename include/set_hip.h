@@ -245,6 +245,31 @@ int set_editnet_sample(const SetEditNetWeights* w, const SetEditNetDims* d, cons
                        int64_t start_idx, int64_t end_idx, int max_len, uint64_t seed, uint64_t offset,
                        int64_t* seq, float* seq_logp, void* ws, size_t ws_bytes, void* stream);
 
+/* Temperature, top-k and nucleus (top-p) truncation of the sampled pick.  NULL and {1, 0, 1} are neutral: the call is then
+ * the one without options, bit for bit.  For one row of logits x[v], v < V (slabs summed, bias added):
+ *   1. y[v] = x[v] * (1.0f / temperature), the reciprocal formed once on the host in float.
+ *   2. top_k (off when 0 or >= V): tk = the top_k-th largest y; kept = {v : y[v] >= tk}.  Every tie at tk is kept, so the
+ *      set may hold more than top_k words.
+ *   3. top_p (off when 1), over what step 2 kept: m[v] = exp(y[v] - max y), M = sum of m over the kept set; tp = the largest
+ *      value whose set {v kept : y[v] >= tp} has mass >= top_p * M; kept = that set — the value group that crosses the mass
+ *      is included with all of its ties.
+ *   Comparisons are on float values (-0.0 == +0.0).  The kept set always contains the arg-max.
+ *   Draw: inverse CDF over the kept set in the kernel's fixed enumeration, the same one Philox uniform per (seed, offset,
+ *   row, t); words outside the kept set have mass 0.  step_logp / seq_logp = (y[w] - max y) - log(sum of m over the kept set),
+ *   the log-probability under the distribution sampled from; lse = log-sum-exp of y over the kept set.  raw_ids, the <end>
+ *   rewrite, the `unfinished` latch, alive, the embedding gather and the LSTM tail are those of the call without options.
+ *   Selection is exact and deterministic (bitwise descent over the ordered key of the float: integer counts for top-k, a
+ *   fixed-order mass for top-p; no floating-point atomics).
+ *   SET_ERR_ARG (before any HIP call, nothing written): temperature not finite or outside [1e-3, 1e3], top_k < 0, top_p not
+ *   finite or outside (0, 1]. */
+typedef struct SetSampleOpts { float temperature; int32_t top_k; float top_p; int32_t pad_; } SetSampleOpts;
+/* set_editnet_sample with the options applied at every timestep */
+int set_editnet_sample_opts(const SetEditNetWeights* w, const SetEditNetDims* d, const float* X,
+                            const float* image_mean, const int64_t* prev, const int64_t* prevlen,
+                            int64_t start_idx, int64_t end_idx, int max_len, uint64_t seed, uint64_t offset,
+                            int64_t* seq, float* seq_logp, void* ws, size_t ws_bytes, void* stream,
+                            const SetSampleOpts* opts);
+
 /* Teacher-forced XE forward (editnet.py:479-548, eval mode, use_ss=False) on a batch already
  * sorted by decreasing caption length.  caps (B,Lc) int64 sorted; host_decode_lengths[B] on the
  * HOST, non-increasing; predictions (B,maxT,V) is fully overwritten (zeros where not decoded). */
@@ -412,6 +437,11 @@ size_t set_ensemble_beam_xbuf_bytes(const SetEditNetDims* de, const SetDcnetDims
 int set_dcnet_sample(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* prev,
                      const int64_t* prevlen, int64_t start_idx, int64_t end_idx, int max_len, uint64_t seed,
                      uint64_t offset, int64_t* seq, float* seq_logp, void* ws, size_t ws_bytes, void* stream);
+/* set_dcnet_sample with SetSampleOpts applied at every timestep (see set_editnet_sample_opts) */
+int set_dcnet_sample_opts(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* prev,
+                          const int64_t* prevlen, int64_t start_idx, int64_t end_idx, int max_len, uint64_t seed,
+                          uint64_t offset, int64_t* seq, float* seq_logp, void* ws, size_t ws_bytes, void* stream,
+                          const SetSampleOpts* opts);
 int set_dcnet_xe_forward(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* caps,
                          int64_t caps_stride, const int* host_decode_lengths, const int64_t* prev,
                          const int64_t* prevlen, float* predictions, void* ws, size_t ws_bytes,
@@ -750,6 +780,11 @@ int set_pack_f32(float* dst, int64_t ldd, int rows, int nseg, const float* const
 int set_sample_pick_f32(const float* logits, int64_t ld_logits, int B, int V, int t, int max_len, int64_t end_idx,
                         uint64_t seed, uint64_t offset, int64_t* seq, int64_t* it, int32_t* unfinished,
                         int32_t* alive, int64_t* raw_ids, float* lse, float* step_logp, void* stream);
+/* set_sample_pick_f32 with options (SetSampleOpts, above set_editnet_sample_opts) */
+int set_sample_pick_opts_f32(const float* logits, int64_t ld_logits, int B, int V, int t, int max_len, int64_t end_idx,
+                             uint64_t seed, uint64_t offset, int64_t* seq, int64_t* it, int32_t* unfinished,
+                             int32_t* alive, int64_t* raw_ids, float* lse, float* step_logp, void* stream,
+                             const SetSampleOpts* opts);
 /* backward of step_logp w.r.t. logits: dlogits[b,v] = g[b] (1[v == raw_id_b] - exp(logits[b,v] - lse[b])); rows
  * with raw_id < 0 get zeros */
 int set_sample_logp_bwd_f32(const float* logits, int64_t ld_logits, const float* lse, const int64_t* raw_ids,
@@ -800,6 +835,9 @@ typedef struct SetPickArgs {
     int32_t n, B, V, t, max_len, D, mode, pad_;
 } SetPickArgs;
 int set_pick_slabs_f32(const SetPickArgs* args, void* stream);
+/* the same with SetSampleOpts in sample mode (see set_sample_pick_opts_f32).  The greedy mode takes no options: non-NULL
+ * opts that are not neutral give SET_ERR_ARG there. */
+int set_pick_slabs_opts_f32(const SetPickArgs* args, const SetSampleOpts* opts, void* stream);
 
 /* Beam-search step epilogue for NI images x k hypotheses (rows i*k+j), replacing the host bookkeeping of
  * editnet.py:654-699 / dcnet.py:450-500 / eval_full.py:150-200: log_softmax (or, with logits2, the ensemble

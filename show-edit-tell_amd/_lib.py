@@ -187,6 +187,35 @@ class PickArgs(C.Structure):
 PICK_GREEDY, PICK_SAMPLE = 0, 1
 
 
+class SampleOpts(C.Structure):
+    """include/set_hip.h SetSampleOpts: temperature, top-k and top-p of the sampled pick ({1, 0, 1}: neutral)"""
+    _fields_ = [("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("pad_", C.c_int32)]
+
+
+def sample_opts(temperature=1.0, top_k=0, top_p=1.0):
+    """None for neutral values (the caller then makes the call without options), a checked SampleOpts otherwise"""
+    import math
+    if float(temperature) == 1.0 and int(top_k) == 0 and float(top_p) == 1.0:
+        return None
+    t, p = float(temperature), float(top_p)
+    if not (math.isfinite(t) and 1e-3 <= t <= 1e3):
+        raise ValueError("temperature must be a finite number in [1e-3, 1e3], got %r" % (temperature,))
+    if int(top_k) != top_k or top_k < 0:
+        raise ValueError("top_k must be an integer >= 0 (0: off), got %r" % (top_k,))
+    if not (math.isfinite(p) and 0.0 < p <= 1.0):
+        raise ValueError("top_p must lie in (0, 1] (1: off), got %r" % (top_p,))
+    return SampleOpts(temperature=t, top_k=int(top_k), top_p=p)
+
+
+def refuse_sample_opts(sample_max, sample_rl, grad_path):
+    """non-neutral sampling options where nothing is sampled, or where the log-probs would need a backward that is not built"""
+    if sample_max or not sample_rl:
+        raise ValueError("temperature / top_k / top_p apply to the sampled rollout only (sample_max=False, sample_rl=True)")
+    if grad_path:
+        raise ValueError("temperature / top_k / top_p are not supported in the grad-enabled rollout (train mode or parameters "
+                         "that require grad): call the model in eval mode under torch.no_grad()")
+
+
 class SlabSrc(C.Structure):
     """include/set_hip.h SetSlabSrc: one addend of a gradient that is still split-K partials"""
     _fields_ = [("p", C.c_void_p), ("slab_stride", C.c_int64), ("ld", C.c_int64), ("nslab", C.c_int32), ("rows", C.c_int32)]
@@ -269,6 +298,8 @@ PROTOTYPES = {
                                                _P, _P, _P, _Z, _P, _P]),
     "set_editnet_sample": (_I, [C.POINTER(EditNetWeights), C.POINTER(EditNetDims), _P, _P, _P, _P, _L, _L, _I, _U, _U, _P,
                                 _P, _P, _Z, _P]),
+    "set_editnet_sample_opts": (_I, [C.POINTER(EditNetWeights), C.POINTER(EditNetDims), _P, _P, _P, _P, _L, _L, _I, _U, _U, _P,
+                                     _P, _P, _Z, _P, C.POINTER(SampleOpts)]),
     "set_editnet_xe_forward": (_I, [C.POINTER(EditNetWeights), C.POINTER(EditNetDims), _P, _P, _P, _L,
                                     C.POINTER(C.c_int), _P, _P, _P, _P, _Z, _P]),
     "set_editnet_edit_trace_workspace_bytes": (_Z, [C.POINTER(EditNetDims), _I]),
@@ -296,6 +327,8 @@ PROTOTYPES = {
     "set_ensemble_beam_xbuf_bytes": (_Z, [C.POINTER(EditNetDims), C.POINTER(DcnetDims)]),
     "set_dcnet_sample": (_I, [C.POINTER(DcnetWeights), C.POINTER(DcnetDims), _P, _P, _L, _L, _I, _U, _U, _P, _P, _P, _Z,
                               _P]),
+    "set_dcnet_sample_opts": (_I, [C.POINTER(DcnetWeights), C.POINTER(DcnetDims), _P, _P, _L, _L, _I, _U, _U, _P, _P, _P, _Z,
+                                   _P, C.POINTER(SampleOpts)]),
     "set_dcnet_xe_forward": (_I, [C.POINTER(DcnetWeights), C.POINTER(DcnetDims), _P, _L, C.POINTER(C.c_int), _P, _P,
                                   _P, _P, _Z, _P]),
     "set_dcnet_xe_forward_hidden": (_I, [C.POINTER(DcnetWeights), C.POINTER(DcnetDims), _P, _L, C.POINTER(C.c_int), _P,
@@ -366,9 +399,11 @@ PROTOTYPES = {
     "set_rowsum_mask_f32": (_I, [_P, _L, _I, _I, _P, _P]),
     "set_pack_f32": (_I, [_P, _L, _I, _I, C.POINTER(_P), C.POINTER(_L), C.POINTER(_I), _I, _P]),
     "set_sample_pick_f32": (_I, [_P, _L, _I, _I, _I, _I, _L, _U, _U, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "set_sample_pick_opts_f32": (_I, [_P, _L, _I, _I, _I, _I, _L, _U, _U, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(SampleOpts)]),
     "set_sample_logp_bwd_f32": (_I, [_P, _L, _P, _P, _P, _P, _L, _I, _I, _P]),
     "set_philox4x32": (_I, [_P, _I, _U, _U, _P]),
     "set_pick_slabs_f32": (_I, [C.POINTER(PickArgs), _P]),
+    "set_pick_slabs_opts_f32": (_I, [C.POINTER(PickArgs), C.POINTER(SampleOpts), _P]),
     "set_beam_pick_f32": (_I, [_P, _P, _L, _I, _I, _I, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "set_beam_pick_nbest_f32": (_I, [_P, _P, _L, _I, _I, _I, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "set_beam_gather_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),

@@ -363,8 +363,10 @@ int set_dcnet_greedy_pick(const SetDcnetWeights* w, const SetDcnetDims* d, const
 // free-running decode (dcnet_rl.py:286-346): sample == 0 greedy, 1 multinomial
 static int dcnet_rollout(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* prev, const int64_t* prevlen,
                          int64_t start_idx, int64_t end_idx, int max_len, int sample, uint64_t seed, uint64_t offset,
-                         int64_t* seq, float* seq_logp, void* ws, size_t ws_bytes, void* stream) {
+                         int64_t* seq, float* seq_logp, void* ws, size_t ws_bytes, void* stream,
+                         const SetSampleOpts* opts = nullptr) {
     if (!w || !prev || !prevlen || !seq || !seq_logp || max_len <= 0) return SET_ERR_ARG;
+    SET_TRY(sample_opts_check(opts));
     DcnetWs W;
     SET_TRY(prep(d, ws, ws_bytes, &W));
     if (max_len > d->maxT || start_idx < 0 || start_idx >= d->V) return SET_ERR_ARG;
@@ -418,7 +420,7 @@ static int dcnet_rollout(const SetDcnetWeights* w, const SetDcnetDims* d, const 
         if (sample)
             SET_TRY(sample_pick(lg, pick_bias, d->V, t, max_len, end_idx, (long long*)seq, seq_logp, W.it, W.unfinished,
                                 W.alive, emb_needed ? w->embed : nullptr, W.emb, d->E, B, seed, offset, nullptr, nullptr,
-                                nullptr, st, a_done ? &tail : nullptr));
+                                nullptr, st, a_done ? &tail : nullptr, opts));
         else
             SET_TRY(greedy_pick(lg, pick_bias, d->V, t, max_len, end_idx, (long long*)seq, seq_logp, W.it, W.unfinished,
                                 W.alive, emb_needed ? w->embed : nullptr, W.emb, d->E, B, st, a_done ? &tail : nullptr));
@@ -474,6 +476,13 @@ int set_dcnet_sample(const SetDcnetWeights* w, const SetDcnetDims* d, const int6
                      float* seq_logp, void* ws, size_t ws_bytes, void* stream) {
     return dcnet_rollout(w, d, prev, prevlen, start_idx, end_idx, max_len, 1, seed, offset, seq, seq_logp, ws, ws_bytes,
                          stream);
+}
+
+int set_dcnet_sample_opts(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* prev, const int64_t* prevlen,
+                          int64_t start_idx, int64_t end_idx, int max_len, uint64_t seed, uint64_t offset, int64_t* seq,
+                          float* seq_logp, void* ws, size_t ws_bytes, void* stream, const SetSampleOpts* opts) {
+    return dcnet_rollout(w, d, prev, prevlen, start_idx, end_idx, max_len, 1, seed, offset, seq, seq_logp, ws, ws_bytes,
+                         stream, opts);
 }
 
 // dcnet_with_mse.py:321,341 (`decoder_last_hidden[:batch_size_t] = h2.clone()` at every step): last_hidden (B, D, sorted

@@ -562,8 +562,9 @@ int set_editnet_greedy_pick(const SetEditNetWeights* w, const SetEditNetDims* d,
 static int rollout(const SetEditNetWeights* w, const SetEditNetDims* d, const float* X, const float* image_mean,
                    const int64_t* prev, const int64_t* prevlen, int64_t start_idx, int64_t end_idx, int max_len,
                    int sample, uint64_t seed, uint64_t offset, int64_t* seq, float* seq_logp, void* ws, size_t ws_bytes,
-                   void* stream, bool begun = false) {
+                   void* stream, bool begun = false, const SetSampleOpts* opts = nullptr) {
     if (!w || !X || (!begun && (!prev || !prevlen)) || !seq || !seq_logp || max_len <= 0) return SET_ERR_ARG;
+    SET_TRY(sample_opts_check(opts));
     EditNetWs W;
     SET_TRY(prep(d, ws, ws_bytes, &W));
     if (max_len + 1 > d->maxT + 1 || start_idx < 0 || start_idx >= d->V) return SET_ERR_ARG;
@@ -630,7 +631,7 @@ static int rollout(const SetEditNetWeights* w, const SetEditNetDims* d, const fl
         if (sample)
             SET_TRY(sample_pick(lg, pick_bias, d->V, t, max_len, end_idx, (long long*)seq, seq_logp, W.it, W.unfinished,
                                 W.alive, emb_needed ? w->embed : nullptr, W.emb, d->D, B, seed, offset, nullptr, nullptr,
-                                nullptr, st, a_done ? &tail : nullptr));
+                                nullptr, st, a_done ? &tail : nullptr, opts));
         else
             SET_TRY(greedy_pick(lg, pick_bias, d->V, t, max_len, end_idx, (long long*)seq, seq_logp, W.it, W.unfinished,
                                 W.alive, emb_needed ? w->embed : nullptr, W.emb, d->D, B, st, a_done ? &tail : nullptr));
@@ -700,6 +701,14 @@ int set_editnet_sample(const SetEditNetWeights* w, const SetEditNetDims* d, cons
                        void* stream) {
     return rollout(w, d, X, image_mean, prev, prevlen, start_idx, end_idx, max_len, 1, seed, offset, seq, seq_logp, ws,
                    ws_bytes, stream);
+}
+
+int set_editnet_sample_opts(const SetEditNetWeights* w, const SetEditNetDims* d, const float* X, const float* image_mean,
+                            const int64_t* prev, const int64_t* prevlen, int64_t start_idx, int64_t end_idx, int max_len,
+                            uint64_t seed, uint64_t offset, int64_t* seq, float* seq_logp, void* ws, size_t ws_bytes,
+                            void* stream, const SetSampleOpts* opts) {
+    return rollout(w, d, X, image_mean, prev, prevlen, start_idx, end_idx, max_len, 1, seed, offset, seq, seq_logp, ws,
+                   ws_bytes, stream, false, opts);
 }
 
 int set_editnet_xe_forward(const SetEditNetWeights* w, const SetEditNetDims* d, const float* X,

@@ -333,20 +333,39 @@ int philox_fill(uint32_t* out, int n, unsigned long long seed, unsigned long lon
     return SET_OK;
 }
 
+// ---- truncated sampling (include/set_hip.h SetSampleOpts): y = x * inv_t, then top-k, then top-p over what top-k kept.
+// Both thresholds are found by a bitwise descent over the order-preserving 32-bit key of the float (at most 32 block
+// reductions each: an integer count for top-k, a fixed-order mass for top-p), so the kept set {key >= thr} is exact,
+// takes every tie at its boundary and does not depend on the launch.  Words outside it are masked to -inf, after which the
+// draw below is the untruncated one.
+struct SampleTrunc {
+    float inv_t = 1.f;
+    int top_k = 0;        // 0: off (the host maps top_k >= V to 0)
+    float top_p = 1.f;    // 1: off
+};
+// a < b as floats  <=>  key(a) < key(b) (non-NaN); -0.0 and +0.0 share a key, as they compare equal
+__device__ __forceinline__ uint32_t order_key(float f) {
+    const uint32_t u = __float_as_uint(f);
+    if (u == 0x80000000u) return 0x80000000u;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
 struct SampleOut {
     long long* raw_ids;   // (B) sampled word BEFORE the <end> -> 0 rewriting; -1 once the loop has been left
     float* lse;           // (B) log-sum-exp of the row (for the backward of the gathered log-prob)
     float* step_logp;     // (B) this step's log-prob (0 once the loop has been left)
 };
 
-template <bool REG, bool TAIL>
+template <bool REG, bool TAIL, bool TRUNC>
 __global__ void __launch_bounds__(256) sample_pick_k(Slabs logits, const float* bias, int V, int t, int max_len,
                                                      long long end_idx, long long* seq, float* seq_logp,
                                                      long long* it_buf, int* unfinished, int* alive,
                                                      const float* table, float* emb_out, int D,
                                                      unsigned long long seed, unsigned long long offset,
-                                                     SampleOut so, const LstmTail tail) {
+                                                     SampleOut so, const LstmTail tail, const SampleTrunc trunc) {
     __shared__ float s_red[4];
+    __shared__ int s_cnt[2][4];          // TRUNC: per-wave partials of one descent pass, double-buffered (one barrier a pass)
+    __shared__ float s_mass[2][4];
     __shared__ float s_scan[4];
     __shared__ float s_max;
     __shared__ long long s_tok;
@@ -355,6 +374,16 @@ __global__ void __launch_bounds__(256) sample_pick_k(Slabs logits, const float* 
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     f32x4 x[GP_MAXQ];
     float best = -INFINITY;
+    uint32_t thr = 0;                                    // TRUNC: the kept set is {order_key(y) >= thr}
+    // the generic path's logit, re-read (TRUNC: scaled, and -inf outside the kept set once thr stands)
+    auto val = [&](int v) -> float {
+        float xv = logit_at(logits, bias, b, v);
+        if (TRUNC) {
+            xv *= trunc.inv_t;
+            if (order_key(xv) < thr) xv = -INFINITY;
+        }
+        return xv;
+    };
     if (REG) {
         const float* row = logits.p + (long long)b * logits.ld;
 #pragma unroll
@@ -379,13 +408,13 @@ __global__ void __launch_bounds__(256) sample_pick_k(Slabs logits, const float* 
             const int v = (tid + 256 * q) * 4;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                if (v + e < V) { if (bias) x[q][e] += bias[v + e]; }
+                if (v + e < V) { if (bias) x[q][e] += bias[v + e]; if (TRUNC) x[q][e] *= trunc.inv_t; }
                 else x[q][e] = -INFINITY;
                 best = fmaxf(best, x[q][e]);
             }
         }
     } else {
-        for (int v = tid; v < V; v += 256) best = fmaxf(best, logit_at(logits, bias, b, v));
+        for (int v = tid; v < V; v += 256) best = fmaxf(best, val(v));
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) best = fmaxf(best, __shfl_xor(best, o));
@@ -393,6 +422,88 @@ __global__ void __launch_bounds__(256) sample_pick_k(Slabs logits, const float* 
     if (tid == 0) s_pick = -1;
     __syncthreads();
     best = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
+    if (TRUNC && (trunc.top_k > 0 || trunc.top_p < 1.f)) {
+        // Every pass is block-uniform: each wave leaves one partial in LDS, one barrier, every thread adds the four in the
+        // same order.  Padding columns (-inf) never change a decision: they lie below every threshold that matters.
+        uint32_t key[GP_MAXQ][4];
+        if (REG) {
+#pragma unroll
+            for (int q = 0; q < GP_MAXQ; ++q)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) key[q][e] = order_key(x[q][e]);
+        }
+        int pass = 0;
+        uint32_t lo = 0;
+        if (trunc.top_k > 0) {           // lo = key of the top_k-th largest value: the largest lo with |{key >= lo}| >= top_k
+            for (int bit = 31; bit >= 0; --bit, ++pass) {
+                const uint32_t cand = lo | (1u << bit);
+                int c = 0;               // wave-uniform
+                if (REG) {
+#pragma unroll
+                    for (int q = 0; q < GP_MAXQ; ++q)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) c += __popcll(__ballot(key[q][e] >= cand));
+                } else {
+                    for (int v0 = 0; v0 < V; v0 += 256) {
+                        const int v = v0 + tid;
+                        c += __popcll(__ballot(v < V && order_key(val(v)) >= cand));
+                    }
+                }
+                if (lane == 0) s_cnt[pass & 1][wave] = c;
+                __syncthreads();
+                const int* sc = s_cnt[pass & 1];
+                if ((sc[0] + sc[1]) + (sc[2] + sc[3]) >= trunc.top_k) lo = cand;
+            }
+            thr = lo;                    // (the generic path's val() masks with it from here on)
+        }
+        if (trunc.top_p < 1.f) {
+            // mass of {kept by top-k, key >= cand}: per thread in enumeration order, xor tree over the wave, waves in index
+            // order — one fixed order for every cand, so the sum of these non-negative terms is monotone in cand
+            float m[GP_MAXQ][4];
+            if (REG) {
+#pragma unroll
+                for (int q = 0; q < GP_MAXQ; ++q)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) m[q][e] = key[q][e] >= lo ? expf(x[q][e] - best) : 0.f;
+            }
+            auto mass_ge = [&](uint32_t cand) -> float {
+                float sm = 0.f;
+                if (REG) {
+#pragma unroll
+                    for (int q = 0; q < GP_MAXQ; ++q)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) sm += key[q][e] >= cand ? m[q][e] : 0.f;
+                } else {
+                    for (int v = tid; v < V; v += 256) {
+                        const float yv = val(v);
+                        sm += order_key(yv) >= cand ? expf(yv - best) : 0.f;
+                    }
+                }
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) sm += __shfl_xor(sm, o);
+                if (lane == 0) s_mass[pass & 1][wave] = sm;
+                __syncthreads();
+                const float* sp = s_mass[pass & 1];
+                ++pass;
+                return (sp[0] + sp[1]) + (sp[2] + sp[3]);
+            };
+            const float need = trunc.top_p * mass_ge(lo);
+            uint32_t hi = 0;             // the largest hi with mass_ge(hi) >= need; hi >= lo as mass_ge(lo) >= need
+            for (int bit = 31; bit >= 0; --bit) {
+                const uint32_t cand = hi | (1u << bit);
+                if (mass_ge(cand) >= need) hi = cand;
+            }
+            thr = hi;
+        }
+        const uint32_t kbest = order_key(best);
+        if (thr > kbest) thr = kbest;    // the arg-max is always kept
+        if (REG) {
+#pragma unroll
+            for (int q = 0; q < GP_MAXQ; ++q)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) if (key[q][e] < thr) x[q][e] = -INFINITY;
+        }
+    }
     // per-thread probability mass (unnormalised), then inclusive scan over the threads
     float mass = 0.f;
     if (REG) {
@@ -401,7 +512,7 @@ __global__ void __launch_bounds__(256) sample_pick_k(Slabs logits, const float* 
 #pragma unroll
             for (int e = 0; e < 4; ++e) mass += expf(x[q][e] - best);                  // exp(-inf) == 0
     } else {
-        for (int v = tid; v < V; v += 256) mass += expf(logit_at(logits, bias, b, v) - best);
+        for (int v = tid; v < V; v += 256) mass += expf(val(v) - best);
     }
     float incl = mass;
 #pragma unroll
@@ -446,7 +557,7 @@ __global__ void __launch_bounds__(256) sample_pick_k(Slabs logits, const float* 
             int last = -1;
             float last_x = 0.f;
             for (int v = tid; v < V; v += 256) {
-                const float xv = logit_at(logits, bias, b, v);
+                const float xv = val(v);
                 const float pe = expf(xv - best);
                 if (pe > 0.f) { last = v; last_x = xv; }
                 c += pe;
@@ -463,7 +574,7 @@ __global__ void __launch_bounds__(256) sample_pick_k(Slabs logits, const float* 
         float px = s_pick_x;
         if (pick < 0) {                          // cannot happen for finite logits; keep the row well defined
             pick = 0;
-            px = REG ? best : logit_at(logits, bias, b, 0);
+            px = REG ? best : val(0);
         }
         const float lse = best + logf(total);
         const float logp = (px - best) - logf(total);
@@ -509,20 +620,31 @@ __global__ void __launch_bounds__(256) sample_pick_k(Slabs logits, const float* 
 int sample_pick(Slabs logits, const float* bias, int V, int t, int max_len, long long end_idx, long long* seq,
                 float* seq_logp, long long* it, int* unfinished, int* alive, const float* table, float* emb_out, int D,
                 int B, unsigned long long seed, unsigned long long offset, long long* raw_ids, float* lse,
-                float* step_logp, hipStream_t s, const LstmTail* tail) {
+                float* step_logp, hipStream_t s, const LstmTail* tail, const SetSampleOpts* opts) {
     if (B <= 0) return SET_OK;
     if (D & 3) return SET_ERR_UNSUPPORTED;
     if (tail && !tail_ok(*tail)) return SET_ERR_ARG;
+    if (sample_opts_check(opts) != SET_OK) return SET_ERR_ARG;
     const LstmTail tl = tail ? *tail : LstmTail();
-    ProfScope ps("sample_pick", s, 0.0,
+    SampleTrunc tc;
+    if (opts) {
+        tc.inv_t = 1.0f / opts->temperature;
+        tc.top_k = opts->top_k >= V ? 0 : opts->top_k;
+        tc.top_p = opts->top_p;
+    }
+    // nothing to scale and nothing to cut: the untruncated instantiation, as before there were options
+    const bool trunc = tc.inv_t != 1.f || tc.top_k > 0 || tc.top_p < 1.f;
+    ProfScope ps(trunc ? "sample_pick_trunc" : "sample_pick", s, 0.0,
                  4.0 * B * (1.0 * V * logits.n + 2.0 * D + (tail ? tl.D * (4.0 * (tl.g0.n + 2) + 3.0) : 0.0)));
     const bool reg = V <= 4 * 256 * GP_MAXQ && !(logits.ld & 3) && !(logits.stride & 3) && aligned16(logits.p);
     SampleOut so{raw_ids, lse, step_logp};
-#define SET_PICK_LAUNCH(REG, TAIL)                                                                                    \
-    hipLaunchKernelGGL((sample_pick_k<REG, TAIL>), dim3(B), dim3(256), 0, s, logits, bias, V, t, max_len, end_idx, seq, \
-                       seq_logp, it, unfinished, alive, table, emb_out, D, seed, offset, so, tl)
-    if (reg) { if (tail) SET_PICK_LAUNCH(true, true); else SET_PICK_LAUNCH(true, false); }
-    else { if (tail) SET_PICK_LAUNCH(false, true); else SET_PICK_LAUNCH(false, false); }
+#define SET_PICK_LAUNCH(REG, TAIL, TRUNC)                                                                                    \
+    hipLaunchKernelGGL((sample_pick_k<REG, TAIL, TRUNC>), dim3(B), dim3(256), 0, s, logits, bias, V, t, max_len, end_idx, seq, \
+                       seq_logp, it, unfinished, alive, table, emb_out, D, seed, offset, so, tl, tc)
+#define SET_PICK_LAUNCH2(REG, TAIL) do { if (trunc) SET_PICK_LAUNCH(REG, TAIL, true); else SET_PICK_LAUNCH(REG, TAIL, false); } while (0)
+    if (reg) { if (tail) SET_PICK_LAUNCH2(true, true); else SET_PICK_LAUNCH2(true, false); }
+    else { if (tail) SET_PICK_LAUNCH2(false, true); else SET_PICK_LAUNCH2(false, false); }
+#undef SET_PICK_LAUNCH2
 #undef SET_PICK_LAUNCH
     SET_LAUNCH_CHECK();
     return SET_OK;

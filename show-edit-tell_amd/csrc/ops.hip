@@ -531,16 +531,24 @@ int set_caption_encoder_f32(const SetEditNetWeights* w, const int64_t* seq, cons
 }
 
 // ---- multinomial sampling epilogue as an operator (editnet_rl.py:521-543 / dcnet_rl.py:320-340)
-int set_sample_pick_f32(const float* logits, int64_t ld_logits, int B, int V, int t, int max_len, int64_t end_idx,
-                        uint64_t seed, uint64_t offset, int64_t* seq, int64_t* it, int32_t* unfinished, int32_t* alive,
-                        int64_t* raw_ids, float* lse, float* step_logp, void* stream) {
+int set_sample_pick_opts_f32(const float* logits, int64_t ld_logits, int B, int V, int t, int max_len, int64_t end_idx,
+                             uint64_t seed, uint64_t offset, int64_t* seq, int64_t* it, int32_t* unfinished, int32_t* alive,
+                             int64_t* raw_ids, float* lse, float* step_logp, void* stream, const SetSampleOpts* opts) {
     if (!logits || !seq || !it || !unfinished || !alive || B <= 0 || V <= 0 || t < 0 || max_len <= 0 || ld_logits < V)
         return SET_ERR_ARG;
+    SET_TRY(sample_opts_check(opts));
     hipStream_t st = (hipStream_t)stream;
     if (t == 0) SET_TRY(set_tokens((long long*)it, 0, unfinished, alive, max_len + 2, B, st));
     Slabs lg{logits, 0, ld_logits, 1};
     return sample_pick(lg, nullptr, V, t, max_len, end_idx, (long long*)seq, nullptr, (long long*)it, unfinished, alive,
-                       nullptr, nullptr, 4, B, seed, offset, (long long*)raw_ids, lse, step_logp, st);
+                       nullptr, nullptr, 4, B, seed, offset, (long long*)raw_ids, lse, step_logp, st, nullptr, opts);
+}
+
+int set_sample_pick_f32(const float* logits, int64_t ld_logits, int B, int V, int t, int max_len, int64_t end_idx,
+                        uint64_t seed, uint64_t offset, int64_t* seq, int64_t* it, int32_t* unfinished, int32_t* alive,
+                        int64_t* raw_ids, float* lse, float* step_logp, void* stream) {
+    return set_sample_pick_opts_f32(logits, ld_logits, B, V, t, max_len, end_idx, seed, offset, seq, it, unfinished, alive,
+                                    raw_ids, lse, step_logp, stream, nullptr);
 }
 
 int set_sample_logp_bwd_f32(const float* logits, int64_t ld_logits, const float* lse, const int64_t* raw_ids,
@@ -556,11 +564,13 @@ int set_philox4x32(uint32_t* out, int n, uint64_t seed, uint64_t offset, void* s
 }
 
 // the pick kernels with every argument of the decode loops (tests/test_hip_pick_epilogues.py); no state is initialised here
-int set_pick_slabs_f32(const SetPickArgs* a, void* stream) {
+int set_pick_slabs_opts_f32(const SetPickArgs* a, const SetSampleOpts* opts, void* stream) {
     if (!a || !a->logits || !a->seq || !a->it || !a->unfinished || !a->alive) return SET_ERR_ARG;
     if (a->mode != SET_PICK_GREEDY && a->mode != SET_PICK_SAMPLE) return SET_ERR_ARG;
     if (a->mode == SET_PICK_GREEDY && !a->seq_logp) return SET_ERR_ARG;
     if (a->B <= 0 || a->V <= 0 || a->n <= 0 || a->t < 0 || a->max_len <= 0 || a->ld < a->V) return SET_ERR_ARG;
+    SET_TRY(sample_opts_check(opts));
+    if (a->mode == SET_PICK_GREEDY && !sample_opts_neutral(opts)) return SET_ERR_ARG;      // the arg-max has no options
     hipStream_t st = (hipStream_t)stream;
     Slabs lg{a->logits, a->stride, a->ld, a->n};
     LstmTail tl;
@@ -573,9 +583,11 @@ int set_pick_slabs_f32(const SetPickArgs* a, void* stream) {
     if (a->mode == SET_PICK_SAMPLE)
         return sample_pick(lg, a->bias, a->V, a->t, a->max_len, a->end_idx, (long long*)a->seq, a->seq_logp, (long long*)a->it,
                            a->unfinished, a->alive, a->table, a->emb_out, a->D, a->B, a->seed, a->offset, (long long*)a->raw_ids,
-                           a->lse, a->step_logp, st, a->tail ? &tl : nullptr);
+                           a->lse, a->step_logp, st, a->tail ? &tl : nullptr, opts);
     return greedy_pick(lg, a->bias, a->V, a->t, a->max_len, a->end_idx, (long long*)a->seq, a->seq_logp, (long long*)a->it,
                        a->unfinished, a->alive, a->table, a->emb_out, a->D, a->B, st, a->tail ? &tl : nullptr);
 }
+
+int set_pick_slabs_f32(const SetPickArgs* a, void* stream) { return set_pick_slabs_opts_f32(a, nullptr, stream); }
 
 }  // extern "C"

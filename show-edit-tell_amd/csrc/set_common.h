@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <cmath>
 #include "../../include/set_hip.h"
 
 // experiment (EXPERIMENTS 5.7): -DSET_EXP_VGPR_CAP=w asks for w waves per SIMD (w = 4: at most 128 registers) of the short decode kernels (co-residency with the
@@ -427,10 +428,23 @@ struct LstmTail {
 int greedy_pick(Slabs logits, const float* bias, int V, int t, int max_len, long long end_idx,
                 long long* seq, float* seq_logp, long long* it, int* unfinished, int* alive,
                 const float* table, float* emb_out, int D, int B, hipStream_t s, const LstmTail* tail = nullptr);
+// opts (include/set_hip.h SetSampleOpts; NULL: neutral): temperature, top-k and top-p of the draw.  Neutral options launch the
+// untruncated kernel.
 int sample_pick(Slabs logits, const float* bias, int V, int t, int max_len, long long end_idx, long long* seq,
                 float* seq_logp, long long* it, int* unfinished, int* alive, const float* table, float* emb_out, int D,
                 int B, unsigned long long seed, unsigned long long offset, long long* raw_ids, float* lse,
-                float* step_logp, hipStream_t s, const LstmTail* tail = nullptr);
+                float* step_logp, hipStream_t s, const LstmTail* tail = nullptr, const SetSampleOpts* opts = nullptr);
+// what the *_opts entry points refuse with SET_ERR_ARG before they touch anything
+inline int sample_opts_check(const SetSampleOpts* o) {
+    if (!o) return SET_OK;
+    if (!std::isfinite(o->temperature) || o->temperature < 1e-3f || o->temperature > 1e3f) return SET_ERR_ARG;
+    if (o->top_k < 0) return SET_ERR_ARG;
+    if (!std::isfinite(o->top_p) || !(o->top_p > 0.f) || o->top_p > 1.f) return SET_ERR_ARG;
+    return SET_OK;
+}
+inline bool sample_opts_neutral(const SetSampleOpts* o) {
+    return !o || (o->temperature == 1.f && o->top_k == 0 && o->top_p == 1.f);
+}
 int sample_logp_bwd(const float* logits, long long ld, const float* lse, const long long* ids, const float* g,
                     float* dlogits, long long ldd, int B, int V, hipStream_t s);
 // edit_trace.hip: the record of ONE forced timestep (set_editnet_edit_trace), taken from what the step left in the workspace.

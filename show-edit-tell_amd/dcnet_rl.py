@@ -18,9 +18,15 @@ class DAE(_DAE_XE):
 
     max_len = 18
 
-    def forward(self, word_map, encoded_previous_captions, previous_cap_length, sample_max=True, sample_rl=False):
+    def forward(self, word_map, encoded_previous_captions, previous_cap_length, sample_max=True, sample_rl=False,
+                temperature=1.0, top_k=0, top_p=1.0):
+        """temperature / top_k / top_p: see editnet_rl.DecoderC.forward (no-grad sampled rollout only)"""
         _require_cuda(encoded_previous_captions, "previous captions")
-        if (self.training or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()))):
+        opts = _lib.sample_opts(temperature, top_k, top_p)
+        grad_path = self.training or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()))
+        if opts is not None:
+            _lib.refuse_sample_opts(sample_max, sample_rl, grad_path)
+        if grad_path:
             return self._rollout_autograd(word_map, encoded_previous_captions, previous_cap_length, sample_max, sample_rl)
         lib = _lib.load()
         dev = encoded_previous_captions.device
@@ -43,6 +49,12 @@ class DAE(_DAE_XE):
             if sample_rl:        # multinomial sampling, eval mode, no gradients: fused device loop, Philox epilogue
                 from . import rng
                 seed = rng.next_seed()
+                if opts is not None:
+                    check(lib.set_dcnet_sample_opts(C.byref(w), C.byref(dims), ptr(prev), ptr(plen), int(word_map['<start>']),
+                                                    int(word_map['<end>']), max_len, seed, rng.offset(rng.SITE_ROLLOUT),
+                                                    ptr(seq), ptr(seq_logp), ptr(ws), ws.numel(), stream_of(dev),
+                                                    C.byref(opts)), "set_dcnet_sample_opts")
+                    return seq, seq_logp
                 check(lib.set_dcnet_sample(C.byref(w), C.byref(dims), ptr(prev), ptr(plen), int(word_map['<start>']),
                                            int(word_map['<end>']), max_len, seed, rng.offset(rng.SITE_ROLLOUT), ptr(seq),
                                            ptr(seq_logp), ptr(ws),

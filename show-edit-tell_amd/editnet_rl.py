@@ -30,11 +30,17 @@ class DecoderC(_DecoderXE):
     row_limits = None
 
     def forward(self, word_map, encoded_previous_captions, previous_cap_length, image_features, sample_max=True,
-                sample_rl=False, image_mean=None, repeat_images=1):
+                sample_rl=False, image_mean=None, repeat_images=1, temperature=1.0, top_k=0, top_p=1.0):
         """repeat_images = n (an extension for BASELINE.json configs[4], n sampled rollouts per image): `image_features`
-        holds B images while the captions hold n * B rows, sample-major (row s * B + b belongs to image b)."""
+        holds B images while the captions hold n * B rows, sample-major (row s * B + b belongs to image b).
+        temperature / top_k / top_p (include/set_hip.h SetSampleOpts; 1 / 0 / 1 are neutral): the distribution the no-grad
+        sampled rollout (sample_rl=True, sample_max=False) draws every word from; seqLogprobs are taken under it."""
         _require_cuda(image_features, "image features")
-        if (self.training or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()))):
+        opts = _lib.sample_opts(temperature, top_k, top_p)
+        grad_path = self.training or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()))
+        if opts is not None:
+            _lib.refuse_sample_opts(sample_max, sample_rl, grad_path)
+        if grad_path:
             return self._rollout_autograd(word_map, encoded_previous_captions, previous_cap_length, image_features,
                                           sample_max, sample_rl, image_mean, repeat_images)
         if repeat_images > 1:
@@ -52,13 +58,13 @@ class DecoderC(_DecoderXE):
         lib.set_decode_row_limits(_lib.ptr(limits) if limits is not None else None)
         try:
             return self._decode_nograd(lib, word_map, encoded_previous_captions, previous_cap_length, image_features,
-                                       sample_rl, image_mean)
+                                       sample_rl, image_mean, opts)
         finally:
             if limits is not None:
                 lib.set_decode_row_limits(None)
 
     def _decode_nograd(self, lib, word_map, encoded_previous_captions, previous_cap_length, image_features, sample_rl,
-                       image_mean):
+                       image_mean, opts=None):
         dev = image_features.device
         X = _f32c(image_features)
         prev = _i64c(encoded_previous_captions)
@@ -99,6 +105,12 @@ class DecoderC(_DecoderXE):
         if sample_rl:        # multinomial sampling, eval mode, no gradients: fused device loop with the Philox epilogue
             from . import rng
             seed = rng.next_seed()                                      # torch.manual_seed() makes it reproducible
+            if opts is not None:
+                check(lib.set_editnet_sample_opts(C.byref(w), C.byref(dims), ptr(X), ptr(mean), ptr(prev), ptr(plen),
+                                                  int(word_map['<start>']), int(word_map['<end>']), max_len, seed,
+                                                  rng.offset(rng.SITE_ROLLOUT), ptr(seq), ptr(seq_logp), ptr(ws), ws.numel(),
+                                                  stream_of(dev), C.byref(opts)), "set_editnet_sample_opts")
+                return seq, seq_logp
             check(lib.set_editnet_sample(C.byref(w), C.byref(dims), ptr(X), ptr(mean), ptr(prev), ptr(plen),
                                          int(word_map['<start>']), int(word_map['<end>']), max_len, seed,
                                          rng.offset(rng.SITE_ROLLOUT), ptr(seq),

@@ -587,6 +587,35 @@ class EditTrace:
         return out
 
 
+@torch.no_grad()
+def sample_captions(model, *inputs_and_word_map, n_samples=5, temperature=1.0, top_k=0, top_p=1.0):
+    """n_samples sampled captions per image from ONE fused rollout:
+        seq, seq_logp = sample_captions(decoder, image_features, previous_caption, prev_caplen, word_map, n_samples=5, top_p=0.9)
+        seq, seq_logp = sample_captions(dae, previous_caption, prev_caplen, word_map, temperature=0.8, top_k=50)
+    EditNet (editnet_rl.DecoderC) takes image_features (NI,R,F), previous_caption (NI,T), prev_caplen (NI,1); DCNet
+    (dcnet_rl.DAE) the caption pair only.  Every image's rows are repeated n_samples times (row i * n_samples + j is sample j of
+    image i): the rows differ in their index, hence in their Philox counters, hence in their draws.  Returns seq (NI, n_samples,
+    max_len) int64 and seq_logp (NI, n_samples, max_len), the log-probs under the tempered / truncated distribution sampled
+    from.  The seed comes from rng.next_seed() as in the models' own sampled path: torch.manual_seed() reproduces a call."""
+    *inputs, word_map = inputs_and_word_map
+    if len(inputs) not in (2, 3):
+        raise ValueError("sample_captions(model, [image_features,] previous_caption, prev_caplen, word_map, ...)")
+    n = int(n_samples)
+    if n < 1:
+        raise ValueError("n_samples must be >= 1, got %r" % (n_samples,))
+    model.eval()
+    prev = inputs[-2].long().repeat_interleave(n, 0).contiguous()
+    plen = inputs[-1].reshape(-1).long().repeat_interleave(n, 0).contiguous()
+    kw = dict(sample_max=False, sample_rl=True, temperature=temperature, top_k=top_k, top_p=top_p)
+    if len(inputs) == 3:
+        X = inputs[0].float().repeat_interleave(n, 0).contiguous()
+        seq, logp = model(word_map, prev, plen, X, **kw)
+    else:
+        seq, logp = model(word_map, prev, plen, **kw)
+    NI = seq.shape[0] // n
+    return seq.view(NI, n, -1), logp.view(NI, n, -1)
+
+
 def tokens_from_greedy(seq, word_map):
     """(B, max_len) greedy / sampled output -> forced token lists: `<start>` in front and, for rows that ended before
     max_len, `<end>` behind (the decode loops store `<end>` as 0, editnet_rl.py:531)."""
