@@ -13,6 +13,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import DcnetDims, DcnetWeights, DCNET_WEIGHT_FIELDS, EditNetWeights, check, ptr, stream_of
+from .native_model import NativeModel
 from .editnet import _HipLinear, _HipLSTMCell, _f32c, _i64c, _require_cuda, _wants_grad
 
 
@@ -109,7 +110,7 @@ class CaptionAttention(nn.Module):
         return ctx
 
 
-class DAE(nn.Module):
+class DAE(NativeModel):
     """reference dcnet.py:273-350 — XE (teacher-forced) forward."""
 
     def __init__(self, word_map, emb_file, decoder_dim=1024, attention_dim=512, caption_features_dim=512, emb_dim=1024):
@@ -128,127 +129,36 @@ class DAE(nn.Module):
         self.decoder_dim = decoder_dim
         self.dropout = nn.Dropout(0.5)
         self._dims_cfg = (decoder_dim, attention_dim, caption_features_dim, emb_dim)
-        self._ws = None
-        self._ws_key = None
-
-    # the reference checkpoints pickle the whole module (dcnet.py:131-138): GPU workspaces and the derived token table
-    # must not travel
-    def __getstate__(self):
-        state = dict(self.__dict__)
-        state["_ws"] = state["_ws_key"] = None
-        for k in ("_tok_state", "_ws_cache", "_fwd_seed", "_grad_buckets"):
-            state.pop(k, None)
-        return state
-
-    def invalidate_token_table(self):
-        """Drop the derived inference-time token table (see _token_table); same contract as editnet.DecoderC's."""
-        self.__dict__.pop("_tok_state", None)
-
-    def train(self, mode=True):
-        if bool(mode) != self.training:
-            self.invalidate_token_table()
-        return super().train(mode)
-
-    def load_state_dict(self, *args, **kwargs):
-        self.invalidate_token_table()
-        return super().load_state_dict(*args, **kwargs)
 
     def __setstate__(self, state):
         import weakref
         super().__setstate__(state)
         self.caption_encoder._owner = weakref.ref(self)
 
-    def _apply(self, fn, *args, **kwargs):
-        self._ws = self._ws_key = None
-        self.__dict__.pop("_ws_cache", None)
-        self.__dict__.pop("_grad_buckets", None)
-        self.invalidate_token_table()
-        return super()._apply(fn, *args, **kwargs)
+    # ---- what NativeModel needs to know about this model ------------------------------------
+    _ABI = "dcnet"
+    _DIMS_CLS, _WEIGHTS_CLS, _WEIGHT_FIELDS = DcnetDims, DcnetWeights, DCNET_WEIGHT_FIELDS
+    _DISPLAY, _HANDLE = "DCNet", "dae"
 
-    def init_hidden_state(self, batch_size):
-        dev = self.fc.weight.device
-        return (torch.zeros(batch_size, self.decoder_dim, device=dev),
-                torch.zeros(batch_size, self.decoder_dim, device=dev))
-
-    # ---- runtime plumbing
-    def _weights(self, dims=None):
-        """Pack the parameter pointers; with `dims` (no-grad decode paths) also attach the token table when valid."""
-        w = _lib.pack_weights(DcnetWeights, DCNET_WEIGHT_FIELDS, dict(self.named_parameters()), self.fc.weight.device)
-        if dims is not None:
-            tab = self._token_table(dims)
-            if tab is not None:
-                w.tok_table = tab.data_ptr()
-        return w
-
-    # The contractions whose only input is a token (attention_lstm.W_ih[:, :E] relu(E[v]) and the BiLSTM encoder's two
-    # input projections) are folded into a (V, 4D + 8C) table (include/set_hip.h: SetDcnetWeights.tok_table).  Same
-    # life cycle as editnet.DecoderC._token_table: built once the same source weights have been seen on two consecutive
-    # no-grad calls, dropped when any of them changes (tensor._version / data_ptr), on train()/eval() switches,
-    # load_state_dict() and device moves; SET_TOKEN_TABLE=0 disables, =1 forces, SET_TOKEN_TABLE_VERIFY=1 re-checks.
-    def _token_table(self, dims):
-        import os
-        mode = os.environ.get("SET_TOKEN_TABLE", "auto")
-        if mode == "0" or dims.D % 64 or dims.C % 128:
-            return None
+    def _token_table_sources(self):
+        """attention_lstm.W_ih[:, :E] relu(E[v]) and the BiLSTM encoder's two input projections (set_hip.h)"""
         enc = self.caption_encoder.lstm_encoder
-        src = (self.embed.embedding.weight, self.attention_lstm.weight_ih, enc.weight_ih_l0, enc.bias_ih_l0,
-               enc.weight_ih_l0_reverse, enc.bias_ih_l0_reverse)
-        from . import optim as _optim
-        sig = tuple((t.data_ptr(), t._version) for t in src) + (_optim.weights_epoch(),)
-        st = self.__dict__.setdefault("_tok_state", {"sig": None, "seen": 0, "table": None})
-        if st["sig"] != sig:
-            st.update(sig=sig, seen=1, table=None)
-        else:
-            st["seen"] += 1
-        if st["table"] is None and (mode == "1" or st["seen"] >= 2):
-            lib = _lib.load()
-            dev = self.fc.weight.device
-            table = torch.empty(lib.set_dcnet_token_table_bytes(C.byref(dims)) // 4, dtype=torch.float32, device=dev)
-            ws = torch.empty(lib.set_dcnet_token_table_workspace_bytes(C.byref(dims)), dtype=torch.uint8, device=dev)
-            w = _lib.pack_weights(DcnetWeights, DCNET_WEIGHT_FIELDS, dict(self.named_parameters()), dev)
-            check(lib.set_dcnet_build_token_table(C.byref(w), C.byref(dims), ptr(table), ptr(ws), ws.numel(), stream_of(dev)),
-                  "set_dcnet_build_token_table")
-            torch.cuda.current_stream(dev).synchronize()
-            st["table"] = table
-            st["check"] = torch.stack([t.detach().double().sum() for t in src]).cpu()
-        if st["table"] is not None and os.environ.get("SET_TOKEN_TABLE_VERIFY") == "1":
-            now = torch.stack([t.detach().double().sum() for t in src]).cpu()
-            if not torch.equal(now, st["check"]):
-                raise _lib.SetError("token table is stale: a source weight changed without bumping tensor._version "
-                                    "(in-place .data write?); call dae.invalidate_token_table()")
-        return st["table"]
+        return (self.embed.embedding.weight, self.attention_lstm.weight_ih, enc.weight_ih_l0, enc.bias_ih_l0,
+                enc.weight_ih_l0_reverse, enc.bias_ih_l0_reverse)
+
+    def _token_table_supported(self, dims):
+        return dims.D % 64 == 0 and dims.C % 128 == 0
 
     def _dims(self, B, T, maxT):
         D, A, Cc, E = self._dims_cfg
         return DcnetDims(B=B, T=T, D=D, A=A, C=Cc, E=E, V=self.vocab_size, maxT=maxT)
 
-    def _workspace(self, dims):
-        """One workspace per (dims, device, stream), as DecoderC._workspace: concurrent decodes on different streams (the
-        self-critical step runs the greedy baseline on a side stream underneath the sampled rollout) must not share
-        recurrent state or split-K slabs."""
-        lib = _lib.load()
-        dev = self.fc.weight.device
-        key = tuple(getattr(dims, f) for f, _ in DcnetDims._fields_) + (str(dev), torch.cuda.current_stream(dev).cuda_stream)
-        cache = self.__dict__.setdefault("_ws_cache", {})
-        ws = cache.get(key)
-        if ws is None:
-            n = lib.set_dcnet_workspace_bytes(C.byref(dims))
-            if n == 0:
-                raise _lib.SetError("unsupported DCNet dims %r" % (key,))
-            if len(cache) >= 24:
-                cache.clear()
-            ws = cache[key] = torch.empty(n, dtype=torch.uint8, device=dev)
-        self._ws, self._ws_key = ws, key
-        return ws
-
-    def ws_tensor(self, dims, name, shape, dtype=torch.float32):
-        lib = _lib.load()
-        p = lib.set_dcnet_ws_tensor(C.byref(dims), ptr(self._ws), name.encode())
-        if not p:
-            raise KeyError(name)
-        off = p - self._ws.data_ptr()
-        n = int(torch.tensor(shape).prod().item()) * torch.empty((), dtype=dtype).element_size()
-        return self._ws[off:off + n].view(dtype).view(*shape)
+    def _beam_layout(self, begin_args, max_steps):
+        """as editnet.DecoderC._beam_layout, for begin_args = (prev (NI,T), plen (NI)) and set_dcnet_begin"""
+        NI, T = begin_args[0].shape
+        D, A, Cc, _ = self._dims_cfg
+        return (lambda k: self._dims(NI * k, T, max_steps + 1)), (
+            ("enc", (T, 2 * Cc)), ("final_hidden", (2 * Cc,)), ("mask", (T,)), ("att1_c", (T, A)), ("pre1", (4 * D,)))
 
     def _encode(self, src, src_len):
         """caption_encoder(src, src_len) -> (outputs (B,Tmax,2C), final_hidden (B,2C), mask (B,Tmax))"""
@@ -271,7 +181,7 @@ class DAE(nn.Module):
     def forward(self, encoded_captions, caption_lengths, encoded_previous_captions, previous_cap_length):
         """reference dcnet.py:303-350; returns (predictions, encoded_captions sorted, decode_lengths, sort_ind)."""
         _require_cuda(encoded_captions, "captions")
-        if self.training or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())):
+        if self._grad_path():
             return self._forward_autograd(encoded_captions, caption_lengths, encoded_previous_captions,
                                           previous_cap_length)
         lib = _lib.load()

@@ -23,7 +23,7 @@ class DAE(_DAE_XE):
         """temperature / top_k / top_p: see editnet_rl.DecoderC.forward (no-grad sampled rollout only)"""
         _require_cuda(encoded_previous_captions, "previous captions")
         opts = _lib.sample_opts(temperature, top_k, top_p)
-        grad_path = self.training or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()))
+        grad_path = self._grad_path()
         if opts is not None:
             _lib.refuse_sample_opts(sample_max, sample_rl, grad_path)
         if grad_path:
@@ -36,37 +36,21 @@ class DAE(_DAE_XE):
         dims = self._dims(B, prev.shape[1], max_len + 1)
         ws = self._workspace(dims)
         w = self._weights(dims)
-        limits = getattr(self, "row_limits", None)             # see editnet_rl.DecoderC.row_limits
-        if limits is not None:
-            if limits.dtype != torch.int32 or not limits.is_cuda or limits.numel() != B:
-                raise _lib.SetError("row_limits must be an int32 device tensor with one entry per row")
-            limits = limits.contiguous()
-        seq = torch.empty(B, max_len, dtype=torch.long, device=dev)
-        seq_logp = torch.empty(B, max_len, dtype=torch.float32, device=dev)
-        # (thread-local library state, set for the duration of this enqueue only — see editnet_rl.DecoderC.forward)
-        lib.set_decode_row_limits(ptr(limits) if limits is not None else None)
-        try:
+        with self._row_limits_scope(lib, B):
+            seq = torch.empty(B, max_len, dtype=torch.long, device=dev)
+            seq_logp = torch.empty(B, max_len, dtype=torch.float32, device=dev)
             if sample_rl:        # multinomial sampling, eval mode, no gradients: fused device loop, Philox epilogue
                 from . import rng
-                seed = rng.next_seed()
-                if opts is not None:
-                    check(lib.set_dcnet_sample_opts(C.byref(w), C.byref(dims), ptr(prev), ptr(plen), int(word_map['<start>']),
-                                                    int(word_map['<end>']), max_len, seed, rng.offset(rng.SITE_ROLLOUT),
-                                                    ptr(seq), ptr(seq_logp), ptr(ws), ws.numel(), stream_of(dev),
-                                                    C.byref(opts)), "set_dcnet_sample_opts")
-                    return seq, seq_logp
-                check(lib.set_dcnet_sample(C.byref(w), C.byref(dims), ptr(prev), ptr(plen), int(word_map['<start>']),
-                                           int(word_map['<end>']), max_len, seed, rng.offset(rng.SITE_ROLLOUT), ptr(seq),
-                                           ptr(seq_logp), ptr(ws),
-                                           ws.numel(), stream_of(dev)), "set_dcnet_sample")
+                # (a NULL SetSampleOpts* is the call without options, bit for bit: include/set_hip.h)
+                check(lib.set_dcnet_sample_opts(C.byref(w), C.byref(dims), ptr(prev), ptr(plen), int(word_map['<start>']),
+                                                int(word_map['<end>']), max_len, rng.next_seed(), rng.offset(rng.SITE_ROLLOUT),
+                                                ptr(seq), ptr(seq_logp), ptr(ws), ws.numel(), stream_of(dev),
+                                                C.byref(opts) if opts is not None else None), "set_dcnet_sample_opts")
                 return seq, seq_logp
             check(lib.set_dcnet_greedy(C.byref(w), C.byref(dims), ptr(prev), ptr(plen), int(word_map['<start>']),
                                        int(word_map['<end>']), max_len, ptr(seq), ptr(seq_logp), ptr(ws), ws.numel(),
                                        stream_of(dev)), "set_dcnet_greedy")
             return seq, seq_logp
-        finally:
-            if limits is not None:
-                lib.set_decode_row_limits(None)
 
 
 def _dae_rollout(self, word_map, encoded_previous_captions, previous_cap_length, sample_max, sample_rl):

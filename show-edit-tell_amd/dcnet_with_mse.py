@@ -28,7 +28,7 @@ class DAE(_dcnet.DAE):
     def forward(self, encoded_captions, caption_lengths, encoded_previous_captions, previous_cap_length):
         """returns (predictions, encoded_captions sorted, decode_lengths, sort_ind, gd_final_hidden, decoder_last_hidden)"""
         _require_cuda(encoded_captions, "captions")
-        if self.training or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())):
+        if self._grad_path():
             return self._forward_autograd(encoded_captions, caption_lengths, encoded_previous_captions,
                                           previous_cap_length, hidden=True)
         caption_lengths, sort_ind = caption_lengths.squeeze(1).sort(dim=0, descending=True, stable=True)

@@ -26,6 +26,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import EditNetDims, EditNetWeights, EDITNET_WEIGHT_FIELDS, check, ptr, stream_of
+from .native_model import NativeModel
 
 
 import os as _os
@@ -411,7 +412,7 @@ class _HipLinear(nn.Linear):
         return y.reshape(*lead, N)
 
 
-class DecoderC(nn.Module):
+class DecoderC(NativeModel):
     """reference editnet.py:449-548 — XE (teacher-forced) forward."""
 
     _visual_attention_cls = VisualAttentionC
@@ -436,142 +437,36 @@ class DecoderC(nn.Module):
             raise ValueError("the reference's cat shapes force decoder_dim == caption_features_dim == emb_dim")
         self._attention_dim = attention_dim
         self._image_features_dim = image_features_dim
-        self._ws = None
-        self._ws_key = None
 
-    # ---- runtime state is NOT part of the module's persistent state --------------------------------------
-    # The reference checkpoints pickle the whole module (editnet.py:168-175, `'decoder': decoder`) and callers may
-    # copy.deepcopy a decoder: GPU workspaces, the derived token table and the last autograd graph must not travel.
-    _RUNTIME_ATTRS = ("_ws", "_ws_key", "_ws_cache", "_tok_state", "_last_hidden", "_fwd_seed", "_fed_tokens", "_grad_buckets",
-                      "_ahead", "_ahead_free", "_ahead_hits", "_ahead_busy")
+    # ---- what NativeModel needs to know about this model ------------------------------------
+    _ABI = "editnet"
+    _DIMS_CLS, _WEIGHTS_CLS, _WEIGHT_FIELDS = EditNetDims, EditNetWeights, EDITNET_WEIGHT_FIELDS
+    _DISPLAY, _HANDLE = "EditNet", "decoder"
+    _DIMS_HINT = " (contraction dims must be multiples of 32)"
 
-    def __getstate__(self):
-        state = dict(self.__dict__)
-        for k in self._RUNTIME_ATTRS:
-            state.pop(k, None)
-        state["_ws"] = state["_ws_key"] = None
-        return state
-
-    def invalidate_token_table(self):
-        """Drop the derived inference-time token table (see _token_table).  It is rebuilt automatically after two
-        further no-grad calls.  Called on every train() <-> eval() switch, load_state_dict() and device / dtype move;
-        call it yourself after writing weights in a way autograd cannot see (`p.data.add_()`, `dist.broadcast(p.data)`,
-        raw-pointer updates): such writes do not bump `tensor._version`, which is all the cache can observe
-        without a device->host synchronisation (SET_TOKEN_TABLE_VERIFY=1 adds that check for debugging)."""
-        self.__dict__.pop("_tok_state", None)
-
-    def train(self, mode=True):
-        if bool(mode) != self.training:          # an actual train <-> eval switch (eval() on an eval module keeps the table)
-            self.invalidate_token_table()
-        return super().train(mode)
-
-    def load_state_dict(self, *args, **kwargs):
-        self.invalidate_token_table()
-        return super().load_state_dict(*args, **kwargs)
-
-    def _apply(self, fn, *args, **kwargs):
-        self.invalidate_token_table()
-        self.__dict__.pop("_ws_cache", None)
-        self.__dict__.pop("_ahead", None)
-        self.__dict__.pop("_ahead_free", None)
-        self.__dict__.pop("_grad_buckets", None)
-        self._ws = self._ws_key = None
-        return super()._apply(fn, *args, **kwargs)
-
-    # ---- reference API ---------------------------------------------------------------------
-    def init_hidden_state(self, batch_size):
-        dev = self.fc.weight.device          # the parameters' device (the reference uses a module global)
-        h = torch.zeros(batch_size, self.decoder_dim, device=dev)
-        c = torch.zeros(batch_size, self.decoder_dim, device=dev)
-        return h, c
-
-    # ---- runtime plumbing ------------------------------------------------------------------
-    def _weights(self, dims=None):
-        """Pack the parameter pointers; with `dims`, also attach the inference-time token table when it
-        is valid (see _token_table)."""
-        dev = self.fc.weight.device
-        params = dict(self.named_parameters())
-        w = _lib.pack_weights(EditNetWeights, EDITNET_WEIGHT_FIELDS, params, dev)
-        if dims is not None:
-            tab = self._token_table(dims)
-            if tab is not None:
-                w.tok_table = tab.data_ptr()
-        return w
-
-    # The three contractions of the step whose only input is the current token are folded into a
-    # (V,10D) table (include/set_hip.h: tok_table).  The table is derived from six parameter tensors
-    # and is rebuilt whenever any of them changes (tensor._version / data_ptr), on every train()/eval()
-    # switch, load_state_dict() and device move (invalidate_token_table); it is only built once the same
-    # weights have been seen on two consecutive no-grad calls, so SCST training (weights change every
-    # iteration, and the loop toggles eval()/train()) never pays for it.  In-place writes through `.data`
-    # are invisible to `_version`: call invalidate_token_table() after them.
-    # SET_TOKEN_TABLE=0 disables, =1 forces, SET_TOKEN_TABLE_VERIFY=1 re-checks a checksum of the six
-    # source tensors on every use (one device->host sync per call; debugging aid).
-    def _token_table(self, dims):
-        import os
-        mode = os.environ.get("SET_TOKEN_TABLE", "auto")
-        if mode == "0" or dims.D % 64:
-            return None
+    def _token_table_sources(self):
+        """the three contractions of the step whose only input is the current token, and the encoder's x2h (set_hip.h)"""
         cell = self.caption_encoder.lstm_encoder_cell
-        src = (self.embed.embedding.weight, self.attention_lstm.weight_ih, self.caption_attention.tc_affine.weight,
-               self.caption_attention.context_gate.weight, cell.x2h.weight, cell.x2h.bias)
-        from . import optim as _optim
-        sig = tuple((t.data_ptr(), t._version) for t in src) + (_optim.weights_epoch(),)
-        st = self.__dict__.setdefault("_tok_state", {"sig": None, "seen": 0, "table": None})
-        if st["sig"] != sig:
-            st.update(sig=sig, seen=1, table=None)
-        else:
-            st["seen"] += 1
-        if st["table"] is None and (mode == "1" or st["seen"] >= 2):
-            lib = _lib.load()
-            dev = self.fc.weight.device
-            table = torch.empty(lib.set_editnet_token_table_bytes(C.byref(dims)) // 4, dtype=torch.float32, device=dev)
-            ws = torch.empty(lib.set_editnet_token_table_workspace_bytes(C.byref(dims)), dtype=torch.uint8, device=dev)
-            w = _lib.pack_weights(EditNetWeights, EDITNET_WEIGHT_FIELDS, dict(self.named_parameters()), dev)
-            check(lib.set_editnet_build_token_table(C.byref(w), C.byref(dims), ptr(table), ptr(ws), ws.numel(),
-                                                    stream_of(dev)), "set_editnet_build_token_table")
-            torch.cuda.current_stream(dev).synchronize()        # other streams may use the table next
-            st["table"] = table
-            st["check"] = torch.stack([t.detach().double().sum() for t in src]).cpu()
-        if st["table"] is not None and os.environ.get("SET_TOKEN_TABLE_VERIFY") == "1":
-            now = torch.stack([t.detach().double().sum() for t in src]).cpu()
-            if not torch.equal(now, st["check"]):
-                raise _lib.SetError("token table is stale: a source weight changed without bumping tensor._version "
-                                    "(in-place .data write?); call decoder.invalidate_token_table()")
-        return st["table"]
+        return (self.embed.embedding.weight, self.attention_lstm.weight_ih, self.caption_attention.tc_affine.weight,
+                self.caption_attention.context_gate.weight, cell.x2h.weight, cell.x2h.bias)
+
+    def _token_table_supported(self, dims):
+        return dims.D % 64 == 0
 
     def _dims(self, B, T, R, maxT):
         return EditNetDims(B=B, T=T, R=R, F=self._image_features_dim, D=self.decoder_dim, A=self._attention_dim,
                            V=self.vocab_size, maxT=maxT, adaptive=self._adaptive)
 
-    def _workspace(self, dims):
-        """One workspace per (dims, device, stream): concurrent decodes on different streams must not share
-        recurrent state or split-K slabs."""
-        lib = _lib.load()
-        dev = self.fc.weight.device
-        key = tuple(getattr(dims, f) for f, _ in EditNetDims._fields_) + (str(dev), torch.cuda.current_stream(dev).cuda_stream)
-        cache = self.__dict__.setdefault("_ws_cache", {})
-        ws = cache.get(key)
-        if ws is None:
-            n = lib.set_editnet_workspace_bytes(C.byref(dims))
-            if n == 0:
-                raise _lib.SetError("unsupported EditNet dims %r (contraction dims must be multiples of 32)" % (key,))
-            if len(cache) >= 24:
-                cache.clear()
-            ws = torch.empty(n, dtype=torch.uint8, device=dev)
-            cache[key] = ws
-        self._ws, self._ws_key = ws, key
-        return ws
-
-    def ws_tensor(self, dims, name, shape, dtype=torch.float32):
-        """View of a named workspace tensor (debug / tests)."""
-        lib = _lib.load()
-        p = lib.set_editnet_ws_tensor(C.byref(dims), ptr(self._ws), name.encode())
-        if not p:
-            raise KeyError(name)
-        off = p - self._ws.data_ptr()
-        n = int(torch.tensor(shape).prod().item()) * torch.empty((), dtype=dtype).element_size()
-        return self._ws[off:off + n].view(dtype).view(*shape)
+    def _beam_layout(self, begin_args, max_steps):
+        """Beam search (evaluate._FusedModel): dims_of(k), the dims of a workspace with k rows per image of the prologue inputs
+        `begin_args` = (X (NI,R,F), image_mean (NI,F) or None, prev (NI,T), plen (NI)), and the (name, per-row shape) table of
+        the invariants set_editnet_begin leaves in it.  image_mean: the attention LSTM's image input (adaptive features: the mean
+        over the valid regions, editnet_adaptive.py:625-633); None = the mean over all R regions (editnet.py:503)."""
+        X, _, prev, _ = begin_args
+        (NI, R, _), T, D, A = X.shape, prev.shape[1], self.decoder_dim, self._attention_dim
+        return (lambda k: self._dims(NI * k, T, R, max_steps + 1)), (
+            ("H", (T, D)), ("M", (T, D)), ("mask", (T,)), ("att1", (R, A)), ("att1_c", (T, A)), ("pre1", (4 * D,)),
+            ("rmask", (R,)), ("cap_proj", (T, 2 * D)), ("mem_proj", (T, D)))
 
     def forward(self, image_features, encoded_captions, caption_lengths, encoded_previous_captions,
                 previous_cap_length, use_ss=False, ss_prob=0.0, image_mean=None):
@@ -580,8 +475,7 @@ class DecoderC(nn.Module):
         _require_cuda(image_features, "image features")
         # the fused C path is the eval-mode, no-grad, teacher-forced loop; everything else (train mode =
         # dropout, scheduled sampling, gradients) follows the reference loop over the HIP operators
-        if (self.training or (use_ss and ss_prob > 0.0)
-                or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()))):
+        if (use_ss and ss_prob > 0.0) or self._grad_path():
             return self._forward_autograd(image_features, encoded_captions, caption_lengths,
                                           encoded_previous_captions, previous_cap_length, use_ss, ss_prob, image_mean)
         lib = _lib.load()

@@ -25,9 +25,6 @@ class DecoderC(_DecoderXE):
     """reference editnet_rl.py:455-549"""
 
     max_len = 18
-    # Optional per-row cap on the caption length of the no-grad greedy loop (include/set_hip.h set_decode_row_limits): an
-    # int32 device tensor of B entries, or None.  Row b is ended by the loop after at most row_limits[b] words.
-    row_limits = None
 
     def forward(self, word_map, encoded_previous_captions, previous_cap_length, image_features, sample_max=True,
                 sample_rl=False, image_mean=None, repeat_images=1, temperature=1.0, top_k=0, top_p=1.0):
@@ -37,7 +34,7 @@ class DecoderC(_DecoderXE):
         sampled rollout (sample_rl=True, sample_max=False) draws every word from; seqLogprobs are taken under it."""
         _require_cuda(image_features, "image features")
         opts = _lib.sample_opts(temperature, top_k, top_p)
-        grad_path = self.training or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()))
+        grad_path = self._grad_path()
         if opts is not None:
             _lib.refuse_sample_opts(sample_max, sample_rl, grad_path)
         if grad_path:
@@ -47,21 +44,10 @@ class DecoderC(_DecoderXE):
             image_features = image_features.repeat(repeat_images, 1, 1)
             image_mean = None if image_mean is None else image_mean.repeat(repeat_images, 1)
         lib = _lib.load()
-        limits = self.row_limits
-        if limits is not None:
-            if limits.dtype != torch.int32 or not limits.is_cuda or limits.numel() != image_features.shape[0]:
-                raise _lib.SetError("row_limits must be an int32 device tensor with one entry per row")
-            limits = limits.contiguous()
-        # the limit pointer is thread-local state of the library that every greedy pick of this host thread reads: it is set
-        # for the duration of THIS enqueue only (it used to stay set — a later caller with another B, or after the
-        # tensor was freed, would have read it)
-        lib.set_decode_row_limits(_lib.ptr(limits) if limits is not None else None)
-        try:
+        # the row limits hold around the whole enqueue, the paths that pick up work run ahead included
+        with self._row_limits_scope(lib, image_features.shape[0]):
             return self._decode_nograd(lib, word_map, encoded_previous_captions, previous_cap_length, image_features,
                                        sample_rl, image_mean, opts)
-        finally:
-            if limits is not None:
-                lib.set_decode_row_limits(None)
 
     def _decode_nograd(self, lib, word_map, encoded_previous_captions, previous_cap_length, image_features, sample_rl,
                        image_mean, opts=None):
@@ -105,16 +91,12 @@ class DecoderC(_DecoderXE):
         if sample_rl:        # multinomial sampling, eval mode, no gradients: fused device loop with the Philox epilogue
             from . import rng
             seed = rng.next_seed()                                      # torch.manual_seed() makes it reproducible
-            if opts is not None:
-                check(lib.set_editnet_sample_opts(C.byref(w), C.byref(dims), ptr(X), ptr(mean), ptr(prev), ptr(plen),
-                                                  int(word_map['<start>']), int(word_map['<end>']), max_len, seed,
-                                                  rng.offset(rng.SITE_ROLLOUT), ptr(seq), ptr(seq_logp), ptr(ws), ws.numel(),
-                                                  stream_of(dev), C.byref(opts)), "set_editnet_sample_opts")
-                return seq, seq_logp
-            check(lib.set_editnet_sample(C.byref(w), C.byref(dims), ptr(X), ptr(mean), ptr(prev), ptr(plen),
-                                         int(word_map['<start>']), int(word_map['<end>']), max_len, seed,
-                                         rng.offset(rng.SITE_ROLLOUT), ptr(seq),
-                                         ptr(seq_logp), ptr(ws), ws.numel(), stream_of(dev)), "set_editnet_sample")
+            # (a NULL SetSampleOpts* is the call without options, bit for bit: include/set_hip.h)
+            check(lib.set_editnet_sample_opts(C.byref(w), C.byref(dims), ptr(X), ptr(mean), ptr(prev), ptr(plen),
+                                              int(word_map['<start>']), int(word_map['<end>']), max_len, seed,
+                                              rng.offset(rng.SITE_ROLLOUT), ptr(seq), ptr(seq_logp), ptr(ws), ws.numel(),
+                                              stream_of(dev), C.byref(opts) if opts is not None else None),
+                  "set_editnet_sample_opts")
             return seq, seq_logp
         check(lib.set_editnet_greedy(C.byref(w), C.byref(dims), ptr(X), ptr(mean), ptr(prev), ptr(plen),
                                      int(word_map['<start>']), int(word_map['<end>']), max_len, ptr(seq),
@@ -128,7 +110,7 @@ class DecoderC(_DecoderXE):
         these very tensors finds the prologue done and runs only its timestep loop (bit-identical results).  Call it from a
         side stream while the previous batch decodes — `pipeline.DevicePrefetcher(..., begin_ahead=...)` does that.
         Eval mode / no-grad only; anything else is ignored (the forward then runs its own prologue)."""
-        if self.training or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())):
+        if self._grad_path():
             return False
         _require_cuda(image_features, "image features")
         lib = _lib.load()
@@ -140,7 +122,7 @@ class DecoderC(_DecoderXE):
         dims = self._dims(X.shape[0], prev.shape[1], X.shape[1], self.max_len + 1)
         cur = torch.cuda.current_stream(dev)
         free = self.__dict__.setdefault("_ahead_free", [])
-        key = tuple(getattr(dims, f) for f, _ in _lib.EditNetDims._fields_) + (str(dev),)
+        key = self._dims_key(dims)
         ticket = None
         for i, t in enumerate(free):
             if t["dims_key"] == key:
@@ -148,11 +130,7 @@ class DecoderC(_DecoderXE):
                 cur.wait_event(ticket["done"])          # its previous decode must have finished with the workspace
                 break
         if ticket is None:
-            n = lib.set_editnet_workspace_bytes(C.byref(dims))
-            if n == 0:
-                raise _lib.SetError("unsupported EditNet dims %r" % (key,))
-            ticket = {"dims_key": key, "ws": torch.empty(n, dtype=torch.uint8, device=dev),
-                      "event": torch.cuda.Event(), "done": torch.cuda.Event()}
+            ticket = {"dims_key": key, "ws": self._new_workspace(dims), "event": torch.cuda.Event(), "done": torch.cuda.Event()}
         w = self._weights(dims)
         check(lib.set_editnet_begin(C.byref(w), C.byref(dims), ptr(X), ptr(mean), ptr(prev), ptr(plen), ptr(ticket["ws"]),
                                     ticket["ws"].numel(), stream_of(dev)), "set_editnet_begin")
@@ -180,7 +158,7 @@ class DecoderC(_DecoderXE):
         evaluate(): fixed weights, one batch after the other) this keeps several decodes in flight without the caller
         managing streams; a weight update in between discards the result and the forward decodes again.  Same kernels,
         same arithmetic: bit-identical to the plain call."""
-        if self.training or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())):
+        if self._grad_path():
             return False
         pending = self.__dict__.setdefault("_ahead", [])
         X = _f32c(image_features)

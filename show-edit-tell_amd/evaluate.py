@@ -32,91 +32,43 @@ def sentence(seq, word_map):
 # <end>; the answer is the best COMPLETED hypothesis (first maximum), or seqs[0][:18] at the step limit.
 # ------------------------------------------------------------------------------------------------
 class _FusedModel:
-    """Prologue once per image, invariants replicated k times into a (NI*k)-row workspace."""
+    """Prologue once per image, invariants replicated k times into a (NI*k)-row workspace.  `begin_args`: the tensors
+    set_<abi>_begin takes between the dims and the workspace (one row per image); `step_args`: the per-image tensors whose
+    k-fold replication set_<abi>_step takes in front of the words.  The model's `_beam_layout` gives the dims for k rows per image and the
+    (name, per-row shape) table of the invariants the prologue leaves behind."""
 
-    def _views(self, lib_ws_tensor, dims, ws, name, shape):
-        import ctypes as C
-        p = lib_ws_tensor(C.byref(dims), ws.data_ptr(), name.encode())
-        if not p:
-            raise KeyError(name)
-        off = p - ws.data_ptr()
-        n = 4
-        for s_ in shape:
-            n *= s_
-        return ws[off:off + n].view(torch.float32).view(*shape)
-
-
-class _FusedEditNet(_FusedModel):
-    """image_mean (NI, F) or None: the attention LSTM's image input (adaptive features: the mean over the valid regions,
-    editnet_adaptive.py:625-633); None = the mean over all R regions (editnet.py:503)."""
-
-    def __init__(self, decoder, X, prev, plen, k, max_steps, image_mean=None):
+    def __init__(self, model, begin_args, step_args, k, max_steps):
         import ctypes as C
         from . import _lib
         from ._lib import check, ptr, stream_of
-        lib = self.lib = _lib.load()
-        dev = X.device
-        NI, R, _ = X.shape
-        T, D, A = prev.shape[1], decoder.decoder_dim, decoder._attention_dim
-        self.st = stream_of(dev)
-        d_img = decoder._dims(NI, T, R, max_steps + 1)
-        self.w = decoder._weights(d_img)
-        ws_img = torch.empty(lib.set_editnet_workspace_bytes(C.byref(d_img)), dtype=torch.uint8, device=dev)
-        check(lib.set_editnet_begin(C.byref(self.w), C.byref(d_img), ptr(X), None if image_mean is None else ptr(image_mean),
-                                    ptr(prev), ptr(plen), ptr(ws_img), ws_img.numel(), self.st), "set_editnet_begin")
-        self.B = B = NI * k
-        self.dims = d_b = decoder._dims(B, T, R, max_steps + 1)
-        self.ws = ws_b = torch.empty(lib.set_editnet_workspace_bytes(C.byref(d_b)), dtype=torch.uint8, device=dev)
-        for name, shp in (("H", (T, D)), ("M", (T, D)), ("mask", (T,)), ("att1", (R, A)), ("att1_c", (T, A)),
-                          ("pre1", (4 * D,)), ("rmask", (R,)), ("cap_proj", (T, 2 * D)), ("mem_proj", (T, D))):
-            self._views(lib.set_editnet_ws_tensor, d_b, ws_b, name, (B,) + shp).copy_(
-                self._views(lib.set_editnet_ws_tensor, d_img, ws_img, name, (NI,) + shp).repeat_interleave(k, 0))
-        self.Xk = X.repeat_interleave(k, 0).contiguous()
-        self.states = [self._views(lib.set_editnet_ws_tensor, d_b, ws_b, n, (B, D)) for n in ("h1", "c1", "h2", "c2")]
+        lib = _lib.load()
+        begin, self._step = "set_%s_begin" % model._ABI, "set_%s_step" % model._ABI
+        self.step_fn = getattr(lib, self._step)
+        self.st = stream_of(model.fc.weight.device)
+        dims_of, invariants = model._beam_layout(begin_args, max_steps)
+        d_img = dims_of(1)
+        self.w = model._weights(d_img)
+        ws_img = model._new_workspace(d_img)
+        check(getattr(lib, begin)(C.byref(self.w), C.byref(d_img), *(ptr(t) for t in begin_args), ptr(ws_img), ws_img.numel(),
+                                  self.st), begin)
+        self.dims = d_b = dims_of(k)
+        NI, self.B = d_img.B, d_b.B
+        self.ws = ws_b = model._new_workspace(d_b)
+        for name, shp in invariants:
+            model.ws_tensor(d_b, name, (self.B,) + shp, ws=ws_b).copy_(
+                model.ws_tensor(d_img, name, (NI,) + shp, ws=ws_img).repeat_interleave(k, 0))
+        self.step_args = [t.repeat_interleave(k, 0).contiguous() for t in step_args]      # (kept alive for step_ptrs)
+        self.step_ptrs = tuple(ptr(t) for t in self.step_args)
+        self.D = D = model.decoder_dim
+        self.states = [model.ws_tensor(d_b, n, (self.B, D), ws=ws_b) for n in ("h1", "c1", "h2", "c2")]
         for s_ in self.states:
             s_.zero_()
-        self.D = D
 
     def step(self, words, logits):
         import ctypes as C
         from ._lib import check, ptr
-        check(self.lib.set_editnet_step(C.byref(self.w), C.byref(self.dims), ptr(self.Xk), ptr(words), 1, self.B,
-                                        ptr(logits), logits.shape[1], ptr(self.ws), self.ws.numel(), self.st),
-              "set_editnet_step")
-
-
-class _FusedDcnet(_FusedModel):
-    def __init__(self, dae, prev, plen, k, max_steps):
-        import ctypes as C
-        from . import _lib
-        from ._lib import check, ptr, stream_of
-        lib = self.lib = _lib.load()
-        dev = prev.device
-        NI, T = prev.shape
-        D, A, Cc, _ = dae._dims_cfg
-        self.st = stream_of(dev)
-        d_img = dae._dims(NI, T, max_steps + 1)
-        self.w = dae._weights(d_img)
-        ws_img = torch.empty(lib.set_dcnet_workspace_bytes(C.byref(d_img)), dtype=torch.uint8, device=dev)
-        check(lib.set_dcnet_begin(C.byref(self.w), C.byref(d_img), ptr(prev), ptr(plen), ptr(ws_img), ws_img.numel(),
-                                  self.st), "set_dcnet_begin")
-        self.B = B = NI * k
-        self.dims = d_b = dae._dims(B, T, max_steps + 1)
-        self.ws = ws_b = torch.empty(lib.set_dcnet_workspace_bytes(C.byref(d_b)), dtype=torch.uint8, device=dev)
-        for name, shp in (("enc", (T, 2 * Cc)), ("final_hidden", (2 * Cc,)), ("mask", (T,)), ("att1_c", (T, A)),
-                          ("pre1", (4 * D,))):
-            self._views(lib.set_dcnet_ws_tensor, d_b, ws_b, name, (B,) + shp).copy_(
-                self._views(lib.set_dcnet_ws_tensor, d_img, ws_img, name, (NI,) + shp).repeat_interleave(k, 0))
-        self.states = [self._views(lib.set_dcnet_ws_tensor, d_b, ws_b, n, (B, D)) for n in ("h1", "c1", "h2", "c2")]
-        for s_ in self.states:
-            s_.zero_()
-        self.D = D
-
-    def step(self, words, logits):
-        import ctypes as C
-        from ._lib import check, ptr
-        check(self.lib.set_dcnet_step(C.byref(self.w), C.byref(self.dims), ptr(words), 1, self.B, ptr(logits),
-                                      logits.shape[1], ptr(self.ws), self.ws.numel(), self.st), "set_dcnet_step")
+        check(self.step_fn(C.byref(self.w), C.byref(self.dims), *self.step_ptrs, ptr(words), 1, self.B,
+                           ptr(logits), logits.shape[1], ptr(self.ws), self.ws.numel(), self.st), self._step)
 
 
 def _check_n_best(n_best, beam_size):
@@ -225,7 +177,7 @@ def beam_search_editnet_batched(decoder, image_features, previous_caption, prev_
     X = image_features.float().contiguous()
     prev = previous_caption.long().contiguous()
     plen = prev_caplen.reshape(-1).long().contiguous()
-    m = _FusedEditNet(decoder, X, prev, plen, beam_size, max_steps)
+    m = _FusedModel(decoder, (X, None, prev, plen), (X,), beam_size, max_steps)
     res = _fused_beam([m], X.shape[0], beam_size, decoder.vocab_size, word_map, X.device, max_steps,
                       return_scores=return_scores, n_best=n_best)
     return _with_trace(res, True, return_scores, decoder, X, prev, plen, word_map, n_best=n_best) if return_trace else res
@@ -239,7 +191,7 @@ def beam_search_dcnet_batched(dae, previous_caption, prev_caplen, word_map, beam
     dae.eval()
     prev = previous_caption.long().contiguous()
     plen = prev_caplen.reshape(-1).long().contiguous()
-    m = _FusedDcnet(dae, prev, plen, beam_size, max_steps)
+    m = _FusedModel(dae, (prev, plen), (), beam_size, max_steps)
     return _fused_beam([m], prev.shape[0], beam_size, dae.vocab_size, word_map, prev.device, max_steps,
                        return_scores=return_scores, n_best=n_best)
 
@@ -257,8 +209,8 @@ def beam_search_ensemble_batched(decoder, dae, image_features, previous_caption,
     X = image_features.float().contiguous()
     prev = previous_caption.long().contiguous()
     plen = prev_caplen.reshape(-1).long().contiguous()
-    e = _FusedEditNet(decoder, X, prev, plen, beam_size, max_steps)
-    d = _FusedDcnet(dae, prev, plen, beam_size, max_steps)
+    e = _FusedModel(decoder, (X, None, prev, plen), (X,), beam_size, max_steps)
+    d = _FusedModel(dae, (prev, plen), (), beam_size, max_steps)
     res = _fused_beam([e, d], X.shape[0], beam_size, decoder.vocab_size, word_map, X.device, max_steps,
                       return_scores=return_scores, n_best=n_best)
     return _with_trace(res, True, return_scores, decoder, X, prev, plen, word_map, n_best=n_best) if return_trace else res
@@ -525,7 +477,7 @@ def beam_search_adaptive_batched(decoder, image_features, image_mean, previous_c
     decoder.eval()
     prev = previous_caption.long().contiguous()
     plen = prev_caplen.reshape(-1).long().contiguous()
-    m = _FusedEditNet(decoder, X, prev, plen, beam_size, max_steps, image_mean=mean)
+    m = _FusedModel(decoder, (X, mean, prev, plen), (X,), beam_size, max_steps)
     res = _fused_beam([m], X.shape[0], beam_size, decoder.vocab_size, word_map, X.device, max_steps,
                       return_scores=return_scores, n_best=n_best)
     return (_with_trace(res, True, return_scores, decoder, X, prev, plen, word_map, image_mean=mean, n_best=n_best)
