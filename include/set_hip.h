@@ -785,10 +785,31 @@ int set_sample_pick_opts_f32(const float* logits, int64_t ld_logits, int B, int 
                              uint64_t seed, uint64_t offset, int64_t* seq, int64_t* it, int32_t* unfinished,
                              int32_t* alive, int64_t* raw_ids, float* lse, float* step_logp, void* stream,
                              const SetSampleOpts* opts);
+/* set_sample_pick_opts_f32 that also records the kept set: kept_key (B) uint32, may be NULL.  Row b's kept set is
+ * {v : order_key(y[v]) >= kept_key[b]}, y = fl32(logits * (1.0f / temperature)) and order_key the order-preserving key of a float
+ * (u = bits of f; 0x80000000 for -0.0; ~u when the sign bit is set, u | 0x80000000 otherwise): the threshold the kernel found
+ * after its "arg-max is always kept" clamp, 0 when nothing is cut (top_k off or >= V, top_p == 1) and with neutral or NULL opts.
+ * Every other output is that of set_sample_pick_opts_f32 bit for bit; refusals are the same. */
+int set_sample_pick_opts_key_f32(const float* logits, int64_t ld_logits, int B, int V, int t, int max_len, int64_t end_idx,
+                                 uint64_t seed, uint64_t offset, int64_t* seq, int64_t* it, int32_t* unfinished,
+                                 int32_t* alive, int64_t* raw_ids, float* lse, float* step_logp, void* stream,
+                                 const SetSampleOpts* opts, uint32_t* kept_key);
 /* backward of step_logp w.r.t. logits: dlogits[b,v] = g[b] (1[v == raw_id_b] - exp(logits[b,v] - lse[b])); rows
  * with raw_id < 0 get zeros */
 int set_sample_logp_bwd_f32(const float* logits, int64_t ld_logits, const float* lse, const int64_t* raw_ids,
                             const float* g, float* dlogits, int64_t ld_dlogits, int B, int V, void* stream);
+/* backward of the step_logp of set_sample_pick_opts_key_f32 (the log-prob under the distribution sampled from), for `rows` rows
+ * in ONE launch (a rollout's (T, B) logs are T * B rows): with inv_t = 1.0f / temperature, y = fl32(logits[r,v] * inv_t),
+ *     dlogits[r,v] = g[r] * inv_t * (1[v == raw_id_r] - (order_key(y) >= kept_key[r] ? exp(y - lse[r]) : 0)).
+ * The kept set is piecewise constant in the logits and is held constant; y is the rounded product the forward compared, so words
+ * outside the set get exactly 0.  Rows with raw_id < 0 get zeros.  kept_key NULL: every word is kept; opts NULL: neutral — with
+ * both the values are those of set_sample_logp_bwd_f32 bit for bit.  Rows are read and written 16 bytes at a time when
+ * ld_logits and ld_dlogits are multiples of 4 and both bases are 16-byte aligned, by scalar accesses otherwise; columns
+ * V .. ld_dlogits-1 are not written.  SET_ERR_ARG (before any HIP call, nothing written) for a NULL pointer other than
+ * kept_key / opts, rows <= 0, V <= 0, a leading dimension below V and for options set_sample_pick_opts_f32 refuses. */
+int set_sample_logp_bwd_opts_f32(const float* logits, int64_t ld_logits, const float* lse, const int64_t* raw_ids,
+                                 const uint32_t* kept_key, const float* g, float* dlogits, int64_t ld_dlogits, int rows, int V,
+                                 const SetSampleOpts* opts, void* stream);
 /* the device RNG itself (tests: known-answer vectors): out (n,4) uint32 = Philox4x32-10(counter (i,0,offset), key seed) */
 int set_philox4x32(uint32_t* out, int n, uint64_t seed, uint64_t offset, void* stream);
 

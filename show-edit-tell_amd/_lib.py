@@ -400,7 +400,9 @@ PROTOTYPES = {
     "set_pack_f32": (_I, [_P, _L, _I, _I, C.POINTER(_P), C.POINTER(_L), C.POINTER(_I), _I, _P]),
     "set_sample_pick_f32": (_I, [_P, _L, _I, _I, _I, _I, _L, _U, _U, _P, _P, _P, _P, _P, _P, _P, _P]),
     "set_sample_pick_opts_f32": (_I, [_P, _L, _I, _I, _I, _I, _L, _U, _U, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(SampleOpts)]),
+    "set_sample_pick_opts_key_f32": (_I, [_P, _L, _I, _I, _I, _I, _L, _U, _U, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(SampleOpts), _P]),
     "set_sample_logp_bwd_f32": (_I, [_P, _L, _P, _P, _P, _P, _L, _I, _I, _P]),
+    "set_sample_logp_bwd_opts_f32": (_I, [_P, _L, _P, _P, _P, _P, _P, _L, _I, _I, C.POINTER(SampleOpts), _P]),
     "set_philox4x32": (_I, [_P, _I, _U, _U, _P]),
     "set_pick_slabs_f32": (_I, [C.POINTER(PickArgs), _P]),
     "set_pick_slabs_opts_f32": (_I, [C.POINTER(PickArgs), C.POINTER(SampleOpts), _P]),

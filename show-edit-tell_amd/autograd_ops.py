@@ -1074,7 +1074,7 @@ class SampleState:
 
 class _SamplePick(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, state, t):
+    def forward(ctx, logits, state, t, opts=None):
         lib = _lib.load()
         logits = _c(logits)
         B, V = logits.shape
@@ -1082,6 +1082,19 @@ class _SamplePick(torch.autograd.Function):
         raw = torch.empty(B, dtype=torch.long, device=dev)
         lse = torch.empty(B, dtype=torch.float32, device=dev)
         logp = torch.empty(B, dtype=torch.float32, device=dev)
+        ctx.opts = opts
+        if opts is not None:     # the kept set's threshold is saved: the backward differentiates the distribution sampled from
+            if V & 3:            # rows padded to 16 bytes: the register path's word enumeration, as in the sequence nodes
+                padded = torch.empty(B, (V + 3) & ~3, dtype=torch.float32, device=dev)[:, :V]
+                padded.copy_(logits)
+                logits = padded
+            key = torch.empty(B, dtype=torch.int32, device=dev)
+            check(lib.set_sample_pick_opts_key_f32(ptr(logits), logits.stride(0), B, V, t, state.max_len, state.end_idx,
+                                                   state.seed, state.offset, ptr(state.seq), ptr(state.tokens[t + 1]),
+                                                   ptr(state.unfinished), ptr(state.alive), ptr(raw), ptr(lse), ptr(logp),
+                                                   stream_of(dev), C.byref(opts), ptr(key)), "set_sample_pick_opts_key_f32")
+            ctx.save_for_backward(logits, lse, raw, key)
+            return logp
         check(lib.set_sample_pick_f32(ptr(logits), logits.stride(0), B, V, t, state.max_len, state.end_idx, state.seed,
                                       state.offset, ptr(state.seq), ptr(state.tokens[t + 1]), ptr(state.unfinished),
                                       ptr(state.alive), ptr(raw), ptr(lse), ptr(logp), stream_of(dev)),
@@ -1091,13 +1104,18 @@ class _SamplePick(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        logits, lse, raw = ctx.saved_tensors
+        logits, lse, raw = ctx.saved_tensors[:3]
         lib = _lib.load()
         B, V = logits.shape
-        d = torch.empty_like(logits)
+        d = torch.empty(B, V, dtype=torch.float32, device=logits.device)
+        if ctx.opts is not None:
+            check(lib.set_sample_logp_bwd_opts_f32(ptr(logits), logits.stride(0), ptr(lse), ptr(raw), ptr(ctx.saved_tensors[3]),
+                                                   ptr(_c(g)), ptr(d), d.stride(0), B, V, C.byref(ctx.opts),
+                                                   stream_of(logits.device)), "set_sample_logp_bwd_opts_f32")
+            return d, None, None, None
         check(lib.set_sample_logp_bwd_f32(ptr(logits), logits.stride(0), ptr(lse), ptr(raw), ptr(_c(g)), ptr(d),
                                           d.stride(0), B, V, stream_of(logits.device)), "set_sample_logp_bwd_f32")
-        return d, None, None
+        return d, None, None, None
 
 
 def philox_categorical(logits, seed, offset):
@@ -1117,8 +1135,9 @@ def philox_categorical(logits, seed, offset):
     return i64[2]
 
 
-def sample_pick(logits, state, t):
+def sample_pick(logits, state, t, opts=None):
     """One sampled step: draws it ~ softmax(logits) on the device (Philox), applies the <end> / unfinished / break
     bookkeeping into `state` (seq[:, t], tokens[t + 1]) and returns log_softmax(logits)[it] (B), differentiable
-    w.r.t. logits.  No host synchronisation."""
-    return _SamplePick.apply(logits, state, t)
+    w.r.t. logits.  No host synchronisation.  opts (_lib.sample_opts; None: neutral): temperature, top-k and top-p of the
+    draw — the log-prob and its gradient are those of the distribution sampled from, its kept set held constant."""
+    return _SamplePick.apply(logits, state, t, opts)

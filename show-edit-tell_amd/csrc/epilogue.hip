@@ -354,6 +354,7 @@ struct SampleOut {
     long long* raw_ids;   // (B) sampled word BEFORE the <end> -> 0 rewriting; -1 once the loop has been left
     float* lse;           // (B) log-sum-exp of the row (for the backward of the gathered log-prob)
     float* step_logp;     // (B) this step's log-prob (0 once the loop has been left)
+    uint32_t* kept_key;   // (B) or NULL: thr of the kept set {order_key(y) >= thr} the row was drawn from (0: every word)
 };
 
 template <bool REG, bool TAIL, bool TRUNC>
@@ -590,6 +591,7 @@ __global__ void __launch_bounds__(256) sample_pick_k(Slabs logits, const float* 
         if (so.raw_ids) so.raw_ids[b] = broken ? -1 : (long long)pick;
         if (so.lse) so.lse[b] = lse;
         if (so.step_logp) so.step_logp[b] = broken ? 0.f : logp;
+        if (so.kept_key) so.kept_key[b] = thr;
         unfinished[b] = unf;
         if (unf) atomicAdd(&alive[t], 1);
         it_buf[b] = it;
@@ -620,7 +622,7 @@ __global__ void __launch_bounds__(256) sample_pick_k(Slabs logits, const float* 
 int sample_pick(Slabs logits, const float* bias, int V, int t, int max_len, long long end_idx, long long* seq,
                 float* seq_logp, long long* it, int* unfinished, int* alive, const float* table, float* emb_out, int D,
                 int B, unsigned long long seed, unsigned long long offset, long long* raw_ids, float* lse,
-                float* step_logp, hipStream_t s, const LstmTail* tail, const SetSampleOpts* opts) {
+                float* step_logp, hipStream_t s, const LstmTail* tail, const SetSampleOpts* opts, uint32_t* kept_key) {
     if (B <= 0) return SET_OK;
     if (D & 3) return SET_ERR_UNSUPPORTED;
     if (tail && !tail_ok(*tail)) return SET_ERR_ARG;
@@ -637,7 +639,7 @@ int sample_pick(Slabs logits, const float* bias, int V, int t, int max_len, long
     ProfScope ps(trunc ? "sample_pick_trunc" : "sample_pick", s, 0.0,
                  4.0 * B * (1.0 * V * logits.n + 2.0 * D + (tail ? tl.D * (4.0 * (tl.g0.n + 2) + 3.0) : 0.0)));
     const bool reg = V <= 4 * 256 * GP_MAXQ && !(logits.ld & 3) && !(logits.stride & 3) && aligned16(logits.p);
-    SampleOut so{raw_ids, lse, step_logp};
+    SampleOut so{raw_ids, lse, step_logp, kept_key};
 #define SET_PICK_LAUNCH(REG, TAIL, TRUNC)                                                                                    \
     hipLaunchKernelGGL((sample_pick_k<REG, TAIL, TRUNC>), dim3(B), dim3(256), 0, s, logits, bias, V, t, max_len, end_idx, seq, \
                        seq_logp, it, unfinished, alive, table, emb_out, D, seed, offset, so, tl, tc)
@@ -669,6 +671,63 @@ int sample_logp_bwd(const float* logits, long long ld, const float* lse, const l
                     float* dlogits, long long ldd, int B, int V, hipStream_t s) {
     if (B <= 0) return SET_OK;
     hipLaunchKernelGGL(sample_logp_bwd_k, dim3(B), dim3(256), 0, s, logits, ld, lse, ids, g, dlogits, ldd, V);
+    SET_LAUNCH_CHECK();
+    return SET_OK;
+}
+
+// The same gradient under SetSampleOpts, over any number of rows (the sequence nodes: all T * B rows of a rollout at once):
+//   d logits[r, v] = g[r] * inv_t * (1[v == id_r] - (order_key(y) >= key_r ? exp(y - lse_r) : 0)),   y = fl32(logits[r, v] * inv_t)
+// key_r is the threshold sample_pick_k left in SampleOut::kept_key (NULL: 0, every word kept); the kept set is piecewise constant
+// in the logits and is held constant.  y is the rounded product the forward compared (no fma with the subtraction of lse), so
+// the set is the forward's bit for bit; with inv_t == 1 and key 0 the values are sample_logp_bwd_k's.  One workgroup per row;
+// VEC: rows read and written as float4 (ld, ldd multiples of 4, bases 16-byte aligned), the V % 4 tail by scalar accesses —
+// columns V .. ldd-1 are never written.
+template <bool VEC>
+__global__ void __launch_bounds__(256) sample_logp_bwd_opts_k(const float* logits, long long ld, const float* lse,
+                                                              const long long* ids, const uint32_t* kept_key, const float* g,
+                                                              float* dlogits, long long ldd, int V, float inv_t) {
+    const long long r = blockIdx.x;
+    const int tid = threadIdx.x;
+    const long long id = ids[r];
+    const float gb = g[r] * inv_t, l = lse[r];
+    const uint32_t thr = kept_key ? kept_key[r] : 0u;
+    const float* x = logits + r * ld;
+    float* d = dlogits + r * ldd;
+    auto grad = [&](float xv, int v) -> float {
+        if (id < 0) return 0.f;
+        const float y = __fmul_rn(xv, inv_t);
+        const float p = order_key(y) >= thr ? expf(y - l) : 0.f;
+        return gb * ((v == id ? 1.f : 0.f) - p);
+    };
+    if (VEC) {
+        const int V4 = V & ~3;
+        for (int v = tid * 4; v < V4; v += 1024) {
+            const f32x4 xv = *reinterpret_cast<const f32x4*>(x + v);
+            f32x4 dv;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) dv[e] = grad(xv[e], v + e);
+            *reinterpret_cast<f32x4*>(d + v) = dv;
+        }
+        if (V4 + tid < V) d[V4 + tid] = grad(x[V4 + tid], V4 + tid);
+    } else {
+        for (int v = tid; v < V; v += 256) d[v] = grad(x[v], v);
+    }
+}
+
+int sample_logp_bwd_opts(const float* logits, long long ld, const float* lse, const long long* ids, const uint32_t* kept_key,
+                         const float* g, float* dlogits, long long ldd, int rows, int V, const SetSampleOpts* opts,
+                         hipStream_t s) {
+    if (rows <= 0) return SET_OK;
+    if (sample_opts_check(opts) != SET_OK) return SET_ERR_ARG;
+    const float inv_t = opts ? 1.0f / opts->temperature : 1.f;
+    ProfScope ps("sample_logp_bwd_opts", s, 0.0, 8.0 * rows * V);
+    const bool vec = !(ld & 3) && !(ldd & 3) && aligned16(logits) && aligned16(dlogits);
+    if (vec)
+        hipLaunchKernelGGL(sample_logp_bwd_opts_k<true>, dim3(rows), dim3(256), 0, s, logits, ld, lse, ids, kept_key, g, dlogits,
+                           ldd, V, inv_t);
+    else
+        hipLaunchKernelGGL(sample_logp_bwd_opts_k<false>, dim3(rows), dim3(256), 0, s, logits, ld, lse, ids, kept_key, g, dlogits,
+                           ldd, V, inv_t);
     SET_LAUNCH_CHECK();
     return SET_OK;
 }

@@ -429,11 +429,12 @@ int greedy_pick(Slabs logits, const float* bias, int V, int t, int max_len, long
                 long long* seq, float* seq_logp, long long* it, int* unfinished, int* alive,
                 const float* table, float* emb_out, int D, int B, hipStream_t s, const LstmTail* tail = nullptr);
 // opts (include/set_hip.h SetSampleOpts; NULL: neutral): temperature, top-k and top-p of the draw.  Neutral options launch the
-// untruncated kernel.
+// untruncated kernel.  kept_key (B) or NULL: the threshold of every row's kept set {order_key(y) >= thr}, 0 when nothing is cut.
 int sample_pick(Slabs logits, const float* bias, int V, int t, int max_len, long long end_idx, long long* seq,
                 float* seq_logp, long long* it, int* unfinished, int* alive, const float* table, float* emb_out, int D,
                 int B, unsigned long long seed, unsigned long long offset, long long* raw_ids, float* lse,
-                float* step_logp, hipStream_t s, const LstmTail* tail = nullptr, const SetSampleOpts* opts = nullptr);
+                float* step_logp, hipStream_t s, const LstmTail* tail = nullptr, const SetSampleOpts* opts = nullptr,
+                uint32_t* kept_key = nullptr);
 // what the *_opts entry points refuse with SET_ERR_ARG before they touch anything
 inline int sample_opts_check(const SetSampleOpts* o) {
     if (!o) return SET_OK;
@@ -447,6 +448,10 @@ inline bool sample_opts_neutral(const SetSampleOpts* o) {
 }
 int sample_logp_bwd(const float* logits, long long ld, const float* lse, const long long* ids, const float* g,
                     float* dlogits, long long ldd, int B, int V, hipStream_t s);
+// the same under options and a recorded kept set (kept_key NULL: every word), any number of rows in one launch
+int sample_logp_bwd_opts(const float* logits, long long ld, const float* lse, const long long* ids, const uint32_t* kept_key,
+                         const float* g, float* dlogits, long long ldd, int rows, int V, const SetSampleOpts* opts,
+                         hipStream_t s);
 // edit_trace.hip: the record of ONE forced timestep (set_editnet_edit_trace), taken from what the step left in the workspace.
 // One workgroup per row: copies the two attention rows, first-index arg-max of alpha_c, the copy gate
 // sigmoid((gn + bn) + (cmem_pre + bm)) with its mean over D, log-sum-exp of the logits (slabs in index order, + bias) and the

@@ -52,9 +52,15 @@ class DAE(_DAE_XE):
                                        stream_of(dev)), "set_dcnet_greedy")
             return seq, seq_logp
 
+    def sample_rollout(self, word_map, encoded_previous_captions, previous_cap_length, temperature=1.0, top_k=0, top_p=1.0):
+        """see editnet_rl.DecoderC.sample_rollout"""
+        _require_cuda(encoded_previous_captions, "previous captions")
+        return self._sample_rollout((word_map, encoded_previous_captions, previous_cap_length), {}, temperature, top_k, top_p)
 
-def _dae_rollout(self, word_map, encoded_previous_captions, previous_cap_length, sample_max, sample_rl):
-    """dcnet_rl.py:286-346 over autograd-wrapped HIP operators (sampled SCST rollout / multinomial sampling)."""
+
+def _dae_rollout(self, word_map, encoded_previous_captions, previous_cap_length, sample_max, sample_rl, opts=None):
+    """dcnet_rl.py:286-346 over autograd-wrapped HIP operators (sampled SCST rollout / multinomial sampling).  opts: see
+    editnet_rl.DecoderC._rollout_autograd."""
     import torch.nn.functional as F
     from . import autograd_ops as A
     from . import rng
@@ -75,7 +81,7 @@ def _dae_rollout(self, word_map, encoded_previous_captions, previous_cap_length,
         from . import dcnet_sequence as S
         cfg = S.SeqConfig([], training, p_emb, 0.0, p_out, seed,
                           rollout=dict(max_len=max_len, start_idx=int(word_map['<start>']), end_idx=int(word_map['<end>']),
-                                       seed=seed, offset=rng.offset(rng.SITE_ROLLOUT)))
+                                       seed=seed, offset=rng.offset(rng.SITE_ROLLOUT), opts=opts))
         return S.dcnet_sequence(cfg, enc, final_hidden, mask, att1_c, torch.zeros(1, 1, dtype=torch.long, device=dev),
                                 S.dae_params(self))
     unfinished = None
@@ -90,7 +96,7 @@ def _dae_rollout(self, word_map, encoded_previous_captions, previous_cap_length,
         if t == max_len:
             break
         if sample_rl:                    # dcnet_rl.py:320-340 on the device (Philox draw), no host sync
-            logps.append(A.sample_pick(logits, state, t))
+            logps.append(A.sample_pick(logits, state, t, opts))
             continue
         sample_logp, it = torch.max(F.log_softmax(logits, dim=1), 1)
         it = it.clone()
@@ -129,3 +135,6 @@ class DAEWithAR(nn.Module):
 
     def forward(self, *args, **kwargs):
         return self.dae(*args, **kwargs)
+
+    def sample_rollout(self, *args, **kwargs):
+        return self.dae.sample_rollout(*args, **kwargs)

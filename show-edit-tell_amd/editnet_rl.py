@@ -49,6 +49,14 @@ class DecoderC(_DecoderXE):
             return self._decode_nograd(lib, word_map, encoded_previous_captions, previous_cap_length, image_features,
                                        sample_rl, image_mean, opts)
 
+    def sample_rollout(self, word_map, encoded_previous_captions, previous_cap_length, image_features, image_mean=None,
+                       repeat_images=1, temperature=1.0, top_k=0, top_p=1.0):
+        """One sampled rollout under temperature / top_k / top_p, with or without gradients (native_model._sample_rollout):
+        the entry self-critical training with a tempered or truncated policy goes through (train.scst_train_step)."""
+        _require_cuda(image_features, "image features")
+        return self._sample_rollout((word_map, encoded_previous_captions, previous_cap_length, image_features),
+                                    dict(image_mean=image_mean, repeat_images=repeat_images), temperature, top_k, top_p)
+
     def _decode_nograd(self, lib, word_map, encoded_previous_captions, previous_cap_length, image_features, sample_rl,
                        image_mean, opts=None):
         dev = image_features.device
@@ -202,12 +210,13 @@ class DecoderC(_DecoderXE):
         return None
 
     def _rollout_autograd(self, word_map, encoded_previous_captions, previous_cap_length, image_features, sample_max,
-                          sample_rl, image_mean=None, repeat_images=1):
+                          sample_rl, image_mean=None, repeat_images=1, opts=None):
         """The reference loop editnet_rl.py:485-549 over autograd-wrapped HIP operators: used for the
         sampled SCST rollout (train mode, dropout active, gradients flow through seqLogprobs) and for
         the grad-enabled greedy decode.  Sampling runs in the HIP epilogue `set_sample_pick_f32` (Philox draw,
         log-prob gather, <end> / unfinished / break bookkeeping on the device): the sampled loop never synchronises
-        with the host (the reference does every step, editnet_rl.py:546)."""
+        with the host (the reference does every step, editnet_rl.py:546).  opts (_lib.SampleOpts or None; sample_rollout): the
+        sampled rollout draws from, and differentiates, the tempered / truncated distribution."""
         from . import autograd_ops as A
         from . import rng
         if self._adaptive:
@@ -244,7 +253,7 @@ class DecoderC(_DecoderXE):
             from . import xe_sequence as S
             cfg = S.SeqConfig([], training, p_emb, p_reg, p_out, seed,
                               rollout=dict(max_len=max_len, start_idx=int(word_map['<start>']), end_idx=int(word_map['<end>']),
-                                           seed=seed, offset=rng.offset(rng.SITE_ROLLOUT)))
+                                           seed=seed, offset=rng.offset(rng.SITE_ROLLOUT), opts=opts))
             return S.xe_sequence(cfg, X, mean, H, M, final_hidden, mask, att1_c_all, Y if self.training else att1_eval,
                                  torch.zeros(1, 1, dtype=torch.long, device=dev), S.decoder_params(self))
         unfinished = None
@@ -277,7 +286,7 @@ class DecoderC(_DecoderXE):
             if t == max_len:
                 break
             if sample_rl:                # editnet_rl.py:521-543 on the device, no host sync
-                logps.append(A.sample_pick(logits, state, t))
+                logps.append(A.sample_pick(logits, state, t, opts))
                 continue
             logprobs = F.log_softmax(logits, dim=1)
             sample_logp, it = torch.max(logprobs, 1)

@@ -91,6 +91,18 @@ class NativeModel(nn.Module):
         """True when a call of the model runs the autograd route: train mode (dropout), or gradients are wanted"""
         return self.training or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()))
 
+    def _sample_rollout(self, lead, tail, temperature, top_k, top_p):
+        """The body of the models' `sample_rollout(...)`: one sampled rollout -> (seq, seqLogprobs) under temperature / top_k /
+        top_p (include/set_hip.h SetSampleOpts).  `forward` refuses the options where gradients flow; here the grad path (train
+        mode, or parameters that require grad) runs the autograd rollout with them: seqLogprobs are the log-probs of the
+        distribution sampled from and their backward holds every step's kept set constant (set_sample_logp_bwd_opts_f32).
+        Without gradients, and with neutral options, this is forward(sample_max=False, sample_rl=True, ...) call for call.
+        lead / tail: the model's positional arguments before, and keyword arguments after, (sample_max, sample_rl)."""
+        opts = _lib.sample_opts(temperature, top_k, top_p)
+        if opts is None or not self._grad_path():
+            return self.forward(*lead, sample_max=False, sample_rl=True, **tail, temperature=temperature, top_k=top_k, top_p=top_p)
+        return self._rollout_autograd(*lead, False, True, **tail, opts=opts)
+
     def _entry(self, lib, what):
         return getattr(lib, "set_%s_%s" % (self._ABI, what))
 

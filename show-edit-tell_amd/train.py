@@ -513,32 +513,46 @@ def _repeater(n_samples):
     return lambda t: t if n_samples == 1 else t.repeat(n_samples, *([1] * (t.dim() - 1)))
 
 
+def _sample_kw(temperature, top_k, top_p):
+    """{} for neutral values: the step then makes the calls it made before there were options"""
+    from . import _lib
+    return {} if _lib.sample_opts(temperature, top_k, top_p) is None else dict(temperature=temperature, top_k=top_k, top_p=top_p)
+
+
 def scst_train_step(decoder, optimizer, word_map, image_features, previous_caption, prev_caplen, ground_truth,
-                    scorer, n_samples=1, cider_weight=1.0, group=None):
+                    scorer, n_samples=1, cider_weight=1.0, group=None, temperature=1.0, top_k=0, top_p=1.0):
     """One self-critical step of editnet_rl.py:649-686 on this rank's shard.  The reference draws one sample per
     image; BASELINE.json config 5 asks for 5: all samples enter one RewardCriterion over n_samples * B rows.  As in
     the XE step the loss is normalised by the GLOBAL mask count so that N ranks reproduce one big batch.
+    temperature / top_k / top_p (include/set_hip.h SetSampleOpts): the policy the samples are drawn from AND differentiated
+    (`decoder.sample_rollout`; every step's kept set is held constant); the greedy baseline takes no options.
     Returns (mean reward of the samples on this rank, GLOBAL loss value)."""
     rep = _repeater(n_samples)
+    kw = _sample_kw(temperature, top_k, top_p)
     return _scst_step(
         decoder, optimizer,
         lambda: decoder(word_map, previous_caption, prev_caplen, image_features, sample_max=True, sample_rl=False),
         # (the image features go in ONCE with the repeat count: relu(att_embed(X)) has no dropout before it, so it is
         # contracted for the B images and its rows repeated — not for n_samples * B copies of the same regions, forward and
         # weight gradient alike; the rollout's region stream still gets its own row per sample)
-        lambda: decoder(word_map, rep(previous_caption), rep(prev_caplen), image_features, sample_max=False,
-                        sample_rl=True, repeat_images=n_samples),
+        (lambda: decoder(word_map, rep(previous_caption), rep(prev_caplen), image_features, sample_max=False,
+                         sample_rl=True, repeat_images=n_samples)) if not kw else
+        (lambda: decoder.sample_rollout(word_map, rep(previous_caption), rep(prev_caplen), image_features,
+                                        repeat_images=n_samples, **kw)),
         rep, ground_truth, scorer, n_samples, cider_weight, image_features.device, group)
 
 
 def dcnet_scst_train_step(dae, optimizer, word_map, previous_caption, prev_caplen, ground_truth, scorer, n_samples=1,
-                          cider_weight=1.0, group=None):
+                          cider_weight=1.0, group=None, temperature=1.0, top_k=0, top_p=1.0):
     """The text-only twin (dcnet_rl.py:451-493): `dae` is a dcnet_rl.DAE or the DAEWithAR wrapper the reference
     trains (its forward delegates to `.dae`; `affine_hidden` receives no gradient from this loss, as in the reference).
+    temperature / top_k / top_p: see scst_train_step.
     Returns (mean reward of the samples on this rank, GLOBAL loss value)."""
     rep = _repeater(n_samples)
+    kw = _sample_kw(temperature, top_k, top_p)
     return _scst_step(
         dae, optimizer,
         lambda: dae(word_map, previous_caption, prev_caplen, sample_max=True, sample_rl=False),
-        lambda: dae(word_map, rep(previous_caption), rep(prev_caplen), sample_max=False, sample_rl=True),
+        (lambda: dae(word_map, rep(previous_caption), rep(prev_caplen), sample_max=False, sample_rl=True)) if not kw else
+        (lambda: dae.sample_rollout(word_map, rep(previous_caption), rep(prev_caplen), **kw)),
         rep, ground_truth, scorer, n_samples, cider_weight, previous_caption.device, group)

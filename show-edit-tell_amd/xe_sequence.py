@@ -291,6 +291,13 @@ class _XESequence(torch.autograd.Function):
             L["LOGITS"] = _e(T, B, V, dev=dev)
             L["RAW"] = torch.empty(T, B, dtype=torch.long, device=dev)
             L["LSE"], L["LOGP"] = _e(T, B, dev=dev), _e(T, B, dev=dev)
+            ro_opts = ro.get("opts")       # _lib.SampleOpts or None: with options every step also logs its kept set's threshold
+            if ro_opts is not None:
+                L["KEY"] = torch.empty(T, B, dtype=torch.int32, device=dev)
+                # rows padded to 16 bytes: the pick reads them into registers (the word enumeration of the fused no-grad rollout:
+                # the same seed draws the same words) and the backward reads them as float4
+                L["LOGITS"] = _e(T, B, (V + 3) & ~3, dev=dev)[:, :, :V]
+                ld_lg = L["LOGITS"].stride(1)
         scale_off = rng.offset              # (site, t) -> Philox offset; sites 1 = embedding, 2 = regions, 3 = h2 before fc, 4 = SS draw
 
         # editnet.py:441-443 in train mode: att1(t) = features_att(dropout_t(relu(att_embed(X)))) does not depend on the
@@ -394,10 +401,18 @@ class _XESequence(torch.autograd.Function):
             if ro is not None:             # editnet_rl.py:514-547: scores of this step, then the device sampling epilogue
                 hz = L["H2D"][t] if (train and cfg.p_out > 0) else L["H2"][t + 1]
                 ops.linear(hz, P["fc_w"], P["fc_b"], L["LOGITS"][t], B)
-                check(lib.set_sample_pick_f32(L["LOGITS"][t].data_ptr(), V, B, V, t, T, state.end_idx, state.seed, state.offset,
-                                              state.seq.data_ptr(), state.tokens[t + 1].data_ptr(), state.unfinished.data_ptr(),
-                                              state.alive.data_ptr(), L["RAW"][t].data_ptr(), L["LSE"][t].data_ptr(),
-                                              L["LOGP"][t].data_ptr(), st), "set_sample_pick_f32")
+                if ro_opts is not None:
+                    check(lib.set_sample_pick_opts_key_f32(L["LOGITS"][t].data_ptr(), ld_lg, B, V, t, T, state.end_idx, state.seed,
+                                                           state.offset, state.seq.data_ptr(), state.tokens[t + 1].data_ptr(),
+                                                           state.unfinished.data_ptr(), state.alive.data_ptr(),
+                                                           L["RAW"][t].data_ptr(), L["LSE"][t].data_ptr(), L["LOGP"][t].data_ptr(),
+                                                           st, C.byref(ro_opts), L["KEY"][t].data_ptr()),
+                          "set_sample_pick_opts_key_f32")
+                else:
+                    check(lib.set_sample_pick_f32(L["LOGITS"][t].data_ptr(), V, B, V, t, T, state.end_idx, state.seed, state.offset,
+                                                  state.seq.data_ptr(), state.tokens[t + 1].data_ptr(),
+                                                  state.unfinished.data_ptr(), state.alive.data_ptr(), L["RAW"][t].data_ptr(),
+                                                  L["LSE"][t].data_ptr(), L["LOGP"][t].data_ptr(), st), "set_sample_pick_f32")
         if adaptive and count_truncation_bites(L["RMASK"] if train else rmask_eval, bts):
             global TRUNCATION_FALLBACKS
             TRUNCATION_FALLBACKS += 1
@@ -448,7 +463,12 @@ class _XESequence(torch.autograd.Function):
         if cfg.rollout is not None:        # d seq_logp -> d scores of every step (sampling epilogue backward)
             dl = dlogp.t().contiguous()                            # (T, B)
             dp = A.zero_padded_rows(T, B, V, dev)          # rows padded to 16 bytes: the fc contractions read them in place
-            for t in range(T):
+            ro_opts = cfg.rollout.get("opts")
+            if ro_opts is not None:        # the truncated log-prob: all T * B rows of the (contiguous) logs in ONE launch
+                check(lib.set_sample_logp_bwd_opts_f32(L["LOGITS"].data_ptr(), L["LOGITS"].stride(1), L["LSE"].data_ptr(), L["RAW"].data_ptr(),
+                                                       L["KEY"].data_ptr(), dl.data_ptr(), dp.data_ptr(), dp.stride(1), T * B, V,
+                                                       C.byref(ro_opts), st), "set_sample_logp_bwd_opts_f32")
+            for t in (range(T) if ro_opts is None else ()):
                 check(lib.set_sample_logp_bwd_f32(L["LOGITS"][t].data_ptr(), V, L["LSE"][t].data_ptr(), L["RAW"][t].data_ptr(),
                                                   dl[t].data_ptr(), dp[t].data_ptr(), dp.stride(1), B, V, st),
                       "set_sample_logp_bwd_f32")
