@@ -270,6 +270,48 @@ int set_editnet_sample_opts(const SetEditNetWeights* w, const SetEditNetDims* d,
                             int64_t* seq, float* seq_logp, void* ws, size_t ws_bytes, void* stream,
                             const SetSampleOpts* opts);
 
+/* Gumbel-max draw: the second sampler of the free-running loops (the inverse-CDF sampler above stays the default and keeps its
+ * draws bit for bit).  For one row of logits x[v], v < V (slabs summed, bias added), at timestep t of batch row `row`:
+ *   y[v] = fl32(x[v] * (1.0f / temperature))                   — the same inv_t as SetSampleOpts, the product rounded
+ *   g[v] = -logf(E),  E = -log(u),  u = (r + 1/2) 2^-32,  r = output word (v & 3) of
+ *          Philox4x32-10(key = (seed_lo, seed_hi), counter = (row, t + 256 ((v >> 2) + 1), offset_lo, offset_hi))
+ *          E is formed without cancellation: r < 2^31: -logf((r + 0.5f) 2^-32); otherwise -log1pf(-vv) with
+ *          vv = (float)(2^32 - r) 2^-32 - 2^-33 from the exact integer.  E is never 0 or infinite; g lies in about [-3.2, 22.9].
+ *   s[v] = fl32(y[v] + g[v]);   word = the FIRST maximum of s (ties to the lowest index).
+ * The word is exactly a draw from softmax(y).  step_logp / seq_logp = (y[w] - max y) - log sum exp(y - max y) and lse = the
+ * log-sum-exp of y are taken over the unperturbed y, as in the untruncated sampled pick; raw_ids, the <end> rewrite, the
+ * `unfinished` latch, alive, the embedding gather and the LSTM tail are those of set_sample_pick_f32.
+ * The inverse-CDF sampler's uniform uses counter word 1 = t < 256, so the two streams share no counter.  The draw does not
+ * depend on the launch geometry: the per-step kernel and the persistent launch draw the same word from the same (seed, offset).
+ * SetSampleOpts carries the temperature only.  SET_ERR_ARG (before any HIP call, nothing written): options
+ * set_sample_pick_opts_f32 refuses, top_k != 0, top_p != 1, max_len > 255 (or t > 255), V > 2^26 - 4 (the last quad's counter
+ * word would wrap onto the uniform's; every V >= 2^26 is refused with it).
+ * Float64 restatement: tests/gumbel_oracle.py.
+ *
+ * set_editnet_sample_gumbel: the free-running loop of set_editnet_sample_opts with this draw, on the per-step kernels. */
+int set_editnet_sample_gumbel(const SetEditNetWeights* w, const SetEditNetDims* d, const float* X,
+                              const float* image_mean, const int64_t* prev, const int64_t* prevlen,
+                              int64_t start_idx, int64_t end_idx, int max_len, uint64_t seed, uint64_t offset,
+                              int64_t* seq, float* seq_logp, void* ws, size_t ws_bytes, void* stream,
+                              const SetSampleOpts* opts);
+/* The same loop as prologue + ONE persistent launch (csrc/decode_persistent_wide.hip, sampled mode) for 1 .. 16 rows, fixed
+ * features and an active token table: every workgroup forms the noise of its own vocabulary rows and publishes, per (row,
+ * slice), the slice's log-sum-exp of y, the first arg-max of s, max s and y there; every workgroup combines the slices in slice
+ * order.  Tokens are those of set_editnet_sample_gumbel for the same (seed, offset) wherever the two routes' logits (equal to
+ * 1e-4) do not bring the two largest perturbed scores within that distance; seq_logp agrees to 1e-4.  A timed-out exchange
+ * poisons seq_logp with NaN and seq with 0 (SET_ERR_FAULT at the next call), as in the greedy launch.
+ * SET_ERR_UNSUPPORTED (take set_editnet_sample_gumbel), answered BEFORE anything is touched: every case in which
+ * set_editnet_beam_persistent answers it for fixed features (no token table, dimensions the launch does not cover, another
+ * process owns the device's persistent launches), more than 16 rows, adaptive features, SET_DEC_PERSISTENT=0.  Only a device
+ * whose LDS limit or resident-workgroup capacity turns out too small is answered after the prologue has been written into `ws`
+ * and seq / seq_logp have been cleared.  SET_ERR_ARG: as above, and max_len > d->maxT.
+ * Parity: tests/test_hip_gumbel_sampling.py. */
+int set_editnet_gumbel_persistent(const SetEditNetWeights* w, const SetEditNetDims* d, const float* X,
+                                  const float* image_mean, const int64_t* prev, const int64_t* prevlen,
+                                  int64_t start_idx, int64_t end_idx, int max_len, uint64_t seed, uint64_t offset,
+                                  int64_t* seq, float* seq_logp, void* ws, size_t ws_bytes, void* stream,
+                                  const SetSampleOpts* opts);
+
 /* Teacher-forced XE forward (editnet.py:479-548, eval mode, use_ss=False) on a batch already
  * sorted by decreasing caption length.  caps (B,Lc) int64 sorted; host_decode_lengths[B] on the
  * HOST, non-increasing; predictions (B,maxT,V) is fully overwritten (zeros where not decoded). */
@@ -442,6 +484,12 @@ int set_dcnet_sample_opts(const SetDcnetWeights* w, const SetDcnetDims* d, const
                           const int64_t* prevlen, int64_t start_idx, int64_t end_idx, int max_len, uint64_t seed,
                           uint64_t offset, int64_t* seq, float* seq_logp, void* ws, size_t ws_bytes, void* stream,
                           const SetSampleOpts* opts);
+/* the loop of set_dcnet_sample_opts with the Gumbel-max draw (the contract above set_editnet_sample_gumbel; per-step kernels:
+ * DCNet's persistent launch and the ensemble's have no sampled mode) */
+int set_dcnet_sample_gumbel(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* prev,
+                            const int64_t* prevlen, int64_t start_idx, int64_t end_idx, int max_len, uint64_t seed,
+                            uint64_t offset, int64_t* seq, float* seq_logp, void* ws, size_t ws_bytes, void* stream,
+                            const SetSampleOpts* opts);
 int set_dcnet_xe_forward(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* caps,
                          int64_t caps_stride, const int* host_decode_lengths, const int64_t* prev,
                          const int64_t* prevlen, float* predictions, void* ws, size_t ws_bytes,
@@ -812,6 +860,15 @@ int set_sample_logp_bwd_opts_f32(const float* logits, int64_t ld_logits, const f
                                  const SetSampleOpts* opts, void* stream);
 /* the device RNG itself (tests: known-answer vectors): out (n,4) uint32 = Philox4x32-10(counter (i,0,offset), key seed) */
 int set_philox4x32(uint32_t* out, int n, uint64_t seed, uint64_t offset, void* stream);
+/* The Gumbel-max pick of one timestep (the contract above set_editnet_sample_gumbel): the arguments, outputs and bookkeeping
+ * of set_sample_pick_opts_f32 — one workgroup per row, t = 0 initialises it / unfinished / alive — with the word drawn as the
+ * first maximum of y + g.  opts carries the temperature only (NULL: 1); top_k != 0 or top_p != 1 answers SET_ERR_ARG. */
+int set_gumbel_pick_f32(const float* logits, int64_t ld_logits, int B, int V, int t, int max_len, int64_t end_idx,
+                        uint64_t seed, uint64_t offset, int64_t* seq, int64_t* it, int32_t* unfinished, int32_t* alive,
+                        int64_t* raw_ids, float* lse, float* step_logp, void* stream, const SetSampleOpts* opts);
+/* out (rows, V) fp32 = the noise g[v] of (seed, offset, row, t, v) of that contract, row = 0 .. rows - 1: the test hook of the
+ * noise, as set_philox4x32 is of the raw generator.  SET_ERR_ARG: NULL out, rows / V <= 0, t outside [0, 255], V > 2^26 - 4. */
+int set_gumbel_fill_f32(float* out, int rows, int V, int t, uint64_t seed, uint64_t offset, void* stream);
 
 /* The vocabulary-row epilogue of one free-running timestep (csrc/epilogue.hip greedy_pick_k / sample_pick_k) with every
  * argument the decode loops give it, for direct tests: one workgroup per row turns

@@ -207,6 +207,31 @@ def sample_opts(temperature=1.0, top_k=0, top_p=1.0):
     return SampleOpts(temperature=t, top_k=int(top_k), top_p=p)
 
 
+SAMPLERS = ("cdf", "gumbel")
+
+
+def check_sampler_name(sampler, top_k, top_p):
+    """the part of check_sampler that needs no tensor: made first, so that a wrong option is a ValueError wherever the inputs live"""
+    if sampler not in SAMPLERS:
+        raise ValueError("sampler must be one of %r, got %r" % (SAMPLERS, sampler))
+    if sampler == "gumbel" and (int(top_k) != 0 or float(top_p) != 1.0):
+        raise ValueError('sampler="gumbel" takes the temperature only: top_k / top_p truncation needs sampler="cdf"')
+
+
+def check_sampler(sampler, opts, sample_max, sample_rl, grad_path):
+    """sampler="cdf" (default: the inverse-CDF draw) | "gumbel" (the Gumbel-max draw, include/set_hip.h): "gumbel" takes the
+    temperature only and exists on the no-grad sampled rollout only.  Returns True for "gumbel"."""
+    if sampler == "cdf":
+        return False
+    check_sampler_name(sampler, 0 if opts is None else opts.top_k, 1.0 if opts is None else opts.top_p)
+    if sample_max or not sample_rl:
+        raise ValueError('sampler="gumbel" applies to the sampled rollout only (sample_max=False, sample_rl=True)')
+    if grad_path:
+        raise ValueError('sampler="gumbel" is not supported in the grad-enabled rollout (train mode or parameters that require '
+                         "grad): call the model in eval mode under torch.no_grad()")
+    return True
+
+
 def refuse_sample_opts(sample_max, sample_rl, grad_path):
     """non-neutral sampling options where nothing is sampled, or where the log-probs would need a backward that is not built"""
     if sample_max or not sample_rl:
@@ -300,6 +325,10 @@ PROTOTYPES = {
                                 _P, _P, _Z, _P]),
     "set_editnet_sample_opts": (_I, [C.POINTER(EditNetWeights), C.POINTER(EditNetDims), _P, _P, _P, _P, _L, _L, _I, _U, _U, _P,
                                      _P, _P, _Z, _P, C.POINTER(SampleOpts)]),
+    "set_editnet_sample_gumbel": (_I, [C.POINTER(EditNetWeights), C.POINTER(EditNetDims), _P, _P, _P, _P, _L, _L, _I, _U, _U, _P,
+                                       _P, _P, _Z, _P, C.POINTER(SampleOpts)]),
+    "set_editnet_gumbel_persistent": (_I, [C.POINTER(EditNetWeights), C.POINTER(EditNetDims), _P, _P, _P, _P, _L, _L, _I, _U, _U, _P,
+                                           _P, _P, _Z, _P, C.POINTER(SampleOpts)]),
     "set_editnet_xe_forward": (_I, [C.POINTER(EditNetWeights), C.POINTER(EditNetDims), _P, _P, _P, _L,
                                     C.POINTER(C.c_int), _P, _P, _P, _P, _Z, _P]),
     "set_editnet_edit_trace_workspace_bytes": (_Z, [C.POINTER(EditNetDims), _I]),
@@ -329,6 +358,8 @@ PROTOTYPES = {
                               _P]),
     "set_dcnet_sample_opts": (_I, [C.POINTER(DcnetWeights), C.POINTER(DcnetDims), _P, _P, _L, _L, _I, _U, _U, _P, _P, _P, _Z,
                                    _P, C.POINTER(SampleOpts)]),
+    "set_dcnet_sample_gumbel": (_I, [C.POINTER(DcnetWeights), C.POINTER(DcnetDims), _P, _P, _L, _L, _I, _U, _U, _P, _P, _P, _Z,
+                                     _P, C.POINTER(SampleOpts)]),
     "set_dcnet_xe_forward": (_I, [C.POINTER(DcnetWeights), C.POINTER(DcnetDims), _P, _L, C.POINTER(C.c_int), _P, _P,
                                   _P, _P, _Z, _P]),
     "set_dcnet_xe_forward_hidden": (_I, [C.POINTER(DcnetWeights), C.POINTER(DcnetDims), _P, _L, C.POINTER(C.c_int), _P,
@@ -404,6 +435,8 @@ PROTOTYPES = {
     "set_sample_logp_bwd_f32": (_I, [_P, _L, _P, _P, _P, _P, _L, _I, _I, _P]),
     "set_sample_logp_bwd_opts_f32": (_I, [_P, _L, _P, _P, _P, _P, _P, _L, _I, _I, C.POINTER(SampleOpts), _P]),
     "set_philox4x32": (_I, [_P, _I, _U, _U, _P]),
+    "set_gumbel_pick_f32": (_I, [_P, _L, _I, _I, _I, _I, _L, _U, _U, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(SampleOpts)]),
+    "set_gumbel_fill_f32": (_I, [_P, _I, _I, _I, _U, _U, _P]),
     "set_pick_slabs_f32": (_I, [C.POINTER(PickArgs), _P]),
     "set_pick_slabs_opts_f32": (_I, [C.POINTER(PickArgs), C.POINTER(SampleOpts), _P]),
     "set_beam_pick_f32": (_I, [_P, _P, _L, _I, _I, _I, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -360,13 +360,14 @@ int set_dcnet_greedy_pick(const SetDcnetWeights* w, const SetDcnetDims* d, const
                        w->embed, W.emb, d->E, d->B, st);
 }
 
-// free-running decode (dcnet_rl.py:286-346): sample == 0 greedy, 1 multinomial
+// free-running decode (dcnet_rl.py:286-346): sample == 0 greedy, 1 multinomial (inverse CDF), 2 multinomial by the Gumbel-max draw
 static int dcnet_rollout(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* prev, const int64_t* prevlen,
                          int64_t start_idx, int64_t end_idx, int max_len, int sample, uint64_t seed, uint64_t offset,
                          int64_t* seq, float* seq_logp, void* ws, size_t ws_bytes, void* stream,
                          const SetSampleOpts* opts = nullptr) {
     if (!w || !prev || !prevlen || !seq || !seq_logp || max_len <= 0) return SET_ERR_ARG;
     SET_TRY(sample_opts_check(opts));
+    if (sample == 2) SET_TRY(gumbel_opts_check(opts, d ? d->V : 0, max_len));
     DcnetWs W;
     SET_TRY(prep(d, ws, ws_bytes, &W));
     if (max_len > d->maxT || start_idx < 0 || start_idx >= d->V) return SET_ERR_ARG;
@@ -417,7 +418,11 @@ static int dcnet_rollout(const SetDcnetWeights* w, const SetDcnetDims* d, const 
             tail.tab = w->tok_table; tail.ld_tab = 4LL * d->D + 8LL * d->C; tail.col0 = 0; tail.nrows = d->V;
             tail.c_in = W.c1; tail.c_out = W.c1; tail.h_out = W.h1; tail.D = d->D;
         }
-        if (sample)
+        if (sample == 2)
+            SET_TRY(gumbel_pick(lg, pick_bias, d->V, t, max_len, end_idx, (long long*)seq, seq_logp, W.it, W.unfinished,
+                                W.alive, emb_needed ? w->embed : nullptr, W.emb, d->E, B, seed, offset, nullptr, nullptr,
+                                nullptr, st, a_done ? &tail : nullptr, opts));
+        else if (sample)
             SET_TRY(sample_pick(lg, pick_bias, d->V, t, max_len, end_idx, (long long*)seq, seq_logp, W.it, W.unfinished,
                                 W.alive, emb_needed ? w->embed : nullptr, W.emb, d->E, B, seed, offset, nullptr, nullptr,
                                 nullptr, st, a_done ? &tail : nullptr, opts));
@@ -482,6 +487,13 @@ int set_dcnet_sample_opts(const SetDcnetWeights* w, const SetDcnetDims* d, const
                           int64_t start_idx, int64_t end_idx, int max_len, uint64_t seed, uint64_t offset, int64_t* seq,
                           float* seq_logp, void* ws, size_t ws_bytes, void* stream, const SetSampleOpts* opts) {
     return dcnet_rollout(w, d, prev, prevlen, start_idx, end_idx, max_len, 1, seed, offset, seq, seq_logp, ws, ws_bytes,
+                         stream, opts);
+}
+
+int set_dcnet_sample_gumbel(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* prev, const int64_t* prevlen,
+                            int64_t start_idx, int64_t end_idx, int max_len, uint64_t seed, uint64_t offset, int64_t* seq,
+                            float* seq_logp, void* ws, size_t ws_bytes, void* stream, const SetSampleOpts* opts) {
+    return dcnet_rollout(w, d, prev, prevlen, start_idx, end_idx, max_len, 2, seed, offset, seq, seq_logp, ws, ws_bytes,
                          stream, opts);
 }
 

@@ -184,13 +184,17 @@ struct PDecEditArgs {
     long long start_idx, end_idx;
     // teacher-forced mode (set_editnet_xe_forward, editnet.py:505-546): words from caps, scores of the first bt rows written
     // out, no pick and no sixth exchange
-    const long long* caps; long long caps_stride;
+    const long long* caps;
+    union { long long caps_stride; unsigned long long gm_seed; };       // Gumbel-max sampled mode (caps == NULL, no beam): the noise's seed,
     union {                                      // (one of the two modes: the argument block keeps its size and layout)
         float* predictions;                      // (B, maxT, V) teacher-forced mode
         const float* rmask;                      // (B, R) beam mode over adaptive features (RREG > 64): 0 = padded region
     };
-    long long ld_pred_b;
-    int dlen[PDW_MAXB];                          // decode lengths, descending
+    union { long long ld_pred_b; unsigned long long gm_offset; };       // ... its offset
+    union {
+        int dlen[PDW_MAXB];                      // decode lengths, descending
+        float gm_inv_t;                          // ... and 1 / temperature (the block keeps its size and layout, as above)
+    };
     int stamp_wg;
     unsigned long long* stamps;
     // beam mode of the wide variant (set_editnet_beam_persistent): the rows are the k hypotheses of ONE image
@@ -205,7 +209,7 @@ struct PDecEditArgs {
 
 // the wide variant's launch (decode_persistent_wide.hip); P is complete except for the exchange pointers it lays out itself
 int editnet_persistent_wide_launch(PDecEditArgs& P, void* xbuf, PersistentGuard& guard, hipStream_t s, bool* unsupported, bool beam = false,
-                                   bool wide_regions = false);
+                                   bool wide_regions = false, bool sample = false);
 size_t editnet_persistent_wide_xbytes(int B, int D, int A, int R = 0);
 // shared with the ensemble launch (decode_persistent_ensemble.hip), whose argument block embeds a PDecEditArgs: the weight /
 // dimension fields of P from (w, d, max_len); [status line | EditNet's seven exchange regions] laid out from x (returns the

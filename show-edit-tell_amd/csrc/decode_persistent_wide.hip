@@ -40,6 +40,7 @@
 // kernel's own (the ensemble kernel carries a copy): the order of its loads and the three rotating weight buffers are its
 // schedule.
 #include "beam_persistent.h"
+#include "philox.h"
 
 namespace set {
 
@@ -60,7 +61,9 @@ constexpr int pw_vcols(int rreg) { return rreg > 64 ? rreg : 64; }
 // beam search over adaptive features (editnet_adaptive.py:614-735): up to 128 zero-padded regions whose scores are masked to
 // -1e10 where P.rmask == 0 (step_attention_k), two scores per lane in the softmax.  The masked weights underflow to exactly 0,
 // which is the reference's truncation to max(att_masks.sum(1)): all rows of a beam launch are the same image.
-template <bool BEAM, int RREG>
+// SAMPLE: the greedy loop with the Gumbel-max draw (philox.h; set_editnet_gumbel_persistent) in place of the arg-max — "sampled
+// mode" below.  An arg-max over perturbed scores, so the grid combines it exactly as it combines the greedy one.
+template <bool BEAM, int RREG, bool SAMPLE = false>
 __global__ void __launch_bounds__(PDEC_THREADS, 1) editnet_persistent_wide_k(const PDecEditArgs P) {
     constexpr int RS = RREG + 1, VC = pw_vcols(RREG);
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -557,6 +560,100 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) editnet_persistent_wide_k(con
             if (sKleft == 0) break;                              // every hypothesis has ended (editnet.py:700-701)
             continue;
         }
+        if constexpr (SAMPLE) {
+            // ================= sampled mode: the word of row b is the first maximum of s[v] = y[v] + g[v], y = fl(x inv_t), g = the
+            // noise keyed by (seed, offset, b, t, v) — the per-step pick's (epilogue.hip gumbel_pick_k) definition, word for word.
+            // X6 carries per (row, slice) the four words the combine needs, in the greedy triple's region (its pad word is used):
+            // [log-sum-exp of y over the slice (max y and sum exp folded into one word) | first arg-max of s | max s | y there].
+            // A lane owns ONE vocabulary row; the slice boundaries are not quad-aligned, so every lane calls Philox for its own
+            // quad and selects its word.
+            ++tag;
+            for (int b = kq; b < B; b += 4) {
+                const int row = row0 + lane;
+                const bool ok = lane < 16 * PDEC_FC_TILES && lane < P.rpw && row < V;
+                float y = -INFINITY, sv = -INFINITY;
+                if (ok) {
+                    const int j = lane >> 4, rr = lane & 15, o = j * 256 + b * 16 + rr;
+                    const float x = (((sRed[o] + sRed[3 * 256 + o]) + sRed[6 * 256 + o]) + sRed[9 * 256 + o]) + fcb_lane;
+                    y = __fmul_rn(x, P.gm_inv_t);
+                    sv = y + gumbel_at(P.gm_seed, P.gm_offset, b, t, row);
+                }
+                const float my = pw_wmax(y);
+                float se = (ok && my > -INFINITY) ? expf(y - my) : 0.f;
+                if (ok && my == -INFINITY) se = y;                   // no finite score here: NaN scores reach the sum, as in the greedy path
+                se = pw_wsum(se);
+                const float lse = my == -INFINITY ? (se == 0.f ? -INFINITY : se) : my + logf(se);
+                float best = -INFINITY;
+                int bi = 0x7fffffff;
+                if (sv > best) { best = sv; bi = row; }
+                pw_wargmax(best, bi);
+                const float yw = bi == 0x7fffffff ? 0.f : pw_lane(y, bi - row0);
+                if (lane < 4) ll_put(fcrs, (b * G + wg) * 4 + lane, lane == 0 ? lse : (lane == 1 ? __int_as_float(bi) : (lane == 2 ? best : yw)), tag);
+            }
+            if (more) {                                              // S1' (see the greedy path)
+                acc1 = acc1n;
+                pd_mma(acc1, wc, aX);
+                acc2 = zero4;
+                pd_mma(acc2, wb, aX);
+            }
+            PW_SYNC();
+            PD_STAMP(14);
+            PW_STAGE(fcrs, sX, B * G, 4, 4);
+            PW_SYNC();
+            PD_STAMP(15);
+            // ---- every workgroup combines the G entries of every row in slice order: same word everywhere
+            for (int b = kq; b < B; b += 4) {
+                float pl[4], ps[4], py[4];
+                int pi[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int wi = lane + 64 * i;
+                    const bool have = wi < G;
+                    const f32x4 e4 = have ? *reinterpret_cast<const f32x4*>(sF + (b * G + wi) * 4) : zero4;
+                    pl[i] = have ? e4[0] : -INFINITY;
+                    pi[i] = have ? __float_as_int(e4[1]) : 0x7fffffff;
+                    ps[i] = have ? e4[2] : -INFINITY;
+                    py[i] = e4[3];
+                }
+                float best = -INFINITY, yb = 0.f;
+                int bi = 0x7fffffff;
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    if (ps[i] > best || (ps[i] == best && pi[i] < bi)) { best = ps[i]; bi = pi[i]; yb = py[i]; }
+                const int mine = bi;                                 // this lane's candidate; the winner's y travels from its lane
+                pw_wargmax(best, bi);
+                const unsigned long long own = __ballot(mine == bi && bi != 0x7fffffff);
+                const float yw = own ? pw_lane(yb, __ffsll((long long)own) - 1) : 0.f;
+                const float m = pw_wmax(fmaxf(fmaxf(pl[0], pl[1]), fmaxf(pl[2], pl[3])));
+                float tot = 0.f;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) tot += (pl[i] == -INFINITY) ? 0.f : (m == -INFINITY ? pl[i] : expf(pl[i] - m));
+                tot = pw_wsum(tot);
+                if (lane == 0) {
+                    float logp = yw - (m + logf(tot));               // log_softmax(y) at the drawn word
+                    if (bi == 0x7fffffff) { bi = 0; logp = __builtin_nanf(""); }   // all-NaN row: word 0 and a NaN log-prob
+                    long long it = bi;
+                    if (it == P.end_idx) it = 0;
+                    const int unf = (t == 0) ? (it > 0) : (sUnf[b] && it > 0);
+                    it = unf ? it : 0;
+                    if (wg == 0) {
+                        P.seq[(long long)b * P.max_len + t] = it;
+                        P.seq_logp[(long long)b * P.max_len + t] = logp;
+                        P.unfinished[b] = unf;
+                        P.it[b] = it;
+                    }
+                    sTok[b] = it;
+                    sUnf[b] = unf;
+                }
+            }
+            PW_SYNC();
+            PD_STAMP(16);
+            int alive = 0;
+            for (int b = 0; b < B; ++b) alive += sUnf[b];
+            if (wg == 0 && tid == 0) P.alive[t] = alive;
+            if (alive == 0) break;
+            continue;
+        }
         ++tag;                                                   // X6: triples
         if (worker) {
             for (int b = kq; b < B; b += 4) {
@@ -718,17 +815,19 @@ bool editnet_persistent_wide_ok(int B, int D, int A, int T, int R, int V, bool w
     return true;
 }
 
-// the three instantiations: [0] beam over up to 128 masked regions, [1] beam, [2] greedy / teacher-forced.  (Listed in the order in
+// the four instantiations: [0] beam over up to 128 masked regions, [1] beam, [2] greedy / teacher-forced, [3] Gumbel-max sampled.  (Listed in the order in
 // which the kernels have always been instantiated: the device code object stays byte for byte the same.)
 #define PWIDE_K(...) {reinterpret_cast<const void*>(&editnet_persistent_wide_k<__VA_ARGS__>)}
-static PersistentKernel g_pwide_k[3] = {PWIDE_K(true, PDEC_RREG_WIDE), PWIDE_K(true, PDEC_RREG), PWIDE_K(false, PDEC_RREG)};
+static PersistentKernel g_pwide_k[4] = {PWIDE_K(true, PDEC_RREG_WIDE), PWIDE_K(true, PDEC_RREG), PWIDE_K(false, PDEC_RREG),
+                                        PWIDE_K(false, PDEC_RREG, true)};      // [3] Gumbel-max sampled (appended: see above)
 #undef PWIDE_K
 
 int editnet_persistent_wide_launch(PDecEditArgs& P, void* xbuf, PersistentGuard& guard, hipStream_t s, bool* unsupported, bool beam,
-                                   bool wide_regions) {
+                                   bool wide_regions, bool sample) {
     *unsupported = true;
     const int B = P.B, D = P.D, A = P.A, G = D / 4;
     if (wide_regions && (!beam || !P.rmask)) return SET_OK;          // the wide instantiation is the adaptive beam search only
+    if (sample && (beam || P.caps)) return SET_OK;                   // the sampled mode is the free-running loop's only
     if (!editnet_persistent_wide_ok(B, D, A, P.T, P.R, P.V, wide_regions)) return SET_OK;
     if (beam && (B > PW_BEAM_K || P.caps || (long long)B * P.V >= 0x7fffffffLL)) return SET_OK;
     {
@@ -742,8 +841,8 @@ int editnet_persistent_wide_launch(PDecEditArgs& P, void* xbuf, PersistentGuard&
     if (lds_max > 156 * 1024) lds_max = 156 * 1024;
     if (lds > lds_max) return SET_OK;
     const double wbytes = 4.0 * ((double)P.V * D + 5.0 * 4 * D * D + 3.0 * D * D + 2.0 * A * D);
-    const int rc = pdec_launch(g_pwide_k[wide_regions ? 0 : beam ? 1 : 2], guard, G, lds, lds_max, &P, xbuf, editnet_persistent_wide_xbytes(B, D, A, P.R),
-                               s, {beam ? "persistent_beam" : "persistent_decode", 2.0 * B * wbytes / 4.0 * P.max_len, wbytes * P.max_len},
+    const int rc = pdec_launch(g_pwide_k[sample ? 3 : wide_regions ? 0 : beam ? 1 : 2], guard, G, lds, lds_max, &P, xbuf, editnet_persistent_wide_xbytes(B, D, A, P.R),
+                               s, {beam ? "persistent_beam" : sample ? "persistent_gumbel" : "persistent_decode", 2.0 * B * wbytes / 4.0 * P.max_len, wbytes * P.max_len},
                                {&P.stamps, &P.stamp_wg, 16, P.max_len});
     *unsupported = rc == SET_ERR_UNSUPPORTED;
     return *unsupported ? SET_OK : rc;
@@ -781,7 +880,7 @@ int editnet_persistent_greedy(const SetEditNetWeights* w, const SetEditNetDims* 
                               const float* att1_c, const float* mask, const float* capP, const float* memQ, const float* Mem,
                               const float* pv, void* xbuf, long long* it, int* unfinished, int* alive, long long start_idx,
                               long long end_idx, int max_len, long long* seq, float* seq_logp, hipStream_t s,
-                              const PDecTeacher* teach, const PDecBeam* beam) {
+                              const PDecTeacher* teach, const PDecBeam* beam, const PDecSample* samp) {
     const bool wide = beam && d->adaptive;              // adaptive beam search: region mask, up to 128 regions
     if (beam) {         // beam mode lives in the wide variant, whatever the row count
         if (!env_int("SET_DEC_PERSISTENT", 1) || max_len < 1 || (d->adaptive && !beam->rmask) || persistent_disabled() ||
@@ -794,11 +893,12 @@ int editnet_persistent_greedy(const SetEditNetWeights* w, const SetEditNetDims* 
     P.start_idx = start_idx; P.end_idx = end_idx;
     if (teach) pdec_teacher_fill(P, *teach);
     if (beam) { pdec_beam_fill(P, *beam); if (wide) P.rmask = beam->rmask; }
+    if (samp) { P.gm_seed = samp->seed; P.gm_offset = samp->offset; P.gm_inv_t = samp->inv_t; }
     PersistentGuard guard;
     if (guard.rc != SET_OK) return guard.rc;
     pdec_guard_fill(P, guard);
     bool unsupported = true;
-    const int rc = editnet_persistent_wide_launch(P, xbuf, guard, s, &unsupported, beam != nullptr, wide);      // (lays out the exchange region)
+    const int rc = editnet_persistent_wide_launch(P, xbuf, guard, s, &unsupported, beam != nullptr, wide, samp != nullptr);      // (lays out the exchange region)
     return rc != SET_OK ? rc : (unsupported ? SET_ERR_UNSUPPORTED : SET_OK);
 }
 

@@ -557,6 +557,8 @@ int set_editnet_greedy_pick(const SetEditNetWeights* w, const SetEditNetDims* d,
 }
 
 // free-running decode (editnet_rl.py:485-549): sample == 0 greedy (sample_max), 1 multinomial (sample_rl)
+// (inverse CDF, sample_pick), 2 multinomial by the Gumbel-max draw (gumbel_pick; per-step kernels: the persistent launch of that
+// draw is set_editnet_gumbel_persistent, which the caller tries first)
 // `begun`: the workspace already holds a completed set_editnet_begin for these inputs (the per-sequence prologue ran
 // earlier, possibly on another stream that this one has been made to wait for): only the timestep loop runs here
 static int rollout(const SetEditNetWeights* w, const SetEditNetDims* d, const float* X, const float* image_mean,
@@ -565,6 +567,7 @@ static int rollout(const SetEditNetWeights* w, const SetEditNetDims* d, const fl
                    void* stream, bool begun = false, const SetSampleOpts* opts = nullptr) {
     if (!w || !X || (!begun && (!prev || !prevlen)) || !seq || !seq_logp || max_len <= 0) return SET_ERR_ARG;
     SET_TRY(sample_opts_check(opts));
+    if (sample == 2) SET_TRY(gumbel_opts_check(opts, d ? d->V : 0, max_len));
     EditNetWs W;
     SET_TRY(prep(d, ws, ws_bytes, &W));
     if (max_len + 1 > d->maxT + 1 || start_idx < 0 || start_idx >= d->V) return SET_ERR_ARG;
@@ -628,7 +631,11 @@ static int rollout(const SetEditNetWeights* w, const SetEditNetDims* d, const fl
             tail.tab = w->tok_table; tail.ld_tab = 10LL * d->D; tail.col0 = 0; tail.nrows = d->V;
             tail.c_in = W.c1; tail.c_out = W.c1; tail.h_out = W.h1; tail.D = d->D;
         }
-        if (sample)
+        if (sample == 2)
+            SET_TRY(gumbel_pick(lg, pick_bias, d->V, t, max_len, end_idx, (long long*)seq, seq_logp, W.it, W.unfinished,
+                                W.alive, emb_needed ? w->embed : nullptr, W.emb, d->D, B, seed, offset, nullptr, nullptr,
+                                nullptr, st, a_done ? &tail : nullptr, opts));
+        else if (sample)
             SET_TRY(sample_pick(lg, pick_bias, d->V, t, max_len, end_idx, (long long*)seq, seq_logp, W.it, W.unfinished,
                                 W.alive, emb_needed ? w->embed : nullptr, W.emb, d->D, B, seed, offset, nullptr, nullptr,
                                 nullptr, st, a_done ? &tail : nullptr, opts));
@@ -709,6 +716,41 @@ int set_editnet_sample_opts(const SetEditNetWeights* w, const SetEditNetDims* d,
                             void* stream, const SetSampleOpts* opts) {
     return rollout(w, d, X, image_mean, prev, prevlen, start_idx, end_idx, max_len, 1, seed, offset, seq, seq_logp, ws,
                    ws_bytes, stream, false, opts);
+}
+
+int set_editnet_sample_gumbel(const SetEditNetWeights* w, const SetEditNetDims* d, const float* X, const float* image_mean,
+                              const int64_t* prev, const int64_t* prevlen, int64_t start_idx, int64_t end_idx, int max_len,
+                              uint64_t seed, uint64_t offset, int64_t* seq, float* seq_logp, void* ws, size_t ws_bytes,
+                              void* stream, const SetSampleOpts* opts) {
+    return rollout(w, d, X, image_mean, prev, prevlen, start_idx, end_idx, max_len, 2, seed, offset, seq, seq_logp, ws,
+                   ws_bytes, stream, false, opts);
+}
+
+// the loop of set_editnet_sample_gumbel as prologue + ONE persistent launch (decode_persistent_wide.hip, sampled mode)
+int set_editnet_gumbel_persistent(const SetEditNetWeights* w, const SetEditNetDims* d, const float* X, const float* image_mean,
+                                  const int64_t* prev, const int64_t* prevlen, int64_t start_idx, int64_t end_idx, int max_len,
+                                  uint64_t seed, uint64_t offset, int64_t* seq, float* seq_logp, void* ws, size_t ws_bytes,
+                                  void* stream, const SetSampleOpts* opts) {
+    if (!w || !d || !X || !prev || !prevlen || !seq || !seq_logp || max_len <= 0) return SET_ERR_ARG;
+    SET_TRY(gumbel_opts_check(opts, d->V, max_len));
+    if (max_len > d->maxT || start_idx < 0 || start_idx >= d->V) return SET_ERR_ARG;
+    // (nothing is touched before the checks that can answer SET_ERR_UNSUPPORTED)
+    if (!(w->tok_table && (d->D % 64 == 0) && env_int("SET_NO_FUSED", 0) == 0)) return SET_ERR_UNSUPPORTED;
+    if (!editnet_persistent_ok(d, max_len)) return SET_ERR_UNSUPPORTED;       // rows > 16, adaptive features, SET_DEC_PERSISTENT=0, ...
+    EditNetWs W;
+    SET_TRY(prep(d, ws, ws_bytes, &W));
+    hipStream_t st = (hipStream_t)stream;
+    SET_TRY(begin_impl(w, d, X, image_mean, prev, prevlen, W, st));            // (includes Pv = X x2h[:, 2D:]^T: editnet_persistent_ok holds)
+    const PDecSample samp{seed, offset, opts ? 1.0f / opts->temperature : 1.f};
+    // (a device whose LDS limit or residency turns out too small is answered by the launch itself, after these fills: the caller
+    // then runs set_editnet_sample_gumbel, which writes every output again)
+    SET_HIP_TRY(hipMemsetAsync(seq, 0, sizeof(int64_t) * d->B * max_len, st));
+    SET_HIP_TRY(hipMemsetAsync(seq_logp, 0, sizeof(float) * d->B * max_len, st));
+    SET_TRY(set_tokens(W.it, start_idx, W.unfinished, W.alive, d->maxT + 2, d->B, st));
+    const int rc = editnet_persistent_greedy(w, d, W.pre1, W.att1, W.att1_c, W.mask, W.cap_proj, W.mem_proj, W.Mem, W.pd_pv, W.pd_x,
+                                             W.it, W.unfinished, W.alive, start_idx, end_idx, max_len, (long long*)seq, seq_logp, st,
+                                             nullptr, nullptr, &samp);
+    return rc;
 }
 
 int set_editnet_xe_forward(const SetEditNetWeights* w, const SetEditNetDims* d, const float* X,

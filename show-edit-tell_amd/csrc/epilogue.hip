@@ -652,6 +652,205 @@ int sample_pick(Slabs logits, const float* bias, int V, int t, int max_len, long
     return SET_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Gumbel-max pick (include/set_hip.h "Gumbel-max draw"): the word of row b at timestep t is the FIRST maximum of
+// s[v] = y[v] + g[v], y = (logits + bias) * inv_t, g = the noise of philox.h keyed by (seed, offset, b, t, v) — exactly a draw
+// from softmax(y), and an arg-max, so it does not depend on how the vocabulary is cut over threads or workgroups: the
+// persistent launch (decode_persistent_wide.hip, SAMPLE) draws the same word from the same seed.  step_logp / lse are over
+// the unperturbed y, as in the untruncated sampled pick; the bookkeeping after the draw is sample_pick_k's.
+// One workgroup per row; a thread owns whole quads of the vocabulary (one Philox call serves four words).
+// ---------------------------------------------------------------------------------------------
+template <bool REG, bool TAIL>
+__global__ void __launch_bounds__(256) gumbel_pick_k(Slabs logits, const float* bias, int V, int t, int max_len,
+                                                     long long end_idx, long long* seq, float* seq_logp,
+                                                     long long* it_buf, int* unfinished, int* alive,
+                                                     const float* table, float* emb_out, int D,
+                                                     unsigned long long seed, unsigned long long offset,
+                                                     SampleOut so, const LstmTail tail, float inv_t) {
+    __shared__ float s_my[4], s_bs[4], s_by[4], s_sum[4];
+    __shared__ int s_bi[4];
+    __shared__ long long s_tok;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    f32x4 x[GP_MAXQ];
+    float my = -INFINITY;                    // max y
+    float bs = -INFINITY, by = 0.f;          // max s, y at its first arg-max
+    int bi = 0x7fffffff;
+    // one quad: y of its words (-inf past V), the running max y and (max s, first arg-max, y there) in ascending word order
+    auto quad = [&](int j, f32x4& y) {
+        uint32_t c[4];
+        gumbel_quad_words(seed, offset, b, t, j, c);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int v = 4 * j + e;
+            if (v < V) {
+                const float s = y[e] + gumbel_of_word(c[e]);
+                my = fmaxf(my, y[e]);
+                if (s > bs) { bs = s; bi = v; by = y[e]; }
+            } else {
+                y[e] = -INFINITY;
+            }
+        }
+    };
+    if (REG) {
+        const float* row = logits.p + (long long)b * logits.ld;
+#pragma unroll
+        for (int q = 0; q < GP_MAXQ; ++q) {
+            const int v = (tid + 256 * q) * 4;
+            x[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            if (v < V) x[q] = *reinterpret_cast<const f32x4*>(row + v);
+        }
+        for (int i = 1; i < logits.n; ++i) {             // K-slabs in index order, as sample_pick_k
+            f32x4 y[GP_MAXQ];
+#pragma unroll
+            for (int q = 0; q < GP_MAXQ; ++q) {
+                const int v = (tid + 256 * q) * 4;
+                y[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
+                if (v < V) y[q] = *reinterpret_cast<const f32x4*>(row + (long long)i * logits.stride + v);
+            }
+#pragma unroll
+            for (int q = 0; q < GP_MAXQ; ++q) x[q] += y[q];
+        }
+#pragma unroll
+        for (int q = 0; q < GP_MAXQ; ++q) {
+            const int v = (tid + 256 * q) * 4;
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (v + e < V) { if (bias) x[q][e] += bias[v + e]; x[q][e] = __fmul_rn(x[q][e], inv_t); }   // (rounded: never an fma with the noise)
+            if (v < V) quad(tid + 256 * q, x[q]);
+            else x[q] = (f32x4){-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+        }
+    } else {
+        for (int j = tid; 4 * j < V; j += 256) {
+            f32x4 y;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) y[e] = 4 * j + e < V ? __fmul_rn(logit_at(logits, bias, b, 4 * j + e), inv_t) : -INFINITY;
+            quad(j, y);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        my = fmaxf(my, __shfl_xor(my, o));
+        const float os = __shfl_xor(bs, o), oy = __shfl_xor(by, o);
+        const int oi = __shfl_xor(bi, o);
+        if (os > bs || (os == bs && oi < bi)) { bs = os; bi = oi; by = oy; }
+    }
+    if (lane == 0) { s_my[wave] = my; s_bs[wave] = bs; s_bi[wave] = bi; s_by[wave] = by; }
+    __syncthreads();
+    my = fmaxf(fmaxf(s_my[0], s_my[1]), fmaxf(s_my[2], s_my[3]));
+    bs = s_bs[0]; bi = s_bi[0]; by = s_by[0];
+#pragma unroll
+    for (int w = 1; w < 4; ++w)
+        if (s_bs[w] > bs || (s_bs[w] == bs && s_bi[w] < bi)) { bs = s_bs[w]; bi = s_bi[w]; by = s_by[w]; }
+    float sum = 0.f;
+    if (REG) {
+#pragma unroll
+        for (int q = 0; q < GP_MAXQ; ++q)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) sum += expf(x[q][e] - my);                    // exp(-inf) == 0 past V
+    } else {
+        for (int v = tid; v < V; v += 256) sum += expf(__fmul_rn(logit_at(logits, bias, b, v), inv_t) - my);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    if (lane == 0) s_sum[wave] = sum;
+    __syncthreads();
+    if (tid == 0) {
+        const float total = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
+        const float lse = my + logf(total);
+        float logp = (by - my) - logf(total);
+        int pick = bi;
+        if (pick == 0x7fffffff) { pick = 0; logp = __builtin_nanf(""); }       // no comparison succeeded: the row is all NaN
+        long long it = pick;
+        if (it == end_idx) it = 0;
+        int unf = (t == 0) ? (it > 0) : (unfinished[b] && it > 0);
+        it = unf ? it : 0;
+        const bool broken = (t > 0) && (alive[t - 1] == 0);
+        if (t < max_len && !broken) {
+            seq[(long long)b * max_len + t] = it;
+            if (seq_logp) seq_logp[(long long)b * max_len + t] = logp;
+        }
+        if (so.raw_ids) so.raw_ids[b] = broken ? -1 : (long long)pick;
+        if (so.lse) so.lse[b] = lse;
+        if (so.step_logp) so.step_logp[b] = broken ? 0.f : logp;
+        unfinished[b] = unf;
+        if (unf) atomicAdd(&alive[t], 1);
+        it_buf[b] = it;
+        s_tok = it;
+    }
+    __syncthreads();
+    if (emb_out && table) {
+        const long long tok = s_tok;
+        for (int d = tid * 4; d < D; d += 1024) {
+            f32x4 v = *reinterpret_cast<const f32x4*>(table + tok * D + d);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
+            *reinterpret_cast<f32x4*>(emb_out + (long long)b * D + d) = v;
+        }
+    }
+    if (TAIL) {
+        const float* trow = tail_row(tail, s_tok);
+        for (int j = tid * 4; j < tail.D; j += 1024) {
+            TailRegs r2;
+            TailRow w2;
+            tail_fetch(tail, b, j, r2);
+            tail_row_fetch(tail, j, trow, w2);
+            tail_finish(tail, b, j, w2, r2);
+        }
+    }
+}
+
+int gumbel_opts_check(const SetSampleOpts* opts, int V, int max_len) {
+    if (sample_opts_check(opts) != SET_OK) return SET_ERR_ARG;
+    if (opts && (opts->top_k != 0 || opts->top_p != 1.f)) return SET_ERR_ARG;       // the arg-max draw has no truncation
+    if (max_len > GUMBEL_MAX_LEN || V > GUMBEL_MAX_V) return SET_ERR_ARG;            // the noise counters (philox.h)
+    return SET_OK;
+}
+
+int gumbel_pick(Slabs logits, const float* bias, int V, int t, int max_len, long long end_idx, long long* seq,
+                float* seq_logp, long long* it, int* unfinished, int* alive, const float* table, float* emb_out, int D,
+                int B, unsigned long long seed, unsigned long long offset, long long* raw_ids, float* lse,
+                float* step_logp, hipStream_t s, const LstmTail* tail, const SetSampleOpts* opts) {
+    if (gumbel_opts_check(opts, V, max_len) != SET_OK || t > GUMBEL_MAX_LEN) return SET_ERR_ARG;
+    if (B <= 0) return SET_OK;
+    if (D & 3) return SET_ERR_UNSUPPORTED;
+    if (tail && !tail_ok(*tail)) return SET_ERR_ARG;
+    const LstmTail tl = tail ? *tail : LstmTail();
+    const float inv_t = opts ? 1.0f / opts->temperature : 1.f;
+    ProfScope ps("gumbel_pick", s, 0.0,
+                 4.0 * B * (1.0 * V * logits.n + 2.0 * D + (tail ? tl.D * (4.0 * (tl.g0.n + 2) + 3.0) : 0.0)));
+    const bool reg = V <= 4 * 256 * GP_MAXQ && !(logits.ld & 3) && !(logits.stride & 3) && aligned16(logits.p);
+    SampleOut so{raw_ids, lse, step_logp, nullptr};
+#define SET_PICK_LAUNCH(REG, TAIL)                                                                                    \
+    hipLaunchKernelGGL((gumbel_pick_k<REG, TAIL>), dim3(B), dim3(256), 0, s, logits, bias, V, t, max_len, end_idx, seq, \
+                       seq_logp, it, unfinished, alive, table, emb_out, D, seed, offset, so, tl, inv_t)
+    if (reg) { if (tail) SET_PICK_LAUNCH(true, true); else SET_PICK_LAUNCH(true, false); }
+    else { if (tail) SET_PICK_LAUNCH(false, true); else SET_PICK_LAUNCH(false, false); }
+#undef SET_PICK_LAUNCH
+    SET_LAUNCH_CHECK();
+    return SET_OK;
+}
+
+// out (rows, V) = the noise g of (seed, offset, row, t, v): the test hook of the definition in philox.h
+__global__ void __launch_bounds__(256) gumbel_fill_k(float* out, int rows, int V, int t, unsigned long long seed,
+                                                     unsigned long long offset) {
+    const int nq = (V + 3) >> 2;
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;       // (row, quad)
+    if (i >= (long long)rows * nq) return;
+    const int row = (int)(i / nq), j = (int)(i % nq);
+    uint32_t c[4];
+    gumbel_quad_words(seed, offset, row, t, j, c);
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        if (4 * j + e < V) out[(long long)row * V + 4 * j + e] = gumbel_of_word(c[e]);
+}
+
+int gumbel_fill(float* out, int rows, int V, int t, unsigned long long seed, unsigned long long offset, hipStream_t s) {
+    const long long n = (long long)rows * ((V + 3) >> 2);
+    hipLaunchKernelGGL(gumbel_fill_k, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, out, rows, V, t, seed, offset);
+    SET_LAUNCH_CHECK();
+    return SET_OK;
+}
+
 // d logits[b, v] = g[b] * (1[v == id_b] - softmax(logits[b])[v])   (gradient of the gathered log-softmax;
 // rows with id < 0 — steps after the loop was left — get zeros)
 __global__ void __launch_bounds__(256) sample_logp_bwd_k(const float* logits, long long ld, const float* lse,

@@ -576,6 +576,27 @@ int set_sample_logp_bwd_opts_f32(const float* logits, int64_t ld_logits, const f
                                 opts, (hipStream_t)stream);
 }
 
+// ---- the Gumbel-max pick as an operator, and its noise (philox.h)
+int set_gumbel_pick_f32(const float* logits, int64_t ld_logits, int B, int V, int t, int max_len, int64_t end_idx,
+                        uint64_t seed, uint64_t offset, int64_t* seq, int64_t* it, int32_t* unfinished, int32_t* alive,
+                        int64_t* raw_ids, float* lse, float* step_logp, void* stream, const SetSampleOpts* opts) {
+    if (!logits || !seq || !it || !unfinished || !alive || B <= 0 || V <= 0 || t < 0 || max_len <= 0 || ld_logits < V)
+        return SET_ERR_ARG;
+    SET_TRY(gumbel_opts_check(opts, V, max_len));
+    if (t > 255) return SET_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (t == 0) SET_TRY(set_tokens((long long*)it, 0, unfinished, alive, max_len + 2, B, st));
+    Slabs lg{logits, 0, ld_logits, 1};
+    return gumbel_pick(lg, nullptr, V, t, max_len, end_idx, (long long*)seq, nullptr, (long long*)it, unfinished, alive,
+                       nullptr, nullptr, 4, B, seed, offset, (long long*)raw_ids, lse, step_logp, st, nullptr, opts);
+}
+
+int set_gumbel_fill_f32(float* out, int rows, int V, int t, uint64_t seed, uint64_t offset, void* stream) {
+    if (!out || rows <= 0 || V <= 0 || t < 0 || t > 255) return SET_ERR_ARG;
+    SET_TRY(gumbel_opts_check(nullptr, V, 1));
+    return gumbel_fill(out, rows, V, t, seed, offset, (hipStream_t)stream);
+}
+
 int set_philox4x32(uint32_t* out, int n, uint64_t seed, uint64_t offset, void* stream) {
     if (!out || n < 0) return SET_ERR_ARG;
     return philox_fill(out, n, seed, offset, (hipStream_t)stream);

@@ -292,6 +292,8 @@ struct PDecTeacher { const int64_t* caps; long long caps_stride; float* predicti
                      float* last_h2 = nullptr; };
 // beam mode (one image, rows = hypotheses); rmask != NULL: adaptive features (region mask (B, R), up to PDEC_RREG_WIDE regions)
 struct PDecBeam { int* hist_par; int64_t* hist_word; float* best_score; int64_t* best_word; int* result; const float* rmask = nullptr; float* hist_score = nullptr; };
+// Gumbel-max sampled mode of EditNet's launch (set_editnet_gumbel_persistent): the key of the noise and 1 / temperature
+struct PDecSample { unsigned long long seed, offset; float inv_t; };
 // decode_persistent.hip: the greedy loop of a small batch as one launch with grid barriers
 constexpr int PDEC_MAXB = 8;          // rows of the <= 8-row persistent decode kernels
 constexpr int PDW_MAXB = 16;          // rows of the wide EditNet variant (decode_persistent_wide.hip): one full 16-row MFMA tile
@@ -312,7 +314,7 @@ int editnet_persistent_greedy(const SetEditNetWeights* w, const SetEditNetDims* 
                               const float* att1_c, const float* mask, const float* capP, const float* memQ, const float* Mem,
                               const float* pv, void* xbuf, long long* it, int* unfinished, int* alive, long long start_idx,
                               long long end_idx, int max_len, long long* seq, float* seq_logp, hipStream_t s,
-                              const PDecTeacher* teach = nullptr, const PDecBeam* beam = nullptr);
+                              const PDecTeacher* teach = nullptr, const PDecBeam* beam = nullptr, const PDecSample* samp = nullptr);
 
 // decode_persistent_ensemble.hip: the EditNet + DCNet ensemble's beam search of one image as one launch.  The model halves of
 // its host side live with their models (editnet.hip / dcnet.hip): `check` answers what set_*_beam_persistent answers before
@@ -446,6 +448,15 @@ inline int sample_opts_check(const SetSampleOpts* o) {
 inline bool sample_opts_neutral(const SetSampleOpts* o) {
     return !o || (o->temperature == 1.f && o->top_k == 0 && o->top_p == 1.f);
 }
+// Gumbel-max pick (epilogue.hip gumbel_pick_k; the draw: philox.h): the arguments of sample_pick; opts carries the temperature only.
+// gumbel_opts_check: what every Gumbel entry refuses with SET_ERR_ARG before any HIP call (options sample_opts_check refuses,
+// top_k != 0, top_p != 1, max_len > 255, V beyond the noise counters)
+int gumbel_opts_check(const SetSampleOpts* opts, int V, int max_len);
+int gumbel_pick(Slabs logits, const float* bias, int V, int t, int max_len, long long end_idx, long long* seq,
+                float* seq_logp, long long* it, int* unfinished, int* alive, const float* table, float* emb_out, int D,
+                int B, unsigned long long seed, unsigned long long offset, long long* raw_ids, float* lse,
+                float* step_logp, hipStream_t s, const LstmTail* tail = nullptr, const SetSampleOpts* opts = nullptr);
+int gumbel_fill(float* out, int rows, int V, int t, unsigned long long seed, unsigned long long offset, hipStream_t s);
 int sample_logp_bwd(const float* logits, long long ld, const float* lse, const long long* ids, const float* g,
                     float* dlogits, long long ldd, int B, int V, hipStream_t s);
 // the same under options and a recorded kept set (kept_key NULL: every word), any number of rows in one launch

@@ -19,11 +19,15 @@ class DAE(_DAE_XE):
     max_len = 18
 
     def forward(self, word_map, encoded_previous_captions, previous_cap_length, sample_max=True, sample_rl=False,
-                temperature=1.0, top_k=0, top_p=1.0):
-        """temperature / top_k / top_p: see editnet_rl.DecoderC.forward (no-grad sampled rollout only)"""
+                temperature=1.0, top_k=0, top_p=1.0, sampler="cdf"):
+        """temperature / top_k / top_p / sampler: see editnet_rl.DecoderC.forward (no-grad sampled rollout only; "gumbel" runs on
+        the per-step kernels here)"""
+        if sampler != "cdf":
+            _lib.check_sampler_name(sampler, top_k, top_p)
         _require_cuda(encoded_previous_captions, "previous captions")
         opts = _lib.sample_opts(temperature, top_k, top_p)
         grad_path = self._grad_path()
+        gumbel = _lib.check_sampler(sampler, opts, sample_max, sample_rl, grad_path)
         if opts is not None:
             _lib.refuse_sample_opts(sample_max, sample_rl, grad_path)
         if grad_path:
@@ -42,10 +46,12 @@ class DAE(_DAE_XE):
             if sample_rl:        # multinomial sampling, eval mode, no gradients: fused device loop, Philox epilogue
                 from . import rng
                 # (a NULL SetSampleOpts* is the call without options, bit for bit: include/set_hip.h)
-                check(lib.set_dcnet_sample_opts(C.byref(w), C.byref(dims), ptr(prev), ptr(plen), int(word_map['<start>']),
-                                                int(word_map['<end>']), max_len, rng.next_seed(), rng.offset(rng.SITE_ROLLOUT),
-                                                ptr(seq), ptr(seq_logp), ptr(ws), ws.numel(), stream_of(dev),
-                                                C.byref(opts) if opts is not None else None), "set_dcnet_sample_opts")
+                fn, name = ((lib.set_dcnet_sample_gumbel, "set_dcnet_sample_gumbel") if gumbel else
+                            (lib.set_dcnet_sample_opts, "set_dcnet_sample_opts"))
+                check(fn(C.byref(w), C.byref(dims), ptr(prev), ptr(plen), int(word_map['<start>']),
+                         int(word_map['<end>']), max_len, rng.next_seed(), rng.offset(rng.SITE_ROLLOUT),
+                         ptr(seq), ptr(seq_logp), ptr(ws), ws.numel(), stream_of(dev),
+                         C.byref(opts) if opts is not None else None), name)
                 return seq, seq_logp
             check(lib.set_dcnet_greedy(C.byref(w), C.byref(dims), ptr(prev), ptr(plen), int(word_map['<start>']),
                                        int(word_map['<end>']), max_len, ptr(seq), ptr(seq_logp), ptr(ws), ws.numel(),

@@ -27,14 +27,19 @@ class DecoderC(_DecoderXE):
     max_len = 18
 
     def forward(self, word_map, encoded_previous_captions, previous_cap_length, image_features, sample_max=True,
-                sample_rl=False, image_mean=None, repeat_images=1, temperature=1.0, top_k=0, top_p=1.0):
+                sample_rl=False, image_mean=None, repeat_images=1, temperature=1.0, top_k=0, top_p=1.0, sampler="cdf"):
         """repeat_images = n (an extension for BASELINE.json configs[4], n sampled rollouts per image): `image_features`
         holds B images while the captions hold n * B rows, sample-major (row s * B + b belongs to image b).
         temperature / top_k / top_p (include/set_hip.h SetSampleOpts; 1 / 0 / 1 are neutral): the distribution the no-grad
-        sampled rollout (sample_rl=True, sample_max=False) draws every word from; seqLogprobs are taken under it."""
+        sampled rollout (sample_rl=True, sample_max=False) draws every word from; seqLogprobs are taken under it.
+        sampler: "cdf" (default, the inverse-CDF draw) or "gumbel" (the Gumbel-max draw of include/set_hip.h: temperature only,
+        no-grad only; 1 .. 16 rows run as one persistent launch, anything else on the per-step kernels with the same draws)."""
+        if sampler != "cdf":
+            _lib.check_sampler_name(sampler, top_k, top_p)
         _require_cuda(image_features, "image features")
         opts = _lib.sample_opts(temperature, top_k, top_p)
         grad_path = self._grad_path()
+        gumbel = _lib.check_sampler(sampler, opts, sample_max, sample_rl, grad_path)
         if opts is not None:
             _lib.refuse_sample_opts(sample_max, sample_rl, grad_path)
         if grad_path:
@@ -47,7 +52,7 @@ class DecoderC(_DecoderXE):
         # the row limits hold around the whole enqueue, the paths that pick up work run ahead included
         with self._row_limits_scope(lib, image_features.shape[0]):
             return self._decode_nograd(lib, word_map, encoded_previous_captions, previous_cap_length, image_features,
-                                       sample_rl, image_mean, opts)
+                                       sample_rl, image_mean, opts, gumbel)
 
     def sample_rollout(self, word_map, encoded_previous_captions, previous_cap_length, image_features, image_mean=None,
                        repeat_images=1, temperature=1.0, top_k=0, top_p=1.0):
@@ -58,7 +63,7 @@ class DecoderC(_DecoderXE):
                                     dict(image_mean=image_mean, repeat_images=repeat_images), temperature, top_k, top_p)
 
     def _decode_nograd(self, lib, word_map, encoded_previous_captions, previous_cap_length, image_features, sample_rl,
-                       image_mean, opts=None):
+                       image_mean, opts=None, gumbel=False):
         dev = image_features.device
         X = _f32c(image_features)
         prev = _i64c(encoded_previous_captions)
@@ -99,6 +104,19 @@ class DecoderC(_DecoderXE):
         if sample_rl:        # multinomial sampling, eval mode, no gradients: fused device loop with the Philox epilogue
             from . import rng
             seed = rng.next_seed()                                      # torch.manual_seed() makes it reproducible
+            if gumbel:
+                # one persistent launch where it applies (1 .. 16 rows, fixed features, token table), the per-step loop with
+                # the same draws otherwise
+                args = (C.byref(w), C.byref(dims), ptr(X), ptr(mean), ptr(prev), ptr(plen), int(word_map['<start>']),
+                        int(word_map['<end>']), max_len, seed, rng.offset(rng.SITE_ROLLOUT), ptr(seq), ptr(seq_logp), ptr(ws),
+                        ws.numel(), stream_of(dev), C.byref(opts) if opts is not None else None)
+                rc = lib.set_editnet_gumbel_persistent(*args)
+                if rc == 2:                              # SET_ERR_UNSUPPORTED: nothing was touched
+                    rc = lib.set_editnet_sample_gumbel(*args)
+                    check(rc, "set_editnet_sample_gumbel")
+                else:
+                    check(rc, "set_editnet_gumbel_persistent")
+                return seq, seq_logp
             # (a NULL SetSampleOpts* is the call without options, bit for bit: include/set_hip.h)
             check(lib.set_editnet_sample_opts(C.byref(w), C.byref(dims), ptr(X), ptr(mean), ptr(prev), ptr(plen),
                                               int(word_map['<start>']), int(word_map['<end>']), max_len, seed,

@@ -540,7 +540,7 @@ class EditTrace:
 
 
 @torch.no_grad()
-def sample_captions(model, *inputs_and_word_map, n_samples=5, temperature=1.0, top_k=0, top_p=1.0):
+def sample_captions(model, *inputs_and_word_map, n_samples=5, temperature=1.0, top_k=0, top_p=1.0, sampler="cdf"):
     """n_samples sampled captions per image from ONE fused rollout:
         seq, seq_logp = sample_captions(decoder, image_features, previous_caption, prev_caplen, word_map, n_samples=5, top_p=0.9)
         seq, seq_logp = sample_captions(dae, previous_caption, prev_caplen, word_map, temperature=0.8, top_k=50)
@@ -548,7 +548,9 @@ def sample_captions(model, *inputs_and_word_map, n_samples=5, temperature=1.0, t
     (dcnet_rl.DAE) the caption pair only.  Every image's rows are repeated n_samples times (row i * n_samples + j is sample j of
     image i): the rows differ in their index, hence in their Philox counters, hence in their draws.  Returns seq (NI, n_samples,
     max_len) int64 and seq_logp (NI, n_samples, max_len), the log-probs under the tempered / truncated distribution sampled
-    from.  The seed comes from rng.next_seed() as in the models' own sampled path: torch.manual_seed() reproduces a call."""
+    from.  The seed comes from rng.next_seed() as in the models' own sampled path: torch.manual_seed() reproduces a call.
+    sampler="gumbel": the Gumbel-max draw (temperature only) — for EditNet and n_samples * NI <= 16 rows the whole rollout is one
+    persistent launch; "cdf" (default) is the inverse-CDF draw with its draws unchanged."""
     *inputs, word_map = inputs_and_word_map
     if len(inputs) not in (2, 3):
         raise ValueError("sample_captions(model, [image_features,] previous_caption, prev_caplen, word_map, ...)")
@@ -559,6 +561,8 @@ def sample_captions(model, *inputs_and_word_map, n_samples=5, temperature=1.0, t
     prev = inputs[-2].long().repeat_interleave(n, 0).contiguous()
     plen = inputs[-1].reshape(-1).long().repeat_interleave(n, 0).contiguous()
     kw = dict(sample_max=False, sample_rl=True, temperature=temperature, top_k=top_k, top_p=top_p)
+    if sampler != "cdf":
+        kw["sampler"] = sampler
     if len(inputs) == 3:
         X = inputs[0].float().repeat_interleave(n, 0).contiguous()
         seq, logp = model(word_map, prev, plen, X, **kw)
