@@ -484,12 +484,28 @@ int set_dcnet_sample_opts(const SetDcnetWeights* w, const SetDcnetDims* d, const
                           const int64_t* prevlen, int64_t start_idx, int64_t end_idx, int max_len, uint64_t seed,
                           uint64_t offset, int64_t* seq, float* seq_logp, void* ws, size_t ws_bytes, void* stream,
                           const SetSampleOpts* opts);
-/* the loop of set_dcnet_sample_opts with the Gumbel-max draw (the contract above set_editnet_sample_gumbel; per-step kernels:
- * DCNet's persistent launch and the ensemble's have no sampled mode) */
+/* the loop of set_dcnet_sample_opts with the Gumbel-max draw (the contract above set_editnet_sample_gumbel), on the per-step
+ * kernels */
 int set_dcnet_sample_gumbel(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* prev,
                             const int64_t* prevlen, int64_t start_idx, int64_t end_idx, int max_len, uint64_t seed,
                             uint64_t offset, int64_t* seq, float* seq_logp, void* ws, size_t ws_bytes, void* stream,
                             const SetSampleOpts* opts);
+/* The same loop as prologue + ONE persistent launch (csrc/decode_persistent.hip, sampled mode) for 1 .. 8 rows and an active
+ * token table: every workgroup forms the noise of its own vocabulary rows and publishes, per (row, slice), the slice's
+ * log-sum-exp of y, the first arg-max of s, max s and y there (the four words of the greedy launch's fc exchange); every
+ * workgroup combines the slices in slice order.  Tokens are those of set_dcnet_sample_gumbel for the same (seed, offset) wherever
+ * the two routes' logits (equal to 1e-4) do not bring the two largest perturbed scores within that distance; seq_logp agrees to
+ * 1e-4.  A timed-out exchange poisons seq_logp with NaN and seq with 0 (SET_ERR_FAULT at the next call), as in the greedy launch.
+ * SET_ERR_UNSUPPORTED (take set_dcnet_sample_gumbel), answered BEFORE anything is touched: no token table, more than 8 rows,
+ * dimensions the launch does not cover, SET_DEC_PERSISTENT=0, row limits in force (set_decode_row_limits), another process owns
+ * the device's persistent launches.  Only a device whose LDS limit or resident-workgroup capacity turns out too small is answered
+ * after the prologue has been written into `ws` and seq / seq_logp have been cleared.  SET_ERR_ARG: as above set_editnet_sample_gumbel,
+ * and max_len > d->maxT.
+ * Parity: tests/test_hip_dcnet_gumbel_persistent.py. */
+int set_dcnet_gumbel_persistent(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* prev,
+                                const int64_t* prevlen, int64_t start_idx, int64_t end_idx, int max_len, uint64_t seed,
+                                uint64_t offset, int64_t* seq, float* seq_logp, void* ws, size_t ws_bytes, void* stream,
+                                const SetSampleOpts* opts);
 int set_dcnet_xe_forward(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* caps,
                          int64_t caps_stride, const int* host_decode_lengths, const int64_t* prev,
                          const int64_t* prevlen, float* predictions, void* ws, size_t ws_bytes,

@@ -360,6 +360,8 @@ PROTOTYPES = {
                                    _P, C.POINTER(SampleOpts)]),
     "set_dcnet_sample_gumbel": (_I, [C.POINTER(DcnetWeights), C.POINTER(DcnetDims), _P, _P, _L, _L, _I, _U, _U, _P, _P, _P, _Z,
                                      _P, C.POINTER(SampleOpts)]),
+    "set_dcnet_gumbel_persistent": (_I, [C.POINTER(DcnetWeights), C.POINTER(DcnetDims), _P, _P, _L, _L, _I, _U, _U, _P, _P, _P, _Z,
+                                         _P, C.POINTER(SampleOpts)]),
     "set_dcnet_xe_forward": (_I, [C.POINTER(DcnetWeights), C.POINTER(DcnetDims), _P, _L, C.POINTER(C.c_int), _P, _P,
                                   _P, _P, _Z, _P]),
     "set_dcnet_xe_forward_hidden": (_I, [C.POINTER(DcnetWeights), C.POINTER(DcnetDims), _P, _L, C.POINTER(C.c_int), _P,

@@ -361,6 +361,7 @@ int set_dcnet_greedy_pick(const SetDcnetWeights* w, const SetDcnetDims* d, const
 }
 
 // free-running decode (dcnet_rl.py:286-346): sample == 0 greedy, 1 multinomial (inverse CDF), 2 multinomial by the Gumbel-max draw
+// (gumbel_pick; per-step kernels: the persistent launch of that draw is set_dcnet_gumbel_persistent, which the caller tries first)
 static int dcnet_rollout(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* prev, const int64_t* prevlen,
                          int64_t start_idx, int64_t end_idx, int max_len, int sample, uint64_t seed, uint64_t offset,
                          int64_t* seq, float* seq_logp, void* ws, size_t ws_bytes, void* stream,
@@ -495,6 +496,31 @@ int set_dcnet_sample_gumbel(const SetDcnetWeights* w, const SetDcnetDims* d, con
                             float* seq_logp, void* ws, size_t ws_bytes, void* stream, const SetSampleOpts* opts) {
     return dcnet_rollout(w, d, prev, prevlen, start_idx, end_idx, max_len, 2, seed, offset, seq, seq_logp, ws, ws_bytes,
                          stream, opts);
+}
+
+// the loop of set_dcnet_sample_gumbel as prologue + ONE persistent launch (decode_persistent.hip, sampled mode)
+int set_dcnet_gumbel_persistent(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* prev, const int64_t* prevlen,
+                                int64_t start_idx, int64_t end_idx, int max_len, uint64_t seed, uint64_t offset, int64_t* seq,
+                                float* seq_logp, void* ws, size_t ws_bytes, void* stream, const SetSampleOpts* opts) {
+    if (!w || !d || !prev || !prevlen || !seq || !seq_logp || max_len <= 0) return SET_ERR_ARG;
+    SET_TRY(gumbel_opts_check(opts, d->V, max_len));
+    if (max_len > d->maxT || start_idx < 0 || start_idx >= d->V) return SET_ERR_ARG;
+    SET_TRY(check_dims(d));
+    // (nothing is touched before the checks that can answer SET_ERR_UNSUPPORTED)
+    if (!table_active(w, d)) return SET_ERR_UNSUPPORTED;
+    if (g_row_limit || !dcnet_persistent_ok(d, max_len)) return SET_ERR_UNSUPPORTED;   // rows > 8, SET_DEC_PERSISTENT=0, dims, row limits
+    DcnetWs W;
+    SET_TRY(prep(d, ws, ws_bytes, &W));
+    hipStream_t st = (hipStream_t)stream;
+    SET_TRY(begin_impl(w, d, prev, prevlen, W, st));              // (includes Pc = enc W_ih[:, D:]^T: dcnet_persistent_ok holds)
+    const PDecSample samp{seed, offset, opts ? 1.0f / opts->temperature : 1.f};
+    // (a device whose LDS limit or residency turns out too small is answered by the launch itself, after these fills: the caller
+    // then runs set_dcnet_sample_gumbel, which writes every output again)
+    SET_HIP_TRY(hipMemsetAsync(seq, 0, sizeof(int64_t) * d->B * max_len, st));
+    SET_HIP_TRY(hipMemsetAsync(seq_logp, 0, sizeof(float) * d->B * max_len, st));
+    SET_TRY(set_tokens(W.it, start_idx, W.unfinished, W.alive, d->maxT + 2, d->B, st));
+    return dcnet_persistent_greedy(w, d, W.pre1, W.att1_c, W.mask, W.pd_pc, W.pd_x, W.it, W.unfinished, W.alive, start_idx, end_idx,
+                                   max_len, (long long*)seq, seq_logp, st, nullptr, nullptr, &samp);
 }
 
 // dcnet_with_mse.py:321,341 (`decoder_last_hidden[:batch_size_t] = h2.clone()` at every step): last_hidden (B, D, sorted

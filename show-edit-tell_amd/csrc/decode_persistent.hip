@@ -27,6 +27,9 @@
 // are contracted while the fc triples of timestep t travel (S1'), and the B <= 4 variant has no loop around its per-row work.
 // Teacher-forced mode (set_dcnet_xe_forward): words from the captions, scores written by the owners of the vocabulary rows,
 // three exchanges.
+// Sampled mode (set_dcnet_gumbel_persistent): the free-running loop with the Gumbel-max draw (philox.h) in place of the arg-max —
+// the fc exchange's four words per (row, slice) carry (log-sum-exp of y, first arg-max of y + g, max of y + g, y there); same
+// exchanges, same LDS.
 // Same residency rule, fault word and event chain as the persistent encoder (grid_barrier.h PersistentGuard).  A poll that
 // times out poisons seq_logp with NaN; the host raises SET_ERR_FAULT at its next call.
 // Shared with the other two persistent decode kernels: the beam mode's pick (beam_persistent.h) and, on the host, the launch
@@ -35,6 +38,7 @@
 // DCNet half).  Deliberately NOT shared: the phase code of the timestep — where a tile's loads sit between
 // the MFMAs is the schedule, and a function boundary there changes the instructions of a kernel at the register ceiling.
 #include "beam_persistent.h"
+#include "philox.h"
 
 namespace set {
 
@@ -80,7 +84,11 @@ struct PDecDcnetArgs {
     float* bm_best_score;                        // [1] best completed hypothesis (-inf: none)
     long long* bm_best_word;                     // [1] its last word (<end>)
     int* bm_result;                              // [4] pick index and parent slot of the best completed hypothesis, k_left, picks made
-    float* bm_hist_score;                        // (max_len, 4) or NULL: value of every counted pick, -inf elsewhere (n-best).  Last member
+    float* bm_hist_score;                        // (max_len, 4) or NULL: value of every counted pick, -inf elsewhere (n-best)
+    // sampled mode (SAMPLE, set_dcnet_gumbel_persistent): key of the Gumbel noise (philox.h) and 1 / temperature.  After
+    // bm_hist_score, for the same reason
+    unsigned long long gm_seed, gm_offset;
+    float gm_inv_t;
 };
 
 // RES: B <= 4 and T <= PDEC_TREG — a wave scores ONE fixed row, whose hoisted cap_features_att rows (loop-invariant, T x A
@@ -102,8 +110,11 @@ struct PDecDcnetArgs {
 // and need no permutation.  The per-sequence operands (pre1, att1_c, mask, pc) are REPLICATED k times by the prologue, as
 // on the EditNet path (the rows of the workspace hold the image's previous caption k times).  A template parameter, not a
 // runtime test, like LH.
-template <bool RES, bool LH = false, bool BEAM = false>
+// SAMPLE: free-running only, without LH and BEAM; the greedy loop with the Gumbel-max draw (philox.h; set_dcnet_gumbel_persistent)
+// in place of the arg-max epilogue (X4 / S6) — "sampled mode" below.  A template parameter, not a runtime test, like LH and BEAM.
+template <bool RES, bool LH = false, bool BEAM = false, bool SAMPLE = false>
 __global__ void __launch_bounds__(PDEC_THREADS, 1) dcnet_persistent_k(const PDecDcnetArgs P) {
+    static_assert(!SAMPLE || (!LH && !BEAM), "the sampled mode is the free-running greedy loop's only");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __shared__ long long sTok[PDEC_MAXB];
     __shared__ int sUnf[PDEC_MAXB];
@@ -223,13 +234,13 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) dcnet_persistent_k(const PDec
         PD_STAMP(0);
         float tg[4] = {0.f, 0.f, 0.f, 0.f};
         int bt = B;                                              // teacher-forced: rows whose caption is still running (sorted batch)
-        if (!BEAM && P.caps) {
+        if (!BEAM && !SAMPLE && P.caps) {
             bt = 0;
             for (int b = 0; b < B; ++b) bt += P.dlen[b] > t ? 1 : 0;
             if (bt == 0) break;
         }
         if (pair) {
-            long long tok = (!BEAM && P.caps) ? P.caps[(long long)pb * P.caps_stride + t] : sTok[pb];
+            long long tok = (!BEAM && !SAMPLE && P.caps) ? P.caps[(long long)pb * P.caps_stride + t] : sTok[pb];
             tok = tok < 0 ? 0 : (tok >= V ? V - 1 : tok);          // same clamp as embed_relu_k
             const float* trow = P.tok_table + tok * P.ld_tab + u0 + pu;
 #pragma unroll
@@ -385,7 +396,7 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) dcnet_persistent_k(const PDec
             sRed[(kq * 3 + 2) * 256 + (4 * g + e) * 16 + r] = accf2[e];
         }
         __syncthreads();
-        if (!BEAM && P.caps) {
+        if (!BEAM && !SAMPLE && P.caps) {
             // teacher-forced: the scores themselves, rows 0 .. bt - 1 (dcnet.py:347: predictions[:batch_size_t, t, :] = preds)
             for (int b = kq; b < bt; b += 4) {
                 const int j = lane >> 4, rr = lane & 15, row = row0 + lane;
@@ -487,6 +498,109 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) dcnet_persistent_k(const PDec
             if (sKleft[0] == 0) break;                           // every hypothesis has ended (dcnet.py:507-508)
             continue;
         }
+        if constexpr (SAMPLE) {
+            // ================= sampled mode: the word of row b is the first maximum of s[v] = y[v] + g[v], y = fl(x inv_t), g = the
+            // noise keyed by (seed, offset, b, t, v) — the per-step pick's (epilogue.hip gumbel_pick_k) and
+            // editnet_persistent_wide_k<SAMPLE>'s definition, word for word.  X4 keeps its four words per (row, slice) and its
+            // region; they carry [log-sum-exp of y over the slice (max y and sum exp folded into one word) | first arg-max of s |
+            // max s | y there].  A lane owns ONE vocabulary row; the slice boundaries are not quad-aligned, so every lane calls
+            // Philox for its own quad and selects its word.  (After the timestep's last fc MFMA and before S1': only the two
+            // tiles of S1' are in flight.)
+            ++tag;
+            {   // (resident variant: one row per wave, no loop — see the attention phase)
+                auto row_work = [&](const int b) {
+                    const int row = row0 + lane;
+                    const bool ok = lane < 16 * PDEC_FC_TILES && lane < P.rpw && row < V;
+                    float y = -INFINITY, sv = -INFINITY;
+                    if (ok) {
+                        const int j = lane >> 4, rr = lane & 15, o = j * 256 + b * 16 + rr;
+                        const float x = (((sRed[o] + sRed[3 * 256 + o]) + sRed[6 * 256 + o]) + sRed[9 * 256 + o]) + fcb_lane;
+                        y = __fmul_rn(x, P.gm_inv_t);
+                        sv = y + gumbel_at(P.gm_seed, P.gm_offset, b, t, row);
+                    }
+                    const float my = pw_wmax(y);
+                    float se = (ok && my > -INFINITY) ? expf(y - my) : 0.f;
+                    if (ok && my == -INFINITY) se = y;                   // no finite score here: NaN scores reach the sum, as in the greedy path
+                    se = pw_wsum(se);
+                    const float lse = my == -INFINITY ? (se == 0.f ? -INFINITY : se) : my + logf(se);
+                    float best = -INFINITY;
+                    int bi = 0x7fffffff;
+                    if (sv > best) { best = sv; bi = row; }
+                    pw_wargmax(best, bi);
+                    const float yw = bi == 0x7fffffff ? 0.f : pw_lane(y, bi - row0);
+                    if (lane < 4) ll_put(fcrs, (b * G + wg) * 4 + lane, lane == 0 ? lse : (lane == 1 ? __int_as_float(bi) : (lane == 2 ? best : yw)), tag);
+                };
+                if constexpr (RES) { if (kq < B) row_work(kq); }
+                else { for (int b = kq; b < B; b += 4) row_work(b); }
+            }
+            PD_STAMP(11);
+            if (more) {                                              // S1' (see the greedy path)
+                acc1 = zero4; acc2 = zero4;
+                pd_mma(acc1, wb, aH2);
+                pd_load(wb, pT2);
+                pd_mma(acc1, wa, aH1);
+                pd_mma(acc2, wb, aH2);
+            }
+            PD_STAMP(12);
+            ll_stage<256, 8>(fcrs, sF, B * G, 4, 4, tag, watch, tid);
+            __syncthreads();
+            // ---- every workgroup combines the G entries of every row in slice order: same word everywhere
+            {
+                auto row_work = [&](const int b) {
+                    float pl[4], ps[4], py[4];
+                    int pi[4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const int wi = lane + 64 * i;
+                        const bool have = wi < G;
+                        const f32x4 e4 = have ? *reinterpret_cast<const f32x4*>(sF + (b * G + wi) * 4) : zero4;
+                        pl[i] = have ? e4[0] : -INFINITY;
+                        pi[i] = have ? __float_as_int(e4[1]) : 0x7fffffff;
+                        ps[i] = have ? e4[2] : -INFINITY;
+                        py[i] = e4[3];
+                    }
+                    float best = -INFINITY, yb = 0.f;
+                    int bi = 0x7fffffff;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        if (ps[i] > best || (ps[i] == best && pi[i] < bi)) { best = ps[i]; bi = pi[i]; yb = py[i]; }
+                    const int mine = bi;                             // this lane's candidate; the winner's y travels from its lane
+                    pw_wargmax(best, bi);
+                    const unsigned long long own = __ballot(mine == bi && bi != 0x7fffffff);
+                    const float yw = own ? pw_lane(yb, __ffsll((long long)own) - 1) : 0.f;
+                    const float m = pw_wmax(fmaxf(fmaxf(pl[0], pl[1]), fmaxf(pl[2], pl[3])));
+                    float tot = 0.f;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) tot += (pl[i] == -INFINITY) ? 0.f : (m == -INFINITY ? pl[i] : expf(pl[i] - m));
+                    tot = pw_wsum(tot);
+                    if (lane == 0) {
+                        float logp = yw - (m + logf(tot));           // log_softmax(y) at the drawn word
+                        if (bi == 0x7fffffff) { bi = 0; logp = __builtin_nanf(""); }   // all-NaN row: word 0 and a NaN log-prob
+                        long long it = bi;
+                        if (it == P.end_idx) it = 0;
+                        const int unf = (t == 0) ? (it > 0) : (sUnf[b] && it > 0);
+                        it = unf ? it : 0;
+                        if (wg == 0) {
+                            P.seq[(long long)b * P.max_len + t] = it;
+                            P.seq_logp[(long long)b * P.max_len + t] = logp;
+                            P.unfinished[b] = unf;
+                            P.it[b] = it;
+                        }
+                        sTok[b] = it;
+                        sUnf[b] = unf;
+                    }
+                };
+                if constexpr (RES) { if (kq < B) row_work(kq); }
+                else { for (int b = kq; b < B; b += 4) row_work(b); }
+            }
+            __syncthreads();
+            PD_STAMP(13);
+            int alive = 0;
+            for (int b = 0; b < B; ++b) alive += sUnf[b];
+            if (wg == 0 && tid == 0) P.alive[t] = alive;
+            if (alive == 0) break;                                    // dcnet_rl.py:341-342: every caption has ended
+            continue;
+        }
         ++tag;                                                   // X4: (max, arg-max, sum exp) of every workgroup's rows
         {   // (resident variant: one row per wave, no loop — see the attention phase)
             auto row_work = [&](const int b) {
@@ -581,7 +695,7 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) dcnet_persistent_k(const PDec
         const float qnan = __builtin_nanf("");
         if constexpr (BEAM) {
             if (wg == 0 && tid == 0) pb_poison(P.bm_best_score, P.bm_result);
-        } else if (P.caps) {
+        } else if (!SAMPLE && P.caps) {
             // teacher-forced: EVERY score this workgroup wrote (its vocabulary rows, all rows and timesteps) — each workgroup
             // poisons its own region after its own loop, so no later store of another workgroup can undo it
             const int row0 = wg * P.rpw;
@@ -626,20 +740,23 @@ bool dcnet_persistent_beam_ok(const SetDcnetDims* d, int max_picks) {
     return d->B <= PW_BEAM_K && (long long)d->B * d->V < 0x7fffffffLL && dcnet_persistent_ok(d, max_picks);
 }
 
-// the six instantiations: [resident (B <= 4 and T <= PDEC_TREG), general][beam, teacher-forced with last_h2, every other launch].
-// (Listed in the order in which the kernels have always been instantiated: the device code object stays byte for byte the same.)
+// the eight instantiations: [resident (B <= 4 and T <= PDEC_TREG), general][beam, teacher-forced with last_h2, every other launch,
+// Gumbel-max sampled].  (The first three columns keep the order in which the kernels have always been instantiated; the sampled
+// column is appended: the instructions of the six earlier kernels stay as they were.)
 #define PDEC_K(...) {reinterpret_cast<const void*>(&dcnet_persistent_k<__VA_ARGS__>)}
-static PersistentKernel g_pdec_k[2][3] = {{PDEC_K(true, false, true), PDEC_K(true, true), PDEC_K(true)},
-                                          {PDEC_K(false, false, true), PDEC_K(false, true), PDEC_K(false)}};
+static PersistentKernel g_pdec_k[2][4] = {{PDEC_K(true, false, true), PDEC_K(true, true), PDEC_K(true), PDEC_K(true, false, false, true)},
+                                          {PDEC_K(false, false, true), PDEC_K(false, true), PDEC_K(false), PDEC_K(false, false, false, true)}};
 #undef PDEC_K
 
 // the greedy loop after set_dcnet_begin's prologue.  `pc` = the hoisted context products (B, T, 4D), `xbuf` = exchange region
 // (dcnet_persistent_xbytes).  SET_ERR_UNSUPPORTED: nothing was touched, the caller runs the per-step loop.
+// samp: the sampled mode (set_dcnet_gumbel_persistent), free-running only — not with teach or beam.
 int dcnet_persistent_greedy(const SetDcnetWeights* w, const SetDcnetDims* d, const float* pre1, const float* att1_c,
                             const float* mask, const float* pc, void* xbuf, long long* it, int* unfinished, int* alive,
                             long long start_idx, long long end_idx, int max_len, long long* seq, float* seq_logp,
-                            hipStream_t s, const PDecTeacher* teach, const PDecBeam* beam) {
+                            hipStream_t s, const PDecTeacher* teach, const PDecBeam* beam, const PDecSample* samp) {
     if (!dcnet_persistent_ok(d, max_len)) return SET_ERR_UNSUPPORTED;
+    if (samp && (teach || beam)) return SET_ERR_UNSUPPORTED;
     if (beam && (teach || !dcnet_persistent_beam_ok(d, max_len))) return SET_ERR_UNSUPPORTED;
     const int B = d->B, D = d->D, G = D / 4;
     PDecDcnetArgs P{};
@@ -654,6 +771,7 @@ int dcnet_persistent_greedy(const SetDcnetWeights* w, const SetDcnetDims* d, con
     P.start_idx = start_idx; P.end_idx = end_idx;
     if (teach) { pdec_teacher_fill(P, *teach); P.last_h2 = teach->last_h2; }
     if (beam) pdec_beam_fill(P, *beam);
+    if (samp) { P.gm_seed = samp->seed; P.gm_offset = samp->offset; P.gm_inv_t = samp->inv_t; }
     const bool lh = P.caps && P.last_h2, bm = beam != nullptr, res = B <= 4 && d->T <= PDEC_TREG;
     PersistentGuard guard;
     if (guard.rc != SET_OK) return guard.rc;
@@ -662,10 +780,11 @@ int dcnet_persistent_greedy(const SetDcnetWeights* w, const SetDcnetDims* d, con
     const int lds = pdec_lds_floats(B, D, d->A, bm) * (int)sizeof(float);
     const int lds_max = pdec_lds_floats(bm ? PW_BEAM_K : PDEC_MAXB, D, d->A, bm) * (int)sizeof(float);
     const double wbytes = 4.0 * ((double)d->V * D + 4.0 * 4 * D * D + (double)d->A * D);
-    // no word of an earlier decode may carry a tag of this one (the candidate words at the end are the beam mode's alone)
-    return pdec_launch(g_pdec_k[res ? 0 : 1][bm ? 0 : lh ? 1 : 2], guard, G, lds, lds_max, &P, xbuf,
+    // no word of an earlier decode may carry a tag of this one (the candidate words at the end are the beam mode's alone; the
+    // sampled mode's words are the greedy launch's)
+    return pdec_launch(g_pdec_k[res ? 0 : 1][bm ? 0 : lh ? 1 : samp ? 3 : 2], guard, G, lds, lds_max, &P, xbuf,
                        bm ? dcnet_persistent_xbytes(B, D, d->A) : (size_t)((char*)P.x_fcb - (char*)xbuf), s,
-                       {bm ? "persistent_beam" : "persistent_decode", 2.0 * B * wbytes / 4.0 * max_len, wbytes * max_len},
+                       {bm ? "persistent_beam" : samp ? "persistent_gumbel" : "persistent_decode", 2.0 * B * wbytes / 4.0 * max_len, wbytes * max_len},
                        {&P.stamps, &P.stamp_wg, 13, max_len});
 }
 

@@ -292,7 +292,8 @@ struct PDecTeacher { const int64_t* caps; long long caps_stride; float* predicti
                      float* last_h2 = nullptr; };
 // beam mode (one image, rows = hypotheses); rmask != NULL: adaptive features (region mask (B, R), up to PDEC_RREG_WIDE regions)
 struct PDecBeam { int* hist_par; int64_t* hist_word; float* best_score; int64_t* best_word; int* result; const float* rmask = nullptr; float* hist_score = nullptr; };
-// Gumbel-max sampled mode of EditNet's launch (set_editnet_gumbel_persistent): the key of the noise and 1 / temperature
+// Gumbel-max sampled mode of EditNet's and DCNet's launches (set_editnet_gumbel_persistent, set_dcnet_gumbel_persistent): the key
+// of the noise and 1 / temperature
 struct PDecSample { unsigned long long seed, offset; float inv_t; };
 // decode_persistent.hip: the greedy loop of a small batch as one launch with grid barriers
 constexpr int PDEC_MAXB = 8;          // rows of the <= 8-row persistent decode kernels
@@ -302,7 +303,8 @@ bool dcnet_persistent_ok(const SetDcnetDims* d, int max_len);
 int dcnet_persistent_greedy(const SetDcnetWeights* w, const SetDcnetDims* d, const float* pre1, const float* att1_c,
                             const float* mask, const float* pc, void* xbuf, long long* it, int* unfinished, int* alive,
                             long long start_idx, long long end_idx, int max_len, long long* seq, float* seq_logp,
-                            hipStream_t s, const PDecTeacher* teach = nullptr, const PDecBeam* beam = nullptr);
+                            hipStream_t s, const PDecTeacher* teach = nullptr, const PDecBeam* beam = nullptr,
+                            const PDecSample* samp = nullptr);
 bool dcnet_persistent_beam_ok(const SetDcnetDims* d, int max_picks);           // one image's beam search as one launch (k <= 4)
 
 size_t editnet_persistent_xbytes(int B, int D, int A, int R = 0);   // R > 64: room for R visual scores per row

@@ -20,8 +20,8 @@ class DAE(_DAE_XE):
 
     def forward(self, word_map, encoded_previous_captions, previous_cap_length, sample_max=True, sample_rl=False,
                 temperature=1.0, top_k=0, top_p=1.0, sampler="cdf"):
-        """temperature / top_k / top_p / sampler: see editnet_rl.DecoderC.forward (no-grad sampled rollout only; "gumbel" runs on
-        the per-step kernels here)"""
+        """temperature / top_k / top_p / sampler: see editnet_rl.DecoderC.forward (no-grad sampled rollout only; "gumbel" is one
+        persistent launch for 1 .. 8 rows with the token table built, the per-step kernels with the same draws otherwise)"""
         if sampler != "cdf":
             _lib.check_sampler_name(sampler, top_k, top_p)
         _require_cuda(encoded_previous_captions, "previous captions")
@@ -46,12 +46,20 @@ class DAE(_DAE_XE):
             if sample_rl:        # multinomial sampling, eval mode, no gradients: fused device loop, Philox epilogue
                 from . import rng
                 # (a NULL SetSampleOpts* is the call without options, bit for bit: include/set_hip.h)
-                fn, name = ((lib.set_dcnet_sample_gumbel, "set_dcnet_sample_gumbel") if gumbel else
-                            (lib.set_dcnet_sample_opts, "set_dcnet_sample_opts"))
-                check(fn(C.byref(w), C.byref(dims), ptr(prev), ptr(plen), int(word_map['<start>']),
-                         int(word_map['<end>']), max_len, rng.next_seed(), rng.offset(rng.SITE_ROLLOUT),
-                         ptr(seq), ptr(seq_logp), ptr(ws), ws.numel(), stream_of(dev),
-                         C.byref(opts) if opts is not None else None), name)
+                args = (C.byref(w), C.byref(dims), ptr(prev), ptr(plen), int(word_map['<start>']),
+                        int(word_map['<end>']), max_len, rng.next_seed(), rng.offset(rng.SITE_ROLLOUT),
+                        ptr(seq), ptr(seq_logp), ptr(ws), ws.numel(), stream_of(dev),
+                        C.byref(opts) if opts is not None else None)
+                if gumbel:
+                    # one persistent launch where it applies (1 .. 8 rows, token table), the per-step loop with the same draws
+                    # otherwise
+                    rc = lib.set_dcnet_gumbel_persistent(*args)
+                    if rc == 2:                          # SET_ERR_UNSUPPORTED: nothing was touched
+                        check(lib.set_dcnet_sample_gumbel(*args), "set_dcnet_sample_gumbel")
+                    else:
+                        check(rc, "set_dcnet_gumbel_persistent")
+                    return seq, seq_logp
+                check(lib.set_dcnet_sample_opts(*args), "set_dcnet_sample_opts")
                 return seq, seq_logp
             check(lib.set_dcnet_greedy(C.byref(w), C.byref(dims), ptr(prev), ptr(plen), int(word_map['<start>']),
                                        int(word_map['<end>']), max_len, ptr(seq), ptr(seq_logp), ptr(ws), ws.numel(),

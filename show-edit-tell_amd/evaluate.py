@@ -549,8 +549,8 @@ def sample_captions(model, *inputs_and_word_map, n_samples=5, temperature=1.0, t
     image i): the rows differ in their index, hence in their Philox counters, hence in their draws.  Returns seq (NI, n_samples,
     max_len) int64 and seq_logp (NI, n_samples, max_len), the log-probs under the tempered / truncated distribution sampled
     from.  The seed comes from rng.next_seed() as in the models' own sampled path: torch.manual_seed() reproduces a call.
-    sampler="gumbel": the Gumbel-max draw (temperature only) — for EditNet and n_samples * NI <= 16 rows the whole rollout is one
-    persistent launch; "cdf" (default) is the inverse-CDF draw with its draws unchanged."""
+    sampler="gumbel": the Gumbel-max draw (temperature only) — for n_samples * NI <= 16 rows (EditNet) or <= 8 rows (DCNet) the
+    whole rollout is one persistent launch; "cdf" (default) is the inverse-CDF draw with its draws unchanged."""
     *inputs, word_map = inputs_and_word_map
     if len(inputs) not in (2, 3):
         raise ValueError("sample_captions(model, [image_features,] previous_caption, prev_caplen, word_map, ...)")
