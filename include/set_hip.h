@@ -961,6 +961,53 @@ int set_beam_pick_nbest_f32(const float* logits, const float* logits2, int64_t l
 int set_beam_gather_f32(float* s0, float* s1, float* s2, float* s3, const int32_t* rows, int NI, int k, int D,
                         void* stream);
 
+/* Stochastic beam search pick (Kool, van Hoof, Welling, ICML 2019; csrc/sbs.hip): one timestep t (0-based, t <= 254) of a
+ * search that leaves, per image, k <= 8 DISTINCT sequences which are an exact sample WITHOUT replacement from the model's
+ * sequence distribution, in draw order.  NI images x k slots; slot j of image i is logits row r = i k + j.
+ * Slot state (updated in place): phi (log-probability of the prefix), G (its perturbed log-probability; -inf = dead slot),
+ * finished, len (tokens so far) and the tokens themselves, seqs (NI, k, Lmax), WITHOUT <start>, <end> stored as end_idx.
+ * Before step 0 the caller sets, per image, slot 0 to phi = G = 0 and every other slot to G = -inf, finished = len = 0 and
+ * n_open = 1.
+ *   live, unfinished slot j:
+ *     y[v]    = fl32(x[v] * (1.0f / temperature))                 (the product rounded, as in the Gumbel-max draw)
+ *     phi'[v] = phi_j + (y[v] - logsumexp(y))
+ *     g[v]    = phi'[v] + noise(seed, offset, r, t, v)            (the noise of the Gumbel-max draw above, csrc/philox.h)
+ *     Z       = max_v g[v]
+ *     u       = (G_j - g[v]) + log(1 - exp(g[v] - Z))             (log(1 - exp(d)) as log(-expm1(d)) for d > -log 2, log1p(-exp(d))
+ *     g~[v]   = G_j - max(u, 0) - log1p(exp(-|u|))                 otherwise)
+ *     the first arg-max of g gets g~ = G_j exactly (u = -inf there); words with y = -inf are never candidates.
+ *   finished slot j: ONE candidate, itself: g~ = G_j, phi and tokens unchanged, flat index j V + end_idx; its row is not read.
+ *   pick: the k largest g~ over all candidates of the image, ties to the lowest flat index j V + v.  g~ is increasing in g for
+ *     a fixed parent, so the candidates of a parent are its k best words by (g descending, v ascending).
+ * Output slots are in pick order (slot 0 has the largest G).  Per output slot: phi, G, finished (parent finished, or word ==
+ * end_idx), len, the tokens re-indexed by parent and extended (seqs_in -> seqs_out; entries past len are not written),
+ * words = the next input word (0 for a finished or dead slot) and rows = the parent row for set_beam_gather_f32 (the slot's
+ * own row for a finished parent and for a dead slot).  Fewer than k finite candidates leave dead slots (G = phi = -inf, len 0).
+ * n_open (NI) = the live unfinished slots after the pick.  An image with n_open == 0 on entry is a no-op: state untouched,
+ * words = 0, rows = identity, and its k Lmax tokens are copied from seqs_in to seqs_out so that the caller's buffer swap holds.
+ * Two launches (one workgroup per row, then one wave per image); rows of up to 12288 words with ld % 4 == 0 on a 16-byte-
+ * aligned base are read once as float4 into registers, any other row by scalar reads (three sweeps over the row: callers pad
+ * the leading dimension, as evaluate.sample_captions_distinct does); the outputs do not depend on the path.
+ * ws: set_sbs_workspace_bytes(NI, k) bytes (0 for NI <= 0 or k outside 1 .. 8), 16-byte aligned.
+ * SET_ERR_ARG (before any HIP call, nothing written): a NULL args or pointer field, NI <= 0, k outside 1 .. 8, V <= 0, t outside
+ * 0 .. 254, V > 2^26 - 4, ld < V, end_idx outside 0 .. V - 1 (<end> is a word of the vocabulary), Lmax < t + 1, seqs_in ==
+ * seqs_out, a workspace that is too small or misaligned, options
+ * set_sample_pick_opts_f32 refuses, top_k != 0, top_p != 1 (opts carries the temperature only; NULL: 1).
+ * Float64 restatement: tests/sbs_oracle.py. */
+typedef struct SetSbsArgs {
+    const float* logits; int64_t ld;             /* (NI k, ld) */
+    int64_t end_idx;
+    uint64_t seed, offset;
+    float* phi; float* G; int32_t* finished; int32_t* len;      /* (NI, k) */
+    const int64_t* seqs_in; int64_t* seqs_out;   /* (NI, k, Lmax) */
+    int64_t* words; int32_t* rows;               /* (NI k) */
+    int32_t* n_open;                             /* (NI) */
+    void* ws; size_t ws_bytes;
+    int32_t NI, k, V, t, Lmax, pad_;
+} SetSbsArgs;
+size_t set_sbs_workspace_bytes(int NI, int k);
+int set_sbs_pick_f32(const SetSbsArgs* args, const SetSampleOpts* opts, void* stream);
+
 /* General-layout fp32 GEMM on the MFMA pipe, used for the Linear backward (replaces the cuBLAS calls
  * autograd makes for nn.Linear / nn.LSTMCell: dX = dY.W and dW += dY^T.X):
  *     C[m,n] (+)= sum_k a(m,k) * b(n,k)

@@ -187,6 +187,15 @@ class PickArgs(C.Structure):
 PICK_GREEDY, PICK_SAMPLE = 0, 1
 
 
+class SbsArgs(C.Structure):
+    """include/set_hip.h SetSbsArgs (set_sbs_pick_f32: the stochastic beam search pick)"""
+    _fields_ = [("logits", C.c_void_p), ("ld", C.c_int64), ("end_idx", C.c_int64), ("seed", C.c_uint64), ("offset", C.c_uint64),
+                ("phi", C.c_void_p), ("G", C.c_void_p), ("finished", C.c_void_p), ("len", C.c_void_p), ("seqs_in", C.c_void_p),
+                ("seqs_out", C.c_void_p), ("words", C.c_void_p), ("rows", C.c_void_p), ("n_open", C.c_void_p), ("ws", C.c_void_p),
+                ("ws_bytes", C.c_size_t), ("NI", C.c_int32), ("k", C.c_int32), ("V", C.c_int32), ("t", C.c_int32),
+                ("Lmax", C.c_int32), ("pad_", C.c_int32)]
+
+
 class SampleOpts(C.Structure):
     """include/set_hip.h SetSampleOpts: temperature, top-k and top-p of the sampled pick ({1, 0, 1}: neutral)"""
     _fields_ = [("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("pad_", C.c_int32)]
@@ -444,6 +453,8 @@ PROTOTYPES = {
     "set_beam_pick_f32": (_I, [_P, _P, _L, _I, _I, _I, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "set_beam_pick_nbest_f32": (_I, [_P, _P, _L, _I, _I, _I, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "set_beam_gather_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "set_sbs_workspace_bytes": (_Z, [_I, _I]),
+    "set_sbs_pick_f32": (_I, [C.POINTER(SbsArgs), C.POINTER(SampleOpts), _P]),
     "set_gemm_group_f32": (_I, [C.POINTER(GemmDesc), _I, _I, _I, _P, _Z, _P]),
     "set_gemm_group_slabs_f32": (_I, [C.POINTER(GemmDesc), _I, _I, _I, _P, _Z, C.POINTER(SlabSrc), _P]),
     "set_editnet_xe_train_loop_f32": (_I, [C.POINTER(XELoopArgs), _P]),

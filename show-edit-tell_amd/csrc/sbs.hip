@@ -1,0 +1,296 @@
+// Stochastic beam search (Kool, van Hoof, Welling, "Stochastic Beams and Where to Find Them", ICML 2019): the pick of one
+// timestep for NI images x k slots (include/set_hip.h "Stochastic beam search pick").  The k slots of an image end up holding
+// k DISTINCT prefixes that are an exact sample without replacement from the model's sequence distribution, in draw order.
+//
+// Two launches:
+//   sbs_rows_k    one workgroup per (image, slot) row — the V-sized work: the row read, log-sum-exp of y, the Gumbel noise of
+//                 philox.h, g[v] = phi'[v] + noise, and the row's k best (g, v) with phi' there.  The conditioned score g~ is
+//                 increasing in g for a fixed parent, so a parent can only place its own k best g among the image's k picks:
+//                 the transform is applied to k values per parent, never to V.
+//   sbs_merge_k   one wave per image: the transform of the k x k candidates, finished slots as one candidate each, the flat
+//                 top-k (ties: lowest flat index j V + v), and the bookkeeping.
+// Both row-read paths (float4 into registers / scalar re-reads) give every thread the same quads in the same order and
+// feed one set of lambdas, so the outputs do not depend on the path.  No floating-point atomics, no scratch.
+#include "set_common.h"
+#include "philox.h"
+
+namespace set {
+
+typedef float sbs_f32x4 __attribute__((ext_vector_type(4)));
+constexpr int SBS_KMAX = 8;
+constexpr int SBS_MAXQ = 12;                 // register path: rows of up to 4 * 256 * 12 = 12288 words
+constexpr int SBS_NONE = 0x7fffffff;
+
+struct SbsRowArgs {
+    const float* logits; long long ld;
+    int k, V, t;
+    float inv_t;
+    unsigned long long seed, offset;
+    const float* phi; const float* G; const int* fin; const int* n_open;
+    float* cand_g; float* cand_phi; int* cand_v;         // (NI * k, SBS_KMAX)
+};
+
+template <bool REG>
+__global__ void __launch_bounds__(256) sbs_rows_k(const SbsRowArgs a) {
+    __shared__ float s_red[4];
+    __shared__ float s_bv[2][4];
+    __shared__ int s_bi[2][4];
+    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int V = a.V;
+    const float Gj = a.G[r], phij = a.phi[r];
+    // a dead slot, a finished slot (one candidate: itself) and every slot of a closed image offer no words: nothing is read
+    if (Gj == -INFINITY || a.fin[r] != 0 || a.n_open[r / a.k] == 0) return;
+    const float* row = a.logits + (long long)r * a.ld;
+    sbs_f32x4 x[SBS_MAXQ];
+    if (REG) {
+#pragma unroll
+        for (int q = 0; q < SBS_MAXQ; ++q) {
+            const int v = (tid + 256 * q) * 4;
+            x[q] = (sbs_f32x4){-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+            if (v < V) {
+                const sbs_f32x4 w = *reinterpret_cast<const sbs_f32x4*>(row + v);
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (v + e < V) x[q][e] = __fmul_rn(w[e], a.inv_t);
+            }
+        }
+    }
+    // every thread visits its quads tid, tid + 256, ... in that order on either path; words past V are -inf
+    auto sweep = [&](auto&& f) {
+        if (REG) {
+#pragma unroll
+            for (int q = 0; q < SBS_MAXQ; ++q)
+                if ((tid + 256 * q) * 4 < V) f(tid + 256 * q, x[q]);
+        } else {
+            for (int j = tid; 4 * j < V; j += 256) {
+                sbs_f32x4 y;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) y[e] = 4 * j + e < V ? __fmul_rn(row[4 * j + e], a.inv_t) : -INFINITY;
+                f(j, y);
+            }
+        }
+    };
+    float my = -INFINITY;
+    sweep([&](int, const sbs_f32x4& y) { my = fmaxf(my, fmaxf(fmaxf(y[0], y[1]), fmaxf(y[2], y[3]))); });
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) my = fmaxf(my, __shfl_xor(my, o));
+    if (lane == 0) s_red[wave] = my;
+    __syncthreads();
+    my = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
+    __syncthreads();
+    float sum = 0.f;
+    sweep([&](int, const sbs_f32x4& y) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) sum += expf(y[e] - my);                           // exp(-inf) == 0
+    });
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    if (lane == 0) s_red[wave] = sum;
+    __syncthreads();
+    const float lse = my + logf((s_red[0] + s_red[1]) + (s_red[2] + s_red[3]));
+    // the thread's own best SBS_KMAX words by (g descending, v ascending): it meets its words in ascending order, so a strict
+    // comparison keeps the lower word in front
+    float tv[SBS_KMAX], tp[SBS_KMAX];
+    int ti[SBS_KMAX];
+#pragma unroll
+    for (int i = 0; i < SBS_KMAX; ++i) { tv[i] = -INFINITY; tp[i] = 0.f; ti[i] = SBS_NONE; }
+    sweep([&](int j, const sbs_f32x4& y) {
+        uint32_t c[4];
+        gumbel_quad_words(a.seed, a.offset, r, a.t, j, c);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (!(y[e] > -INFINITY)) continue;                                        // -inf (and past V): never a candidate
+            const float ph = phij + (y[e] - lse);
+            const float g = ph + gumbel_of_word(c[e]);
+            if (g > tv[SBS_KMAX - 1]) {
+                tv[SBS_KMAX - 1] = g; tp[SBS_KMAX - 1] = ph; ti[SBS_KMAX - 1] = 4 * j + e;
+#pragma unroll
+                for (int i = SBS_KMAX - 1; i > 0; --i)
+                    if (tv[i] > tv[i - 1]) {
+                        const float fv = tv[i], fp = tp[i]; const int fi = ti[i];
+                        tv[i] = tv[i - 1]; tp[i] = tp[i - 1]; ti[i] = ti[i - 1];
+                        tv[i - 1] = fv; tp[i - 1] = fp; ti[i - 1] = fi;
+                    }
+            }
+        }
+    });
+    // k rounds: the workgroup's best head wins, its owner records and pops it
+    float* cg = a.cand_g + (long long)r * SBS_KMAX;
+    float* cp = a.cand_phi + (long long)r * SBS_KMAX;
+    int* cv = a.cand_v + (long long)r * SBS_KMAX;
+    for (int n = 0; n < a.k; ++n) {
+        float bv = tv[0];
+        int bi = ti[0];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ov = __shfl_xor(bv, o);
+            const int oi = __shfl_xor(bi, o);
+            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+        }
+        if (lane == 0) { s_bv[n & 1][wave] = bv; s_bi[n & 1][wave] = bi; }
+        __syncthreads();
+        bv = s_bv[n & 1][0]; bi = s_bi[n & 1][0];
+#pragma unroll
+        for (int w = 1; w < 4; ++w) {
+            const float ov = s_bv[n & 1][w];
+            const int oi = s_bi[n & 1][w];
+            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+        }
+        if (bi == SBS_NONE) {                                                         // the row has run out of words
+            if (tid == 0) { cg[n] = -INFINITY; cp[n] = 0.f; cv[n] = 0; }
+        } else if (ti[0] == bi) {
+            cg[n] = tv[0]; cp[n] = tp[0]; cv[n] = bi;
+#pragma unroll
+            for (int i = 0; i + 1 < SBS_KMAX; ++i) { tv[i] = tv[i + 1]; tp[i] = tp[i + 1]; ti[i] = ti[i + 1]; }
+            tv[SBS_KMAX - 1] = -INFINITY; ti[SBS_KMAX - 1] = SBS_NONE;
+        }
+    }
+}
+
+struct SbsMergeArgs {
+    int k, V, Lmax;
+    long long end_idx;
+    float* phi; float* G; int* fin; int* len;            // (NI, k), updated in place
+    const long long* seqs_in; long long* seqs_out;       // (NI, k, Lmax)
+    long long* words; int* rows; int* n_open;
+    const float* cand_g; const float* cand_phi; const int* cand_v;
+};
+
+// log(1 - exp(d)), d <= 0, without cancellation near d = 0 (d == 0 gives -inf)
+__device__ __forceinline__ float sbs_log1mexp(float d) {
+    return d > -0.6931472f ? logf(-expm1f(d)) : log1pf(-expf(d));
+}
+
+// one wave per image; lane c < k * k is candidate (parent c / k, the parent's rank-(c % k) word)
+__global__ void __launch_bounds__(64) sbs_merge_k(const SbsMergeArgs a) {
+    __shared__ int s_src[SBS_KMAX], s_len[SBS_KMAX], s_ext[SBS_KMAX];
+    __shared__ long long s_word[SBS_KMAX];
+    const int img = blockIdx.x, lane = threadIdx.x, k = a.k;
+    const int base = img * k;
+    const long long* sin = a.seqs_in + (long long)base * a.Lmax;
+    long long* sout = a.seqs_out + (long long)base * a.Lmax;
+    if (a.n_open[img] == 0) {                            // closed: the state stays, the tokens follow the buffer swap
+        if (lane < k) { a.words[base + lane] = 0; a.rows[base + lane] = base + lane; }
+        for (int e = lane; e < k * a.Lmax; e += 64) sout[e] = sin[e];
+        return;
+    }
+    const int p = lane / k, i = lane - p * k;
+    float val = -INFINITY, nphi = 0.f;
+    int flat = SBS_NONE, word = 0, pfin = 0, plen = 0;
+    if (lane < k * k) {
+        const float Gp = a.G[base + p];
+        pfin = a.fin[base + p];
+        plen = a.len[base + p];
+        if (Gp == -INFINITY) {
+            // a dead slot has no candidates
+        } else if (pfin) {
+            if (i == 0) { val = Gp; nphi = a.phi[base + p]; word = (int)a.end_idx; flat = p * a.V + word; }
+        } else {
+            const long long c = (long long)(base + p) * SBS_KMAX;
+            const float g = a.cand_g[c + i];
+            if (g > -INFINITY) {
+                word = a.cand_v[c + i];
+                nphi = a.cand_phi[c + i];
+                flat = p * a.V + word;
+                if (i == 0) {
+                    val = Gp;                            // the arg-max child inherits the parent's score exactly
+                } else {
+                    const float Z = a.cand_g[c];
+                    const float u = (Gp - g) + sbs_log1mexp(g - Z);      // -inf when g == Z
+                    val = Gp - fmaxf(u, 0.f) - log1pf(expf(-fabsf(u)));
+                }
+            }
+        }
+    }
+    __syncthreads();                                     // every read of the slot state precedes every write below
+    // rank by counting: candidates ahead of this one in (value descending, flat index ascending, lane ascending)
+    int rank = 0;
+    for (int l = 0; l < 64; ++l) {
+        const float ov = __shfl(val, l);
+        const int of = __shfl(flat, l);
+        rank += (ov > val || (ov == val && (of < flat || (of == flat && l < lane)))) ? 1 : 0;
+    }
+    const bool slot = rank < k;                          // this lane fills output slot `rank`
+    const bool hit = slot && val > -INFINITY;
+    const bool nfin = hit && (pfin || (long long)word == a.end_idx);
+    const unsigned long long open = __ballot(hit && !nfin);
+    if (lane == 0) a.n_open[img] = __popcll(open);
+    if (slot) {
+        const int o = base + rank;
+        const bool ext = hit && !pfin;                   // a live parent's child: one more token
+        a.G[o] = hit ? val : -INFINITY;
+        a.phi[o] = hit ? nphi : -INFINITY;
+        a.fin[o] = nfin ? 1 : 0;
+        a.len[o] = hit ? plen + (ext ? 1 : 0) : 0;
+        a.words[o] = (hit && !nfin) ? (long long)word : 0;
+        a.rows[o] = ext ? base + p : o;
+        s_src[rank] = hit ? p : -1;
+        s_len[rank] = plen;
+        s_ext[rank] = ext ? 1 : 0;
+        s_word[rank] = word;
+    }
+    __syncthreads();
+    for (int s = 0; s < k; ++s) {
+        if (s_src[s] < 0) continue;
+        const int n = s_len[s] < a.Lmax ? s_len[s] : a.Lmax;
+        const long long* from = sin + (long long)s_src[s] * a.Lmax;
+        long long* to = sout + (long long)s * a.Lmax;
+        for (int e = lane; e < n; e += 64) to[e] = from[e];
+        if (lane == 0 && s_ext[s] && n < a.Lmax) to[n] = s_word[s];
+    }
+}
+
+}  // namespace set
+
+using namespace set;
+
+extern "C" {
+
+size_t set_sbs_workspace_bytes(int NI, int k) {
+    if (NI <= 0 || k < 1 || k > SBS_KMAX) return 0;
+    return 3 * round_up((size_t)NI * k * SBS_KMAX * sizeof(float), 256);
+}
+
+int set_sbs_pick_f32(const SetSbsArgs* a, const SetSampleOpts* opts, void* stream) {
+    if (!a || !a->logits || !a->phi || !a->G || !a->finished || !a->len || !a->seqs_in || !a->seqs_out || !a->words || !a->rows ||
+        !a->n_open || !a->ws)
+        return SET_ERR_ARG;
+    if (a->NI <= 0 || a->k < 1 || a->k > SBS_KMAX || a->V <= 0 || a->t < 0 || a->t > GUMBEL_MAX_LEN - 1 || a->ld < a->V ||
+        a->Lmax < a->t + 1 || a->seqs_in == a->seqs_out || a->end_idx < 0 || a->end_idx >= a->V)
+        return SET_ERR_ARG;                              // (<end> is a word: a finished slot's flat index j V + end_idx stays inside slot j)
+    SET_TRY(gumbel_opts_check(opts, a->V, 1));           // temperature only; V within the noise counters
+    if ((long long)a->NI * a->k >= 0x7fffffffLL / SBS_KMAX) return SET_ERR_ARG;
+    if (a->ws_bytes < set_sbs_workspace_bytes(a->NI, a->k) || !aligned16(a->ws)) return SET_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const int B = a->NI * a->k;
+    Carver cv(a->ws);
+    SbsRowArgs ra;
+    ra.logits = a->logits; ra.ld = a->ld; ra.k = a->k; ra.V = a->V; ra.t = a->t;
+    ra.inv_t = opts ? 1.0f / opts->temperature : 1.f;
+    ra.seed = a->seed; ra.offset = a->offset;
+    ra.phi = a->phi; ra.G = a->G; ra.fin = a->finished; ra.n_open = a->n_open;
+    ra.cand_g = cv.take<float>((size_t)B * SBS_KMAX);
+    ra.cand_phi = cv.take<float>((size_t)B * SBS_KMAX);
+    ra.cand_v = cv.take<int>((size_t)B * SBS_KMAX);
+    SbsMergeArgs ma;
+    ma.k = a->k; ma.V = a->V; ma.Lmax = a->Lmax; ma.end_idx = a->end_idx;
+    ma.phi = a->phi; ma.G = a->G; ma.fin = a->finished; ma.len = a->len;
+    ma.seqs_in = (const long long*)a->seqs_in; ma.seqs_out = (long long*)a->seqs_out;
+    ma.words = (long long*)a->words; ma.rows = a->rows; ma.n_open = a->n_open;
+    ma.cand_g = ra.cand_g; ma.cand_phi = ra.cand_phi; ma.cand_v = ra.cand_v;
+    const bool reg = a->V <= 4 * 256 * SBS_MAXQ && !(a->ld & 3) && aligned16(a->logits);
+    {
+        ProfScope ps(reg ? "sbs_rows" : "sbs_rows_scalar", st, 0.0, (reg ? 4.0 : 12.0) * B * a->V);
+        if (reg) hipLaunchKernelGGL((sbs_rows_k<true>), dim3(B), dim3(256), 0, st, ra);
+        else hipLaunchKernelGGL((sbs_rows_k<false>), dim3(B), dim3(256), 0, st, ra);
+        SET_LAUNCH_CHECK();
+    }
+    {
+        ProfScope ps("sbs_merge", st, 0.0, 16.0 * B * (a->t + 1));
+        hipLaunchKernelGGL(sbs_merge_k, dim3(a->NI), dim3(64), 0, st, ma);
+        SET_LAUNCH_CHECK();
+    }
+    return SET_OK;
+}
+
+}  // extern "C"

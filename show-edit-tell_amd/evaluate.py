@@ -572,6 +572,103 @@ def sample_captions(model, *inputs_and_word_map, n_samples=5, temperature=1.0, t
     return seq.view(NI, n, -1), logp.view(NI, n, -1)
 
 
+SBS_MAX_SAMPLES = 8     # slots of set_sbs_pick_f32
+
+
+@torch.no_grad()
+def sample_captions_distinct(model, *inputs_and_word_map, n_samples=5, temperature=1.0, max_steps=None, _return_steps=False):
+    """Up to n_samples DISTINCT captions per image, an exact sample WITHOUT replacement from the model's (tempered) sequence
+    distribution, by stochastic beam search (Kool, van Hoof, Welling, ICML 2019; include/set_hip.h set_sbs_pick_f32):
+        out = sample_captions_distinct(decoder, image_features, previous_caption, prev_caplen, word_map, n_samples=5)
+        out = sample_captions_distinct(dae, previous_caption, prev_caplen, word_map, temperature=0.8)
+    EditNet (editnet_rl.DecoderC, fixed features) takes image_features (NI,R,F), previous_caption (NI,T), prev_caplen (NI,1);
+    DCNet (dcnet_rl.DAE) the caption pair only.  One beam-shaped pass for all images: per timestep one decode step over the
+    NI * n_samples slots, the pick, one state re-index; the host polls "no open slot" every 4 steps.  Finished sequences stay in
+    the beam and compete; nothing is deterministic about the result but its seed, which comes from rng.next_seed() as in the
+    sampled rollout (torch.manual_seed() reproduces a call).
+    Returns, per image, a list of up to n_samples entries (tokens, logp, G, finished) in DRAW order (G descending): tokens is a
+    list of max_steps words in the sampled rollouts' convention (<end> stored as 0, zeros behind it; tokens_from_greedy takes
+    them), logp the sequence's log-probability under the tempered model, G its perturbed log-probability.  max_steps defaults
+    to the sampled rollout's max_len; a sequence still open at the limit is returned as it is, with finished=False.  Fewer than
+    n_samples entries come back only when the model gives fewer sequences a non-zero probability.
+    n_samples must be 1 .. 8.  Adaptive features and the ensemble are not covered (ValueError)."""
+    import ctypes as C
+    from . import _lib, rng
+    from ._lib import check, ptr, stream_of
+    *inputs, word_map = inputs_and_word_map
+    if isinstance(model, (tuple, list)) or getattr(model, "_adaptive", 0) or getattr(model, "_ABI", None) not in ("editnet", "dcnet"):
+        raise ValueError("sample_captions_distinct supports editnet_rl.DecoderC with fixed features and dcnet_rl.DAE; adaptive "
+                         "features and the EditNet + DCNet ensemble are not covered")
+    if len(inputs) != (3 if model._ABI == "editnet" else 2):
+        raise ValueError("sample_captions_distinct(model, [image_features,] previous_caption, prev_caplen, word_map, ...): "
+                         "image_features for EditNet, none for DCNet")
+    k = int(n_samples)
+    if k != n_samples or k < 1 or k > SBS_MAX_SAMPLES:
+        raise ValueError("n_samples must be an integer in 1 .. %d, got %r" % (SBS_MAX_SAMPLES, n_samples))
+    opts = _lib.sample_opts(temperature)
+    max_steps = int(getattr(model, "max_len", 18) if max_steps is None else max_steps)
+    if max_steps < 1 or max_steps > 255:
+        raise ValueError("max_steps must lie in 1 .. 255, got %r" % (max_steps,))
+    model.eval()
+    prev = inputs[-2].long().contiguous()
+    plen = inputs[-1].reshape(-1).long().contiguous()
+    if len(inputs) == 3:
+        X = inputs[0].float().contiguous()
+        m = _FusedModel(model, (X, None, prev, plen), (X,), k, max_steps)
+    else:
+        m = _FusedModel(model, (prev, plen), (), k, max_steps)
+    lib = _lib.load()
+    dev, V, NI = prev.device, model.vocab_size, prev.shape[0]
+    st = stream_of(dev)
+    start, end = int(word_map['<start>']), int(word_map['<end>'])
+    B, neg = NI * k, float("-inf")
+    phi = torch.zeros(NI, k, device=dev)
+    G = torch.full((NI, k), neg, device=dev)
+    G[:, 0] = 0.0                                        # step 0: the k rows are identical, only slot 0 is live
+    fin = torch.zeros(NI, k, dtype=torch.int32, device=dev)
+    length = torch.zeros(NI, k, dtype=torch.int32, device=dev)
+    n_open = torch.ones(NI, dtype=torch.int32, device=dev)
+    seqs = [torch.zeros(NI, k, max_steps, dtype=torch.long, device=dev) for _ in range(2)]
+    words = torch.full((B,), start, dtype=torch.long, device=dev)
+    rows = torch.empty(B, dtype=torch.int32, device=dev)
+    # the leading dimension padded as the rollouts' workspace logits are: the pick then reads its rows as float4 (its register
+    # path needs ld % 4 == 0; V = 9490 is no multiple of 4), the step writes V columns of every row
+    ld = (V + 63) // 64 * 64
+    logits = torch.empty(B, ld, dtype=torch.float32, device=dev)
+    ws = torch.empty(lib.set_sbs_workspace_bytes(NI, k), dtype=torch.uint8, device=dev)
+    a = _lib.SbsArgs(logits=logits.data_ptr(), ld=ld, end_idx=end, seed=rng.next_seed(), offset=rng.offset(rng.SITE_ROLLOUT),
+                     phi=phi.data_ptr(), G=G.data_ptr(), finished=fin.data_ptr(), len=length.data_ptr(),
+                     words=words.data_ptr(), rows=rows.data_ptr(), n_open=n_open.data_ptr(), ws=ws.data_ptr(),
+                     ws_bytes=ws.numel(), NI=NI, k=k, V=V, Lmax=max_steps)
+    o = C.byref(opts) if opts is not None else None
+    steps = []
+    s0, s1, s2, s3 = m.states
+    for t in range(max_steps):
+        m.step(words, logits)
+        if _return_steps:
+            steps.append(logits[:, :V].clone())
+        a.t, a.seqs_in, a.seqs_out = t, seqs[0].data_ptr(), seqs[1].data_ptr()
+        check(lib.set_sbs_pick_f32(C.byref(a), o, st), "set_sbs_pick_f32")
+        seqs.reverse()
+        if t + 1 == max_steps:
+            break
+        check(lib.set_beam_gather_f32(ptr(s0), ptr(s1), ptr(s2), ptr(s3), ptr(rows), NI, k, m.D, st), "set_beam_gather_f32")
+        if (t + 1) % 4 == 0 and int(n_open.max()) == 0:          # the only host synchronisation of the search
+            break
+    seqs_c, phi_c, G_c, fin_c, len_c = seqs[0].cpu(), phi.cpu(), G.cpu(), fin.cpu(), length.cpu()
+    out = []
+    for i in range(NI):
+        entries = []
+        for j in range(k):
+            if float(G_c[i, j]) == neg:
+                continue
+            n = int(len_c[i, j])
+            tk = [0 if w == end else w for w in seqs_c[i, j, :n].tolist()]
+            entries.append((tk + [0] * (max_steps - n), float(phi_c[i, j]), float(G_c[i, j]), bool(fin_c[i, j])))
+        out.append(entries)
+    return (out, steps) if _return_steps else out
+
+
 def tokens_from_greedy(seq, word_map):
     """(B, max_len) greedy / sampled output -> forced token lists: `<start>` in front and, for rows that ended before
     max_len, `<end>` behind (the decode loops store `<end>` as 0, editnet_rl.py:531)."""
