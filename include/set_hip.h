@@ -1007,6 +1007,21 @@ typedef struct SetSbsArgs {
 } SetSbsArgs;
 size_t set_sbs_workspace_bytes(int NI, int k);
 int set_sbs_pick_f32(const SetSbsArgs* args, const SetSampleOpts* opts, void* stream);
+/* The same pick for the ENSEMBLE of two models that step on the same words (evaluate.sample_captions_distinct_ensemble; the
+ * beam searches' log((softmax_e + softmax_d) / 2), eval_full.py:151-153).  logits2 (NI k, ld): the second model's rows, with
+ * args->ld and args->V.  Each model is tempered on its own, BEFORE the average:
+ *     y_e[v] = fl32(x_e[v] * (1.0f / temperature)),  y_d[v] likewise from logits2
+ *     p = y_e[v] - logsumexp(y_e),  q = y_d[v] - logsumexp(y_d)          (each log-sum-exp formed as the one-model pick forms its own)
+ *     l[v]    = log(0.5 (exp(p) + exp(q))) = hi + log1p(exp(lo - hi)) - ln 2,  hi = max(p, q), lo = min(p, q)
+ *     phi'[v] = phi_j + l[v],   g[v] = phi'[v] + noise(seed, offset, r, t, v)
+ * and everything from Z on as above.  A word that is -inf in ONE model is a candidate with l = hi - ln 2; a word that is -inf in
+ * both never is.  The averaged probabilities are a distribution over the words, so the result is the exact sample without
+ * replacement from the ensemble's sequence distribution.  A word's noise is that of the one-model pick: it does not depend on
+ * the number of models.  Semantics, refusals, state, outputs and workspace (set_sbs_workspace_bytes) are those of
+ * set_sbs_pick_f32; the register path also needs logits2 16-byte aligned and holds both rows; SET_ERR_ARG for a NULL logits2.
+ * Profile scopes sbs_rows_ens / sbs_rows_ens_scalar, then sbs_merge.  Float64 restatement: tests/sbs_oracle.py on
+ * L = log(0.5 (softmax(y_e) + softmax(y_d))) (tests/sbs_ensemble_fixtures.py). */
+int set_sbs_pick_ensemble_f32(const SetSbsArgs* args, const float* logits2, const SetSampleOpts* opts, void* stream);
 
 /* General-layout fp32 GEMM on the MFMA pipe, used for the Linear backward (replaces the cuBLAS calls
  * autograd makes for nn.Linear / nn.LSTMCell: dX = dY.W and dW += dY^T.X):

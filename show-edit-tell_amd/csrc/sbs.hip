@@ -11,6 +11,12 @@
 //                 top-k (ties: lowest flat index j V + v), and the bookkeeping.
 // Both row-read paths (float4 into registers / scalar re-reads) give every thread the same quads in the same order and
 // feed one set of lambdas, so the outputs do not depend on the path.  No floating-point atomics, no scratch.
+//
+// The two-model pick (set_sbs_pick_ensemble_f32, the EditNet + DCNet ensemble) is sbs_rows_k<.., 2>: a second logits row per
+// slot, both tempered and normalised on their own, the word's log-probability that of the averaged distributions.  The merge
+// sees only candidates and is shared.  The register path HOLDS BOTH ROWS (2 x 12 float4 per thread): no scratch on gfx950, and
+// one workgroup per row leaves at most one workgroup per CU, so the registers cost no occupancy that a launch of <= 128 rows
+// could use; re-reading the second row was therefore not needed.
 #include "set_common.h"
 #include "philox.h"
 
@@ -22,7 +28,7 @@ constexpr int SBS_MAXQ = 12;                 // register path: rows of up to 4 *
 constexpr int SBS_NONE = 0x7fffffff;
 
 struct SbsRowArgs {
-    const float* logits; long long ld;
+    const float* logits; const float* logits2; long long ld;     // logits2: the second model's rows (NM == 2), same V and ld
     int k, V, t;
     float inv_t;
     unsigned long long seed, offset;
@@ -30,9 +36,17 @@ struct SbsRowArgs {
     float* cand_g; float* cand_phi; int* cand_v;         // (NI * k, SBS_KMAX)
 };
 
-template <bool REG>
+// log(0.5 (exp(p) + exp(q))) = hi + log1p(exp(lo - hi)) - ln 2 with hi / lo the larger / smaller of the two; one -inf term gives
+// hi - ln 2, two give -inf (the word is no candidate)
+__device__ __forceinline__ float sbs_mean_logp(float p, float q) {
+    const float hi = fmaxf(p, q), lo = fminf(p, q);
+    return hi > -INFINITY ? (hi + log1pf(expf(lo - hi))) - 0.69314718f : -INFINITY;
+}
+
+// NM models per row: 1 = log_softmax(y); 2 = log(0.5 (softmax(y_e) + softmax(y_d))), each model tempered before the average
+template <bool REG, int NM>
 __global__ void __launch_bounds__(256) sbs_rows_k(const SbsRowArgs a) {
-    __shared__ float s_red[4];
+    __shared__ float s_red[NM][4];
     __shared__ float s_bv[2][4];
     __shared__ int s_bi[2][4];
     const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -41,66 +55,114 @@ __global__ void __launch_bounds__(256) sbs_rows_k(const SbsRowArgs a) {
     // a dead slot, a finished slot (one candidate: itself) and every slot of a closed image offer no words: nothing is read
     if (Gj == -INFINITY || a.fin[r] != 0 || a.n_open[r / a.k] == 0) return;
     const float* row = a.logits + (long long)r * a.ld;
-    sbs_f32x4 x[SBS_MAXQ];
+    const float* row2 = NM == 2 ? a.logits2 + (long long)r * a.ld : row;
+    sbs_f32x4 x[SBS_MAXQ], x2[NM == 2 ? SBS_MAXQ : 1];
     if (REG) {
 #pragma unroll
         for (int q = 0; q < SBS_MAXQ; ++q) {
             const int v = (tid + 256 * q) * 4;
             x[q] = (sbs_f32x4){-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+            if (NM == 2) x2[NM == 2 ? q : 0] = x[q];
             if (v < V) {
                 const sbs_f32x4 w = *reinterpret_cast<const sbs_f32x4*>(row + v);
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
                     if (v + e < V) x[q][e] = __fmul_rn(w[e], a.inv_t);
+                if (NM == 2) {
+                    const sbs_f32x4 w2 = *reinterpret_cast<const sbs_f32x4*>(row2 + v);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if (v + e < V) x2[NM == 2 ? q : 0][e] = __fmul_rn(w2[e], a.inv_t);
+                }
             }
         }
     }
-    // every thread visits its quads tid, tid + 256, ... in that order on either path; words past V are -inf
+    // every thread visits its quads tid, tid + 256, ... in that order on either path, both models' quads of a visit together
+    // (NM == 1: the one row twice); words past V are -inf
     auto sweep = [&](auto&& f) {
         if (REG) {
 #pragma unroll
             for (int q = 0; q < SBS_MAXQ; ++q)
-                if ((tid + 256 * q) * 4 < V) f(tid + 256 * q, x[q]);
+                if ((tid + 256 * q) * 4 < V) f(tid + 256 * q, x[q], NM == 2 ? x2[NM == 2 ? q : 0] : x[q]);
         } else {
             for (int j = tid; 4 * j < V; j += 256) {
-                sbs_f32x4 y;
+                sbs_f32x4 y, y2;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) y[e] = 4 * j + e < V ? __fmul_rn(row[4 * j + e], a.inv_t) : -INFINITY;
-                f(j, y);
+                if (NM == 2) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) y2[e] = 4 * j + e < V ? __fmul_rn(row2[4 * j + e], a.inv_t) : -INFINITY;
+                }
+                f(j, y, NM == 2 ? y2 : y);
             }
         }
     };
-    float my = -INFINITY;
-    sweep([&](int, const sbs_f32x4& y) { my = fmaxf(my, fmaxf(fmaxf(y[0], y[1]), fmaxf(y[2], y[3]))); });
+    // per model: max, sum of exp and log-sum-exp, each formed as the one-model pick forms its own
+    float my[NM], sum[NM], lse[NM];
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) my = fmaxf(my, __shfl_xor(my, o));
-    if (lane == 0) s_red[wave] = my;
-    __syncthreads();
-    my = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
-    __syncthreads();
-    float sum = 0.f;
-    sweep([&](int, const sbs_f32x4& y) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) sum += expf(y[e] - my);                           // exp(-inf) == 0
+    for (int m = 0; m < NM; ++m) { my[m] = -INFINITY; sum[m] = 0.f; }
+    auto max4 = [](const sbs_f32x4& y) { return fmaxf(fmaxf(y[0], y[1]), fmaxf(y[2], y[3])); };
+    sweep([&](int, const sbs_f32x4& y, const sbs_f32x4& y2) {
+        my[0] = fmaxf(my[0], max4(y));
+        if (NM == 2) my[NM - 1] = fmaxf(my[NM - 1], max4(y2));
     });
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-    if (lane == 0) s_red[wave] = sum;
+    for (int m = 0; m < NM; ++m) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) my[m] = fmaxf(my[m], __shfl_xor(my[m], o));
+        if (lane == 0) s_red[m][wave] = my[m];
+    }
     __syncthreads();
-    const float lse = my + logf((s_red[0] + s_red[1]) + (s_red[2] + s_red[3]));
+#pragma unroll
+    for (int m = 0; m < NM; ++m) my[m] = fmaxf(fmaxf(s_red[m][0], s_red[m][1]), fmaxf(s_red[m][2], s_red[m][3]));
+    __syncthreads();
+    sweep([&](int, const sbs_f32x4& y, const sbs_f32x4& y2) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) sum[0] += expf(y[e] - my[0]);                     // exp(-inf) == 0
+        if (NM == 2) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) sum[NM - 1] += expf(y2[e] - my[NM - 1]);
+        }
+    });
+#pragma unroll
+    for (int m = 0; m < NM; ++m) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) sum[m] += __shfl_xor(sum[m], o);
+        if (lane == 0) s_red[m][wave] = sum[m];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int m = 0; m < NM; ++m) lse[m] = my[m] + logf((s_red[m][0] + s_red[m][1]) + (s_red[m][2] + s_red[m][3]));
+    // two models on the register path: the first row's registers take the word's log-probability under the averaged
+    // distributions here, so that the sweep below is the one-model sweep (and unrolls as it does)
+    if (REG && NM == 2) {
+#pragma unroll
+        for (int q = 0; q < SBS_MAXQ; ++q)
+            if ((tid + 256 * q) * 4 < V) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) x[q][e] = sbs_mean_logp(x[q][e] - lse[0], x2[NM == 2 ? q : 0][e] - lse[NM - 1]);
+            }
+    }
     // the thread's own best SBS_KMAX words by (g descending, v ascending): it meets its words in ascending order, so a strict
     // comparison keeps the lower word in front
     float tv[SBS_KMAX], tp[SBS_KMAX];
     int ti[SBS_KMAX];
 #pragma unroll
     for (int i = 0; i < SBS_KMAX; ++i) { tv[i] = -INFINITY; tp[i] = 0.f; ti[i] = SBS_NONE; }
-    sweep([&](int j, const sbs_f32x4& y) {
+    sweep([&](int j, const sbs_f32x4& y, const sbs_f32x4& y2) {
         uint32_t c[4];
         gumbel_quad_words(a.seed, a.offset, r, a.t, j, c);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            if (!(y[e] > -INFINITY)) continue;                                        // -inf (and past V): never a candidate
-            const float ph = phij + (y[e] - lse);
+            float l;
+            if (NM == 1) {
+                if (!(y[e] > -INFINITY)) continue;                                    // -inf (and past V): never a candidate
+                l = y[e] - lse[0];
+            } else {
+                l = REG ? y[e] : sbs_mean_logp(y[e] - lse[0], y2[e] - lse[NM - 1]);
+                if (!(l > -INFINITY)) continue;                                       // impossible in both models (and past V)
+            }
+            const float ph = phij + l;
             const float g = ph + gumbel_of_word(c[e]);
             if (g > tv[SBS_KMAX - 1]) {
                 tv[SBS_KMAX - 1] = g; tp[SBS_KMAX - 1] = ph; ti[SBS_KMAX - 1] = 4 * j + e;
@@ -251,7 +313,8 @@ size_t set_sbs_workspace_bytes(int NI, int k) {
     return 3 * round_up((size_t)NI * k * SBS_KMAX * sizeof(float), 256);
 }
 
-int set_sbs_pick_f32(const SetSbsArgs* a, const SetSampleOpts* opts, void* stream) {
+// logits2 == nullptr: one model (set_sbs_pick_f32); otherwise the two-model pick
+static int sbs_pick(const SetSbsArgs* a, const float* logits2, const SetSampleOpts* opts, void* stream) {
     if (!a || !a->logits || !a->phi || !a->G || !a->finished || !a->len || !a->seqs_in || !a->seqs_out || !a->words || !a->rows ||
         !a->n_open || !a->ws)
         return SET_ERR_ARG;
@@ -265,7 +328,7 @@ int set_sbs_pick_f32(const SetSbsArgs* a, const SetSampleOpts* opts, void* strea
     const int B = a->NI * a->k;
     Carver cv(a->ws);
     SbsRowArgs ra;
-    ra.logits = a->logits; ra.ld = a->ld; ra.k = a->k; ra.V = a->V; ra.t = a->t;
+    ra.logits = a->logits; ra.logits2 = logits2; ra.ld = a->ld; ra.k = a->k; ra.V = a->V; ra.t = a->t;
     ra.inv_t = opts ? 1.0f / opts->temperature : 1.f;
     ra.seed = a->seed; ra.offset = a->offset;
     ra.phi = a->phi; ra.G = a->G; ra.fin = a->finished; ra.n_open = a->n_open;
@@ -278,11 +341,16 @@ int set_sbs_pick_f32(const SetSbsArgs* a, const SetSampleOpts* opts, void* strea
     ma.seqs_in = (const long long*)a->seqs_in; ma.seqs_out = (long long*)a->seqs_out;
     ma.words = (long long*)a->words; ma.rows = a->rows; ma.n_open = a->n_open;
     ma.cand_g = ra.cand_g; ma.cand_phi = ra.cand_phi; ma.cand_v = ra.cand_v;
-    const bool reg = a->V <= 4 * 256 * SBS_MAXQ && !(a->ld & 3) && aligned16(a->logits);
-    {
+    const bool reg = a->V <= 4 * 256 * SBS_MAXQ && !(a->ld & 3) && aligned16(a->logits) && aligned16(logits2);
+    if (!logits2) {
         ProfScope ps(reg ? "sbs_rows" : "sbs_rows_scalar", st, 0.0, (reg ? 4.0 : 12.0) * B * a->V);
-        if (reg) hipLaunchKernelGGL((sbs_rows_k<true>), dim3(B), dim3(256), 0, st, ra);
-        else hipLaunchKernelGGL((sbs_rows_k<false>), dim3(B), dim3(256), 0, st, ra);
+        if (reg) hipLaunchKernelGGL((sbs_rows_k<true, 1>), dim3(B), dim3(256), 0, st, ra);
+        else hipLaunchKernelGGL((sbs_rows_k<false, 1>), dim3(B), dim3(256), 0, st, ra);
+        SET_LAUNCH_CHECK();
+    } else {
+        ProfScope ps(reg ? "sbs_rows_ens" : "sbs_rows_ens_scalar", st, 0.0, (reg ? 8.0 : 24.0) * B * a->V);
+        if (reg) hipLaunchKernelGGL((sbs_rows_k<true, 2>), dim3(B), dim3(256), 0, st, ra);
+        else hipLaunchKernelGGL((sbs_rows_k<false, 2>), dim3(B), dim3(256), 0, st, ra);
         SET_LAUNCH_CHECK();
     }
     {
@@ -291,6 +359,13 @@ int set_sbs_pick_f32(const SetSbsArgs* a, const SetSampleOpts* opts, void* strea
         SET_LAUNCH_CHECK();
     }
     return SET_OK;
+}
+
+int set_sbs_pick_f32(const SetSbsArgs* a, const SetSampleOpts* opts, void* stream) { return sbs_pick(a, nullptr, opts, stream); }
+
+int set_sbs_pick_ensemble_f32(const SetSbsArgs* a, const float* logits2, const SetSampleOpts* opts, void* stream) {
+    if (!logits2) return SET_ERR_ARG;
+    return sbs_pick(a, logits2, opts, stream);
 }
 
 }  // extern "C"

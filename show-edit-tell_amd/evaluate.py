@@ -575,50 +575,33 @@ def sample_captions(model, *inputs_and_word_map, n_samples=5, temperature=1.0, t
 SBS_MAX_SAMPLES = 8     # slots of set_sbs_pick_f32
 
 
-@torch.no_grad()
-def sample_captions_distinct(model, *inputs_and_word_map, n_samples=5, temperature=1.0, max_steps=None, _return_steps=False):
-    """Up to n_samples DISTINCT captions per image, an exact sample WITHOUT replacement from the model's (tempered) sequence
-    distribution, by stochastic beam search (Kool, van Hoof, Welling, ICML 2019; include/set_hip.h set_sbs_pick_f32):
-        out = sample_captions_distinct(decoder, image_features, previous_caption, prev_caplen, word_map, n_samples=5)
-        out = sample_captions_distinct(dae, previous_caption, prev_caplen, word_map, temperature=0.8)
-    EditNet (editnet_rl.DecoderC, fixed features) takes image_features (NI,R,F), previous_caption (NI,T), prev_caplen (NI,1);
-    DCNet (dcnet_rl.DAE) the caption pair only.  One beam-shaped pass for all images: per timestep one decode step over the
-    NI * n_samples slots, the pick, one state re-index; the host polls "no open slot" every 4 steps.  Finished sequences stay in
-    the beam and compete; nothing is deterministic about the result but its seed, which comes from rng.next_seed() as in the
-    sampled rollout (torch.manual_seed() reproduces a call).
-    Returns, per image, a list of up to n_samples entries (tokens, logp, G, finished) in DRAW order (G descending): tokens is a
-    list of max_steps words in the sampled rollouts' convention (<end> stored as 0, zeros behind it; tokens_from_greedy takes
-    them), logp the sequence's log-probability under the tempered model, G its perturbed log-probability.  max_steps defaults
-    to the sampled rollout's max_len; a sequence still open at the limit is returned as it is, with finished=False.  Fewer than
-    n_samples entries come back only when the model gives fewer sequences a non-zero probability.
-    n_samples must be 1 .. 8.  Adaptive features and the ensemble are not covered (ValueError)."""
-    import ctypes as C
-    from . import _lib, rng
-    from ._lib import check, ptr, stream_of
-    *inputs, word_map = inputs_and_word_map
-    if isinstance(model, (tuple, list)) or getattr(model, "_adaptive", 0) or getattr(model, "_ABI", None) not in ("editnet", "dcnet"):
-        raise ValueError("sample_captions_distinct supports editnet_rl.DecoderC with fixed features and dcnet_rl.DAE; adaptive "
-                         "features and the EditNet + DCNet ensemble are not covered")
-    if len(inputs) != (3 if model._ABI == "editnet" else 2):
-        raise ValueError("sample_captions_distinct(model, [image_features,] previous_caption, prev_caplen, word_map, ...): "
-                         "image_features for EditNet, none for DCNet")
+def _sbs_slots(n_samples, return_threshold):
+    """(n, slots of the search): return_threshold takes one slot more, so n_samples <= 7 with it"""
     k = int(n_samples)
-    if k != n_samples or k < 1 or k > SBS_MAX_SAMPLES:
-        raise ValueError("n_samples must be an integer in 1 .. %d, got %r" % (SBS_MAX_SAMPLES, n_samples))
-    opts = _lib.sample_opts(temperature)
+    top = SBS_MAX_SAMPLES - (1 if return_threshold else 0)
+    if k != n_samples or k < 1 or k > top:
+        raise ValueError("n_samples must be an integer in 1 .. %d%s, got %r"
+                         % (top, " with return_threshold (the threshold is one more slot)" if return_threshold else "", n_samples))
+    return k, k + (1 if return_threshold else 0)
+
+
+def _sbs_max_steps(model, max_steps):
     max_steps = int(getattr(model, "max_len", 18) if max_steps is None else max_steps)
     if max_steps < 1 or max_steps > 255:
         raise ValueError("max_steps must lie in 1 .. 255, got %r" % (max_steps,))
-    model.eval()
-    prev = inputs[-2].long().contiguous()
-    plen = inputs[-1].reshape(-1).long().contiguous()
-    if len(inputs) == 3:
-        X = inputs[0].float().contiguous()
-        m = _FusedModel(model, (X, None, prev, plen), (X,), k, max_steps)
-    else:
-        m = _FusedModel(model, (prev, plen), (), k, max_steps)
+    return max_steps
+
+
+def _sbs_search(models, NI, k, V, word_map, dev, max_steps, opts, return_steps):
+    """The stochastic beam search of NI images x k slots over one _FusedModel (set_sbs_pick_f32) or the EditNet + DCNet pair
+    (set_sbs_pick_ensemble_f32): per timestep every model steps on the same words into its own padded logits, the pick, one
+    set_beam_gather_f32 per model with the pick's rows; the host polls "no open slot" every 4 steps.  Returns (per image the
+    live slots' (tokens, logp, G, finished) in draw order, the per-step logits when asked for: a tensor per step for one model,
+    a tuple of two for the pair)."""
+    import ctypes as C
+    from . import _lib, rng
+    from ._lib import check, ptr, stream_of
     lib = _lib.load()
-    dev, V, NI = prev.device, model.vocab_size, prev.shape[0]
     st = stream_of(dev)
     start, end = int(word_map['<start>']), int(word_map['<end>'])
     B, neg = NI * k, float("-inf")
@@ -634,25 +617,31 @@ def sample_captions_distinct(model, *inputs_and_word_map, n_samples=5, temperatu
     # the leading dimension padded as the rollouts' workspace logits are: the pick then reads its rows as float4 (its register
     # path needs ld % 4 == 0; V = 9490 is no multiple of 4), the step writes V columns of every row
     ld = (V + 63) // 64 * 64
-    logits = torch.empty(B, ld, dtype=torch.float32, device=dev)
+    logits = [torch.empty(B, ld, dtype=torch.float32, device=dev) for _ in models]
     ws = torch.empty(lib.set_sbs_workspace_bytes(NI, k), dtype=torch.uint8, device=dev)
-    a = _lib.SbsArgs(logits=logits.data_ptr(), ld=ld, end_idx=end, seed=rng.next_seed(), offset=rng.offset(rng.SITE_ROLLOUT),
+    a = _lib.SbsArgs(logits=logits[0].data_ptr(), ld=ld, end_idx=end, seed=rng.next_seed(), offset=rng.offset(rng.SITE_ROLLOUT),
                      phi=phi.data_ptr(), G=G.data_ptr(), finished=fin.data_ptr(), len=length.data_ptr(),
                      words=words.data_ptr(), rows=rows.data_ptr(), n_open=n_open.data_ptr(), ws=ws.data_ptr(),
                      ws_bytes=ws.numel(), NI=NI, k=k, V=V, Lmax=max_steps)
     o = C.byref(opts) if opts is not None else None
     steps = []
-    s0, s1, s2, s3 = m.states
     for t in range(max_steps):
-        m.step(words, logits)
-        if _return_steps:
-            steps.append(logits[:, :V].clone())
+        for m, lg in zip(models, logits):
+            m.step(words, lg)
+        if return_steps:
+            got = tuple(lg[:, :V].clone() for lg in logits)
+            steps.append(got[0] if len(models) == 1 else got)
         a.t, a.seqs_in, a.seqs_out = t, seqs[0].data_ptr(), seqs[1].data_ptr()
-        check(lib.set_sbs_pick_f32(C.byref(a), o, st), "set_sbs_pick_f32")
+        if len(models) == 1:
+            check(lib.set_sbs_pick_f32(C.byref(a), o, st), "set_sbs_pick_f32")
+        else:
+            check(lib.set_sbs_pick_ensemble_f32(C.byref(a), ptr(logits[1]), o, st), "set_sbs_pick_ensemble_f32")
         seqs.reverse()
         if t + 1 == max_steps:
             break
-        check(lib.set_beam_gather_f32(ptr(s0), ptr(s1), ptr(s2), ptr(s3), ptr(rows), NI, k, m.D, st), "set_beam_gather_f32")
+        for m in models:
+            s0, s1, s2, s3 = m.states
+            check(lib.set_beam_gather_f32(ptr(s0), ptr(s1), ptr(s2), ptr(s3), ptr(rows), NI, k, m.D, st), "set_beam_gather_f32")
         if (t + 1) % 4 == 0 and int(n_open.max()) == 0:          # the only host synchronisation of the search
             break
     seqs_c, phi_c, G_c, fin_c, len_c = seqs[0].cpu(), phi.cpu(), G.cpu(), fin.cpu(), length.cpu()
@@ -666,7 +655,148 @@ def sample_captions_distinct(model, *inputs_and_word_map, n_samples=5, temperatu
             tk = [0 if w == end else w for w in seqs_c[i, j, :n].tolist()]
             entries.append((tk + [0] * (max_steps - n), float(phi_c[i, j]), float(G_c[i, j]), bool(fin_c[i, j])))
         out.append(entries)
-    return (out, steps) if _return_steps else out
+    return out, steps
+
+
+def _sbs_answer(out, steps, n, return_threshold, return_steps):
+    """the public return convention: out[, kappa][, steps]; with the threshold, the search ran n + 1 slots: the first n entries
+    are the sample and the G of entry n + 1 bounds everything that was not returned (-inf: there is nothing else)"""
+    res = (out,)
+    if return_threshold:
+        res = ([e[:n] for e in out], [e[n][2] if len(e) > n else float("-inf") for e in out])
+    if return_steps:
+        res = res + (steps,)
+    return res[0] if len(res) == 1 else res
+
+
+@torch.no_grad()
+def sample_captions_distinct(model, *inputs_and_word_map, n_samples=5, temperature=1.0, max_steps=None, return_threshold=False,
+                             _return_steps=False):
+    """Up to n_samples DISTINCT captions per image, an exact sample WITHOUT replacement from the model's (tempered) sequence
+    distribution, by stochastic beam search (Kool, van Hoof, Welling, ICML 2019; include/set_hip.h set_sbs_pick_f32):
+        out = sample_captions_distinct(decoder, image_features, previous_caption, prev_caplen, word_map, n_samples=5)
+        out = sample_captions_distinct(dae, previous_caption, prev_caplen, word_map, temperature=0.8)
+    EditNet (editnet_rl.DecoderC, fixed features) takes image_features (NI,R,F), previous_caption (NI,T), prev_caplen (NI,1);
+    DCNet (dcnet_rl.DAE) the caption pair only.  One beam-shaped pass for all images: per timestep one decode step over the
+    NI * n_samples slots, the pick, one state re-index; the host polls "no open slot" every 4 steps.  Finished sequences stay in
+    the beam and compete; nothing is deterministic about the result but its seed, which comes from rng.next_seed() as in the
+    sampled rollout (torch.manual_seed() reproduces a call).
+    Returns, per image, a list of up to n_samples entries (tokens, logp, G, finished) in DRAW order (G descending): tokens is a
+    list of max_steps words in the sampled rollouts' convention (<end> stored as 0, zeros behind it; tokens_from_greedy takes
+    them), logp the sequence's log-probability under the tempered model, G its perturbed log-probability.  max_steps defaults
+    to the sampled rollout's max_len; a sequence still open at the limit is returned as it is, with finished=False.  Fewer than
+    n_samples entries come back only when the model gives fewer sequences a non-zero probability.
+    return_threshold=True: returns (out, kappa).  The search runs n_samples + 1 slots; out[i] holds the first n_samples
+    entries and kappa[i] is the G of entry n_samples + 1 (-inf when the model gives no further sequence a non-zero
+    probability).  A search with m slots returns the m sequences with the largest perturbed scores, so kappa[i] bounds the G
+    of everything not returned: the threshold that sbs_importance_weights needs, after sbs_unconditioned_threshold (the search
+    conditions every image's largest G on being 0; see there).  n_samples <= 7 with the flag, and the draws
+    differ from those of the same seed without it (the slot count enters the row index, hence the noise): they are those of
+    the n_samples + 1 search.
+    n_samples must be 1 .. 8.  Adaptive features are not covered, and a model pair is refused (ValueError): the EditNet + DCNet
+    ensemble has its own entry, sample_captions_distinct_ensemble."""
+    from . import _lib
+    *inputs, word_map = inputs_and_word_map
+    if isinstance(model, (tuple, list)) or getattr(model, "_adaptive", 0) or getattr(model, "_ABI", None) not in ("editnet", "dcnet"):
+        raise ValueError("sample_captions_distinct supports editnet_rl.DecoderC with fixed features and dcnet_rl.DAE; adaptive "
+                         "features and the EditNet + DCNet ensemble are not covered")
+    if len(inputs) != (3 if model._ABI == "editnet" else 2):
+        raise ValueError("sample_captions_distinct(model, [image_features,] previous_caption, prev_caplen, word_map, ...): "
+                         "image_features for EditNet, none for DCNet")
+    n, k = _sbs_slots(n_samples, return_threshold)
+    opts = _lib.sample_opts(temperature)
+    max_steps = _sbs_max_steps(model, max_steps)
+    model.eval()
+    prev = inputs[-2].long().contiguous()
+    plen = inputs[-1].reshape(-1).long().contiguous()
+    if len(inputs) == 3:
+        X = inputs[0].float().contiguous()
+        m = _FusedModel(model, (X, None, prev, plen), (X,), k, max_steps)
+    else:
+        m = _FusedModel(model, (prev, plen), (), k, max_steps)
+    out, steps = _sbs_search([m], prev.shape[0], k, model.vocab_size, word_map, prev.device, max_steps, opts, _return_steps)
+    return _sbs_answer(out, steps, n, return_threshold, _return_steps)
+
+
+@torch.no_grad()
+def sample_captions_distinct_ensemble(decoder, dae, image_features, previous_caption, prev_caplen, word_map, n_samples=5,
+                                      temperature=1.0, max_steps=None, return_threshold=False, _return_steps=False):
+    """sample_captions_distinct for the EditNet + DCNet ENSEMBLE, the model of the reference's published scores
+    (eval_full.py:151-153; beam_search_ensemble*): up to n_samples distinct captions per image, an exact sample without
+    replacement from the sequence distribution whose every step is (softmax_e + softmax_d) / 2.  The averaged probabilities are
+    a distribution over the words at every step, so the construction applies unchanged (include/set_hip.h
+    set_sbs_pick_ensemble_f32).  Both models step on the same words; both states are re-indexed by the pick's rows.
+    The temperature tempers EACH model before the average (softmax(x_e / T) and softmax(x_d / T) are averaged, not the average
+    tempered).  Return convention, max_steps, return_threshold and the seed: sample_captions_distinct; logp is the sequence's
+    log-probability under the tempered ensemble.  max_steps defaults to the decoder's max_len.
+    ValueError: an adaptive-features decoder (the reference's ensemble uses fixed features), models that are not an
+    editnet_rl.DecoderC and a dcnet_rl.DAE, vocabularies of different size, n_samples outside 1 .. 8 (1 .. 7 with
+    return_threshold)."""
+    from . import _lib
+    if getattr(decoder, "_adaptive", 0) or getattr(decoder, "_ABI", None) != "editnet" or getattr(dae, "_ABI", None) != "dcnet":
+        raise ValueError("sample_captions_distinct_ensemble takes an editnet_rl.DecoderC with fixed features and a dcnet_rl.DAE; "
+                         "adaptive features are not covered")
+    if decoder.vocab_size != dae.vocab_size:
+        raise ValueError("sample_captions_distinct_ensemble: the models' vocabularies differ (%d and %d words); the ensemble "
+                         "averages their word distributions" % (decoder.vocab_size, dae.vocab_size))
+    n, k = _sbs_slots(n_samples, return_threshold)
+    opts = _lib.sample_opts(temperature)
+    max_steps = _sbs_max_steps(decoder, max_steps)
+    decoder.eval()
+    dae.eval()
+    X = image_features.float().contiguous()
+    prev = previous_caption.long().contiguous()
+    plen = prev_caplen.reshape(-1).long().contiguous()
+    e = _FusedModel(decoder, (X, None, prev, plen), (X,), k, max_steps)
+    d = _FusedModel(dae, (prev, plen), (), k, max_steps)
+    out, steps = _sbs_search([e, d], X.shape[0], k, decoder.vocab_size, word_map, X.device, max_steps, opts, _return_steps)
+    return _sbs_answer(out, steps, n, return_threshold, _return_steps)
+
+
+def sbs_unconditioned_threshold(kappa, e=None):
+    """The threshold of return_threshold with the conditioning on "the largest perturbed score of the image is 0" taken out:
+        kappa' = -log(exp(-kappa) + E - 1) = -log(expm1(-kappa) + E),   E ~ Exp(1), one draw per image
+    In u = exp(-G) the top-down construction only ever ADDS to the root's u (a child's conditioned u is its parent's plus a
+    difference of its siblings'), so a root at G = Z instead of 0 moves every u of the image by exp(-Z) - 1, and exp(-Z) of a
+    standard Gumbel Z is a standard exponential.  The map is increasing: order and sample are unchanged; the same map takes an
+    entry's G to its unconditioned value.  kappa = -inf stays -inf.
+    kappa: a float or a list of floats (one per image).  e: the exponential draws (a float or a list; tests), default: drawn
+    from torch's CPU generator, so torch.manual_seed() reproduces them.  Float64 on the host."""
+    import numpy as np
+    one = np.ndim(kappa) == 0
+    k = np.atleast_1d(np.asarray(kappa, np.float64))
+    if e is None:
+        e = torch.empty(len(k), dtype=torch.float64).exponential_().numpy()
+    e = np.broadcast_to(np.asarray(e, np.float64), k.shape)
+    with np.errstate(over="ignore", divide="ignore"):
+        out = -np.log(np.expm1(-k) + e)
+    return float(out[0]) if one else out.tolist()
+
+
+def sbs_importance_weights(entries, kappa, normalize=True):
+    """Importance weights of ONE image's stochastic-beam-search sample (Kool, van Hoof, Welling, ICML 2019, section 4.2):
+        out, kappa = sample_captions_distinct(model, ..., n_samples=5, return_threshold=True)
+        kappa = sbs_unconditioned_threshold(kappa)
+        w = sbs_importance_weights(out[i], kappa[i], normalize=False)
+        estimate = sum(w_j * f(entry_j) for w_j, entry_j in zip(w, out[i]))       # unbiased for E[f(caption)]
+    entries: the image's (tokens, logp, G, finished) list; kappa: its threshold.  In float64 on the host:
+        q_j = P(G_j > kappa) = 1 - exp(-exp(logp_j - kappa)) = -expm1(-exp(logp_j - kappa))
+        w_j = exp(logp_j) / q_j
+    kappa = -inf (the sample is the model's whole support) gives q_j = 1 and w_j = p_j.  normalize=True divides the weights by
+    their sum (the self-normalised estimator: biased, lower variance); normalize=False gives the unbiased estimator.
+    UNBIASED ONLY WITH AN UNCONDITIONED THRESHOLD.  The search starts every image's root at G = 0, i.e. it draws the perturbed
+    scores conditioned on their maximum being 0.  That leaves the sample and its order exact, but the raw kappa of
+    return_threshold is the threshold of the conditioned scores, and q_j above is the inclusion probability under independent
+    Gumbel scores: with the raw kappa the estimate is biased (table model of tests/sbs_fixtures.py, 2 of 40 sequences: the
+    estimate of E[1] is 0.84).  Pass kappa through sbs_unconditioned_threshold first.
+    Exact only for FINISHED sequences: an entry cut at max_steps stands for every continuation of its prefix, and its logp is
+    the prefix's.  Returns a float64 numpy array, one weight per entry."""
+    import numpy as np
+    phi = np.array([e[1] for e in entries], np.float64)
+    with np.errstate(over="ignore"):
+        q = -np.expm1(-np.exp(phi - np.float64(kappa)))
+    w = np.exp(phi) / q
+    return w / w.sum() if normalize and len(w) else w
 
 
 def tokens_from_greedy(seq, word_map):
