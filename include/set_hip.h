@@ -1022,6 +1022,33 @@ int set_sbs_pick_f32(const SetSbsArgs* args, const SetSampleOpts* opts, void* st
  * Profile scopes sbs_rows_ens / sbs_rows_ens_scalar, then sbs_merge.  Float64 restatement: tests/sbs_oracle.py on
  * L = log(0.5 (softmax(y_e) + softmax(y_d))) (tests/sbs_ensemble_fixtures.py). */
 int set_sbs_pick_ensemble_f32(const SetSbsArgs* args, const float* logits2, const SetSampleOpts* opts, void* stream);
+/* Both picks under TRUNCATION: opts carries temperature, top_k and top_p (SetSampleOpts; validated as set_sample_pick_opts_f32
+ * validates them; top_k >= V is off).  Every step's WORD distribution is cut to a kept set S and renormalised over it, which is
+ * still a distribution over the words: the top-down construction applies unchanged and the k sequences are the exact sample
+ * without replacement from the truncated model q.  phi is log q(prefix): the log-probability under the truncated, tempered model.
+ * The kept set of a live unfinished row, on z[v] (below), by the rules of the truncated sampled pick (SetSampleOpts above):
+ *   top-k (off at 0 or >= V): every word with z >= the top_k-th largest z, that value's ties all included;
+ *   top-p (off at 1), over what top-k kept: value groups in descending order until their mass sum exp(z - max z) reaches
+ *     top_p M (M: the mass of what top-k kept), the crossing group included whole;
+ *   the arg-max is always kept; comparisons are on values (-0.0 and +0.0 are one group).
+ * The mass of a candidate threshold is summed in one fixed order (per thread in enumeration order, a tree over the wave, waves in
+ * index order); a target closer to a group boundary than float32 summation resolves may fall on either side.
+ *   set_sbs_pick_opts_f32 (one model): z = y = fl32(x * (1.0f / temperature)).  Words outside S are -inf: never candidates.
+ *     phi'[v] = phi_j + (y[v] - logsumexp over S of y), the log-sum-exp formed as the untruncated pick forms its own.
+ *   set_sbs_pick_ensemble_opts_f32: the truncation applies to the ENSEMBLE's word distribution, not to each model.  Each model is
+ *     tempered and normalised on its own over the whole vocabulary and l[v] is formed as above; z = l;
+ *     phi'[v] = phi_j + (l[v] - L_S),   L_S = max l + log(sum over S of exp(l - max l)).
+ * g, Z, g~, the pick and every output are as above with phi' so defined; a word's noise does not depend on the options.  Fewer than
+ * k words in S leave dead slots, as fewer than k finite candidates do (top_k = 1: one live slot per image, phi = G = 0).
+ * NULL opts, or top_k off and top_p == 1: the untruncated kernel, state and outputs byte for byte those of set_sbs_pick_f32 /
+ * set_sbs_pick_ensemble_f32.  Refusals (SET_ERR_ARG before any HIP call, nothing written): those of the entries above except
+ * that top_k > 0 and top_p in (0, 1) are taken; top_k < 0, top_p outside (0, 1] or not finite, a temperature outside 1e-3 .. 1e3.
+ * Workspace: set_sbs_workspace_bytes, unchanged.  Both row-read paths give the same bytes; on the scalar path every pass of the
+ * bitwise descent (32 for top-k, 33 for top-p) re-reads the row, so callers pad the leading dimension.  Profile scopes
+ * sbs_rows_trunc / sbs_rows_trunc_scalar and sbs_rows_ens_trunc / sbs_rows_ens_trunc_scalar (the untruncated scopes when nothing
+ * is cut), then sbs_merge.  Float64 restatement: tests/sbs_trunc_oracle.py. */
+int set_sbs_pick_opts_f32(const SetSbsArgs* args, const SetSampleOpts* opts, void* stream);
+int set_sbs_pick_ensemble_opts_f32(const SetSbsArgs* args, const float* logits2, const SetSampleOpts* opts, void* stream);
 
 /* General-layout fp32 GEMM on the MFMA pipe, used for the Linear backward (replaces the cuBLAS calls
  * autograd makes for nn.Linear / nn.LSTMCell: dX = dY.W and dW += dY^T.X):

@@ -456,6 +456,8 @@ PROTOTYPES = {
     "set_sbs_workspace_bytes": (_Z, [_I, _I]),
     "set_sbs_pick_f32": (_I, [C.POINTER(SbsArgs), C.POINTER(SampleOpts), _P]),
     "set_sbs_pick_ensemble_f32": (_I, [C.POINTER(SbsArgs), _P, C.POINTER(SampleOpts), _P]),
+    "set_sbs_pick_opts_f32": (_I, [C.POINTER(SbsArgs), C.POINTER(SampleOpts), _P]),
+    "set_sbs_pick_ensemble_opts_f32": (_I, [C.POINTER(SbsArgs), _P, C.POINTER(SampleOpts), _P]),
     "set_gemm_group_f32": (_I, [C.POINTER(GemmDesc), _I, _I, _I, _P, _Z, _P]),
     "set_gemm_group_slabs_f32": (_I, [C.POINTER(GemmDesc), _I, _I, _I, _P, _Z, C.POINTER(SlabSrc), _P]),
     "set_editnet_xe_train_loop_f32": (_I, [C.POINTER(XELoopArgs), _P]),

@@ -343,12 +343,6 @@ struct SampleTrunc {
     int top_k = 0;        // 0: off (the host maps top_k >= V to 0)
     float top_p = 1.f;    // 1: off
 };
-// a < b as floats  <=>  key(a) < key(b) (non-NaN); -0.0 and +0.0 share a key, as they compare equal
-__device__ __forceinline__ uint32_t order_key(float f) {
-    const uint32_t u = __float_as_uint(f);
-    if (u == 0x80000000u) return 0x80000000u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 struct SampleOut {
     long long* raw_ids;   // (B) sampled word BEFORE the <end> -> 0 rewriting; -1 once the loop has been left

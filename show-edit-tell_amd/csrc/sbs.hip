@@ -17,6 +17,12 @@
 // sees only candidates and is shared.  The register path HOLDS BOTH ROWS (2 x 12 float4 per thread): no scratch on gfx950, and
 // one workgroup per row leaves at most one workgroup per CU, so the registers cost no occupancy that a launch of <= 128 rows
 // could use; re-reading the second row was therefore not needed.
+//
+// Truncation (set_sbs_pick_opts_f32 / set_sbs_pick_ensemble_opts_f32, sbs_rows_k<.., .., true>): top-k and top-p cut the WORD
+// distribution of every step to a kept set S, by the rules and the bitwise descent of sample_pick_k (epilogue.hip), and the log-
+// sum-exp is taken over S: phi is the log-probability under the truncated, renormalised model, of which the search is then the
+// exact sample without replacement.  One model: S on y.  Two models: S on l, the log of the averaged distributions.  The noise,
+// the candidates' selection and the merge are untouched.
 #include "set_common.h"
 #include "philox.h"
 
@@ -36,6 +42,13 @@ struct SbsRowArgs {
     float* cand_g; float* cand_phi; int* cand_v;         // (NI * k, SBS_KMAX)
 };
 
+// top_k / top_p of a truncated pick.  A kernel argument of its own: SbsRowArgs, and with it every argument offset of the untruncated
+// instantiations, stays as it was.
+struct SbsTrunc {
+    int top_k;                                   // 0: off (the host maps top_k >= V to 0)
+    float top_p;                                 // 1: off
+};
+
 // log(0.5 (exp(p) + exp(q))) = hi + log1p(exp(lo - hi)) - ln 2 with hi / lo the larger / smaller of the two; one -inf term gives
 // hi - ln 2, two give -inf (the word is no candidate)
 __device__ __forceinline__ float sbs_mean_logp(float p, float q) {
@@ -43,10 +56,16 @@ __device__ __forceinline__ float sbs_mean_logp(float p, float q) {
     return hi > -INFINITY ? (hi + log1pf(expf(lo - hi))) - 0.69314718f : -INFINITY;
 }
 
-// NM models per row: 1 = log_softmax(y); 2 = log(0.5 (softmax(y_e) + softmax(y_d))), each model tempered before the average
-template <bool REG, int NM>
-__global__ void __launch_bounds__(256) sbs_rows_k(const SbsRowArgs a) {
+// NM models per row: 1 = log_softmax(y); 2 = log(0.5 (softmax(y_e) + softmax(y_d))), each model tempered before the average.
+// TRUNC: the row's kept set S = {order_key(z) >= thr} is found on z = y (NM == 1) or z = l (NM == 2), words outside S are
+// never candidates and the log-sum-exp runs over S; at least one of tr.top_k / tr.top_p is on (the host launches the untruncated
+// instantiation otherwise).
+template <bool REG, int NM, bool TRUNC>
+__global__ void __launch_bounds__(256) sbs_rows_k(const SbsRowArgs a, const SbsTrunc tr) {
     __shared__ float s_red[NM][4];
+    __shared__ int s_cnt[2][4];          // TRUNC: per-wave partials of one descent pass, double-buffered (one barrier a pass)
+    __shared__ float s_mass[2][4];
+    __shared__ float s_zmax[4];          // TRUNC, NM == 2: the waves' maxima of l
     __shared__ float s_bv[2][4];
     __shared__ int s_bi[2][4];
     const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -57,6 +76,7 @@ __global__ void __launch_bounds__(256) sbs_rows_k(const SbsRowArgs a) {
     const float* row = a.logits + (long long)r * a.ld;
     const float* row2 = NM == 2 ? a.logits2 + (long long)r * a.ld : row;
     sbs_f32x4 x[SBS_MAXQ], x2[NM == 2 ? SBS_MAXQ : 1];
+    uint32_t thr = 0;                                    // TRUNC: S = {order_key(z) >= thr}; 0 until the descent has run
     if (REG) {
 #pragma unroll
         for (int q = 0; q < SBS_MAXQ; ++q) {
@@ -78,7 +98,8 @@ __global__ void __launch_bounds__(256) sbs_rows_k(const SbsRowArgs a) {
         }
     }
     // every thread visits its quads tid, tid + 256, ... in that order on either path, both models' quads of a visit together
-    // (NM == 1: the one row twice); words past V are -inf
+    // (NM == 1: the one row twice); words past V are -inf.  TRUNC, one model: words outside S are -inf once thr stands (the
+    // registers are cut in place, the scalar reads are masked here)
     auto sweep = [&](auto&& f) {
         if (REG) {
 #pragma unroll
@@ -89,6 +110,10 @@ __global__ void __launch_bounds__(256) sbs_rows_k(const SbsRowArgs a) {
                 sbs_f32x4 y, y2;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) y[e] = 4 * j + e < V ? __fmul_rn(row[4 * j + e], a.inv_t) : -INFINITY;
+                if (TRUNC && NM == 1) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) if (order_key(y[e]) < thr) y[e] = -INFINITY;
+                }
                 if (NM == 2) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) y2[e] = 4 * j + e < V ? __fmul_rn(row2[4 * j + e], a.inv_t) : -INFINITY;
@@ -116,6 +141,107 @@ __global__ void __launch_bounds__(256) sbs_rows_k(const SbsRowArgs a) {
 #pragma unroll
     for (int m = 0; m < NM; ++m) my[m] = fmaxf(fmaxf(s_red[m][0], s_red[m][1]), fmaxf(s_red[m][2], s_red[m][3]));
     __syncthreads();
+    // TRUNC, scalar path: quad j of z as the sweeps form it, uncut (NM == 2: lse stands by the time this is called); no read past V
+    auto zquad = [&](int j) -> sbs_f32x4 {
+        sbs_f32x4 z;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int v = 4 * j + e;
+            z[e] = v < V ? __fmul_rn(row[v], a.inv_t) : -INFINITY;
+            if (NM == 2) z[e] = sbs_mean_logp(z[e] - lse[0], (v < V ? __fmul_rn(row2[v], a.inv_t) : -INFINITY) - lse[NM - 1]);
+        }
+        return z;
+    };
+    // TRUNC: thr of the kept set of z with maximum `best`, sample_pick_k's descent (epilogue.hip): every pass is block-uniform,
+    // each wave leaves one partial in LDS, one barrier, every thread adds the four in the same order.  Padding (-inf) never
+    // changes a decision: it lies below every threshold that matters.  The registers are cut to S on the way out.
+    auto kept_threshold = [&](float best) -> uint32_t {
+        uint32_t key[SBS_MAXQ][4];
+        if (REG) {
+#pragma unroll
+            for (int q = 0; q < SBS_MAXQ; ++q)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) key[q][e] = order_key(x[q][e]);
+        }
+        int pass = 0;
+        uint32_t lo = 0, t = 0;
+        if (tr.top_k > 0) {              // lo = key of the top_k-th largest value: the largest lo with |{key >= lo}| >= top_k
+            for (int bit = 31; bit >= 0; --bit, ++pass) {
+                const uint32_t cand = lo | (1u << bit);
+                int c = 0;               // wave-uniform
+                if (REG) {
+#pragma unroll
+                    for (int q = 0; q < SBS_MAXQ; ++q)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) c += __popcll(__ballot(key[q][e] >= cand));
+                } else {
+                    for (int j0 = 0; 4 * j0 < V; j0 += 256) {             // (a block-uniform trip count: every lane votes)
+                        const sbs_f32x4 z = zquad(j0 + tid);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) c += __popcll(__ballot(order_key(z[e]) >= cand));
+                    }
+                }
+                if (lane == 0) s_cnt[pass & 1][wave] = c;
+                __syncthreads();
+                const int* sc = s_cnt[pass & 1];
+                if ((sc[0] + sc[1]) + (sc[2] + sc[3]) >= tr.top_k) lo = cand;
+            }
+            t = lo;
+        }
+        if (tr.top_p < 1.f) {
+            // mass of {kept by top-k, key >= cand}: per thread in enumeration order, xor tree over the wave, waves in index
+            // order — one fixed order for every cand, so the sum of these non-negative terms is monotone in cand
+            float m[SBS_MAXQ][4];
+            if (REG) {
+#pragma unroll
+                for (int q = 0; q < SBS_MAXQ; ++q)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) m[q][e] = key[q][e] >= lo ? expf(x[q][e] - best) : 0.f;
+            }
+            auto mass_ge = [&](uint32_t cand) -> float {
+                float sm = 0.f;
+                if (REG) {
+#pragma unroll
+                    for (int q = 0; q < SBS_MAXQ; ++q)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) sm += key[q][e] >= cand ? m[q][e] : 0.f;
+                } else {
+                    for (int j = tid; 4 * j < V; j += 256) {
+                        const sbs_f32x4 z = zquad(j);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const uint32_t kz = order_key(z[e]);
+                            sm += (kz >= lo && kz >= cand) ? expf(z[e] - best) : 0.f;
+                        }
+                    }
+                }
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) sm += __shfl_xor(sm, o);
+                if (lane == 0) s_mass[pass & 1][wave] = sm;
+                __syncthreads();
+                const float* sp = s_mass[pass & 1];
+                ++pass;
+                return (sp[0] + sp[1]) + (sp[2] + sp[3]);
+            };
+            const float need = tr.top_p * mass_ge(lo);
+            uint32_t hi = 0;             // the largest hi with mass_ge(hi) >= need; hi >= lo as mass_ge(lo) >= need
+            for (int bit = 31; bit >= 0; --bit) {
+                const uint32_t cand = hi | (1u << bit);
+                if (mass_ge(cand) >= need) hi = cand;
+            }
+            t = hi;
+        }
+        const uint32_t kbest = order_key(best);
+        if (t > kbest) t = kbest;        // the arg-max is always kept
+        if (REG) {
+#pragma unroll
+            for (int q = 0; q < SBS_MAXQ; ++q)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) if (key[q][e] < t) x[q][e] = -INFINITY;
+        }
+        return t;
+    };
+    if (TRUNC && NM == 1) thr = kept_threshold(my[0]);   // the sums below then run over S: lse is the log-sum-exp over S
     sweep([&](int, const sbs_f32x4& y, const sbs_f32x4& y2) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) sum[0] += expf(y[e] - my[0]);                     // exp(-inf) == 0
@@ -143,6 +269,37 @@ __global__ void __launch_bounds__(256) sbs_rows_k(const SbsRowArgs a) {
                 for (int e = 0; e < 4; ++e) x[q][e] = sbs_mean_logp(x[q][e] - lse[0], x2[NM == 2 ? q : 0][e] - lse[NM - 1]);
             }
     }
+    // TRUNC, two models: S on l, then L_S = max l + log(sum over S of exp(l - max l)); a kept word's log-probability is l - L_S
+    float LS = 0.f;
+    if (TRUNC && NM == 2) {
+        auto zsweep = [&](auto&& f) {                    // the quads of l in the sweeps' order: the registers, or recomputed
+            if (REG) {
+#pragma unroll
+                for (int q = 0; q < SBS_MAXQ; ++q)
+                    if ((tid + 256 * q) * 4 < V) f(x[q]);
+            } else {
+                for (int j = tid; 4 * j < V; j += 256) f(zquad(j));
+            }
+        };
+        float ml = -INFINITY;
+        zsweep([&](const sbs_f32x4& z) { ml = fmaxf(ml, max4(z)); });
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) ml = fmaxf(ml, __shfl_xor(ml, o));
+        if (lane == 0) s_zmax[wave] = ml;
+        __syncthreads();
+        ml = fmaxf(fmaxf(s_zmax[0], s_zmax[1]), fmaxf(s_zmax[2], s_zmax[3]));
+        thr = kept_threshold(ml);
+        float sm = 0.f;
+        zsweep([&](const sbs_f32x4& z) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) sm += order_key(z[e]) >= thr ? expf(z[e] - ml) : 0.f;
+        });
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) sm += __shfl_xor(sm, o);
+        if (lane == 0) s_red[0][wave] = sm;              // (every read of s_red for lse precedes the barrier above)
+        __syncthreads();
+        LS = ml + logf((s_red[0][0] + s_red[0][1]) + (s_red[0][2] + s_red[0][3]));
+    }
     // the thread's own best SBS_KMAX words by (g descending, v ascending): it meets its words in ascending order, so a strict
     // comparison keeps the lower word in front
     float tv[SBS_KMAX], tp[SBS_KMAX];
@@ -161,6 +318,10 @@ __global__ void __launch_bounds__(256) sbs_rows_k(const SbsRowArgs a) {
             } else {
                 l = REG ? y[e] : sbs_mean_logp(y[e] - lse[0], y2[e] - lse[NM - 1]);
                 if (!(l > -INFINITY)) continue;                                       // impossible in both models (and past V)
+                if (TRUNC) {
+                    if (!REG && order_key(l) < thr) continue;                         // outside S (the registers were cut)
+                    l -= LS;
+                }
             }
             const float ph = phij + l;
             const float g = ph + gumbel_of_word(c[e]);
@@ -313,15 +474,25 @@ size_t set_sbs_workspace_bytes(int NI, int k) {
     return 3 * round_up((size_t)NI * k * SBS_KMAX * sizeof(float), 256);
 }
 
-// logits2 == nullptr: one model (set_sbs_pick_f32); otherwise the two-model pick
-static int sbs_pick(const SetSbsArgs* a, const float* logits2, const SetSampleOpts* opts, void* stream) {
+// logits2 == nullptr: one model (set_sbs_pick_f32); otherwise the two-model pick.  with_trunc: the *_opts entries, whose opts
+// may carry top_k / top_p; the others refuse them
+static int sbs_pick(const SetSbsArgs* a, const float* logits2, const SetSampleOpts* opts, bool with_trunc, void* stream) {
     if (!a || !a->logits || !a->phi || !a->G || !a->finished || !a->len || !a->seqs_in || !a->seqs_out || !a->words || !a->rows ||
         !a->n_open || !a->ws)
         return SET_ERR_ARG;
     if (a->NI <= 0 || a->k < 1 || a->k > SBS_KMAX || a->V <= 0 || a->t < 0 || a->t > GUMBEL_MAX_LEN - 1 || a->ld < a->V ||
         a->Lmax < a->t + 1 || a->seqs_in == a->seqs_out || a->end_idx < 0 || a->end_idx >= a->V)
         return SET_ERR_ARG;                              // (<end> is a word: a finished slot's flat index j V + end_idx stays inside slot j)
-    SET_TRY(gumbel_opts_check(opts, a->V, 1));           // temperature only; V within the noise counters
+    SetSampleOpts tempered = {1.f, 0, 1.f, 0};           // opts without its truncation, for the check of the rest
+    SbsTrunc tc = {0, 1.f};
+    if (with_trunc && opts) {
+        SET_TRY(sample_opts_check(opts));
+        tempered.temperature = opts->temperature;
+        tc.top_k = opts->top_k >= a->V ? 0 : opts->top_k;
+        tc.top_p = opts->top_p;
+    }
+    SET_TRY(gumbel_opts_check(with_trunc ? &tempered : opts, a->V, 1));     // temperature only; V within the noise counters
+    const bool trunc = tc.top_k > 0 || tc.top_p < 1.f;   // nothing to cut: the untruncated instantiation, the same bytes
     if ((long long)a->NI * a->k >= 0x7fffffffLL / SBS_KMAX) return SET_ERR_ARG;
     if (a->ws_bytes < set_sbs_workspace_bytes(a->NI, a->k) || !aligned16(a->ws)) return SET_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
@@ -342,17 +513,24 @@ static int sbs_pick(const SetSbsArgs* a, const float* logits2, const SetSampleOp
     ma.words = (long long*)a->words; ma.rows = a->rows; ma.n_open = a->n_open;
     ma.cand_g = ra.cand_g; ma.cand_phi = ra.cand_phi; ma.cand_v = ra.cand_v;
     const bool reg = a->V <= 4 * 256 * SBS_MAXQ && !(a->ld & 3) && aligned16(a->logits) && aligned16(logits2);
+    // the scalar path re-reads the row in every sweep: three of them, and under truncation one per descent pass (32 for top-k,
+    // 33 for top-p) and, for two models, two more for the maximum and the sum over the kept set
+    const double sweeps = reg ? 1.0 : 3.0 + (trunc ? (tc.top_k > 0 ? 32.0 : 0.0) + (tc.top_p < 1.f ? 33.0 : 0.0) + (logits2 ? 2.0 : 0.0) : 0.0);
+#define SET_SBS_ROWS(REG, NM, TRUNC) hipLaunchKernelGGL((sbs_rows_k<REG, NM, TRUNC>), dim3(B), dim3(256), 0, st, ra, tc)
     if (!logits2) {
-        ProfScope ps(reg ? "sbs_rows" : "sbs_rows_scalar", st, 0.0, (reg ? 4.0 : 12.0) * B * a->V);
-        if (reg) hipLaunchKernelGGL((sbs_rows_k<true, 1>), dim3(B), dim3(256), 0, st, ra);
-        else hipLaunchKernelGGL((sbs_rows_k<false, 1>), dim3(B), dim3(256), 0, st, ra);
+        ProfScope ps(trunc ? (reg ? "sbs_rows_trunc" : "sbs_rows_trunc_scalar") : (reg ? "sbs_rows" : "sbs_rows_scalar"), st, 0.0,
+                     4.0 * sweeps * B * a->V);
+        if (trunc) { if (reg) SET_SBS_ROWS(true, 1, true); else SET_SBS_ROWS(false, 1, true); }
+        else { if (reg) SET_SBS_ROWS(true, 1, false); else SET_SBS_ROWS(false, 1, false); }
         SET_LAUNCH_CHECK();
     } else {
-        ProfScope ps(reg ? "sbs_rows_ens" : "sbs_rows_ens_scalar", st, 0.0, (reg ? 8.0 : 24.0) * B * a->V);
-        if (reg) hipLaunchKernelGGL((sbs_rows_k<true, 2>), dim3(B), dim3(256), 0, st, ra);
-        else hipLaunchKernelGGL((sbs_rows_k<false, 2>), dim3(B), dim3(256), 0, st, ra);
+        ProfScope ps(trunc ? (reg ? "sbs_rows_ens_trunc" : "sbs_rows_ens_trunc_scalar") : (reg ? "sbs_rows_ens" : "sbs_rows_ens_scalar"),
+                     st, 0.0, 8.0 * sweeps * B * a->V);
+        if (trunc) { if (reg) SET_SBS_ROWS(true, 2, true); else SET_SBS_ROWS(false, 2, true); }
+        else { if (reg) SET_SBS_ROWS(true, 2, false); else SET_SBS_ROWS(false, 2, false); }
         SET_LAUNCH_CHECK();
     }
+#undef SET_SBS_ROWS
     {
         ProfScope ps("sbs_merge", st, 0.0, 16.0 * B * (a->t + 1));
         hipLaunchKernelGGL(sbs_merge_k, dim3(a->NI), dim3(64), 0, st, ma);
@@ -361,11 +539,18 @@ static int sbs_pick(const SetSbsArgs* a, const float* logits2, const SetSampleOp
     return SET_OK;
 }
 
-int set_sbs_pick_f32(const SetSbsArgs* a, const SetSampleOpts* opts, void* stream) { return sbs_pick(a, nullptr, opts, stream); }
+int set_sbs_pick_f32(const SetSbsArgs* a, const SetSampleOpts* opts, void* stream) { return sbs_pick(a, nullptr, opts, false, stream); }
 
 int set_sbs_pick_ensemble_f32(const SetSbsArgs* a, const float* logits2, const SetSampleOpts* opts, void* stream) {
     if (!logits2) return SET_ERR_ARG;
-    return sbs_pick(a, logits2, opts, stream);
+    return sbs_pick(a, logits2, opts, false, stream);
+}
+
+int set_sbs_pick_opts_f32(const SetSbsArgs* a, const SetSampleOpts* opts, void* stream) { return sbs_pick(a, nullptr, opts, true, stream); }
+
+int set_sbs_pick_ensemble_opts_f32(const SetSbsArgs* a, const float* logits2, const SetSampleOpts* opts, void* stream) {
+    if (!logits2) return SET_ERR_ARG;
+    return sbs_pick(a, logits2, opts, true, stream);
 }
 
 }  // extern "C"

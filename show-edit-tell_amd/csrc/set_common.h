@@ -450,6 +450,13 @@ inline int sample_opts_check(const SetSampleOpts* o) {
 inline bool sample_opts_neutral(const SetSampleOpts* o) {
     return !o || (o->temperature == 1.f && o->top_k == 0 && o->top_p == 1.f);
 }
+// the order-preserving key of the truncated picks (epilogue.hip sample_pick_k, sbs.hip sbs_rows_k): a < b as floats  <=>
+// key(a) < key(b) (non-NaN); -0.0 and +0.0 share a key, as they compare equal
+__device__ __forceinline__ uint32_t order_key(float f) {
+    const uint32_t u = __float_as_uint(f);
+    if (u == 0x80000000u) return 0x80000000u;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
 // Gumbel-max pick (epilogue.hip gumbel_pick_k; the draw: philox.h): the arguments of sample_pick; opts carries the temperature only.
 // gumbel_opts_check: what every Gumbel entry refuses with SET_ERR_ARG before any HIP call (options sample_opts_check refuses,
 // top_k != 0, top_p != 1, max_len > 255, V beyond the noise counters)

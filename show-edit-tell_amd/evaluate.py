@@ -593,11 +593,11 @@ def _sbs_max_steps(model, max_steps):
 
 
 def _sbs_search(models, NI, k, V, word_map, dev, max_steps, opts, return_steps):
-    """The stochastic beam search of NI images x k slots over one _FusedModel (set_sbs_pick_f32) or the EditNet + DCNet pair
-    (set_sbs_pick_ensemble_f32): per timestep every model steps on the same words into its own padded logits, the pick, one
-    set_beam_gather_f32 per model with the pick's rows; the host polls "no open slot" every 4 steps.  Returns (per image the
-    live slots' (tokens, logp, G, finished) in draw order, the per-step logits when asked for: a tensor per step for one model,
-    a tuple of two for the pair)."""
+    """The stochastic beam search of NI images x k slots over one _FusedModel (set_sbs_pick_opts_f32) or the EditNet + DCNet
+    pair (set_sbs_pick_ensemble_opts_f32; opts: temperature, top_k, top_p, or None): per timestep every model steps on the same
+    words into its own padded logits, the pick, one set_beam_gather_f32 per model with the pick's rows; the host polls "no open
+    slot" every 4 steps.  Returns (per image the live slots' (tokens, logp, G, finished) in draw order, the per-step logits when
+    asked for: a tensor per step for one model, a tuple of two for the pair)."""
     import ctypes as C
     from . import _lib, rng
     from ._lib import check, ptr, stream_of
@@ -633,9 +633,9 @@ def _sbs_search(models, NI, k, V, word_map, dev, max_steps, opts, return_steps):
             steps.append(got[0] if len(models) == 1 else got)
         a.t, a.seqs_in, a.seqs_out = t, seqs[0].data_ptr(), seqs[1].data_ptr()
         if len(models) == 1:
-            check(lib.set_sbs_pick_f32(C.byref(a), o, st), "set_sbs_pick_f32")
+            check(lib.set_sbs_pick_opts_f32(C.byref(a), o, st), "set_sbs_pick_opts_f32")
         else:
-            check(lib.set_sbs_pick_ensemble_f32(C.byref(a), ptr(logits[1]), o, st), "set_sbs_pick_ensemble_f32")
+            check(lib.set_sbs_pick_ensemble_opts_f32(C.byref(a), ptr(logits[1]), o, st), "set_sbs_pick_ensemble_opts_f32")
         seqs.reverse()
         if t + 1 == max_steps:
             break
@@ -670,11 +670,13 @@ def _sbs_answer(out, steps, n, return_threshold, return_steps):
 
 
 @torch.no_grad()
-def sample_captions_distinct(model, *inputs_and_word_map, n_samples=5, temperature=1.0, max_steps=None, return_threshold=False,
-                             _return_steps=False):
+def sample_captions_distinct(model, *inputs_and_word_map, n_samples=5, temperature=1.0, top_k=0, top_p=1.0, max_steps=None,
+                             return_threshold=False, _return_steps=False):
     """Up to n_samples DISTINCT captions per image, an exact sample WITHOUT replacement from the model's (tempered) sequence
-    distribution, by stochastic beam search (Kool, van Hoof, Welling, ICML 2019; include/set_hip.h set_sbs_pick_f32):
+    distribution, by stochastic beam search (Kool, van Hoof, Welling, ICML 2019; include/set_hip.h set_sbs_pick_f32 /
+    set_sbs_pick_opts_f32):
         out = sample_captions_distinct(decoder, image_features, previous_caption, prev_caplen, word_map, n_samples=5)
+        out = sample_captions_distinct(decoder, image_features, previous_caption, prev_caplen, word_map, n_samples=5, top_p=0.9)
         out = sample_captions_distinct(dae, previous_caption, prev_caplen, word_map, temperature=0.8)
     EditNet (editnet_rl.DecoderC, fixed features) takes image_features (NI,R,F), previous_caption (NI,T), prev_caplen (NI,1);
     DCNet (dcnet_rl.DAE) the caption pair only.  One beam-shaped pass for all images: per timestep one decode step over the
@@ -683,16 +685,21 @@ def sample_captions_distinct(model, *inputs_and_word_map, n_samples=5, temperatu
     sampled rollout (torch.manual_seed() reproduces a call).
     Returns, per image, a list of up to n_samples entries (tokens, logp, G, finished) in DRAW order (G descending): tokens is a
     list of max_steps words in the sampled rollouts' convention (<end> stored as 0, zeros behind it; tokens_from_greedy takes
-    them), logp the sequence's log-probability under the tempered model, G its perturbed log-probability.  max_steps defaults
-    to the sampled rollout's max_len; a sequence still open at the limit is returned as it is, with finished=False.  Fewer than
-    n_samples entries come back only when the model gives fewer sequences a non-zero probability.
-    return_threshold=True: returns (out, kappa).  The search runs n_samples + 1 slots; out[i] holds the first n_samples
-    entries and kappa[i] is the G of entry n_samples + 1 (-inf when the model gives no further sequence a non-zero
-    probability).  A search with m slots returns the m sequences with the largest perturbed scores, so kappa[i] bounds the G
-    of everything not returned: the threshold that sbs_importance_weights needs, after sbs_unconditioned_threshold (the search
-    conditions every image's largest G on being 0; see there).  n_samples <= 7 with the flag, and the draws
-    differ from those of the same seed without it (the slot count enters the row index, hence the noise): they are those of
-    the n_samples + 1 search.
+    them), logp the sequence's log-probability under the tempered, truncated model, G its perturbed log-probability.  max_steps
+    defaults to the sampled rollout's max_len; a sequence still open at the limit is returned as it is, with finished=False.
+    Fewer than n_samples entries come back only when the model gives fewer sequences a non-zero probability.
+    top_k / top_p (sample_captions' options; 0 / 1.0: off) cut every step's word distribution to the top_k most probable words
+    and then to the smallest head holding top_p of their mass (ties kept whole), renormalised: the result is the exact sample
+    without replacement from that TRUNCATED model, logp is the log-probability under it, and no returned sequence holds a word
+    outside its step's kept set.  The truncated model has fewer sequences: with top_k=1 it has one, so exactly one entry comes
+    back per image (the greedy words, logp = G = 0).  Neutral values return what the call without them returns.
+    return_threshold=True: returns (out, kappa).  The search runs n_samples + 1 slots; out[i] holds the first n_samples entries
+    and kappa[i] is the G of entry n_samples + 1 (-inf when the model, truncated if top_k / top_p say so, gives no further
+    sequence a non-zero probability).  A search with m slots returns the m sequences with the largest perturbed scores, so
+    kappa[i] bounds the G of everything not returned: the threshold that sbs_importance_weights needs, after
+    sbs_unconditioned_threshold (the search conditions every image's largest G on being 0; see there); under top_k / top_p the
+    weights estimate expectations under the truncated model.  n_samples <= 7 with the flag, and the draws differ from those of
+    the same seed without it (the slot count enters the row index, hence the noise): they are those of the n_samples + 1 search.
     n_samples must be 1 .. 8.  Adaptive features are not covered, and a model pair is refused (ValueError): the EditNet + DCNet
     ensemble has its own entry, sample_captions_distinct_ensemble."""
     from . import _lib
@@ -704,7 +711,7 @@ def sample_captions_distinct(model, *inputs_and_word_map, n_samples=5, temperatu
         raise ValueError("sample_captions_distinct(model, [image_features,] previous_caption, prev_caplen, word_map, ...): "
                          "image_features for EditNet, none for DCNet")
     n, k = _sbs_slots(n_samples, return_threshold)
-    opts = _lib.sample_opts(temperature)
+    opts = _lib.sample_opts(temperature, top_k, top_p)
     max_steps = _sbs_max_steps(model, max_steps)
     model.eval()
     prev = inputs[-2].long().contiguous()
@@ -720,18 +727,23 @@ def sample_captions_distinct(model, *inputs_and_word_map, n_samples=5, temperatu
 
 @torch.no_grad()
 def sample_captions_distinct_ensemble(decoder, dae, image_features, previous_caption, prev_caplen, word_map, n_samples=5,
-                                      temperature=1.0, max_steps=None, return_threshold=False, _return_steps=False):
+                                      temperature=1.0, top_k=0, top_p=1.0, max_steps=None, return_threshold=False,
+                                      _return_steps=False):
     """sample_captions_distinct for the EditNet + DCNet ENSEMBLE, the model of the reference's published scores
     (eval_full.py:151-153; beam_search_ensemble*): up to n_samples distinct captions per image, an exact sample without
     replacement from the sequence distribution whose every step is (softmax_e + softmax_d) / 2.  The averaged probabilities are
     a distribution over the words at every step, so the construction applies unchanged (include/set_hip.h
     set_sbs_pick_ensemble_f32).  Both models step on the same words; both states are re-indexed by the pick's rows.
     The temperature tempers EACH model before the average (softmax(x_e / T) and softmax(x_d / T) are averaged, not the average
-    tempered).  Return convention, max_steps, return_threshold and the seed: sample_captions_distinct; logp is the sequence's
-    log-probability under the tempered ensemble.  max_steps defaults to the decoder's max_len.
+    tempered).  top_k / top_p truncate the ENSEMBLE's word distribution (the average), not each model before it: the kept set
+    is taken on log((softmax_e + softmax_d) / 2) and the average is renormalised over it (set_sbs_pick_ensemble_opts_f32).
+    Return convention, max_steps, return_threshold and the seed: sample_captions_distinct; logp is the sequence's
+    log-probability under the tempered, truncated ensemble (top_k=1: one entry per image; kappa = -inf when the truncated
+    ensemble has no further sequence; the importance weights estimate expectations under it).  max_steps defaults to the
+    decoder's max_len.
     ValueError: an adaptive-features decoder (the reference's ensemble uses fixed features), models that are not an
     editnet_rl.DecoderC and a dcnet_rl.DAE, vocabularies of different size, n_samples outside 1 .. 8 (1 .. 7 with
-    return_threshold)."""
+    return_threshold), options sample_captions refuses."""
     from . import _lib
     if getattr(decoder, "_adaptive", 0) or getattr(decoder, "_ABI", None) != "editnet" or getattr(dae, "_ABI", None) != "dcnet":
         raise ValueError("sample_captions_distinct_ensemble takes an editnet_rl.DecoderC with fixed features and a dcnet_rl.DAE; "
@@ -740,7 +752,7 @@ def sample_captions_distinct_ensemble(decoder, dae, image_features, previous_cap
         raise ValueError("sample_captions_distinct_ensemble: the models' vocabularies differ (%d and %d words); the ensemble "
                          "averages their word distributions" % (decoder.vocab_size, dae.vocab_size))
     n, k = _sbs_slots(n_samples, return_threshold)
-    opts = _lib.sample_opts(temperature)
+    opts = _lib.sample_opts(temperature, top_k, top_p)
     max_steps = _sbs_max_steps(decoder, max_steps)
     decoder.eval()
     dae.eval()
