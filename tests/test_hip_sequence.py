@@ -126,6 +126,56 @@ def test_training_loop_schedules_agree(min_len, monkeypatch):
             assert err < 1e-3, (name, k, err)
 
 
+def _planner_splits(shapes):
+    """whether set_gemm_group_slabs_f32 keeps every one of these (M, N, K) products of the backward loop (layout (0, 1), the loop's
+    own scratch size) as split-K partials"""
+    from show_edit_tell_amd import _lib
+    lib, dev = _lib.load(), _dev()
+    n = len(shapes)
+    descs, outs, keep = (_lib.GemmDesc * n)(), (_lib.SlabSrc * n)(), []
+    for i, (M, N, K) in enumerate(shapes):
+        a, b, c = torch.randn(M, K, device=dev), torch.randn(K, N, device=dev), torch.empty(M, N, device=dev)
+        keep += [a, b, c]
+        descs[i] = _lib.GemmDesc(a.data_ptr(), K, b.data_ptr(), N, c.data_ptr(), N, M, N, K, 0)
+    ws = torch.empty(32 << 20, dtype=torch.uint8, device=dev)
+    _lib.check(lib.set_gemm_group_slabs_f32(descs, n, 0, 1, ws.data_ptr(), ws.numel(), outs, _lib.stream_of(dev)),
+               "set_gemm_group_slabs_f32")
+    torch.cuda.synchronize()
+    return [o.nslab for o in outs]
+
+
+@pytest.mark.parametrize("train", [True, False], ids=["train", "eval"])
+def test_training_loop_schedules_agree_where_products_split(train, monkeypatch):
+    """test_training_loop_schedules_agree at D = 512, where the per-timestep dX products of the backward really are split and
+    every addend list the loops build has nslab >= 2 (at D = 64 / 128 none is): the C timestep loop with its three merged
+    launches against the Python loop with the public *_src_f32 entry points, which tests/test_hip_slab_src.py checks one by
+    one.  Train mode and eval mode (eval accumulates datt1: acc_datt1 = 1).  Same comparisons, same two bounds."""
+    from show_edit_tell_amd import xe_sequence as xs
+    B, V, D, A, F = 8, 203, 512, 32, 256
+    depths = _planner_splits([(B, D, D), (B, D, D)]) + _planner_splits([(B, D, 4 * D)] * 4)
+    assert all(d >= 2 for d in depths), depths
+    m = _build(V, D, A, F)
+    m = m.train() if train else m.eval()
+    inputs = _inputs(B, 36, F, 20, V, 6)                    # ragged lengths: rows leave the batch
+    runs = {}
+    for name, c_loops, step_logs in (("c", True, False), ("c_logs", True, True), ("py", False, False)):
+        monkeypatch.setattr(xs, "_C_LOOPS", c_loops)
+        monkeypatch.setattr(xs, "_STEP_LOGS", step_logs)
+        torch.manual_seed(11)
+        runs[name] = _loss_and_grads(m, inputs, True, True, monkeypatch)
+    p0, g0 = runs["py"]
+    gmax = max(float(g.abs().max()) for g in g0.values())
+    for name in ("c", "c_logs"):
+        p1, g1 = runs[name]
+        assert float((p0 - p1).abs().max()) <= 2e-5 * max(1.0, float(p0.abs().max())), name
+        assert set(g0) == set(g1)
+        for k in g0:
+            if k.endswith("full_att.bias"):
+                continue
+            err = float((g0[k] - g1[k]).abs().max()) / max(float(g0[k].abs().max()), 1e-6 * gmax)
+            assert err < 1e-3, (name, k, err)
+
+
 @pytest.mark.parametrize("order", ["shuffled", "sorted"])
 def test_host_caption_lengths_give_the_same_forward(order, monkeypatch):
     """`DecoderC.with_host_lengths` (the training steps pass the loader's host copy of the lengths): the sort order and the
