@@ -2,12 +2,12 @@
 //   greedy (editnet_rl.py:514-543, dcnet_rl.py:313-340): log_softmax, first arg-max, <end> -> 0,
 //   `unfinished` latch, seq / seqLogprobs stores, early-break emulation, and the NEXT step's
 //   embedding gather relu(E[it]) (editnet.py:300-304) fused in so the loop needs no extra launch.
-#include "set_common.h"
+// The sampled and Gumbel-max picks follow.  What greedy_pick_k and gumbel_pick_k have in common — the fixed-order block sum and the
+// bookkeeping after the word — is row_pick.h (sample_pick_k spells its own out: through the helpers it measured up to 2 % slower); the kernels here differ in how the word is chosen.
+#include "row_pick.h"
 #include "philox.h"
 
 namespace set {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float logit_at(const Slabs& s, const float* bias, long long row, int v) {
     const float* p = s.p + row * s.ld + v;
@@ -82,6 +82,17 @@ __device__ __forceinline__ const float* tail_row(const LstmTail& L, long long to
     tok = tok < 0 ? 0 : (tok >= L.nrows ? L.nrows - 1 : tok);       // clamped like RowGather::row
     return L.tab + tok * L.ld_tab + L.col0;
 }
+// the whole cell of row b for word tok, by the whole workgroup, from column j0 = 4 tid (+ 1024 when the first piece is done)
+__device__ __forceinline__ void pick_tail_rows(const LstmTail& L, int b, long long tok, int j0) {
+    const float* trow = tail_row(L, tok);
+    for (int j = j0; j < L.D; j += 1024) {
+        TailRegs r;
+        TailRow w;
+        tail_fetch(L, b, j, r);
+        tail_row_fetch(L, j, trow, w);
+        tail_finish(L, b, j, w, r);
+    }
+}
 
 static bool tail_ok(const LstmTail& L) {
     return L.D > 0 && !(L.D & 3) && L.g0.p && L.g0.n >= 1 && !(L.g0.ld & 3) && !(L.g0.stride & 3) && aligned16(L.g0.p) &&
@@ -92,9 +103,8 @@ static bool tail_ok(const LstmTail& L) {
 // grid = B rows.  alive[t] counts rows still unfinished after step t (zeroed by the caller);
 // once alive[t-1] == 0 the reference has left its loop (`break`, editnet_rl.py:546) and nothing
 // more is written to seq / seq_logp.
-// REG = true: the row (<= 4*256*GP_MAXQ logits) is read ONCE as float4 (all K-slabs + bias summed
+// REG = true: the row (<= 4*256*ROW_MAXQ logits) is read ONCE as float4 (all K-slabs + bias summed
 // in registers), max / first-argmax and sum-exp are reduced from registers.
-constexpr int GP_MAXQ = 12;
 
 template <bool REG, bool TAIL>
 __global__ void SET_VGPR_CAP __launch_bounds__(256) greedy_pick_k(Slabs logits, const float* bias, int V, int t, int max_len,
@@ -121,16 +131,16 @@ __global__ void SET_VGPR_CAP __launch_bounds__(256) greedy_pick_k(Slabs logits, 
     if (TAIL) { if (tail0) tail_fetch(tail, b, tid * 4, tr); }
     float best = -INFINITY;
     int bi = 0x7fffffff;
-    f32x4 x[GP_MAXQ];
+    f32x4 x[ROW_MAXQ];
     if (REG) {
         const float* row = logits.p + (long long)b * logits.ld;
-        // slab 0 (+ bias), then the remaining K-slabs in index order; GP_MAXQ independent float4 loads
+        // slab 0 (+ bias), then the remaining K-slabs in index order; ROW_MAXQ independent float4 loads
         // are in flight per pass
         const bool bias4 = bias && !(V & 3) && ((reinterpret_cast<uintptr_t>(bias) & 15u) == 0);
         // the bias does not depend on the slabs: request it first (added last, as before)
-        f32x4 bq[GP_MAXQ];
+        f32x4 bq[ROW_MAXQ];
 #pragma unroll
-        for (int q = 0; q < GP_MAXQ; ++q) {
+        for (int q = 0; q < ROW_MAXQ; ++q) {
             const int v = (tid + 256 * q) * 4;
             bq[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
             if (v < V) {
@@ -145,16 +155,16 @@ __global__ void SET_VGPR_CAP __launch_bounds__(256) greedy_pick_k(Slabs logits, 
             }
         }
 #pragma unroll
-        for (int q = 0; q < GP_MAXQ; ++q) {
+        for (int q = 0; q < ROW_MAXQ; ++q) {
             const int v = (tid + 256 * q) * 4;
             x[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
             if (v < V) x[q] = *reinterpret_cast<const f32x4*>(row + v);
         }
         int i = 1;
-        for (; i + 2 <= logits.n; i += 2) {          // two slabs (2 x GP_MAXQ loads) in flight, added in slab order
-            f32x4 y[GP_MAXQ], z[GP_MAXQ];
+        for (; i + 2 <= logits.n; i += 2) {          // two slabs (2 x ROW_MAXQ loads) in flight, added in slab order
+            f32x4 y[ROW_MAXQ], z[ROW_MAXQ];
 #pragma unroll
-            for (int q = 0; q < GP_MAXQ; ++q) {
+            for (int q = 0; q < ROW_MAXQ; ++q) {
                 const int v = (tid + 256 * q) * 4;
                 y[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
                 z[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -164,28 +174,28 @@ __global__ void SET_VGPR_CAP __launch_bounds__(256) greedy_pick_k(Slabs logits, 
                 }
             }
 #pragma unroll
-            for (int q = 0; q < GP_MAXQ; ++q) { x[q] += y[q]; x[q] += z[q]; }
+            for (int q = 0; q < ROW_MAXQ; ++q) { x[q] += y[q]; x[q] += z[q]; }
         }
         for (; i < logits.n; ++i) {
-            f32x4 y[GP_MAXQ];
+            f32x4 y[ROW_MAXQ];
 #pragma unroll
-            for (int q = 0; q < GP_MAXQ; ++q) {
+            for (int q = 0; q < ROW_MAXQ; ++q) {
                 const int v = (tid + 256 * q) * 4;
                 y[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
                 if (v < V) y[q] = *reinterpret_cast<const f32x4*>(row + (long long)i * logits.stride + v);
             }
 #pragma unroll
-            for (int q = 0; q < GP_MAXQ; ++q) x[q] += y[q];
+            for (int q = 0; q < ROW_MAXQ; ++q) x[q] += y[q];
         }
 #pragma unroll
-        for (int q = 0; q < GP_MAXQ; ++q) {
+        for (int q = 0; q < ROW_MAXQ; ++q) {
             const int v = (tid + 256 * q) * 4;
             if (bias) x[q] += bq[q];
 #pragma unroll
             for (int e = 0; e < 4; ++e) if (v + e >= V) x[q][e] = -INFINITY;     // padding columns / rows past V
         }
 #pragma unroll
-        for (int q = 0; q < GP_MAXQ; ++q)
+        for (int q = 0; q < ROW_MAXQ; ++q)
 #pragma unroll
             for (int e = 0; e < 4; ++e)
                 if (x[q][e] > best) { best = x[q][e]; bi = (tid + 256 * q) * 4 + e; }   // ascending index per thread
@@ -215,64 +225,48 @@ __global__ void SET_VGPR_CAP __launch_bounds__(256) greedy_pick_k(Slabs logits, 
     // token-table row NOW, so that round trip runs under the sum-exp pass instead of after the serial bookkeeping
     TailRow tw;
     if (TAIL) {
-        long long it = bi;
-        if (it == end_idx) it = 0;
-        const int unf = (t == 0) ? (it > 0) : (unf_prev && it > 0);
-        it = unf ? it : 0;
+        int unf;
+        const long long it = pick_latch(bi, end_idx, t, unf_prev, unf);
         if (tail0) tail_row_fetch(tail, tid * 4, tail_row(tail, it), tw);
     }
     float sum = 0.f;
     if (REG) {
 #pragma unroll
-        for (int q = 0; q < GP_MAXQ; ++q)
+        for (int q = 0; q < ROW_MAXQ; ++q)
 #pragma unroll
             for (int e = 0; e < 4; ++e) sum += expf(x[q][e] - best);               // exp(-inf) == 0 for padding
     } else {
         for (int v = tid; v < V; v += 256) sum += expf(logit_at(logits, bias, b, v) - best);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-    if (lane == 0) s_sum[wave] = sum;
-    __syncthreads();
+    const float total = block_sum(sum, s_sum);
     if (tid == 0) {
-        const float total = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
         const float logp = (best - best) - logf(total);         // log_softmax at the arg-max
-        long long it = bi;
-        if (it == end_idx) it = 0;
-        int unf = (t == 0) ? (it > 0) : (unf_prev && it > 0);
-        it = unf ? it : 0;
-        const bool broken = (t > 0) && (alive_prev == 0);
-        if (t < max_len && !broken) {
-            seq[(long long)b * max_len + t] = it;
-            seq_logp[(long long)b * max_len + t] = logp;
-        }
-        unfinished[b] = unf;
-        if (unf) atomicAdd(&alive[t], 1);
-        it_buf[b] = it;
-        s_tok = it;
+        pick_commit(b, t, max_len, end_idx, bi, logp, 0.f, unf_prev, alive_prev, seq, seq_logp, it_buf, unfinished, alive,
+                    SampleOut{nullptr, nullptr, nullptr, nullptr}, &s_tok);
     }
     __syncthreads();
-    if (emb_out && table) {
-        const long long tok = s_tok;
-        for (int d = tid * 4; d < D; d += 1024) {
-            f32x4 v = *reinterpret_cast<const f32x4*>(table + tok * D + d);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
-            *reinterpret_cast<f32x4*>(emb_out + (long long)b * D + d) = v;
-        }
-    }
+    if (emb_out && table) pick_embed(table, emb_out, b, s_tok, D);
     if (TAIL) {
         if (tail0) tail_finish(tail, b, tid * 4, tw, tr);
-        const float* trow = tail_row(tail, s_tok);
-        for (int j = tid * 4 + 1024; j < tail.D; j += 1024) {
-            TailRegs r2;
-            TailRow w2;
-            tail_fetch(tail, b, j, r2);
-            tail_row_fetch(tail, j, trow, w2);
-            tail_finish(tail, b, j, w2, r2);
-        }
+        pick_tail_rows(tail, b, s_tok, tid * 4 + 1024);
     }
 }
+
+// ---- host side of the three picks.  pick_args_check: the refusals they share after `B <= 0`, in their order.  SET_PICK_ROWS: one
+// workgroup per row on the arguments every pick function has under these names (B, s, logits .. D), followed by the kernel's own.
+// SET_PICK_DISPATCH: LAUNCH(REG, TAIL) by the row layout (pick_reg_ok) and the presence of a tail.  #undef'd after gumbel_pick.
+static int pick_args_check(int D, const LstmTail* tail) {
+    if (D & 3) return SET_ERR_UNSUPPORTED;
+    return tail && !tail_ok(*tail) ? SET_ERR_ARG : SET_OK;
+}
+#define SET_PICK_ROWS(KERNEL, ...)                                                                                         \
+    hipLaunchKernelGGL(KERNEL, dim3(B), dim3(256), 0, s, logits, bias, V, t, max_len, end_idx, seq, seq_logp, it, unfinished, \
+                       alive, table, emb_out, D, __VA_ARGS__)
+#define SET_PICK_DISPATCH(LAUNCH)                                                 \
+    do {                                                                          \
+        if (pick_reg_ok(logits, V)) { if (tail) LAUNCH(true, true); else LAUNCH(true, false); } \
+        else { if (tail) LAUNCH(false, true); else LAUNCH(false, false); }        \
+    } while (0)
 
 int greedy_pick(Slabs logits, const float* bias, int V, int t, int max_len, long long end_idx, long long* seq,
                 float* seq_logp, long long* it, int* unfinished, int* alive, const float* table, float* emb_out,
@@ -281,17 +275,12 @@ int greedy_pick(Slabs logits, const float* bias, int V, int t, int max_len, long
     return SET_OK;
 #endif
     if (B <= 0) return SET_OK;
-    if (D & 3) return SET_ERR_UNSUPPORTED;
-    if (tail && !tail_ok(*tail)) return SET_ERR_ARG;
+    SET_TRY(pick_args_check(D, tail));
     const LstmTail tl = tail ? *tail : LstmTail();
     ProfScope ps("greedy_pick", s, 0.0,
                  4.0 * B * (2.0 * V * logits.n + 2.0 * D + (tail ? tl.D * (4.0 * (tl.g0.n + 2) + 3.0) : 0.0)));
-    const bool reg = V <= 4 * 256 * GP_MAXQ && !(logits.ld & 3) && !(logits.stride & 3) && aligned16(logits.p);
-#define SET_PICK_LAUNCH(REG, TAIL)                                                                                    \
-    hipLaunchKernelGGL((greedy_pick_k<REG, TAIL>), dim3(B), dim3(256), 0, s, logits, bias, V, t, max_len, end_idx, seq, \
-                       seq_logp, it, unfinished, alive, table, emb_out, D, tl, g_row_limit)
-    if (reg) { if (tail) SET_PICK_LAUNCH(true, true); else SET_PICK_LAUNCH(true, false); }
-    else { if (tail) SET_PICK_LAUNCH(false, true); else SET_PICK_LAUNCH(false, false); }
+#define SET_PICK_LAUNCH(REG, TAIL) SET_PICK_ROWS((greedy_pick_k<REG, TAIL>), tl, g_row_limit)
+    SET_PICK_DISPATCH(SET_PICK_LAUNCH);
 #undef SET_PICK_LAUNCH
     SET_LAUNCH_CHECK();
     return SET_OK;
@@ -337,18 +326,11 @@ int philox_fill(uint32_t* out, int n, unsigned long long seed, unsigned long lon
 // Both thresholds are found by a bitwise descent over the order-preserving 32-bit key of the float (at most 32 block
 // reductions each: an integer count for top-k, a fixed-order mass for top-p), so the kept set {key >= thr} is exact,
 // takes every tie at its boundary and does not depend on the launch.  Words outside it are masked to -inf, after which the
-// draw below is the untruncated one.
+// draw below is the untruncated one.  (sbs.hip sbs_rows_k spells the same descent out over its own enumeration.)
 struct SampleTrunc {
     float inv_t = 1.f;
     int top_k = 0;        // 0: off (the host maps top_k >= V to 0)
     float top_p = 1.f;    // 1: off
-};
-
-struct SampleOut {
-    long long* raw_ids;   // (B) sampled word BEFORE the <end> -> 0 rewriting; -1 once the loop has been left
-    float* lse;           // (B) log-sum-exp of the row (for the backward of the gathered log-prob)
-    float* step_logp;     // (B) this step's log-prob (0 once the loop has been left)
-    uint32_t* kept_key;   // (B) or NULL: thr of the kept set {order_key(y) >= thr} the row was drawn from (0: every word)
 };
 
 template <bool REG, bool TAIL, bool TRUNC>
@@ -367,7 +349,7 @@ __global__ void __launch_bounds__(256) sample_pick_k(Slabs logits, const float* 
     __shared__ int s_pick;
     __shared__ float s_pick_x;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    f32x4 x[GP_MAXQ];
+    f32x4 x[ROW_MAXQ];
     float best = -INFINITY;
     uint32_t thr = 0;                                    // TRUNC: the kept set is {order_key(y) >= thr}
     // the generic path's logit, re-read (TRUNC: scaled, and -inf outside the kept set once thr stands)
@@ -382,24 +364,24 @@ __global__ void __launch_bounds__(256) sample_pick_k(Slabs logits, const float* 
     if (REG) {
         const float* row = logits.p + (long long)b * logits.ld;
 #pragma unroll
-        for (int q = 0; q < GP_MAXQ; ++q) {
+        for (int q = 0; q < ROW_MAXQ; ++q) {
             const int v = (tid + 256 * q) * 4;
             x[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
             if (v < V) x[q] = *reinterpret_cast<const f32x4*>(row + v);
         }
         for (int i = 1; i < logits.n; ++i) {             // K-slabs in index order, as greedy_pick_k
-            f32x4 y[GP_MAXQ];
+            f32x4 y[ROW_MAXQ];
 #pragma unroll
-            for (int q = 0; q < GP_MAXQ; ++q) {
+            for (int q = 0; q < ROW_MAXQ; ++q) {
                 const int v = (tid + 256 * q) * 4;
                 y[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
                 if (v < V) y[q] = *reinterpret_cast<const f32x4*>(row + (long long)i * logits.stride + v);
             }
 #pragma unroll
-            for (int q = 0; q < GP_MAXQ; ++q) x[q] += y[q];
+            for (int q = 0; q < ROW_MAXQ; ++q) x[q] += y[q];
         }
 #pragma unroll
-        for (int q = 0; q < GP_MAXQ; ++q) {
+        for (int q = 0; q < ROW_MAXQ; ++q) {
             const int v = (tid + 256 * q) * 4;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -420,10 +402,10 @@ __global__ void __launch_bounds__(256) sample_pick_k(Slabs logits, const float* 
     if (TRUNC && (trunc.top_k > 0 || trunc.top_p < 1.f)) {
         // Every pass is block-uniform: each wave leaves one partial in LDS, one barrier, every thread adds the four in the
         // same order.  Padding columns (-inf) never change a decision: they lie below every threshold that matters.
-        uint32_t key[GP_MAXQ][4];
+        uint32_t key[ROW_MAXQ][4];
         if (REG) {
 #pragma unroll
-            for (int q = 0; q < GP_MAXQ; ++q)
+            for (int q = 0; q < ROW_MAXQ; ++q)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) key[q][e] = order_key(x[q][e]);
         }
@@ -435,7 +417,7 @@ __global__ void __launch_bounds__(256) sample_pick_k(Slabs logits, const float* 
                 int c = 0;               // wave-uniform
                 if (REG) {
 #pragma unroll
-                    for (int q = 0; q < GP_MAXQ; ++q)
+                    for (int q = 0; q < ROW_MAXQ; ++q)
 #pragma unroll
                         for (int e = 0; e < 4; ++e) c += __popcll(__ballot(key[q][e] >= cand));
                 } else {
@@ -454,10 +436,10 @@ __global__ void __launch_bounds__(256) sample_pick_k(Slabs logits, const float* 
         if (trunc.top_p < 1.f) {
             // mass of {kept by top-k, key >= cand}: per thread in enumeration order, xor tree over the wave, waves in index
             // order — one fixed order for every cand, so the sum of these non-negative terms is monotone in cand
-            float m[GP_MAXQ][4];
+            float m[ROW_MAXQ][4];
             if (REG) {
 #pragma unroll
-                for (int q = 0; q < GP_MAXQ; ++q)
+                for (int q = 0; q < ROW_MAXQ; ++q)
 #pragma unroll
                     for (int e = 0; e < 4; ++e) m[q][e] = key[q][e] >= lo ? expf(x[q][e] - best) : 0.f;
             }
@@ -465,7 +447,7 @@ __global__ void __launch_bounds__(256) sample_pick_k(Slabs logits, const float* 
                 float sm = 0.f;
                 if (REG) {
 #pragma unroll
-                    for (int q = 0; q < GP_MAXQ; ++q)
+                    for (int q = 0; q < ROW_MAXQ; ++q)
 #pragma unroll
                         for (int e = 0; e < 4; ++e) sm += key[q][e] >= cand ? m[q][e] : 0.f;
                 } else {
@@ -494,7 +476,7 @@ __global__ void __launch_bounds__(256) sample_pick_k(Slabs logits, const float* 
         if (thr > kbest) thr = kbest;    // the arg-max is always kept
         if (REG) {
 #pragma unroll
-            for (int q = 0; q < GP_MAXQ; ++q)
+            for (int q = 0; q < ROW_MAXQ; ++q)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) if (key[q][e] < thr) x[q][e] = -INFINITY;
         }
@@ -503,7 +485,7 @@ __global__ void __launch_bounds__(256) sample_pick_k(Slabs logits, const float* 
     float mass = 0.f;
     if (REG) {
 #pragma unroll
-        for (int q = 0; q < GP_MAXQ; ++q)
+        for (int q = 0; q < ROW_MAXQ; ++q)
 #pragma unroll
             for (int e = 0; e < 4; ++e) mass += expf(x[q][e] - best);                  // exp(-inf) == 0
     } else {
@@ -534,7 +516,7 @@ __global__ void __launch_bounds__(256) sample_pick_k(Slabs logits, const float* 
         float pick_x = 0.f;
         if (REG) {
 #pragma unroll
-            for (int q = 0; q < GP_MAXQ; ++q)
+            for (int q = 0; q < ROW_MAXQ; ++q)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const float pe = expf(x[q][e] - best);
@@ -543,7 +525,7 @@ __global__ void __launch_bounds__(256) sample_pick_k(Slabs logits, const float* 
                 }
             if (pick < 0) {                      // rounding left the target at the very end of this thread's span
 #pragma unroll
-                for (int q = 0; q < GP_MAXQ; ++q)
+                for (int q = 0; q < ROW_MAXQ; ++q)
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
                         if (x[q][e] > -INFINITY && expf(x[q][e] - best) > 0.f) { pick = (tid + 256 * q) * 4 + e; pick_x = x[q][e]; }
@@ -618,8 +600,7 @@ int sample_pick(Slabs logits, const float* bias, int V, int t, int max_len, long
                 int B, unsigned long long seed, unsigned long long offset, long long* raw_ids, float* lse,
                 float* step_logp, hipStream_t s, const LstmTail* tail, const SetSampleOpts* opts, uint32_t* kept_key) {
     if (B <= 0) return SET_OK;
-    if (D & 3) return SET_ERR_UNSUPPORTED;
-    if (tail && !tail_ok(*tail)) return SET_ERR_ARG;
+    SET_TRY(pick_args_check(D, tail));
     if (sample_opts_check(opts) != SET_OK) return SET_ERR_ARG;
     const LstmTail tl = tail ? *tail : LstmTail();
     SampleTrunc tc;
@@ -632,15 +613,13 @@ int sample_pick(Slabs logits, const float* bias, int V, int t, int max_len, long
     const bool trunc = tc.inv_t != 1.f || tc.top_k > 0 || tc.top_p < 1.f;
     ProfScope ps(trunc ? "sample_pick_trunc" : "sample_pick", s, 0.0,
                  4.0 * B * (1.0 * V * logits.n + 2.0 * D + (tail ? tl.D * (4.0 * (tl.g0.n + 2) + 3.0) : 0.0)));
-    const bool reg = V <= 4 * 256 * GP_MAXQ && !(logits.ld & 3) && !(logits.stride & 3) && aligned16(logits.p);
     SampleOut so{raw_ids, lse, step_logp, kept_key};
-#define SET_PICK_LAUNCH(REG, TAIL, TRUNC)                                                                                    \
-    hipLaunchKernelGGL((sample_pick_k<REG, TAIL, TRUNC>), dim3(B), dim3(256), 0, s, logits, bias, V, t, max_len, end_idx, seq, \
-                       seq_logp, it, unfinished, alive, table, emb_out, D, seed, offset, so, tl, tc)
-#define SET_PICK_LAUNCH2(REG, TAIL) do { if (trunc) SET_PICK_LAUNCH(REG, TAIL, true); else SET_PICK_LAUNCH(REG, TAIL, false); } while (0)
-    if (reg) { if (tail) SET_PICK_LAUNCH2(true, true); else SET_PICK_LAUNCH2(true, false); }
-    else { if (tail) SET_PICK_LAUNCH2(false, true); else SET_PICK_LAUNCH2(false, false); }
-#undef SET_PICK_LAUNCH2
+#define SET_PICK_LAUNCH(REG, TAIL)                                                                         \
+    do {                                                                                                   \
+        if (trunc) SET_PICK_ROWS((sample_pick_k<REG, TAIL, true>), seed, offset, so, tl, tc);              \
+        else SET_PICK_ROWS((sample_pick_k<REG, TAIL, false>), seed, offset, so, tl, tc);                   \
+    } while (0)
+    SET_PICK_DISPATCH(SET_PICK_LAUNCH);
 #undef SET_PICK_LAUNCH
     SET_LAUNCH_CHECK();
     return SET_OK;
@@ -651,7 +630,7 @@ int sample_pick(Slabs logits, const float* bias, int V, int t, int max_len, long
 // s[v] = y[v] + g[v], y = (logits + bias) * inv_t, g = the noise of philox.h keyed by (seed, offset, b, t, v) — exactly a draw
 // from softmax(y), and an arg-max, so it does not depend on how the vocabulary is cut over threads or workgroups: the
 // persistent launch (decode_persistent_wide.hip, SAMPLE) draws the same word from the same seed.  step_logp / lse are over
-// the unperturbed y, as in the untruncated sampled pick; the bookkeeping after the draw is sample_pick_k's.
+// the unperturbed y, as in the untruncated sampled pick; the bookkeeping after the draw is row_pick.h's.
 // One workgroup per row; a thread owns whole quads of the vocabulary (one Philox call serves four words).
 // ---------------------------------------------------------------------------------------------
 template <bool REG, bool TAIL>
@@ -665,7 +644,7 @@ __global__ void __launch_bounds__(256) gumbel_pick_k(Slabs logits, const float* 
     __shared__ int s_bi[4];
     __shared__ long long s_tok;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    f32x4 x[GP_MAXQ];
+    f32x4 x[ROW_MAXQ];
     float my = -INFINITY;                    // max y
     float bs = -INFINITY, by = 0.f;          // max s, y at its first arg-max
     int bi = 0x7fffffff;
@@ -688,24 +667,24 @@ __global__ void __launch_bounds__(256) gumbel_pick_k(Slabs logits, const float* 
     if (REG) {
         const float* row = logits.p + (long long)b * logits.ld;
 #pragma unroll
-        for (int q = 0; q < GP_MAXQ; ++q) {
+        for (int q = 0; q < ROW_MAXQ; ++q) {
             const int v = (tid + 256 * q) * 4;
             x[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
             if (v < V) x[q] = *reinterpret_cast<const f32x4*>(row + v);
         }
         for (int i = 1; i < logits.n; ++i) {             // K-slabs in index order, as sample_pick_k
-            f32x4 y[GP_MAXQ];
+            f32x4 y[ROW_MAXQ];
 #pragma unroll
-            for (int q = 0; q < GP_MAXQ; ++q) {
+            for (int q = 0; q < ROW_MAXQ; ++q) {
                 const int v = (tid + 256 * q) * 4;
                 y[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
                 if (v < V) y[q] = *reinterpret_cast<const f32x4*>(row + (long long)i * logits.stride + v);
             }
 #pragma unroll
-            for (int q = 0; q < GP_MAXQ; ++q) x[q] += y[q];
+            for (int q = 0; q < ROW_MAXQ; ++q) x[q] += y[q];
         }
 #pragma unroll
-        for (int q = 0; q < GP_MAXQ; ++q) {
+        for (int q = 0; q < ROW_MAXQ; ++q) {
             const int v = (tid + 256 * q) * 4;
 #pragma unroll
             for (int e = 0; e < 4; ++e)
@@ -738,59 +717,24 @@ __global__ void __launch_bounds__(256) gumbel_pick_k(Slabs logits, const float* 
     float sum = 0.f;
     if (REG) {
 #pragma unroll
-        for (int q = 0; q < GP_MAXQ; ++q)
+        for (int q = 0; q < ROW_MAXQ; ++q)
 #pragma unroll
             for (int e = 0; e < 4; ++e) sum += expf(x[q][e] - my);                    // exp(-inf) == 0 past V
     } else {
         for (int v = tid; v < V; v += 256) sum += expf(__fmul_rn(logit_at(logits, bias, b, v), inv_t) - my);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-    if (lane == 0) s_sum[wave] = sum;
-    __syncthreads();
+    const float total = block_sum(sum, s_sum);
     if (tid == 0) {
-        const float total = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
         const float lse = my + logf(total);
         float logp = (by - my) - logf(total);
         int pick = bi;
         if (pick == 0x7fffffff) { pick = 0; logp = __builtin_nanf(""); }       // no comparison succeeded: the row is all NaN
-        long long it = pick;
-        if (it == end_idx) it = 0;
-        int unf = (t == 0) ? (it > 0) : (unfinished[b] && it > 0);
-        it = unf ? it : 0;
-        const bool broken = (t > 0) && (alive[t - 1] == 0);
-        if (t < max_len && !broken) {
-            seq[(long long)b * max_len + t] = it;
-            if (seq_logp) seq_logp[(long long)b * max_len + t] = logp;
-        }
-        if (so.raw_ids) so.raw_ids[b] = broken ? -1 : (long long)pick;
-        if (so.lse) so.lse[b] = lse;
-        if (so.step_logp) so.step_logp[b] = broken ? 0.f : logp;
-        unfinished[b] = unf;
-        if (unf) atomicAdd(&alive[t], 1);
-        it_buf[b] = it;
-        s_tok = it;
+        pick_commit(b, t, max_len, end_idx, pick, logp, lse, t > 0 ? unfinished[b] : 1, t > 0 ? alive[t - 1] : 1, seq,
+                    seq_logp, it_buf, unfinished, alive, so, &s_tok);
     }
     __syncthreads();
-    if (emb_out && table) {
-        const long long tok = s_tok;
-        for (int d = tid * 4; d < D; d += 1024) {
-            f32x4 v = *reinterpret_cast<const f32x4*>(table + tok * D + d);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
-            *reinterpret_cast<f32x4*>(emb_out + (long long)b * D + d) = v;
-        }
-    }
-    if (TAIL) {
-        const float* trow = tail_row(tail, s_tok);
-        for (int j = tid * 4; j < tail.D; j += 1024) {
-            TailRegs r2;
-            TailRow w2;
-            tail_fetch(tail, b, j, r2);
-            tail_row_fetch(tail, j, trow, w2);
-            tail_finish(tail, b, j, w2, r2);
-        }
-    }
+    if (emb_out && table) pick_embed(table, emb_out, b, s_tok, D);
+    if (TAIL) pick_tail_rows(tail, b, s_tok, tid * 4);
 }
 
 int gumbel_opts_check(const SetSampleOpts* opts, int V, int max_len) {
@@ -806,23 +750,21 @@ int gumbel_pick(Slabs logits, const float* bias, int V, int t, int max_len, long
                 float* step_logp, hipStream_t s, const LstmTail* tail, const SetSampleOpts* opts) {
     if (gumbel_opts_check(opts, V, max_len) != SET_OK || t > GUMBEL_MAX_LEN) return SET_ERR_ARG;
     if (B <= 0) return SET_OK;
-    if (D & 3) return SET_ERR_UNSUPPORTED;
-    if (tail && !tail_ok(*tail)) return SET_ERR_ARG;
+    SET_TRY(pick_args_check(D, tail));
     const LstmTail tl = tail ? *tail : LstmTail();
     const float inv_t = opts ? 1.0f / opts->temperature : 1.f;
     ProfScope ps("gumbel_pick", s, 0.0,
                  4.0 * B * (1.0 * V * logits.n + 2.0 * D + (tail ? tl.D * (4.0 * (tl.g0.n + 2) + 3.0) : 0.0)));
-    const bool reg = V <= 4 * 256 * GP_MAXQ && !(logits.ld & 3) && !(logits.stride & 3) && aligned16(logits.p);
     SampleOut so{raw_ids, lse, step_logp, nullptr};
-#define SET_PICK_LAUNCH(REG, TAIL)                                                                                    \
-    hipLaunchKernelGGL((gumbel_pick_k<REG, TAIL>), dim3(B), dim3(256), 0, s, logits, bias, V, t, max_len, end_idx, seq, \
-                       seq_logp, it, unfinished, alive, table, emb_out, D, seed, offset, so, tl, inv_t)
-    if (reg) { if (tail) SET_PICK_LAUNCH(true, true); else SET_PICK_LAUNCH(true, false); }
-    else { if (tail) SET_PICK_LAUNCH(false, true); else SET_PICK_LAUNCH(false, false); }
+#define SET_PICK_LAUNCH(REG, TAIL) SET_PICK_ROWS((gumbel_pick_k<REG, TAIL>), seed, offset, so, tl, inv_t)
+    SET_PICK_DISPATCH(SET_PICK_LAUNCH);
 #undef SET_PICK_LAUNCH
     SET_LAUNCH_CHECK();
     return SET_OK;
 }
+
+#undef SET_PICK_DISPATCH
+#undef SET_PICK_ROWS
 
 // out (rows, V) = the noise g of (seed, offset, row, t, v): the test hook of the definition in philox.h
 __global__ void __launch_bounds__(256) gumbel_fill_k(float* out, int rows, int V, int t, unsigned long long seed,

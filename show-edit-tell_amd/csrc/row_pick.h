@@ -1,0 +1,66 @@
+// The leaf pieces greedy_pick_k and gumbel_pick_k (epilogue.hip) share: the fixed-order block sum and the serial bookkeeping once
+// the word is known.  Workgroups are 256 threads = 4 waves.  Nothing here owns LDS: the kernels declare it and pass it in.
+#pragma once
+#include "set_common.h"
+
+namespace set {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// the xor tree 32 .. 1 over the wave, lane 0 of every wave leaves its value in slot[wave], ONE barrier, then (s0 + s1) + (s2 + s3)
+__device__ __forceinline__ float block_sum(float v, float* slot) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if ((threadIdx.x & 63) == 0) slot[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (slot[0] + slot[1]) + (slot[2] + slot[3]);
+}
+
+// ---- the bookkeeping once the row's word is known (editnet_rl.py:529-547)
+struct SampleOut {
+    long long* raw_ids;   // (B) sampled word BEFORE the <end> -> 0 rewriting; -1 once the loop has been left
+    float* lse;           // (B) log-sum-exp of the row (for the backward of the gathered log-prob)
+    float* step_logp;     // (B) this step's log-prob (0 once the loop has been left)
+    uint32_t* kept_key;   // (B) or NULL: thr of the kept set {order_key(y) >= thr} the row was drawn from (0: every word)
+};
+
+// <end> -> 0 and the `unfinished` latch: the next input word of a row that picked `pick`; unf = the row's latch after the step
+__device__ __forceinline__ long long pick_latch(long long pick, long long end_idx, int t, int unf_prev, int& unf) {
+    long long it = pick;
+    if (it == end_idx) it = 0;
+    unf = (t == 0) ? (it > 0) : (unf_prev && it > 0);
+    return unf ? it : 0;
+}
+
+// ONE thread of row b.  unf_prev / alive_prev = unfinished[b] / alive[t - 1] as they stood before the step (not read at t == 0).
+// Once alive[t - 1] == 0 the reference has left its loop (`break`, editnet_rl.py:546): nothing more goes to seq / seq_logp.
+__device__ __forceinline__ void pick_commit(int b, int t, int max_len, long long end_idx, int pick, float logp, float lse,
+                                            int unf_prev, int alive_prev, long long* seq, float* seq_logp,
+                                            long long* it_buf, int* unfinished, int* alive, const SampleOut& so, long long* s_tok) {
+    int unf;
+    const long long it = pick_latch(pick, end_idx, t, unf_prev, unf);
+    const bool broken = (t > 0) && (alive_prev == 0);
+    if (t < max_len && !broken) {
+        seq[(long long)b * max_len + t] = it;
+        if (seq_logp) seq_logp[(long long)b * max_len + t] = logp;
+    }
+    if (so.raw_ids) so.raw_ids[b] = broken ? -1 : (long long)pick;
+    if (so.lse) so.lse[b] = lse;
+    if (so.step_logp) so.step_logp[b] = broken ? 0.f : logp;
+    unfinished[b] = unf;
+    if (unf) atomicAdd(&alive[t], 1);
+    it_buf[b] = it;
+    *s_tok = it;
+}
+
+// the NEXT step's embedding gather emb_out[b] = relu(table[tok]) (editnet.py:300-304), by the whole workgroup
+__device__ __forceinline__ void pick_embed(const float* table, float* emb_out, int b, long long tok, int D) {
+    for (int d = threadIdx.x * 4; d < D; d += 1024) {
+        f32x4 v = *reinterpret_cast<const f32x4*>(table + tok * D + d);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
+        *reinterpret_cast<f32x4*>(emb_out + (long long)b * D + d) = v;
+    }
+}
+
+}  // namespace set

@@ -30,7 +30,6 @@ namespace set {
 
 typedef float sbs_f32x4 __attribute__((ext_vector_type(4)));
 constexpr int SBS_KMAX = 8;
-constexpr int SBS_MAXQ = 12;                 // register path: rows of up to 4 * 256 * 12 = 12288 words
 constexpr int SBS_NONE = 0x7fffffff;
 
 struct SbsRowArgs {
@@ -75,11 +74,11 @@ __global__ void __launch_bounds__(256) sbs_rows_k(const SbsRowArgs a, const SbsT
     if (Gj == -INFINITY || a.fin[r] != 0 || a.n_open[r / a.k] == 0) return;
     const float* row = a.logits + (long long)r * a.ld;
     const float* row2 = NM == 2 ? a.logits2 + (long long)r * a.ld : row;
-    sbs_f32x4 x[SBS_MAXQ], x2[NM == 2 ? SBS_MAXQ : 1];
+    sbs_f32x4 x[ROW_MAXQ], x2[NM == 2 ? ROW_MAXQ : 1];
     uint32_t thr = 0;                                    // TRUNC: S = {order_key(z) >= thr}; 0 until the descent has run
     if (REG) {
 #pragma unroll
-        for (int q = 0; q < SBS_MAXQ; ++q) {
+        for (int q = 0; q < ROW_MAXQ; ++q) {
             const int v = (tid + 256 * q) * 4;
             x[q] = (sbs_f32x4){-INFINITY, -INFINITY, -INFINITY, -INFINITY};
             if (NM == 2) x2[NM == 2 ? q : 0] = x[q];
@@ -103,7 +102,7 @@ __global__ void __launch_bounds__(256) sbs_rows_k(const SbsRowArgs a, const SbsT
     auto sweep = [&](auto&& f) {
         if (REG) {
 #pragma unroll
-            for (int q = 0; q < SBS_MAXQ; ++q)
+            for (int q = 0; q < ROW_MAXQ; ++q)
                 if ((tid + 256 * q) * 4 < V) f(tid + 256 * q, x[q], NM == 2 ? x2[NM == 2 ? q : 0] : x[q]);
         } else {
             for (int j = tid; 4 * j < V; j += 256) {
@@ -156,10 +155,10 @@ __global__ void __launch_bounds__(256) sbs_rows_k(const SbsRowArgs a, const SbsT
     // each wave leaves one partial in LDS, one barrier, every thread adds the four in the same order.  Padding (-inf) never
     // changes a decision: it lies below every threshold that matters.  The registers are cut to S on the way out.
     auto kept_threshold = [&](float best) -> uint32_t {
-        uint32_t key[SBS_MAXQ][4];
+        uint32_t key[ROW_MAXQ][4];
         if (REG) {
 #pragma unroll
-            for (int q = 0; q < SBS_MAXQ; ++q)
+            for (int q = 0; q < ROW_MAXQ; ++q)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) key[q][e] = order_key(x[q][e]);
         }
@@ -171,7 +170,7 @@ __global__ void __launch_bounds__(256) sbs_rows_k(const SbsRowArgs a, const SbsT
                 int c = 0;               // wave-uniform
                 if (REG) {
 #pragma unroll
-                    for (int q = 0; q < SBS_MAXQ; ++q)
+                    for (int q = 0; q < ROW_MAXQ; ++q)
 #pragma unroll
                         for (int e = 0; e < 4; ++e) c += __popcll(__ballot(key[q][e] >= cand));
                 } else {
@@ -191,10 +190,10 @@ __global__ void __launch_bounds__(256) sbs_rows_k(const SbsRowArgs a, const SbsT
         if (tr.top_p < 1.f) {
             // mass of {kept by top-k, key >= cand}: per thread in enumeration order, xor tree over the wave, waves in index
             // order — one fixed order for every cand, so the sum of these non-negative terms is monotone in cand
-            float m[SBS_MAXQ][4];
+            float m[ROW_MAXQ][4];
             if (REG) {
 #pragma unroll
-                for (int q = 0; q < SBS_MAXQ; ++q)
+                for (int q = 0; q < ROW_MAXQ; ++q)
 #pragma unroll
                     for (int e = 0; e < 4; ++e) m[q][e] = key[q][e] >= lo ? expf(x[q][e] - best) : 0.f;
             }
@@ -202,7 +201,7 @@ __global__ void __launch_bounds__(256) sbs_rows_k(const SbsRowArgs a, const SbsT
                 float sm = 0.f;
                 if (REG) {
 #pragma unroll
-                    for (int q = 0; q < SBS_MAXQ; ++q)
+                    for (int q = 0; q < ROW_MAXQ; ++q)
 #pragma unroll
                         for (int e = 0; e < 4; ++e) sm += key[q][e] >= cand ? m[q][e] : 0.f;
                 } else {
@@ -235,7 +234,7 @@ __global__ void __launch_bounds__(256) sbs_rows_k(const SbsRowArgs a, const SbsT
         if (t > kbest) t = kbest;        // the arg-max is always kept
         if (REG) {
 #pragma unroll
-            for (int q = 0; q < SBS_MAXQ; ++q)
+            for (int q = 0; q < ROW_MAXQ; ++q)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) if (key[q][e] < t) x[q][e] = -INFINITY;
         }
@@ -263,7 +262,7 @@ __global__ void __launch_bounds__(256) sbs_rows_k(const SbsRowArgs a, const SbsT
     // distributions here, so that the sweep below is the one-model sweep (and unrolls as it does)
     if (REG && NM == 2) {
 #pragma unroll
-        for (int q = 0; q < SBS_MAXQ; ++q)
+        for (int q = 0; q < ROW_MAXQ; ++q)
             if ((tid + 256 * q) * 4 < V) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) x[q][e] = sbs_mean_logp(x[q][e] - lse[0], x2[NM == 2 ? q : 0][e] - lse[NM - 1]);
@@ -275,7 +274,7 @@ __global__ void __launch_bounds__(256) sbs_rows_k(const SbsRowArgs a, const SbsT
         auto zsweep = [&](auto&& f) {                    // the quads of l in the sweeps' order: the registers, or recomputed
             if (REG) {
 #pragma unroll
-                for (int q = 0; q < SBS_MAXQ; ++q)
+                for (int q = 0; q < ROW_MAXQ; ++q)
                     if ((tid + 256 * q) * 4 < V) f(x[q]);
             } else {
                 for (int j = tid; 4 * j < V; j += 256) f(zquad(j));
@@ -512,24 +511,23 @@ static int sbs_pick(const SetSbsArgs* a, const float* logits2, const SetSampleOp
     ma.seqs_in = (const long long*)a->seqs_in; ma.seqs_out = (long long*)a->seqs_out;
     ma.words = (long long*)a->words; ma.rows = a->rows; ma.n_open = a->n_open;
     ma.cand_g = ra.cand_g; ma.cand_phi = ra.cand_phi; ma.cand_v = ra.cand_v;
-    const bool reg = a->V <= 4 * 256 * SBS_MAXQ && !(a->ld & 3) && aligned16(a->logits) && aligned16(logits2);
+    const bool reg = pick_reg_ok(Slabs{a->logits, 0, a->ld, 1}, a->V) && aligned16(logits2);
     // the scalar path re-reads the row in every sweep: three of them, and under truncation one per descent pass (32 for top-k,
     // 33 for top-p) and, for two models, two more for the maximum and the sum over the kept set
     const double sweeps = reg ? 1.0 : 3.0 + (trunc ? (tc.top_k > 0 ? 32.0 : 0.0) + (tc.top_p < 1.f ? 33.0 : 0.0) + (logits2 ? 2.0 : 0.0) : 0.0);
+    static const char* const scope[2][2][2] = {          // [two models][truncated][scalar]
+        {{"sbs_rows", "sbs_rows_scalar"}, {"sbs_rows_trunc", "sbs_rows_trunc_scalar"}},
+        {{"sbs_rows_ens", "sbs_rows_ens_scalar"}, {"sbs_rows_ens_trunc", "sbs_rows_ens_trunc_scalar"}}};
 #define SET_SBS_ROWS(REG, NM, TRUNC) hipLaunchKernelGGL((sbs_rows_k<REG, NM, TRUNC>), dim3(B), dim3(256), 0, st, ra, tc)
-    if (!logits2) {
-        ProfScope ps(trunc ? (reg ? "sbs_rows_trunc" : "sbs_rows_trunc_scalar") : (reg ? "sbs_rows" : "sbs_rows_scalar"), st, 0.0,
-                     4.0 * sweeps * B * a->V);
-        if (trunc) { if (reg) SET_SBS_ROWS(true, 1, true); else SET_SBS_ROWS(false, 1, true); }
-        else { if (reg) SET_SBS_ROWS(true, 1, false); else SET_SBS_ROWS(false, 1, false); }
-        SET_LAUNCH_CHECK();
-    } else {
-        ProfScope ps(trunc ? (reg ? "sbs_rows_ens_trunc" : "sbs_rows_ens_trunc_scalar") : (reg ? "sbs_rows_ens" : "sbs_rows_ens_scalar"),
-                     st, 0.0, 8.0 * sweeps * B * a->V);
-        if (trunc) { if (reg) SET_SBS_ROWS(true, 2, true); else SET_SBS_ROWS(false, 2, true); }
-        else { if (reg) SET_SBS_ROWS(true, 2, false); else SET_SBS_ROWS(false, 2, false); }
+#define SET_SBS_ROWS_NM(REG, TRUNC) do { if (logits2) SET_SBS_ROWS(REG, 2, TRUNC); else SET_SBS_ROWS(REG, 1, TRUNC); } while (0)
+#define SET_SBS_ROWS_REG(TRUNC) do { if (reg) SET_SBS_ROWS_NM(true, TRUNC); else SET_SBS_ROWS_NM(false, TRUNC); } while (0)
+    {
+        ProfScope ps(scope[logits2 != nullptr][trunc][!reg], st, 0.0, (logits2 ? 8.0 : 4.0) * sweeps * B * a->V);
+        if (trunc) SET_SBS_ROWS_REG(true); else SET_SBS_ROWS_REG(false);
         SET_LAUNCH_CHECK();
     }
+#undef SET_SBS_ROWS_REG
+#undef SET_SBS_ROWS_NM
 #undef SET_SBS_ROWS
     {
         ProfScope ps("sbs_merge", st, 0.0, 16.0 * B * (a->t + 1));

@@ -220,6 +220,9 @@ struct Slabs {
     int n;
 };
 inline Slabs slabs_of(const GemmProb& g) { return Slabs{g.C, g.slab_stride, g.ldc, g.ksplit}; }
+// the row picks' register path (row_pick.h): rows of up to 4 * 256 * ROW_MAXQ = 12288 words, read once as float4
+constexpr int ROW_MAXQ = 12;
+inline bool pick_reg_ok(const Slabs& l, int V) { return V <= 4 * 256 * ROW_MAXQ && !(l.ld & 3) && !(l.stride & 3) && aligned16(l.p); }
 // sum over the slabs of the float4 at element offset `off` of every slab, added in slab order (the deterministic order every
 // consumer uses).  Up to four slabs are REQUESTED together whatever the count: a `for (i < n) acc += load` loop with a run-time
 // trip count is n dependent round trips (the add of iteration i waits for its load before iteration i + 1 issues), which put

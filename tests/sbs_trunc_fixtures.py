@@ -35,6 +35,10 @@ DIRECT = {
     "v255_k1_ni1_p":       (255, 256, 1, 1, 0.5, 1, 0, 0.9),
     "v255_k3_ni3_kp":      (255, 256, 3, 3, 1.0, 3, 5, 0.9),
     "v255_k8_ni1_k2":      (255, 256, 8, 1, 1.0, 1, 2, 1.0),
+    "v1023_k3_ni1_kp":     (1023, 1024, 3, 1, 1.0, 2, 5, 0.9),       # either side of 256 threads x one quad, on both paths
+    "v1023_k3_ni1_sc_kp":  (1023, 1025, 3, 1, 1.0, 3, 5, 0.9),
+    "v1025_k3_ni1_kp":     (1025, 1028, 3, 1, 1.0, 3, 5, 0.9),
+    "v1025_k3_ni1_sc_kp":  (1025, 1026, 3, 1, 1.0, 1, 5, 0.9),
     "v1027_k8_ni1_p":      (1027, 1028, 8, 1, 0.5, 1, 0, 0.9),
     "v1027_k3_ni3_sc_kp":  (1027, 1027, 3, 3, 1.0, 2, 5, 0.9),
     "v4099_k3_ni1_k5":     (4099, 4100, 3, 1, 1.0, 2, 5, 1.0),
