@@ -1,18 +1,20 @@
 """The DCNet decode loops (reference `dcnet.py:333-348` teacher-forced, `dcnet_rl.py:305-344` sampled) as ONE autograd
-node — the text-only twin of `xe_sequence.py` (see there for the design: per-sequence logs, Philox dropout kernels,
+node: the text-only counterpart of `xe_sequence.py` (see there for the design: per-sequence logs, Philox dropout kernels,
 every "+=" of back-propagation through time as the accumulate flag of a GEMM problem or of the attention backward,
-one contraction per parameter gradient over all T x B rows)."""
+one contraction per parameter gradient over all T x B rows).  This file holds DCNet's own logs, step, BPTT step and list of
+parameter contractions; what surrounds them is shared with EditNet's node (`sequence_common.py`)."""
 from __future__ import annotations
 
 import ctypes as C
 
 import torch
 
-from . import _lib
 from . import autograd_ops as A
 from . import rng
+from . import sequence_common as S
 from ._lib import EditNetWeights, check
-from .xe_sequence import SeqConfig, _Ops, _dvalues, _e, _rows, _z  # noqa: F401
+from .sequence_common import _Ops, _dvalues, _e, _rows, _z, gg
+from .xe_sequence import SeqConfig  # noqa: F401  (re-exported: dcnet.py and dcnet_rl.py build the node's cfg from it)
 
 PARAM_NAMES = ("E", "al_wih", "al_whh", "al_bih", "al_bhh", "ca_dec_w", "ca_dec_b", "ca_full_w", "ca_full_b",
                "ll_wih", "ll_whh", "ll_bih", "ll_bhh", "fc_w", "fc_b")
@@ -48,12 +50,10 @@ class _DcnetSequence(torch.autograd.Function):
         L = {"FH": final_hidden, "EMB": _zl(T, B, E, dev=dev), "X2": _zl(T, B, K2, dev=dev),
              "G1": _zl(T, B, 4 * D, dev=dev), "G2": _zl(T, B, 4 * D, dev=dev), "ALPHAC": _zl(T, B, Tc, dev=dev),
              "ATT2": _e(T, B, Adim, dev=dev)}
-        for k in ("H1", "C1", "H2", "C2"):
-            L[k] = _zl(T + 1, B, D, dev=dev)
-            if uniform:
-                L[k][0].zero_()
+        L.update(S.state_logs(T, B, D, uniform, dev))
         if train and cfg.p_out > 0:
             L["H2D"] = _zl(T, B, D, dev=dev)
+        hout = S.fc_inputs(L, cfg)
         cx = _e(B, Dh, dev=dev)
         # dcnet.py:336 feeds [emb | final_hidden | h2] to the attention LSTM: the final_hidden columns (+ both biases) are
         # contracted once per sequence, every step contracts only the emb / h2 column blocks of weight_ih
@@ -69,23 +69,11 @@ class _DcnetSequence(torch.autograd.Function):
         Etab = P["E"]
         cap_stride = caps.stride(0) if ro is None else 1
         off = rng.offset
-        state = None
-        if ro is not None:
-            state = A.SampleState(B, T, ro["start_idx"], ro["end_idx"], dev, seed=ro.get("seed"), offset=ro.get("offset", 0))
-            L["LOGITS"] = _e(T, B, V, dev=dev)
-            L["RAW"] = torch.empty(T, B, dtype=torch.long, device=dev)
-            L["LSE"], L["LOGP"] = _e(T, B, dev=dev), _e(T, B, dev=dev)
-            ro_opts = ro.get("opts")       # _lib.SampleOpts or None: with options every step also logs its kept set's threshold
-            if ro_opts is not None:
-                L["KEY"] = torch.empty(T, B, dtype=torch.int32, device=dev)
-                # rows padded to 16 bytes: the pick reads them into registers (the word enumeration of the fused no-grad rollout:
-                # the same seed draws the same words) and the backward reads them as float4
-                L["LOGITS"] = _e(T, B, (V + 3) & ~3, dev=dev)[:, :, :V]
-                ld_lg = L["LOGITS"].stride(1)
+        rl = ctx.rl = S.RolloutLog(L, ro, B, T, V, dev) if ro is not None else None
         for t in range(T):
             bt = bts[t]
             emb = L["EMB"][t]
-            tok = caps[:, t] if ro is None else state.tokens[t]
+            tok = caps[:, t] if ro is None else rl.tokens[t]
             if train and cfg.p_embed > 0:
                 check(lib.set_embed_relu_dropout_f32(Etab.data_ptr(), tok.data_ptr(), cap_stride, emb.data_ptr(), E, bt, E,
                                                      Etab.shape[0], cfg.p_embed, cfg.seed, off(1, t), st),
@@ -113,41 +101,16 @@ class _DcnetSequence(torch.autograd.Function):
             if train and cfg.p_out > 0:
                 ops.dropout(L["H2"][t + 1], L["H2D"][t], bt, D, cfg.p_out, cfg.seed, off(3, t))
             if ro is not None:
-                hz = L["H2D"][t] if (train and cfg.p_out > 0) else L["H2"][t + 1]
-                ops.linear(hz, P["fc_w"], P["fc_b"], L["LOGITS"][t], B)
-                if ro_opts is not None:
-                    check(lib.set_sample_pick_opts_key_f32(L["LOGITS"][t].data_ptr(), ld_lg, B, V, t, T, state.end_idx, state.seed,
-                                                           state.offset, state.seq.data_ptr(), state.tokens[t + 1].data_ptr(),
-                                                           state.unfinished.data_ptr(), state.alive.data_ptr(),
-                                                           L["RAW"][t].data_ptr(), L["LSE"][t].data_ptr(), L["LOGP"][t].data_ptr(),
-                                                           st, C.byref(ro_opts), L["KEY"][t].data_ptr()),
-                          "set_sample_pick_opts_key_f32")
-                else:
-                    check(lib.set_sample_pick_f32(L["LOGITS"][t].data_ptr(), V, B, V, t, T, state.end_idx, state.seed, state.offset,
-                                                  state.seq.data_ptr(), state.tokens[t + 1].data_ptr(),
-                                                  state.unfinished.data_ptr(), state.alive.data_ptr(), L["RAW"][t].data_ptr(),
-                                                  L["LSE"][t].data_ptr(), L["LOGP"][t].data_ptr(), st), "set_sample_pick_f32")
-        hout = L["H2D"] if (train and cfg.p_out > 0) else L["H2"][1:]
+                rl.step(ops, hout[t], P["fc_w"], P["fc_b"], t)
         ctx.cfg, ctx.L, ctx.bts, ctx.uniform, ctx.hout = cfg, L, bts, uniform, hout
         ctx.dims = (T, B, Tc, Dh, E, D, Adim, V)
         ctx.save_for_backward(enc, mask, att1_c, caps, *params)
         if ro is not None:
-            ctx.tokens = state.tokens
-            ctx.mark_non_differentiable(state.seq)
-            return state.seq, L["LOGP"].t()
-        if uniform:
-            pred_tb = _e(T, B, V, dev=dev)
-            ops.linear(hout.reshape(T * B, D), P["fc_w"], P["fc_b"], pred_tb.view(T * B, V), T * B)
-            out = pred_tb.transpose(0, 1)
-        else:
-            out = _z(B, T, V, dev=dev)
-            for t in range(T):
-                ops.linear(hout[t], P["fc_w"], P["fc_b"], out[:, t], bts[t])
-        if getattr(cfg, "last_hidden", False):
-            # dcnet_with_mse.py:321,341: h2 of every row at its last step = slot len_b of the state log (slot 0 holds the zero
-            # initial state: a row of decode length 0), before the output dropout
-            idx = torch.tensor(lens, dtype=torch.long, device=dev)
-            return out, L["H2"][idx, torch.arange(B, device=dev)]
+            ctx.mark_non_differentiable(rl.seq)
+            return rl.seq, L["LOGP"].t()
+        out = S.score_head(ops, hout, P["fc_w"], P["fc_b"], bts, uniform)
+        if getattr(cfg, "last_hidden", False):     # dcnet_with_mse.py:321,341
+            return out, S.last_hidden(L["H2"], lens)
         return out
 
     @staticmethod
@@ -161,33 +124,12 @@ class _DcnetSequence(torch.autograd.Function):
         ops = _Ops(dev)
         lib, st = ops.lib, ops.st
         train = cfg.train
-        pidx = {n: i for i, n in enumerate(PARAM_NAMES)}
-        g = [None] * len(PARAM_NAMES)
-        dlast = None                       # d(decoder_last_hidden) (the second output in teacher-forced mode with cfg.last_hidden)
-        if cfg.rollout is None and getattr(cfg, "last_hidden", False) and dlogp is not None:
-            dlast = dlogp.contiguous()
-        if cfg.rollout is not None:
-            dl = dlogp.t().contiguous()
-            dp = A.zero_padded_rows(T, B, V, dev)          # rows padded to 16 bytes: the fc contractions read them in place
-            ro_opts = cfg.rollout.get("opts")
-            if ro_opts is not None:        # the truncated log-prob: all T * B rows of the (contiguous) logs in ONE launch
-                check(lib.set_sample_logp_bwd_opts_f32(L["LOGITS"].data_ptr(), L["LOGITS"].stride(1), L["LSE"].data_ptr(), L["RAW"].data_ptr(),
-                                                       L["KEY"].data_ptr(), dl.data_ptr(), dp.data_ptr(), dp.stride(1), T * B, V,
-                                                       C.byref(ro_opts), st), "set_sample_logp_bwd_opts_f32")
-            for t in (range(T) if ro_opts is None else ()):
-                check(lib.set_sample_logp_bwd_f32(L["LOGITS"][t].data_ptr(), V, L["LSE"][t].data_ptr(), L["RAW"][t].data_ptr(),
-                                                  dl[t].data_ptr(), dp[t].data_ptr(), dp.stride(1), B, V, st),
-                      "set_sample_logp_bwd_f32")
-            L["LOGITS"] = None
-            dp2 = dp.as_strided((T * B, V), (dp.stride(1), 1), dp.storage_offset())
-        else:
-            dp2 = A.score_grad_rows(dpred, bts, ctx.uniform)
-        dH2D = A._dgrad(dp2, P["fc_w"]).view(T, B, D)
-        need_p = ctx.needs_input_grad[6:]
-        if need_p[pidx["fc_b"]]:
-            g[pidx["fc_b"]] = A._bgrad(params[pidx["fc_b"]], dp2)
-        if need_p[pidx["fc_w"]]:          # final now: contracted eagerly so that its all-reduce runs underneath the BPTT loop
-            g[pidx["fc_w"]] = A._wgrad(params[pidx["fc_w"]], dp2, ctx.hout.reshape(T * B, D), eager=True)
+        pg = S.ParamGrads(PARAM_NAMES, params, ctx.needs_input_grad[6:])
+        # d(decoder_last_hidden): the second output in teacher-forced mode with cfg.last_hidden
+        dlast = dlogp.contiguous() if (cfg.rollout is None and getattr(cfg, "last_hidden", False) and dlogp is not None) else None
+        dp2 = ctx.rl.backward(ops, dlogp) if cfg.rollout is not None else A.score_grad_rows(dpred, bts, ctx.uniform)
+        dH2D, g_fc_w, g_fc_b = S.score_head_bwd(dp2, ctx.hout, P["fc_w"], P["fc_b"], pg.wants("fc_w"), pg.wants("fc_b"))
+        pg.put("fc_w", g_fc_w); pg.put("fc_b", g_fc_b)
 
         _zl = _e if ctx.uniform else _z
         DG1, DG2 = _zl(T, B, 4 * D, dev=dev), _zl(T, B, 4 * D, dev=dev)
@@ -199,21 +141,14 @@ class _DcnetSequence(torch.autograd.Function):
         DC2 = [_z(B, D, dev=dev), _z(B, D, dev=dev)]
         demb = _e(B, E, dev=dev)
         al_wih, ll_wih = P["al_wih"], P["ll_wih"]
-        sc_out = 1.0 / (1.0 - cfg.p_out) if (train and cfg.p_out > 0) else 1.0
-        sc_emb = 1.0 / (1.0 - cfg.p_embed) if (train and cfg.p_embed > 0) else 1.0
+        sc_emb = S.dropout_scale(cfg, cfg.p_embed)
         ca_full = P["ca_full_w"].reshape(-1)
-
-        def gg(items):
-            A.gemm_group([(dy, wv, dy.shape[0], wv.shape[1], dy.shape[1], out, acc) for dy, wv, out, acc in items], False, True)
 
         for t in range(T - 1, -1, -1):
             bt = bts[t]
             r = lambda x: _rows(x, bt)
             h1 = L["H1"][t + 1]
-            if dlast is not None:          # rows whose last step this is, [bts[t + 1], bts[t]): d(decoder_last_hidden) joins dh2
-                b0 = bts[t + 1] if t + 1 < T else 0
-                if bt > b0:
-                    ops.pack(DH2[b0:], bt - b0, [dlast[b0:bt]], accumulate=True)
+            S.last_hidden_bwd_step(ops, DH2, dlast, bts, t)
             if train and cfg.p_out > 0:    # h2 does not follow a ReLU: the mask is regenerated, not read off the zero pattern
                 check(lib.set_dropout_bwd_philox_f32(dH2D[t].data_ptr(), D, DH2.data_ptr(), D, bt, D, cfg.p_out, cfg.seed,
                                                      rng.offset(rng.SITE_OUT, t), 1, st), "set_dropout_bwd_philox_f32")
@@ -244,38 +179,24 @@ class _DcnetSequence(torch.autograd.Function):
         sdg1 = DG1.sum(0)                  # loop-invariant input: d final_hidden = (sum_t dgates) . W_ih[:, E:E+Dh]
         dFH = A.gemm(sdg1, False, al_wih[:, E:E + Dh], True, B, Dh, 4 * D)
 
-        need = ctx.needs_input_grad[6:]                       # frozen parameters (requires_grad False) get no gradient
-
-        def W(name, dy, x):
-            if need[pidx[name]]:
-                g[pidx[name]] = A._wgrad(params[pidx[name]], dy, x)
-
-        def Bg(name, dy):
-            if need[pidx[name]]:
-                g[pidx[name]] = A._bgrad(params[pidx[name]], dy)
-
-        ids = caps[:, :T].t().reshape(-1) if cfg.rollout is None else ctx.tokens[:T].reshape(-1)
-        if need[pidx["E"]]:
-            dE = torch.zeros_like(P["E"])
-            dE.index_add_(0, ids, DEMBRAW.view(TB, E))
-            g[pidx["E"]] = dE
+        W, Bg = pg.W, pg.Bg
+        pg.embedding("E", caps[:, :T].t().reshape(-1) if cfg.rollout is None else ctx.rl.tokens[:T].reshape(-1), DEMBRAW.view(TB, E))
         dg1 = DG1.view(TB, 4 * D)
-        if need[pidx["al_wih"]]:           # column blocks [emb | final_hidden | h2]; the invariant one from sum_t dgates
-            g[pidx["al_wih"]] = A._wgrad_blocks(params[pidx["al_wih"]], [
-                (dg1, L["EMB"].view(TB, E), 0), (sdg1, L["FH"], E), (dg1, L["H2"][:T].reshape(TB, D), E + Dh)])
+        # column blocks [emb | final_hidden | h2]; the invariant one from sum_t dgates
+        pg.blocks("al_wih", [(dg1, L["EMB"].view(TB, E), 0), (sdg1, L["FH"], E), (dg1, L["H2"][:T].reshape(TB, D), E + Dh)])
         W("al_whh", dg1, L["H1"][:T].reshape(TB, D))
         Bg("al_bih", dg1); Bg("al_bhh", dg1)
         dg2 = DG2.view(TB, 4 * D)
         W("ll_wih", dg2, L["X2"].view(TB, -1)); W("ll_whh", dg2, L["H2"][:T].reshape(TB, D))
         Bg("ll_bih", dg2); Bg("ll_bhh", dg2)
         W("ca_dec_w", DATT2.view(TB, Adim), L["H1"][1:].reshape(TB, D)); Bg("ca_dec_b", DATT2.view(TB, Adim))
-        if need[pidx["ca_full_w"]]:
-            g[pidx["ca_full_w"]] = A._colsum(DWF.view(TB, Adim)).view(1, Adim)
-        if need[pidx["ca_full_b"]]:
-            g[pidx["ca_full_b"]] = DE.sum().reshape(1)
-        ctx.L = None
+        if pg.wants("ca_full_w"):
+            pg.put("ca_full_w", A._colsum(DWF.view(TB, Adim)).view(1, Adim))
+        if pg.wants("ca_full_b"):
+            pg.put("ca_full_b", DE.sum().reshape(1))
+        ctx.L = ctx.rl = None
         # inputs: cfg, enc, final_hidden, mask, att1_c, caps
-        return (None, denc, dFH, None, datt1c, None) + tuple(g)
+        return (None, denc, dFH, None, datt1c, None) + pg.tuple()
 
 
 def dcnet_sequence(cfg, enc, final_hidden, mask, att1_c, caps, params):

@@ -31,7 +31,9 @@ import torch
 from . import _lib
 from . import autograd_ops as A
 from . import rng
-from ._lib import EditNetWeights, check, ptr, stream_of
+from . import sequence_common as S
+from ._lib import EditNetWeights, check
+from .sequence_common import _Ops, _dvalues, _e, _rows, _z, gg
 
 PARAM_NAMES = (
     "E", "al_wih", "al_whh", "al_bih", "al_bhh",
@@ -99,53 +101,6 @@ def count_truncation_bites(rmask, bts):
     return bool((last > n[:, None]).any().item())
 
 
-def _z(*shape, dev):
-    return torch.zeros(*shape, dtype=torch.float32, device=dev)
-
-
-def _e(*shape, dev):
-    return torch.empty(*shape, dtype=torch.float32, device=dev)
-
-
-class _Ops:
-    """thin, allocation-free callers of the C ABI for one (device, stream)"""
-
-    def __init__(self, dev):
-        self.lib = _lib.load()
-        self.dev = dev
-        self.st = stream_of(dev)
-        self._ws = {}
-
-    def ws(self, key, nbytes):
-        w = self._ws.get(key)
-        if w is None or w.numel() < nbytes:
-            w = self._ws[key] = torch.empty(max(16, nbytes), dtype=torch.uint8, device=self.dev)
-        return w
-
-    def pack(self, dst, rows, srcs, accumulate=False):
-        """dst[:rows, :sum(cols)] (+)= [src0 | src1 | ...]; srcs: 2-D views with unit inner stride"""
-        n = len(srcs)
-        ps = (C.c_void_p * n)(*[s.data_ptr() for s in srcs])
-        ls = (C.c_int64 * n)(*[s.stride(0) for s in srcs])
-        cs = (C.c_int * n)(*[s.shape[1] for s in srcs])
-        check(self.lib.set_pack_f32(dst.data_ptr(), dst.stride(0), rows, n, ps, ls, cs, int(accumulate), self.st), "set_pack_f32")
-
-    def dropout(self, x, y, rows, cols, p, seed, offset):
-        check(self.lib.set_dropout_f32(x.data_ptr(), x.stride(-2), y.data_ptr(), y.stride(-2), rows, cols, p, seed, offset,
-                                       self.st), "set_dropout_f32")
-
-    def dropout_bwd(self, dy, y, dx, rows, cols, scale, accumulate):
-        check(self.lib.set_dropout_bwd_f32(dy.data_ptr(), dy.stride(-2), y.data_ptr(), y.stride(-2), dx.data_ptr(),
-                                           dx.stride(-2), rows, cols, scale, int(accumulate), self.st), "set_dropout_bwd_f32")
-
-    def linear(self, x, w, b, y, M):
-        """y[:M] = x[:M] w^T + b   (x, y: 2-D views, unit inner stride)"""
-        K, N = w.shape[1], w.shape[0]
-        ws = self.ws("lin", self.lib.set_linear_workspace_bytes(M, N, K))
-        check(self.lib.set_linear_f32(x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), ptr(b), y.data_ptr(), y.stride(0),
-                                      M, N, K, _lib.ACT_NONE, ws.data_ptr(), ws.numel(), self.st), "set_linear_f32")
-
-
 _DEMB_HOIST = os.environ.get("SET_DEMB_HOIST", "1") != "0"     # time-batched d emb products of the backward (round 4)
 # round 5: the per-timestep dX products of the backward hand their split-K partials to the kernels that consume them
 # (include/set_hip.h SetSlabSrc / *_src entry points) instead of reducing them with a launch each: 6 launches less per
@@ -192,21 +147,6 @@ def _side_stream(dev):
     return st
 
 
-def _dvalues(alpha, dctx, ops):
-    """dH (B, Tc, D) = sum_t alpha[t, b, :] (outer) dctx[t, b, :] over the per-sequence logs (rows of finished sequences are
-    zero in both), one launch"""
-    T, B, Tc = alpha.shape
-    D = dctx.shape[2]
-    dH = torch.empty(B, Tc, D, dtype=torch.float32, device=alpha.device)
-    check(ops.lib.set_attention_dvalues_f32(alpha.data_ptr(), dctx.data_ptr(), dH.data_ptr(), T, B, Tc, D, 0, ops.st),
-          "set_attention_dvalues_f32")
-    return dH
-
-
-def _rows(t2d, n):
-    return t2d if t2d.shape[0] == n else t2d[:n]
-
-
 class _XESequence(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cfg, X, mean, H, Mem, final_hidden, mask, att1_c, Yin, caps, *params):
@@ -241,10 +181,7 @@ class _XESequence(torch.autograd.Function):
         A.gemm(mean, False, wih[:, 3 * D:], False, B, 4 * D, F, out=pre1, accumulate=True)
         L["FH"], L["MEAN"] = final_hidden, mean
         L["EMB"] = _zl(T, B, D, dev=dev)
-        for k in ("H1", "C1", "H2", "C2"):                    # slot t = state BEFORE step t; slot 0 = the zero initial state
-            L[k] = _zl(T + 1, B, D, dev=dev)
-            if uniform:
-                L[k][0].zero_()
+        L.update(S.state_logs(T, B, D, uniform, dev))
         L["G1"], L["G2"] = _zl(T, B, 4 * D, dev=dev), _zl(T, B, 4 * D, dev=dev)
         L["WHC"] = _zl(T, B, 3 * D, dev=dev)                  # [word | h1 | caption context]
         L["ZT"], L["S"], L["TT"] = (_zl(T, B, D, dev=dev) for _ in range(3))
@@ -285,19 +222,8 @@ class _XESequence(torch.autograd.Function):
             ss_i32 = torch.zeros(B + T + 4, dtype=torch.int32, device=dev)
             ss_f32 = _e(2, B, dev=dev)
             pred_tb = _z(T, B, V, dev=dev)
-        state = None
-        if ro is not None:
-            state = A.SampleState(B, T, ro["start_idx"], ro["end_idx"], dev, seed=ro.get("seed"), offset=ro.get("offset", 0))
-            L["LOGITS"] = _e(T, B, V, dev=dev)
-            L["RAW"] = torch.empty(T, B, dtype=torch.long, device=dev)
-            L["LSE"], L["LOGP"] = _e(T, B, dev=dev), _e(T, B, dev=dev)
-            ro_opts = ro.get("opts")       # _lib.SampleOpts or None: with options every step also logs its kept set's threshold
-            if ro_opts is not None:
-                L["KEY"] = torch.empty(T, B, dtype=torch.int32, device=dev)
-                # rows padded to 16 bytes: the pick reads them into registers (the word enumeration of the fused no-grad rollout:
-                # the same seed draws the same words) and the backward reads them as float4
-                L["LOGITS"] = _e(T, B, (V + 3) & ~3, dev=dev)[:, :, :V]
-                ld_lg = L["LOGITS"].stride(1)
+        rl = ctx.rl = S.RolloutLog(L, ro, B, T, V, dev) if ro is not None else None
+        hout = S.fc_inputs(L, cfg)
         scale_off = rng.offset              # (site, t) -> Philox offset; sites 1 = embedding, 2 = regions, 3 = h2 before fc, 4 = SS draw
 
         # editnet.py:441-443 in train mode: att1(t) = features_att(dropout_t(relu(att_embed(X)))) does not depend on the
@@ -353,7 +279,7 @@ class _XESequence(torch.autograd.Function):
                                               ss_i32[B:].data_ptr(), ss_raw.data_ptr(), ss_f32[0].data_ptr(),
                                               ss_f32[1].data_ptr(), st), "set_sample_pick_f32")
                 L["TOK"][t, :bt] = torch.where(ss_u[t, :bt], ss_raw[:bt], L["TOK"][t, :bt])
-            tok = (L["TOK"][t] if ss else caps[:, t]) if ro is None else state.tokens[t]
+            tok = (L["TOK"][t] if ss else caps[:, t]) if ro is None else rl.tokens[t]
             if train and cfg.p_embed > 0:
                 check(lib.set_embed_relu_dropout_f32(E.data_ptr(), tok.data_ptr(), cap_stride, emb.data_ptr(), D, bt, D, E.shape[0],
                                                      cfg.p_embed, cfg.seed, scale_off(1, t), st), "set_embed_relu_dropout_f32")
@@ -396,53 +322,26 @@ class _XESequence(torch.autograd.Function):
             if train and cfg.p_out > 0:
                 ops.dropout(L["H2"][t + 1], L["H2D"][t], bt, D, cfg.p_out, cfg.seed, scale_off(3, t))
             if ss:                         # the next step may sample from this step's scores: fc per step
-                hz = L["H2D"][t] if (train and cfg.p_out > 0) else L["H2"][t + 1]
-                ops.linear(hz, P["fc_w"], P["fc_b"], pred_tb[t], bt)
-            if ro is not None:             # editnet_rl.py:514-547: scores of this step, then the device sampling epilogue
-                hz = L["H2D"][t] if (train and cfg.p_out > 0) else L["H2"][t + 1]
-                ops.linear(hz, P["fc_w"], P["fc_b"], L["LOGITS"][t], B)
-                if ro_opts is not None:
-                    check(lib.set_sample_pick_opts_key_f32(L["LOGITS"][t].data_ptr(), ld_lg, B, V, t, T, state.end_idx, state.seed,
-                                                           state.offset, state.seq.data_ptr(), state.tokens[t + 1].data_ptr(),
-                                                           state.unfinished.data_ptr(), state.alive.data_ptr(),
-                                                           L["RAW"][t].data_ptr(), L["LSE"][t].data_ptr(), L["LOGP"][t].data_ptr(),
-                                                           st, C.byref(ro_opts), L["KEY"][t].data_ptr()),
-                          "set_sample_pick_opts_key_f32")
-                else:
-                    check(lib.set_sample_pick_f32(L["LOGITS"][t].data_ptr(), V, B, V, t, T, state.end_idx, state.seed, state.offset,
-                                                  state.seq.data_ptr(), state.tokens[t + 1].data_ptr(),
-                                                  state.unfinished.data_ptr(), state.alive.data_ptr(), L["RAW"][t].data_ptr(),
-                                                  L["LSE"][t].data_ptr(), L["LOGP"][t].data_ptr(), st), "set_sample_pick_f32")
+                ops.linear(hout[t], P["fc_w"], P["fc_b"], pred_tb[t], bt)
+            if ro is not None:
+                rl.step(ops, hout[t], P["fc_w"], P["fc_b"], t)
         if adaptive and count_truncation_bites(L["RMASK"] if train else rmask_eval, bts):
             global TRUNCATION_FALLBACKS
             TRUNCATION_FALLBACKS += 1
             raise CountTruncation()
-        hout = L["H2D"] if (train and cfg.p_out > 0) else L["H2"][1:]
-        if ro is not None:
-            ctx.cfg, ctx.L, ctx.bts, ctx.uniform, ctx.hout = cfg, L, bts, True, hout
-            ctx.dims = (T, B, R, F, Tc, D, Adim, V)
-            ctx.tokens = state.tokens
-            ctx.save_for_backward(X, H, Mem, mask, att1_c, Yin, caps, *params)
-            ctx.mark_non_differentiable(state.seq)
-            return state.seq, L["LOGP"].t()
-        if ss:
-            cfg.fed_tokens = L["TOK"]          # (T, B): the words the steps consumed (tests / diagnostics)
-            out = pred_tb.transpose(0, 1)
-        elif uniform:                      # fc over all timesteps at once: (T, B, V), returned as its (B, T, V) view
-            pred_tb = _e(T, B, V, dev=dev)
-            ops.linear(hout.reshape(T * B, D), P["fc_w"], P["fc_b"], pred_tb.view(T * B, V), T * B)
-            out = pred_tb.transpose(0, 1)
-        else:                              # rows that left the batch keep zero scores (editnet.py:547)
-            out = _z(B, T, V, dev=dev)
-            for t in range(T):
-                ops.linear(hout[t], P["fc_w"], P["fc_b"], out[:, t], bts[t])
         ctx.cfg, ctx.L, ctx.bts, ctx.uniform, ctx.hout = cfg, L, bts, uniform, hout
         ctx.dims = (T, B, R, F, Tc, D, Adim, V)
         ctx.save_for_backward(X, H, Mem, mask, att1_c, Yin, caps, *params)
-        if adaptive:                       # h2 of every row at its last step (slot len_b of the state log), row order
-            idx = torch.tensor(lens, dtype=torch.long, device=dev)
-            last_h = L["H2"][idx, torch.arange(B, device=dev)]
-            return out, last_h
+        if ro is not None:
+            ctx.mark_non_differentiable(rl.seq)
+            return rl.seq, L["LOGP"].t()
+        if ss:
+            cfg.fed_tokens = L["TOK"]          # (T, B): the words the steps consumed (tests / diagnostics)
+            out = pred_tb.transpose(0, 1)
+        else:
+            out = S.score_head(ops, hout, P["fc_w"], P["fc_b"], bts, uniform)
+        if adaptive:                       # the second output: `decoder_last_hidden`
+            return out, S.last_hidden(L["H2"], lens)
         return out
 
     @staticmethod
@@ -458,30 +357,12 @@ class _XESequence(torch.autograd.Function):
         train = cfg.train
         K1, K2 = 3 * D + F, 2 * D + F
 
-        need_p = ctx.needs_input_grad[10:]
-        # ---- d scores as (T, B, V), rows of finished sequences zero
-        if cfg.rollout is not None:        # d seq_logp -> d scores of every step (sampling epilogue backward)
-            dl = dlogp.t().contiguous()                            # (T, B)
-            dp = A.zero_padded_rows(T, B, V, dev)          # rows padded to 16 bytes: the fc contractions read them in place
-            ro_opts = cfg.rollout.get("opts")
-            if ro_opts is not None:        # the truncated log-prob: all T * B rows of the (contiguous) logs in ONE launch
-                check(lib.set_sample_logp_bwd_opts_f32(L["LOGITS"].data_ptr(), L["LOGITS"].stride(1), L["LSE"].data_ptr(), L["RAW"].data_ptr(),
-                                                       L["KEY"].data_ptr(), dl.data_ptr(), dp.data_ptr(), dp.stride(1), T * B, V,
-                                                       C.byref(ro_opts), st), "set_sample_logp_bwd_opts_f32")
-            for t in (range(T) if ro_opts is None else ()):
-                check(lib.set_sample_logp_bwd_f32(L["LOGITS"][t].data_ptr(), V, L["LSE"][t].data_ptr(), L["RAW"][t].data_ptr(),
-                                                  dl[t].data_ptr(), dp[t].data_ptr(), dp.stride(1), B, V, st),
-                      "set_sample_logp_bwd_f32")
-            L["LOGITS"] = None
-            dp2 = dp.as_strided((T * B, V), (dp.stride(1), 1), dp.storage_offset())
-        else:                              # the (B, T, V) gradient of the scores, as (t, b) rows
-            dp2 = A.score_grad_rows(dpred, bts, ctx.uniform)
-        # ---- fc: dH2D for all timesteps in one contraction; fc.weight's gradient is final here (eager: its all-reduce
-        # runs underneath the loop below in the data-parallel step)
-        dH2D = A._dgrad(dp2, P["fc_w"]).view(T, B, D)
-        i_w, i_b = PARAM_NAMES.index("fc_w"), PARAM_NAMES.index("fc_b")
-        g_fc_b = A._bgrad(params[i_b], dp2) if need_p[i_b] else None
-        g_fc_w = A._wgrad(params[i_w], dp2, ctx.hout.reshape(T * B, D), eager=True) if need_p[i_w] else None
+        pg = S.ParamGrads(PARAM_NAMES, params, ctx.needs_input_grad[10:])
+        pidx, need = pg.idx, pg.need
+        # ---- d scores as (t, b) rows, rows of finished sequences zero; then fc
+        dp2 = ctx.rl.backward(ops, dlogp) if cfg.rollout is not None else A.score_grad_rows(dpred, bts, ctx.uniform)
+        dH2D, g_fc_w, g_fc_b = S.score_head_bwd(dp2, ctx.hout, P["fc_w"], P["fc_b"], pg.wants("fc_w"), pg.wants("fc_b"))
+        pg.put("fc_w", g_fc_w); pg.put("fc_b", g_fc_b)
 
         # ---- gradient logs (zero rows where a sequence has left the batch) and running accumulators
         _zl = _e if ctx.uniform else _z
@@ -515,19 +396,11 @@ class _XESequence(torch.autograd.Function):
         w_ctx = torch.cat([P["ca_sc_w"], gate_w[:, 2 * D:]], 0)        # (2D, D) against [ds | dz]
         w_word = torch.cat([gate_w[:, :D], tc_w[:, :D]], 0)            # (2D, D) against [dz | dt]
         w_h1 = torch.cat([gate_w[:, D:2 * D], tc_w[:, D:]], 0)         # (2D, D) against [dz | dt]
-        sc_out = 1.0 / (1.0 - cfg.p_out) if (train and cfg.p_out > 0) else 1.0
-        sc_emb = 1.0 / (1.0 - cfg.p_embed) if (train and cfg.p_embed > 0) else 1.0
-        sc_reg = 1.0 / (1.0 - cfg.p_region) if train else 1.0
+        sc_emb, sc_reg = S.dropout_scale(cfg, cfg.p_embed), S.dropout_scale(cfg, cfg.p_region)
         va_full = P["va_full_w"].reshape(-1)
         ca_full = P["ca_full_w"].reshape(-1)
 
-        def gg(items):
-            """[(dy, w_view, out, accumulate)] -> out (+)= dy . w, one grouped launch"""
-            A.gemm_group([(dy, wv, dy.shape[0], wv.shape[1], dy.shape[1], out, acc) for dy, wv, out, acc in items], False, True)
-
         dlast = dlogp.contiguous() if (cfg.rollout is None and cfg.adaptive and dlogp is not None) else None   # 2nd output (adaptive)
-        pidx = {n: i for i, n in enumerate(PARAM_NAMES)}
-        need = ctx.needs_input_grad[10:]                       # frozen parameters (requires_grad False) get no gradient
         mid = T // 2 if (_WGRAD_OVERLAP and T >= 6 and dev.type == "cuda") else 0
         early = None                                           # (side stream, first row of the early share)
 
@@ -713,10 +586,7 @@ class _XESequence(torch.autograd.Function):
             bt = bts[t]
             r = lambda x: _rows(x, bt)
             h1 = L["H1"][t + 1]
-            if dlast is not None:          # rows whose last step this is: d(decoder_last_hidden) joins dh2 here
-                b0 = bts[t + 1] if t + 1 < T else 0
-                if bt > b0:
-                    ops.pack(DH2[b0:], bt - b0, [dlast[b0:bt]], accumulate=True)
+            S.last_hidden_bwd_step(ops, DH2, dlast, bts, t)
             # h2(t) -> fc (through the output dropout); the recurrent / next-step terms are already in DH2
             if train and cfg.p_out > 0:    # h2 does not follow a ReLU: the mask is regenerated, not read off the zero pattern
                 check(lib.set_dropout_bwd_philox_f32(dH2D[t].data_ptr(), D, DH2.data_ptr(), D, bt, D, cfg.p_out, cfg.seed,
@@ -807,34 +677,20 @@ class _XESequence(torch.autograd.Function):
         dFH = A.gemm(sdg1, False, wih[:, D:2 * D], True, B, D, 4 * D)
         # ---- parameter gradients: one contraction per parameter over all (t, b) rows (over the rows of the earlier timesteps
         # only, accumulated onto the side stream's share, when that was launched half way through the loop)
-        g = [None] * len(PARAM_NAMES)
         TB = T * B
         hi = TB
         if early is not None:
             torch.cuda.current_stream(dev).wait_stream(early)
             hi = mid * B
-
-        def W(name, dy, x):
-            if need[pidx[name]]:
-                g[pidx[name]] = A._wgrad(params[pidx[name]], dy[:hi], x[:hi])
-
-        def Bg(name, dy):
-            if need[pidx[name]]:
-                g[pidx[name]] = A._bgrad(params[pidx[name]], dy)
-
-        g[pidx["fc_w"]], g[pidx["fc_b"]] = g_fc_w, g_fc_b
-        ids = caps[:, :T].t().reshape(-1) if cfg.rollout is None else ctx.tokens[:T].reshape(-1)
+        W, Bg = (lambda name, dy, x: pg.W(name, dy, x, hi)), pg.Bg
+        ids = caps[:, :T].t().reshape(-1) if cfg.rollout is None else ctx.rl.tokens[:T].reshape(-1)
         if "TOK" in L:                     # scheduled sampling: the words actually fed
             ids = L["TOK"].reshape(-1)
-        if need[pidx["E"]]:
-            dE = torch.zeros_like(P["E"])
-            dE.index_add_(0, ids, DEMBRAW.view(TB, D))
-            g[pidx["E"]] = dE
+        pg.embedding("E", ids, DEMBRAW.view(TB, D))
         dg1 = DG1.view(TB, 4 * D)
-        if need[pidx["al_wih"]]:           # column blocks [emb | final_hidden | h2 | image_mean]; the invariant ones from sum_t
-            g[pidx["al_wih"]] = A._wgrad_blocks(params[pidx["al_wih"]], [
-                (dg1[:hi], L["EMB"].view(TB, D)[:hi], 0), (sdg1, L["FH"], D), (dg1[:hi], L["H2"][:T].reshape(TB, D)[:hi], 2 * D),
-                (sdg1, L["MEAN"], 3 * D)])
+        # column blocks [emb | final_hidden | h2 | image_mean]; the invariant ones from sum_t
+        pg.blocks("al_wih", [(dg1[:hi], L["EMB"].view(TB, D)[:hi], 0), (sdg1, L["FH"], D),
+                             (dg1[:hi], L["H2"][:T].reshape(TB, D)[:hi], 2 * D), (sdg1, L["MEAN"], 3 * D)])
         W("al_whh", dg1, L["H1"][:T].reshape(TB, D))
         Bg("al_bih", dg1); Bg("al_bhh", dg1)
         dgw = DGW.view(TB, 4 * D)
@@ -854,18 +710,17 @@ class _XESequence(torch.autograd.Function):
         W("ca_dec_w", datt2[:, Adim:], h1_all); Bg("ca_dec_b", datt2[:, Adim:])
         W("va_dec_w", datt2[:, :Adim], h1_all); Bg("va_dec_b", datt2[:, :Adim])
         Bg("ca_full_w", DWFC.view(TB, Adim))
-        if need[pidx["ca_full_b"]]:
-            g[pidx["ca_full_b"]] = DEC.sum().reshape(1)
+        if pg.wants("ca_full_b"):
+            pg.put("ca_full_b", DEC.sum().reshape(1))
         Bg("va_full_w", DWFV.view(TB, Adim))
-        if need[pidx["va_full_b"]]:
-            g[pidx["va_full_b"]] = DEV.sum().reshape(1)
+        if pg.wants("va_full_b"):
+            pg.put("va_full_b", DEV.sum().reshape(1))
         if train:
-            if need[pidx["va_fa_w"]]:
-                g[pidx["va_fa_w"]] = A._wgrad(params[pidx["va_fa_w"]], DATT1.view(TB * R, Adim)[:hi * R], L["FE"].view(TB * R, D)[:hi * R])
+            pg.W("va_fa_w", DATT1.view(TB * R, Adim), L["FE"].view(TB * R, D), hi * R)
             Bg("va_fa_b", DATT1.view(TB * R, Adim))
-        ctx.L = None
+        ctx.L = ctx.rl = None
         # inputs: cfg, X, mean, H, Mem, final_hidden, mask, att1_c, Yin, caps
-        return (None, None, None, dH, dMem, dFH, None, datt1c, dYin, None) + tuple(g)
+        return (None, None, None, dH, dMem, dFH, None, datt1c, dYin, None) + pg.tuple()
 
 
 def xe_sequence(cfg, X, mean, H, Mem, final_hidden, mask, att1_c, Yin, caps, params):
