@@ -146,6 +146,86 @@ __device__ __forceinline__ void pd_mma(f32x4& acc, const f32x4 (&w)[KB], const f
     }
 }
 
+// ---- arithmetic leaves of the three kernels' phase code: registers and LDS in, registers (or one LDS row) out.  None of them
+// holds a weight request, an exchange, a barrier or a stamp — those are the schedule and stay in the kernels, in their order.
+// The operand order of every expression below is the bit contract with the per-step kernels (attention.hip, pointwise.hip) and
+// the reference.  A leaf is called only where it leaves the kernel's VGPR / AGPR counts as they were (these kernels sit at the
+// register ceiling; profiles/pdec_leaves_resources.json): the kernels' headers name the copies that therefore stay inline.
+// row strides of the hoisted-product tables in LDS (caption table: PDEC_TS, region table: pdec_rs(region capacity)): odd, so
+// that the (thread, index) gathers of 256 threads spread over all banks
+constexpr int PDEC_TS = PDEC_TMAX + 1;
+constexpr int pdec_rs(int rreg) { return rreg + 1; }
+
+// the four waves' K-quarter partials of element o of partial tile `tile` (sRed: [4 waves][3 tiles][16][16]), added in wave order;
+// pd_sum4p: the one-tile region of a product kept for the next timestep (sRedP: [4 waves][16][16])
+__device__ __forceinline__ float pd_sum4(const float* s, int tile, int o) {
+    return ((s[tile * 256 + o] + s[(3 + tile) * 256 + o]) + s[(6 + tile) * 256 + o]) + s[(9 + tile) * 256 + o];
+}
+__device__ __forceinline__ float pd_sum4p(const float* p, int op) { return ((p[op] + p[256 + op]) + p[512 + op]) + p[768 + op]; }
+// fc score of batch row b at the vocabulary row lane l owns (row0 + l): tile l / 16, weight row l % 16 of the three fc tiles
+__device__ __forceinline__ float pd_fc_score(const float* sred, int b, int lane, float bias) {
+    return pd_sum4(sred, 0, (lane >> 4) * 256 + b * 16 + (lane & 15)) + bias;
+}
+// same clamp as embed_relu_k
+__device__ __forceinline__ long long pd_clamp_tok(long long tok, int V) { return tok < 0 ? 0 : (tok >= V ? V - 1 : tok); }
+// LSTM cell from its four gate pre-activations (i, f, g, o): c is updated in place, h returned (lstm_pointwise_k in pointwise.hip)
+__device__ __forceinline__ float pd_cell(float gi, float gf, float gg, float go, float& c) {
+    const float ai = pd_sigm(gi), af = pd_sigm(gf), ag = tanhf(gg), ao = pd_sigm(go);
+    c = af * c + ai * ag;
+    return ao * tanhf(c);
+}
+// (max, first arg-max, sum exp) of one batch row over the 48 vocabulary rows of a slice, lane l holding score x of row `row`
+// (ok: the lane has one).  A NaN score never wins a comparison: it reaches the sum instead and the row's log-prob is NaN
+__device__ __forceinline__ void pd_fc_triple(float x, int row, bool ok, float& best, int& bi, float& se) {
+    best = -INFINITY; bi = 0x7fffffff;
+    if (x > best) { best = x; bi = row; }
+    pw_wargmax(best, bi);
+    se = ok ? expf(x - best) : 0.f;
+    if (best == -INFINITY) se = ok ? x : 0.f;            // no finite score here: 0 for an empty range, NaN for NaN scores
+    se = pw_wsum(se);
+}
+
+// ---- EditNet's leaves (decode_persistent_wide.hip S3b .. S5, decode_persistent_ensemble.hip E3b .. E5)
+// softmax over the T caption scores of one row inside a wave (editnet.py:375-376), in place, and SelectC's hard choice
+// (:409-416): lane 0 stores the first arg-max of the weights to *js and the weight of the selected slot to *wj
+__device__ __forceinline__ void pw_cap_softmax(float* row, int T, int lane, int* js_out, float* wj_out) {
+    const float sc = lane < T ? row[lane] : -INFINITY;
+    const float m = pw_wmax(sc);
+    const float ex = lane < T ? expf(sc - m) : 0.f;
+    const float sum = pw_wsum(ex);
+    const float al = ex / sum;
+    if (lane < T) row[lane] = al;
+    // first arg-max of the weights (block_softmax in attention.hip): SelectC's hard choice
+    float best = lane < T ? al : -1.f;
+    int bi = lane < T ? lane : 0x7fffffff;
+    if (!(best > -1.f)) bi = 0x7fffffff;                 // a NaN weight never wins a comparison
+    pw_wargmax(best, bi);
+    const int js = bi == 0x7fffffff ? 0 : bi;
+    const float aj = pw_lane(al, js);
+    if (lane == 0) { *js_out = js; *wj_out = aj * 1.f + (1.f - aj); }   // the reference's fp32 expression (editnet.py:417-418)
+}
+// softmax over R <= 64 visual scores of one row inside a wave (editnet.py:446), in place
+__device__ __forceinline__ void pw_vis_softmax64(float* row, int R, int lane) {
+    const float sc = lane < R ? row[lane] : -INFINITY;
+    const float m = pw_wmax(sc);
+    const float ex = lane < R ? expf(sc - m) : 0.f;
+    const float sum = pw_wsum(ex);
+    if (lane < R) row[lane] = ex / sum;
+}
+// copy_lstm: c_new and the output gate from the gate pre-activations gp[0, 4, 8, 12] (i, f, g, o) and the cell state ...
+__device__ __forceinline__ void pw_cnew_gates(const float* gp, float c2, float& cnv, float& ogv) {
+    const float ai = pd_sigm(gp[0]), af = pd_sigm(gp[4]), ag = tanhf(gp[8]);
+    ogv = pd_sigm(gp[12]);
+    cnv = af * c2 + ai * ag;
+}
+// ... and the copy gate (editnet.py:281-283): a = gate_cnew(c_new) with its bias, cmemv = gate_cmem(sel); c2 is written, h2 returned
+__device__ __forceinline__ float pw_copy_gate(float a, float cmemv, float bcm, float selv, float cnv, float ogv, float& c2) {
+    const float bq = cmemv + bcm;
+    const float cg = pd_sigm(a + bq);
+    c2 = cg * selv + (1.f - cg) * cnv;
+    return ogv * tanhf(c2);
+}
+
 // ---- EditNet: arguments of decode_persistent_wide.hip (1 .. 16 rows; greedy, teacher-forced and beam mode)
 constexpr int PDEC_RREG = 36;      // image regions whose hoisted x2h products a thread keeps in registers
 constexpr int PDEC_RREG_WIDE = 128; // ... in the beam instantiation for adaptive features (10 - 100 zero-padded regions, masked)

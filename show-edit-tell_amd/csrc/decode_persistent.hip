@@ -35,8 +35,10 @@
 // Shared with the other two persistent decode kernels: the beam mode's pick (beam_persistent.h) and, on the host, the launch
 // itself (decode_persistent.h: the per-instantiation record PersistentKernel, pdec_launch from the LDS cap and the residency
 // check to the stamp report, and the fills of the argument block; pdec_dcnet_fill / pdec_dcnet_layout also serve the ensemble's
-// DCNet half).  Deliberately NOT shared: the phase code of the timestep — where a tile's loads sit between
-// the MFMAs is the schedule, and a function boundary there changes the instructions of a kernel at the register ceiling.
+// DCNet half) and arithmetic leaves of the phases (decode_persistent.h: pd_sum4 / pd_sum4p, pd_cell in S1, pd_fc_score,
+// pd_fc_triple, pd_clamp_tok).  Deliberately NOT shared: the schedule of the timestep — where a tile's loads sit between the
+// MFMAs, the exchanges and the barriers — and the language cell and the masked row softmax of S3, which as leaves moved the
+// AGPR counts of the register-resident instantiations (profiles/pdec_leaves_resources.json).
 #include "beam_persistent.h"
 #include "philox.h"
 
@@ -134,7 +136,7 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) dcnet_persistent_k(const PDec
     // beam mode only (pdec_lds_floats): every workgroup's per-slice candidates, language_lstm.W_hh h2 of the previous timestep
     // (added through the parent map), the cell states on their way through the parent map, the candidate lists of the pick and
     // the pick's bookkeeping words
-    float* sFB = sPc + B * 16 * (PDEC_TMAX + 1);         // (B, G, PW_BEAM_W)
+    float* sFB = sPc + B * 16 * PDEC_TS;         // (B, G, PW_BEAM_W)
     float* sRedP = sFB + B * G * PW_BEAM_W;              // [4 waves][16 batch rows][16 weight rows]
     float* sCst = sRedP + 4 * 256;                       // (2, K, 4) c1 | c2 of the owned units
     float* sCand = sCst + 2 * PW_BEAM_K * 4;             // (K, K, 2) (score, flat index) of every row's best K candidates
@@ -209,7 +211,7 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) dcnet_persistent_k(const PDec
     f32x4 wa[PDEC_KB], wb[PDEC_KB];
     // loop-invariant operands of the attention phase: the hoisted context products of this thread's gate row ...
     if (gcol)
-        for (int tt = 0; tt < PDEC_TMAX; ++tt) sPc[tid * (PDEC_TMAX + 1) + tt] = tt < T ? P.pc[((long long)cb * T + tt) * 4 * D + ccol] : 0.f;
+        for (int tt = 0; tt < PDEC_TMAX; ++tt) sPc[tid * PDEC_TS + tt] = tt < T ? P.pc[((long long)cb * T + tt) * 4 * D + ccol] : 0.f;
     __syncthreads();
     // ... and (RES) this wave's row of cap_features_att
     f32x4 a1r[RES ? PDEC_TREG : 1][2];
@@ -241,7 +243,7 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) dcnet_persistent_k(const PDec
         }
         if (pair) {
             long long tok = (!BEAM && !SAMPLE && P.caps) ? P.caps[(long long)pb * P.caps_stride + t] : sTok[pb];
-            tok = tok < 0 ? 0 : (tok >= V ? V - 1 : tok);          // same clamp as embed_relu_k
+            tok = pd_clamp_tok(tok, V);
             const float* trow = P.tok_table + tok * P.ld_tab + u0 + pu;
 #pragma unroll
             for (int q = 0; q < 4; ++q) tg[q] = trow[(long long)q * D];
@@ -266,11 +268,9 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) dcnet_persistent_k(const PDec
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int o = par * 16 + q * 4 + pu;
-                gq[q] = ((((sRed[o] + sRed[3 * 256 + o]) + sRed[6 * 256 + o]) + sRed[9 * 256 + o]) + pre[q]) + tg[q];
+                gq[q] = (pd_sum4(sRed, 0, o) + pre[q]) + tg[q];
             }
-            const float ai = pd_sigm(gq[0]), af = pd_sigm(gq[1]), ag = tanhf(gq[2]), ao = pd_sigm(gq[3]);
-            c1 = af * c1 + ai * ag;
-            ll_put(h1rs, pb * D + u0 + pu, ao * tanhf(c1), tag);
+            ll_put(h1rs, pb * D + u0 + pu, pd_cell(gq[0], gq[1], gq[2], gq[3], c1), tag);
         }
         PD_STAMP(2);
         pd_load(wb, pT3);
@@ -295,14 +295,10 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) dcnet_persistent_k(const PDec
         if (gcol) {
             const int o = cb * 16 + crr;
             if (crr < apw) {
-                const float v = ((sRed[1 * 256 + o] + sRed[4 * 256 + o]) + sRed[7 * 256 + o]) + sRed[10 * 256 + o];
-                ll_put(a2rs, cb * A + wg * apw + crr, v, tag);
+                ll_put(a2rs, cb * A + wg * apw + crr, pd_sum4(sRed, 1, o), tag);
             }
-            g2 = ((sRed[2 * 256 + o] + sRed[5 * 256 + o]) + sRed[8 * 256 + o]) + sRed[11 * 256 + o];
-            if constexpr (BEAM) {                                // + language_lstm.W_hh h2 of the PARENT hypothesis (S1' of the previous timestep)
-                const int op = sPar[cb] * 16 + crr;
-                g2 += ((sRedP[op] + sRedP[256 + op]) + sRedP[512 + op]) + sRedP[768 + op];
-            }
+            g2 = pd_sum4(sRed, 2, o);
+            if constexpr (BEAM) g2 += pd_sum4p(sRedP, sPar[cb] * 16 + crr);   // + language_lstm.W_hh h2 of the PARENT hypothesis (S1' of the previous timestep)
         }
         PD_STAMP(6);
         ll_stage<256, 8>(a2rs, sA2, B, A, A, tag, watch, tid);
@@ -360,7 +356,7 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) dcnet_persistent_k(const PDec
         PD_STAMP(7);
         if (gcol) {
             float s = 0.f;
-            for (int tt = 0; tt < T; ++tt) s += sAl[cb * PDEC_TMAX + tt] * sPc[tid * (PDEC_TMAX + 1) + tt];
+            for (int tt = 0; tt < T; ++tt) s += sAl[cb * PDEC_TMAX + tt] * sPc[tid * PDEC_TS + tt];
             sG[cb * 16 + crr] = (g2 + s) + b2;
         }
         __syncthreads();
@@ -399,12 +395,9 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) dcnet_persistent_k(const PDec
         if (!BEAM && !SAMPLE && P.caps) {
             // teacher-forced: the scores themselves, rows 0 .. bt - 1 (dcnet.py:347: predictions[:batch_size_t, t, :] = preds)
             for (int b = kq; b < bt; b += 4) {
-                const int j = lane >> 4, rr = lane & 15, row = row0 + lane;
-                if (lane < 16 * PDEC_FC_TILES && lane < P.rpw && row < V) {
-                    const int o = j * 256 + b * 16 + rr;
-                    P.predictions[(long long)b * P.ld_pred_b + (long long)t * V + row] =
-                        (((sRed[o] + sRed[3 * 256 + o]) + sRed[6 * 256 + o]) + sRed[9 * 256 + o]) + fcb_lane;
-                }
+                const int row = row0 + lane;
+                if (lane < 16 * PDEC_FC_TILES && lane < P.rpw && row < V)
+                    P.predictions[(long long)b * P.ld_pred_b + (long long)t * V + row] = pd_fc_score(sRed, b, lane, fcb_lane);
             }
             if (more) {                                          // S1' (see below)
                 acc1 = zero4; acc2 = zero4;
@@ -423,13 +416,10 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) dcnet_persistent_k(const PDec
             ++tag;
             if (kq < B) {
                 const int b = kq;
-                const int j = lane >> 4, rr = lane & 15, row = row0 + lane;
+                const int row = row0 + lane;
                 const bool ok = lane < 16 * PDEC_FC_TILES && lane < P.rpw && row < V;
                 float x = -INFINITY;
-                if (ok) {
-                    const int o = j * 256 + b * 16 + rr;
-                    x = (((sRed[o] + sRed[3 * 256 + o]) + sRed[6 * 256 + o]) + sRed[9 * 256 + o]) + fcb_lane;
-                }
+                if (ok) x = pd_fc_score(sRed, b, lane, fcb_lane);
                 pb_vals cvv;
                 pb_idxs cii;
                 pb_slice_topk(x, row, ok, B, cvv, cii);
@@ -513,8 +503,7 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) dcnet_persistent_k(const PDec
                     const bool ok = lane < 16 * PDEC_FC_TILES && lane < P.rpw && row < V;
                     float y = -INFINITY, sv = -INFINITY;
                     if (ok) {
-                        const int j = lane >> 4, rr = lane & 15, o = j * 256 + b * 16 + rr;
-                        const float x = (((sRed[o] + sRed[3 * 256 + o]) + sRed[6 * 256 + o]) + sRed[9 * 256 + o]) + fcb_lane;
+                        const float x = pd_fc_score(sRed, b, lane, fcb_lane);
                         y = __fmul_rn(x, P.gm_inv_t);
                         sv = y + gumbel_at(P.gm_seed, P.gm_offset, b, t, row);
                     }
@@ -604,21 +593,13 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) dcnet_persistent_k(const PDec
         ++tag;                                                   // X4: (max, arg-max, sum exp) of every workgroup's rows
         {   // (resident variant: one row per wave, no loop — see the attention phase)
             auto row_work = [&](const int b) {
-                const int j = lane >> 4, rr = lane & 15, row = row0 + lane;
+                const int row = row0 + lane;
                 const bool ok = lane < 16 * PDEC_FC_TILES && lane < P.rpw && row < V;
                 float x = -INFINITY;
-                if (ok) {
-                    const int o = j * 256 + b * 16 + rr;
-                    x = (((sRed[o] + sRed[3 * 256 + o]) + sRed[6 * 256 + o]) + sRed[9 * 256 + o]) + fcb_lane;
-                }
-                float best = -INFINITY;
-                int bi = 0x7fffffff;
-                if (x > best) { best = x; bi = row; }
-                    pw_wargmax(best, bi);
-                // (a NaN score never wins a comparison: it reaches the sum instead and the row's log-prob is NaN)
-                float se = ok ? expf(x - best) : 0.f;
-                if (best == -INFINITY) se = ok ? x : 0.f;            // no finite score here: 0 for an empty range, NaN for NaN scores
-                se = pw_wsum(se);
+                if (ok) x = pd_fc_score(sRed, b, lane, fcb_lane);
+                float best, se;
+                int bi;
+                pd_fc_triple(x, row, ok, best, bi, se);
                 if (lane < 4) ll_put(fcrs, (b * G + wg) * 4 + lane, lane == 0 ? best : (lane == 1 ? __int_as_float(bi) : (lane == 2 ? se : 0.f)), tag);
             };
             if constexpr (RES) { if (kq < B) row_work(kq); }
@@ -710,7 +691,7 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) dcnet_persistent_k(const PDec
 }
 
 static int pdec_lds_floats(int B, int D, int A, bool beam = false) {
-    const int base = 2 * B * (D + 4) + 4 * 3 * 256 + PDEC_MAXB * PDEC_TMAX + PDEC_MAXB * 16 + B * A + B * (D / 4) * 4 + 2 * A + B * 16 * (PDEC_TMAX + 1);
+    const int base = 2 * B * (D + 4) + 4 * 3 * 256 + PDEC_MAXB * PDEC_TMAX + PDEC_MAXB * 16 + B * A + B * (D / 4) * 4 + 2 * A + B * 16 * PDEC_TS;
     // beam mode: candidates of every slice, W_hh h2 tiles, c1 | c2 table, candidate lists, scores, parents, k_left, best
     return base + (beam ? B * (D / 4) * PW_BEAM_W + 4 * 256 + 2 * PW_BEAM_K * 4 + PW_BEAM_K * PW_BEAM_K * 2 + 2 * PW_BEAM_K + 4 : 0);
 }

@@ -3,10 +3,15 @@
 // ONE launch of D / 4 workgroups for the whole search.  Two one-per-CU grids cannot be resident at once, so this kernel holds
 // BOTH models' state: a workgroup owns four hidden units of EditNet's two cells and of DCNet's two cells, and the SAME
 // vocabulary rows [v0, v1) of both fc layers — both models' logits of a slice meet in one workgroup and no logits travel.
-// The phase code is copied from editnet_persistent_wide_k<BEAM, 36> (decode_persistent_wide.hip) and from the general BEAM
-// instantiation of dcnet_persistent_k (decode_persistent.hip), which stay untouched: in the phase code the order of the loads and
-// the rotating weight buffers are the schedule, and moving it out of those loop bodies changes their instructions.  What does
-// not carry a schedule is shared with those two kernels: the tail of the pick (slice top-k, candidate words, row merge,
+// What is COPIED from editnet_persistent_wide_k<BEAM, 36> (decode_persistent_wide.hip) and from the general BEAM instantiation of
+// dcnet_persistent_k (decode_persistent.hip) is the schedule of the phases: the weight requests (pd_load / pd_load_if) and the
+// rotation of the three weight buffers, the exchanges (ll_put / ll_stage), the barriers, the stamps and the tags, in their
+// order — moving those out of the loop bodies changes the kernels' instructions.  What is SHARED with those two kernels is the
+// arithmetic between those lines, one definition each in decode_persistent.h: pd_sum4 / pd_sum4p (the four waves' partial sums),
+// pd_fc_score, pd_clamp_tok, pd_cell (all four cells), and EditNet's pw_cap_softmax (with SelectC's first arg-max),
+// pw_vis_softmax64, pw_cnew_gates, pw_copy_gate.  Still this kernel's own copies, because as leaves they moved an AGPR count of
+// one of the three kernels (profiles/pdec_leaves_resources.json): the poll of the projections and the two attention scores
+// (E3a), the context gate (E3b) and DCNet's masked row softmax (D3).  Shared further: the tail of the pick (slice top-k, candidate words, row merge,
 // bookkeeping, poison: beam_persistent.h) and, on the host, the launch itself (PersistentKernel / pdec_launch,
 // decode_persistent.h) and the fills and exchange layouts of both models' argument blocks (pdec_edit_fill / pdec_edit_layout,
 // decode_persistent_wide.hip; pdec_dcnet_fill / pdec_dcnet_layout, pdec_beam_fill, decode_persistent.h).  The rows are the
@@ -54,8 +59,6 @@ struct PDecEnsArgs {
 namespace {
 
 constexpr int PE_U = 16;               // 16-byte requests a lane keeps in flight while it fills LDS from an exchange buffer
-constexpr int PE_TS = PDEC_TMAX + 1;   // odd row strides of the hoisted-product tables in LDS (see decode_persistent_wide.hip)
-constexpr int PE_RS = PDEC_RREG + 1;
 constexpr int PE_K = PW_BEAM_K;
 
 #define PE_STAMP(i) if (P.e.stamps && t < PD_STAMP_STEPS && (int)blockIdx.x == P.e.stamp_wg && threadIdx.x == 0) P.e.stamps[t * PD_STAMPS + (i)] = __builtin_amdgcn_s_memrealtime()
@@ -63,7 +66,7 @@ constexpr int PE_K = PW_BEAM_K;
 }  // namespace
 
 __global__ void __launch_bounds__(PDEC_THREADS, 1) ensemble_persistent_k(const PDecEnsArgs P) {
-    constexpr int RS = PE_RS;
+    constexpr int RS = pdec_rs(PDEC_RREG);
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __shared__ long long sTok[PE_K];
     __shared__ int sJs[PE_K];
@@ -87,7 +90,7 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) ensemble_persistent_k(const P
     float* sM = sZ + PE_K * 8;                           // (K, 8)
     float* sPv = sM + PE_K * 8;                          // (B, 16, RREG) hoisted region products of the owned gate rows
     float* sPz = sPv + B * 16 * RS;                      // (B, 8, TMAX) hoisted caption-context products of the owned columns
-    float* sCon = sPz + B * 8 * PE_TS;                   // [cap_decoder_att.b | cap_full_att.w | decoder_att.b | full_att.w] (4, A)
+    float* sCon = sPz + B * 8 * PDEC_TS;                   // [cap_decoder_att.b | cap_full_att.w | decoder_att.b | full_att.w] (4, A)
     float* sRedP = sCon + 4 * A;                         // [4 waves][16][16] copy_lstm.h2h h2 of the previous timestep
     float* sCst = sRedP + 4 * 256;                       // (2, K, 4) c1 | c2 of the owned units
     float* dAl = sCst + 2 * PE_K * 4;                    // DCNet (K, TMAX) attention weights
@@ -95,7 +98,7 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) ensemble_persistent_k(const P
     float* dA2 = dG + PE_K * 16;                         // (B, A) cap_decoder_att(h1)
     float* dCon = dA2 + B * A;                           // [cap_decoder_att.bias | cap_full_att.weight] (2, A)
     float* dPc = dCon + 2 * A;                           // (B, 16, TMAX) hoisted context products of the owned gate rows
-    float* dRedP = dPc + B * 16 * PE_TS;                 // [4 waves][16][16] language_lstm.W_hh h2 of the previous timestep
+    float* dRedP = dPc + B * 16 * PDEC_TS;                 // [4 waves][16][16] language_lstm.W_hh h2 of the previous timestep
     float* dCst = dRedP + 4 * 256;                       // (2, K, 4)
     float* sFB = dCst + 2 * PE_K * 4;                    // (B, G, PW_BEAM_W) every slice's candidates
     float* sCand = sFB + B * G * PW_BEAM_W;              // (K, K, 2) (score, flat index) of every row's best K candidates
@@ -171,13 +174,13 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) ensemble_persistent_k(const P
     }
     if (gcol) {
         for (int rr = 0; rr < PDEC_RREG; ++rr) sPv[tid * RS + rr] = rr < R ? P.e.pv[((long long)cb * R + rr) * 4 * D + ccol] : 0.f;
-        for (int tt = 0; tt < PDEC_TMAX; ++tt) dPc[tid * PE_TS + tt] = tt < T ? P.d.pc[((long long)cb * T + tt) * 4 * D + ccol] : 0.f;
+        for (int tt = 0; tt < PDEC_TMAX; ++tt) dPc[tid * PDEC_TS + tt] = tt < T ? P.d.pc[((long long)cb * T + tt) * 4 * D + ccol] : 0.f;
         b2 = P.e.cl_x2h_b[ccol] + P.e.cl_h2h_b[ccol];
         db2 = P.d.ll_bih[ccol] + P.d.ll_bhh[ccol];
     }
     if (zrole)
         for (int tt = 0; tt < PDEC_TMAX; ++tt)
-            sPz[tid * PE_TS + tt] = tt < T ? P.e.capP[((long long)zb * T + tt) * 2 * D + (zc8 < 4 ? u0 + zc8 : D + u0 + zc8 - 4)] : 0.f;
+            sPz[tid * PDEC_TS + tt] = tt < T ? P.e.capP[((long long)zb * T + tt) * 2 * D + (zc8 < 4 ? u0 + zc8 : D + u0 + zc8 - 4)] : 0.f;
     for (int i = tid; i < A; i += PDEC_THREADS) {
         sCon[i] = P.e.ca_dec_b[i]; sCon[A + i] = P.e.ca_full_w[i]; sCon[2 * A + i] = P.e.va_dec_b[i]; sCon[3 * A + i] = P.e.va_full_w[i];
         dCon[i] = P.d.ca_dec_b[i]; dCon[A + i] = P.d.ca_full_w[i];
@@ -232,7 +235,7 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) ensemble_persistent_k(const P
         float tg[4] = {0.f, 0.f, 0.f, 0.f}, ttc = 0.f, tcg = 0.f, dtg[4] = {0.f, 0.f, 0.f, 0.f};
         if (pair) {
             long long tok = sTok[pb];
-            tok = tok < 0 ? 0 : (tok >= V ? V - 1 : tok);
+            tok = pd_clamp_tok(tok, V);
             const float* trow = P.e.tok_table + tok * P.e.ld_tab + pd;
             const float* drow = P.d.tok_table + tok * P.d.ld_tab + pd;
 #pragma unroll
@@ -264,19 +267,11 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) ensemble_persistent_k(const P
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int o = par * 16 + q * 4 + pu;
-                gq[q] = ((((sRed[o] + sRed[3 * 256 + o]) + sRed[6 * 256 + o]) + sRed[9 * 256 + o]) + pre[q]) + tg[q];
-                dq[q] = ((((sRed[256 + o] + sRed[4 * 256 + o]) + sRed[7 * 256 + o]) + sRed[10 * 256 + o]) + dpre[q]) + dtg[q];
+                gq[q] = (pd_sum4(sRed, 0, o) + pre[q]) + tg[q];
+                dq[q] = (pd_sum4(sRed, 1, o) + dpre[q]) + dtg[q];
             }
-            {
-                const float ai = pd_sigm(gq[0]), af = pd_sigm(gq[1]), ag = tanhf(gq[2]), ao = pd_sigm(gq[3]);
-                c1 = af * c1 + ai * ag;
-                ll_put(h1rs, pb * D + pd, ao * tanhf(c1), tag);
-            }
-            {
-                const float ai = pd_sigm(dq[0]), af = pd_sigm(dq[1]), ag = tanhf(dq[2]), ao = pd_sigm(dq[3]);
-                dc1 = af * dc1 + ai * ag;
-                ll_put(dh1rs, pb * D + pd, ao * tanhf(dc1), tag);
-            }
+            ll_put(h1rs, pb * D + pd, pd_cell(gq[0], gq[1], gq[2], gq[3], c1), tag);
+            ll_put(dh1rs, pb * D + pd, pd_cell(dq[0], dq[1], dq[2], dq[3], dc1), tag);
         }
         pd_load(wb, pT3);
         pd_load_if(wa, pT4, v4);
@@ -301,7 +296,7 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) ensemble_persistent_k(const P
         ++tag;                                                   // X2e: [cap_decoder_att(h1) | decoder_att(h1)]
         if (gcol && crr < 12) {
             const int o = cb * 16 + crr;
-            const float v = ((sRed[1 * 256 + o] + sRed[4 * 256 + o]) + sRed[7 * 256 + o]) + sRed[10 * 256 + o];
+            const float v = pd_sum4(sRed, 1, o);
             if (crr < 8) sM[cb * 8 + crr] = v;
             else ll_put(a2rs, cb * 2 * A + wg * 4 + crr - 8, v, tag);
         }
@@ -360,33 +355,13 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) ensemble_persistent_k(const P
         // ================= E3b: both softmaxes of every row, SelectC's arg-max (editnet.py:375-376, :409-416, :446)
         if (kq < B) {
             const int b = kq;
-            {
-                const float sc = lane < T ? sAlc[b * PDEC_TMAX + lane] : -INFINITY;
-                const float m = pw_wmax(sc);
-                const float ex = lane < T ? expf(sc - m) : 0.f;
-                const float sum = pw_wsum(ex);
-                const float al = ex / sum;
-                if (lane < T) sAlc[b * PDEC_TMAX + lane] = al;
-                float best = lane < T ? al : -1.f;
-                int bi = lane < T ? lane : 0x7fffffff;
-                if (!(best > -1.f)) bi = 0x7fffffff;             // a NaN weight never wins a comparison
-                pw_wargmax(best, bi);
-                const int js = bi == 0x7fffffff ? 0 : bi;
-                const float aj = pw_lane(al, js);
-                if (lane == 0) { sJs[b] = js; sWj[b] = aj * 1.f + (1.f - aj); }   // the reference's fp32 expression (editnet.py:417-418)
-            }
-            {
-                const float sc = lane < R ? sAlv[b * 64 + lane] : -INFINITY;
-                const float m = pw_wmax(sc);
-                const float ex = lane < R ? expf(sc - m) : 0.f;
-                const float sum = pw_wsum(ex);
-                if (lane < R) sAlv[b * 64 + lane] = ex / sum;
-            }
+            pw_cap_softmax(sAlc + b * PDEC_TMAX, T, lane, &sJs[b], &sWj[b]);
+            pw_vis_softmax64(sAlv + b * 64, R, lane);
         }
         PE_SYNC();
         if (zrole) {
             float s = 0.f;
-            for (int tt = 0; tt < T; ++tt) s += sAlc[zb * PDEC_TMAX + tt] * sPz[tid * PE_TS + tt];
+            for (int tt = 0; tt < T; ++tt) s += sAlc[zb * PDEC_TMAX + tt] * sPz[tid * PDEC_TS + tt];
             sZ[zb * 8 + zc8] = s;
         }
         PE_SYNC();
@@ -419,19 +394,15 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) ensemble_persistent_k(const P
             const int o = cb * 16 + crr;
             float s = 0.f;
             for (int rr = 0; rr < R; ++rr) s += sAlv[cb * 64 + rr] * sPv[tid * RS + rr];
-            float g2 = ((sRed[2 * 256 + o] + sRed[5 * 256 + o]) + sRed[8 * 256 + o]) + sRed[11 * 256 + o];
-            const int op = sPar[cb] * 16 + crr;                  // + copy_lstm.h2h h2 of the PARENT hypothesis (S1'e of the previous timestep)
-            g2 += ((sRedP[op] + sRedP[256 + op]) + sRedP[512 + op]) + sRedP[768 + op];
+            float g2 = pd_sum4(sRed, 2, o);
+            g2 += pd_sum4p(sRedP, sPar[cb] * 16 + crr);          // + copy_lstm.h2h h2 of the PARENT hypothesis (S1'e of the previous timestep)
             sG[o] = (g2 + s) + b2;
         }
         PE_SYNC();
         ++tag;                                                   // X4e: c_new
         float cnv = 0.f, ogv = 0.f;
         if (pair) {
-            const float* gp = sG + pb * 16 + pu;
-            const float ai = pd_sigm(gp[0]), af = pd_sigm(gp[4]), ag = tanhf(gp[8]);
-            ogv = pd_sigm(gp[12]);
-            cnv = af * c2 + ai * ag;
+            pw_cnew_gates(sG + pb * 16 + pu, c2, cnv, ogv);
             ll_put(cnrs, pb * D + pd, cnv, tag);
         }
         PE_STAGE(cnrs, sX, B, D, LDH, tag);
@@ -448,12 +419,8 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) ensemble_persistent_k(const P
         PE_SYNC();
         ++tag;                                                   // X5e: h2
         if (pair) {
-            const int o = pb * 16 + pu;
-            const float a = (((sRed[o] + sRed[3 * 256 + o]) + sRed[6 * 256 + o]) + sRed[9 * 256 + o]) + bcn;
-            const float bq = cmemv + bcm;
-            const float cg = pd_sigm(a + bq);
-            c2 = cg * selv + (1.f - cg) * cnv;
-            ll_put(h2rs, pb * D + pd, ogv * tanhf(c2), tag);
+            const float a = pd_sum4(sRed, 0, pb * 16 + pu) + bcn;
+            ll_put(h2rs, pb * D + pd, pw_copy_gate(a, cmemv, bcm, selv, cnv, ogv, c2), tag);
         }
         PE_STAGE(h2rs, sX, B, D, LDH, tag);
         PE_SYNC();
@@ -477,10 +444,7 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) ensemble_persistent_k(const P
         PE_SYNC();
         // wave b keeps EditNet's scores of row b: lane l holds vocabulary row row0 + l of the slice
         float xe = -INFINITY;
-        if (kq < B && fc_ok) {
-            const int o = (lane >> 4) * 256 + kq * 16 + (lane & 15);
-            xe = (((sRed[o] + sRed[3 * 256 + o]) + sRed[6 * 256 + o]) + sRed[9 * 256 + o]) + fcb_e;
-        }
+        if (kq < B && fc_ok) xe = pd_fc_score(sRed, kq, lane, fcb_e);
         // S1'e: attention_lstm.W_ih[:, h2] h2 (+ W_hh h1 from E2) and copy_lstm.h2h h2 for timestep t + 1; the latter goes to LDS:
         // the next timestep adds it through the parent map
         if (more) {
@@ -516,12 +480,10 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) ensemble_persistent_k(const P
         if (gcol) {
             const int o = cb * 16 + crr;
             if (crr < apw) {
-                const float v = ((sRed[1 * 256 + o] + sRed[4 * 256 + o]) + sRed[7 * 256 + o]) + sRed[10 * 256 + o];
-                ll_put(da2rs, cb * A + wg * apw + crr, v, tag);
+                ll_put(da2rs, cb * A + wg * apw + crr, pd_sum4(sRed, 1, o), tag);
             }
-            dg2 = ((sRed[2 * 256 + o] + sRed[5 * 256 + o]) + sRed[8 * 256 + o]) + sRed[11 * 256 + o];
-            const int op = sPar[cb] * 16 + crr;                  // + language_lstm.W_hh h2 of the PARENT hypothesis (S1'd of the previous timestep)
-            dg2 += ((dRedP[op] + dRedP[256 + op]) + dRedP[512 + op]) + dRedP[768 + op];
+            dg2 = pd_sum4(sRed, 2, o);
+            dg2 += pd_sum4p(dRedP, sPar[cb] * 16 + crr);         // + language_lstm.W_hh h2 of the PARENT hypothesis (S1'd of the previous timestep)
         }
         PE_STAGE(da2rs, dA2, B, A, A, tag);
         PE_SYNC();
@@ -568,16 +530,14 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) ensemble_persistent_k(const P
         PE_STAMP(13);
         if (gcol) {
             float s = 0.f;
-            for (int tt = 0; tt < T; ++tt) s += dAl[cb * PDEC_TMAX + tt] * dPc[tid * PE_TS + tt];
+            for (int tt = 0; tt < T; ++tt) s += dAl[cb * PDEC_TMAX + tt] * dPc[tid * PDEC_TS + tt];
             dG[cb * 16 + crr] = (dg2 + s) + db2;
         }
         PE_SYNC();
         ++tag;                                                   // X3d: h2
         if (pair) {
             const float* gp = dG + pb * 16 + pu;
-            const float ai = pd_sigm(gp[0]), af = pd_sigm(gp[4]), ag = tanhf(gp[8]), ao = pd_sigm(gp[12]);
-            dc2 = af * dc2 + ai * ag;
-            ll_put(dh2rs, pb * D + pd, ao * tanhf(dc2), tag);
+            ll_put(dh2rs, pb * D + pd, pd_cell(gp[0], gp[4], gp[8], gp[12], dc2), tag);
         }
         PE_STAGE(dh2rs, sH2, B, D, LDH, tag);
         PE_SYNC();
@@ -605,10 +565,7 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) ensemble_persistent_k(const P
         float xd = -INFINITY;
         if (kq < B) {
             const int b = kq;
-            if (fc_ok) {
-                const int o = (lane >> 4) * 256 + b * 16 + (lane & 15);
-                xd = (((sRed[o] + sRed[3 * 256 + o]) + sRed[6 * 256 + o]) + sRed[9 * 256 + o]) + fcb_d;
-            }
+            if (fc_ok) xd = pd_fc_score(sRed, b, lane, fcb_d);
             const float me = pw_wmax(xe), md = pw_wmax(xd);
             const float se = pw_wsum((fc_ok && me > -INFINITY) ? expf(xe - me) : 0.f);
             const float sd = pw_wsum((fc_ok && md > -INFINITY) ? expf(xd - md) : 0.f);
@@ -715,8 +672,8 @@ namespace {
 int pens_lds_floats(int B, int D, int A) {
     const int G = D / 4;
     const int shared = 2 * B * (D + 4) + 4 * 3 * 256;
-    const int edit = PE_K * (PDEC_TMAX + 64 + 16 + 8 + 8) + B * 16 * PE_RS + B * 8 * PE_TS + 4 * A + 4 * 256 + 2 * PE_K * 4;
-    const int dcn = PE_K * (PDEC_TMAX + 16) + B * A + 2 * A + B * 16 * PE_TS + 4 * 256 + 2 * PE_K * 4;
+    const int edit = PE_K * (PDEC_TMAX + 64 + 16 + 8 + 8) + B * 16 * pdec_rs(PDEC_RREG) + B * 8 * PDEC_TS + 4 * A + 4 * 256 + 2 * PE_K * 4;
+    const int dcn = PE_K * (PDEC_TMAX + 16) + B * A + 2 * A + B * 16 * PDEC_TS + 4 * 256 + 2 * PE_K * 4;
     return shared + edit + dcn + B * G * PW_BEAM_W + PE_K * PE_K * 2;
 }
 

@@ -36,9 +36,12 @@
 // Beam mode (BEAM): the pick — slice top-k, candidate words, row merge, bookkeeping, poison — is beam_persistent.h, shared with
 // DCNet's kernel and the ensemble's.  On the host the launch itself (decode_persistent.h: PersistentKernel, pdec_launch, the
 // fills of the beam / teacher-forced / guard fields) and, with the ensemble launch, the fill of PDecEditArgs and the layout of
-// its seven exchange regions (pdec_edit_fill / pdec_edit_layout below) are shared too.  The phase code is deliberately this
-// kernel's own (the ensemble kernel carries a copy): the order of its loads and the three rotating weight buffers are its
-// schedule.
+// its seven exchange regions (pdec_edit_fill / pdec_edit_layout below) are shared too.  The schedule of the phases — the order
+// of the loads, the three rotating weight buffers, the exchanges and barriers — is deliberately this kernel's own (the ensemble
+// kernel carries a copy); of the arithmetic between those lines pd_sum4 / pd_sum4p, pd_clamp_tok, pw_cap_softmax,
+// pw_vis_softmax64, pw_cnew_gates and pw_copy_gate are leaves of decode_persistent.h, shared.  The cell update of S1, the poll and
+// the scores of S3a, the context gate and the fc score / triple stay written out here: as leaves each of them moved the AGPR
+// count of an instantiation of this kernel (profiles/pdec_leaves_resources.json).
 #include "beam_persistent.h"
 #include "philox.h"
 
@@ -48,8 +51,6 @@ namespace {
 
 constexpr int PW_U = 16;           // 16-byte requests a lane keeps in flight while it fills LDS from an exchange buffer
 // (PW_BEAM_K, PW_BEAM_W, the candidate layout of the beam mode: decode_persistent.h — DCNet's kernel publishes the same words)
-constexpr int PW_TS = PDEC_TMAX + 1;   // row strides of the hoisted-product tables in LDS: odd (region table: RREG + 1), so that the
-                                       // (thread, index) gathers of 256 threads spread over all banks
 // visual scores per row in LDS and in the exchange: 64, or the region capacity above that
 constexpr int pw_vcols(int rreg) { return rreg > 64 ? rreg : 64; }
 
@@ -65,7 +66,7 @@ constexpr int pw_vcols(int rreg) { return rreg > 64 ? rreg : 64; }
 // mode" below.  An arg-max over perturbed scores, so the grid combines it exactly as it combines the greedy one.
 template <bool BEAM, int RREG, bool SAMPLE = false>
 __global__ void __launch_bounds__(PDEC_THREADS, 1) editnet_persistent_wide_k(const PDecEditArgs P) {
-    constexpr int RS = RREG + 1, VC = pw_vcols(RREG);
+    constexpr int RS = pdec_rs(RREG), VC = pw_vcols(RREG);
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __shared__ long long sTok[PDW_MAXB];
     __shared__ int sUnf[PDW_MAXB], sJs[PDW_MAXB];
@@ -84,7 +85,7 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) editnet_persistent_wide_k(con
     float* sM = sZ + PDW_MAXB * 8;                       // (B, 8) [context_gate.W h1 (4) | tc_affine.W h1 (4)]
     float* sPv = sM + PDW_MAXB * 8;                      // (B, 16, RREG) hoisted region products of the owned gate rows
     float* sPz = sPv + B * 16 * RS;                   // (B, 8, TMAX) hoisted caption-context products of the owned columns
-    float* sCon = sPz + B * 8 * PW_TS;               // [cap_decoder_att.b | cap_full_att.w | decoder_att.b | full_att.w] (4, A)
+    float* sCon = sPz + B * 8 * PDEC_TS;               // [cap_decoder_att.b | cap_full_att.w | decoder_att.b | full_att.w] (4, A)
     const float* sF = sX;
     // beam mode only: every workgroup's per-slice candidates, the previous timestep's h2h products (added through the parent
     // map), the cell states on their way through the parent map, the per-row candidate lists of the pick
@@ -153,7 +154,7 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) editnet_persistent_wide_k(con
     }
     if (zrole)
         for (int tt = 0; tt < PDEC_TMAX; ++tt)
-            sPz[tid * PW_TS + tt] = tt < T ? P.capP[((long long)zb * T + tt) * 2 * D + (zc8 < 4 ? u0 + zc8 : D + u0 + zc8 - 4)] : 0.f;
+            sPz[tid * PDEC_TS + tt] = tt < T ? P.capP[((long long)zb * T + tt) * 2 * D + (zc8 < 4 ? u0 + zc8 : D + u0 + zc8 - 4)] : 0.f;
     if (worker)
         for (int i = tid; i < A; i += PDEC_THREADS) {
             sCon[i] = P.ca_dec_b[i]; sCon[A + i] = P.ca_full_w[i]; sCon[2 * A + i] = P.va_dec_b[i]; sCon[3 * A + i] = P.va_full_w[i];
@@ -216,7 +217,7 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) editnet_persistent_wide_k(con
         }
         if (pair) {
             long long tok = P.caps ? P.caps[(long long)pb * P.caps_stride + t] : sTok[pb];
-            tok = tok < 0 ? 0 : (tok >= V ? V - 1 : tok);
+            tok = pd_clamp_tok(tok, V);
             const float* trow = P.tok_table + tok * P.ld_tab + pd;
 #pragma unroll
             for (int q = 0; q < 4; ++q) tg[q] = trow[(long long)q * D];
@@ -270,7 +271,7 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) editnet_persistent_wide_k(con
         ++tag;                                                   // X2: [cap_decoder_att(h1) | decoder_att(h1)]
         if (gcol && crr < 12) {
             const int o = cb * 16 + crr;
-            const float v = ((sRed[1 * 256 + o] + sRed[4 * 256 + o]) + sRed[7 * 256 + o]) + sRed[10 * 256 + o];
+            const float v = pd_sum4(sRed, 1, o);
             if (crr < 8) sM[cb * 8 + crr] = v;
             else ll_put(a2rs, cb * 2 * A + wg * 4 + crr - 8, v, tag);
         }
@@ -331,28 +332,9 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) editnet_persistent_wide_k(con
         // ================= S3b: both softmaxes of every row, SelectC's arg-max (editnet.py:375-376, :409-416, :446)
         if (worker) {
             for (int b = kq; b < B; b += 4) {
-                {
-                    const float sc = lane < T ? sAlc[b * PDEC_TMAX + lane] : -INFINITY;
-                    const float m = pw_wmax(sc);
-                    const float ex = lane < T ? expf(sc - m) : 0.f;
-                    const float sum = pw_wsum(ex);
-                    const float al = ex / sum;
-                    if (lane < T) sAlc[b * PDEC_TMAX + lane] = al;
-                    // first arg-max of the weights (block_softmax in attention.hip): SelectC's hard choice
-                    float best = lane < T ? al : -1.f;
-                    int bi = lane < T ? lane : 0x7fffffff;
-                    if (!(best > -1.f)) bi = 0x7fffffff;         // a NaN weight never wins a comparison
-                    pw_wargmax(best, bi);
-                    const int js = bi == 0x7fffffff ? 0 : bi;
-                    const float aj = pw_lane(al, js);
-                    if (lane == 0) { sJs[b] = js; sWj[b] = aj * 1.f + (1.f - aj); }   // the reference's fp32 expression (editnet.py:417-418)
-                }
+                pw_cap_softmax(sAlc + b * PDEC_TMAX, T, lane, &sJs[b], &sWj[b]);
                 if constexpr (RREG <= 64) {
-                    const float sc = lane < R ? sAlv[b * 64 + lane] : -INFINITY;
-                    const float m = pw_wmax(sc);
-                    const float ex = lane < R ? expf(sc - m) : 0.f;
-                    const float sum = pw_wsum(ex);
-                    if (lane < R) sAlv[b * 64 + lane] = ex / sum;
+                    pw_vis_softmax64(sAlv + b * 64, R, lane);
                 } else {                                         // up to 128 scores: lane l holds regions l and l + 64
                     const int l1 = lane + 64;
                     const float sc0 = lane < R ? sAlv[b * VC + lane] : -INFINITY, sc1 = l1 < R ? sAlv[b * VC + l1] : -INFINITY;
@@ -367,7 +349,7 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) editnet_persistent_wide_k(con
         PW_SYNC();
         if (zrole) {
             float s = 0.f;
-            for (int tt = 0; tt < T; ++tt) s += sAlc[zb * PDEC_TMAX + tt] * sPz[tid * PW_TS + tt];
+            for (int tt = 0; tt < T; ++tt) s += sAlc[zb * PDEC_TMAX + tt] * sPz[tid * PDEC_TS + tt];
             sZ[zb * 8 + zc8] = s;
         }
         PW_SYNC();
@@ -400,11 +382,8 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) editnet_persistent_wide_k(con
             const int o = cb * 16 + crr;
             float s = 0.f;
             for (int rr = 0; rr < R; ++rr) s += sAlv[cb * VC + rr] * sPv[tid * RS + rr];
-            float g2 = ((sRed[2 * 256 + o] + sRed[5 * 256 + o]) + sRed[8 * 256 + o]) + sRed[11 * 256 + o];
-            if (BEAM) {                                          // + copy_lstm.h2h h2 of the PARENT hypothesis (S1' of the previous timestep)
-                const int op = sPar[cb] * 16 + crr;
-                g2 += ((sRedP[op] + sRedP[256 + op]) + sRedP[512 + op]) + sRedP[768 + op];
-            }
+            float g2 = pd_sum4(sRed, 2, o);
+            if (BEAM) g2 += pd_sum4p(sRedP, sPar[cb] * 16 + crr);   // + copy_lstm.h2h h2 of the PARENT hypothesis (S1' of the previous timestep)
             sG[o] = (g2 + s) + b2;
         }
         PW_SYNC();
@@ -412,10 +391,7 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) editnet_persistent_wide_k(con
         ++tag;                                                   // X4: c_new
         float cnv = 0.f, ogv = 0.f;
         if (pair) {
-            const float* gp = sG + pb * 16 + pu;
-            const float ai = pd_sigm(gp[0]), af = pd_sigm(gp[4]), ag = tanhf(gp[8]);
-            ogv = pd_sigm(gp[12]);
-            cnv = af * c2 + ai * ag;
+            pw_cnew_gates(sG + pb * 16 + pu, c2, cnv, ogv);
             ll_put(cnrs, pb * D + pd, cnv, tag);
         }
         PW_STAGE(cnrs, sX, B, D, LDH);
@@ -432,12 +408,8 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) editnet_persistent_wide_k(con
         PW_SYNC();
         ++tag;                                                   // X5: h2
         if (pair) {
-            const int o = pb * 16 + pu;
-            const float a = (((sRed[o] + sRed[3 * 256 + o]) + sRed[6 * 256 + o]) + sRed[9 * 256 + o]) + bcn;
-            const float bq = cmemv + bcm;
-            const float cg = pd_sigm(a + bq);
-            c2 = cg * selv + (1.f - cg) * cnv;
-            ll_put(h2rs, pb * D + pd, ogv * tanhf(c2), tag);
+            const float a = pd_sum4(sRed, 0, pb * 16 + pu) + bcn;
+            ll_put(h2rs, pb * D + pd, pw_copy_gate(a, cmemv, bcm, selv, cnv, ogv, c2), tag);
         }
         PD_STAMP(11);
         PW_STAGE(h2rs, sX, B, D, LDH);
@@ -759,7 +731,7 @@ __global__ void __launch_bounds__(PDEC_THREADS, 1) editnet_persistent_wide_k(con
 }
 
 static int pwide_lds_floats(int B, int D, int A, bool beam = false, int rreg = PDEC_RREG) {
-    const int base = B * (D + 4) + 4 * 3 * 256 + PDW_MAXB * (PDEC_TMAX + pw_vcols(rreg) + 16 + 8 + 8) + B * 16 * (rreg + 1) + B * 8 * PW_TS + 4 * A;
+    const int base = B * (D + 4) + 4 * 3 * 256 + PDW_MAXB * (PDEC_TMAX + pw_vcols(rreg) + 16 + 8 + 8) + B * 16 * pdec_rs(rreg) + B * 8 * PDEC_TS + 4 * A;
     return base + (beam ? B * (D / 4) * PW_BEAM_W + 4 * 256 + 2 * PW_BEAM_K * 4 + PW_BEAM_K * PW_BEAM_K * 2 : 0);
 }
 
