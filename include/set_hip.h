@@ -961,6 +961,42 @@ int set_beam_pick_nbest_f32(const float* logits, const float* logits2, int64_t l
 int set_beam_gather_f32(float* s0, float* s1, float* s2, float* s3, const int32_t* rows, int NI, int k, int D,
                         void* stream);
 
+/* Constrained beam-search pick (csrc/beam_constrained.hip): the step of set_beam_pick_nbest_f32 — same arguments up to n_done,
+ * same state, done_* mandatory — with candidates REMOVED before the flat top-k and completed hypotheses ranked by a
+ * length-normalised score.  Nothing is renormalised: a surviving candidate (j, v) keeps the value scores[j] + logp_j[v].
+ * With s[0 .. L-1] the L = cur_len tokens of slot j (s[0] = <start>), candidate (j, v) is removed if
+ *   a. v is one of the n_banned ids of `banned` (device memory; an id outside [0, V) matches nothing), or
+ *   b. v == end_idx and L - 1 < min_len (L - 1 words have been generated so far), or
+ *   c. no_repeat_ngram = n >= 1, L >= n and some i in 1 .. L - n has s[i .. i+n-2] == s[L-n+1 .. L-1] and s[i+n-1] == v
+ *      (<start> at position 0 never takes part; n = 1: no word twice).
+ * The k largest surviving values (ties: lowest flat index j V + v) are the picks; the first k_left count; parent / word split,
+ * shrinking k, compaction, words, rows and the sequence re-index are those of set_beam_pick_f32.  A counted <end> pick of value x
+ * completes a hypothesis of cur_len generated words whose RANK SCORE is r = x for length_alpha == 0 (no division: bit-equal) and
+ * r = x / powf(cur_len, length_alpha) otherwise: best_score and done_score hold r, the best of a pick is the first maximum of r in
+ * pick order and replaces best_* only when strictly greater.  The running `scores` stay raw sums.
+ * An image with k_left > 0 and NO surviving finite candidate ends there: k_left = 0, scores = -inf, words = 0, rows = identity,
+ * best_* / done_* as they stood, seqs_out not written (as for a finished image).
+ * Neutral constraints {0, 0, 0, 0, NULL}: the integer outputs of set_beam_pick_nbest_f32; floats agree to rounding (another
+ * summation order of the log-sum-exp).  The outputs do not depend on the row layout (float4 reads for ld % 4 == 0, 16-byte
+ * aligned rows and V <= 12288; scalar reads otherwise).
+ * ws: set_beam_pick_constrained_workspace_bytes(NI, k) bytes (0 for NI <= 0 or k outside 1 .. 8), 16-byte aligned.
+ * All before any HIP call — SET_ERR_ARG: a NULL pointer (c, ws and the done_* arrays included), ws misaligned or too small,
+ * no_repeat_ngram outside 0 .. 16, min_len < 0, length_alpha negative or not finite, n_banned outside 0 .. 64 or banned == NULL
+ * with n_banned > 0 (or the reverse), and what set_beam_pick_f32 refuses; SET_ERR_UNSUPPORTED: k > 8, k V >= 2^31 - 1, Lmax > 256. */
+typedef struct SetBeamConstraints {
+    int32_t no_repeat_ngram;      /* 0 = off, 1..16 */
+    int32_t min_len;              /* 0 = off */
+    float   length_alpha;         /* 0 = off, finite, >= 0 */
+    int32_t n_banned;             /* 0..64 */
+    const int64_t* banned;        /* device, n_banned ids; NULL iff n_banned == 0 */
+} SetBeamConstraints;
+size_t set_beam_pick_constrained_workspace_bytes(int NI, int k);
+int set_beam_pick_constrained_f32(const float* logits, const float* logits2, int64_t ld, int NI, int k, int V, int64_t end_idx,
+                                  int cur_len, int Lmax, float* scores, int32_t* k_left, const int64_t* seqs_in,
+                                  int64_t* seqs_out, float* best_score, int64_t* best_seq, int32_t* best_len, int64_t* words,
+                                  int32_t* rows, float* done_score, int64_t* done_seq, int32_t* done_len, int32_t* n_done,
+                                  const SetBeamConstraints* c, void* ws, size_t ws_bytes, void* stream);
+
 /* Stochastic beam search pick (Kool, van Hoof, Welling, ICML 2019; csrc/sbs.hip): one timestep t (0-based, t <= 254) of a
  * search that leaves, per image, k <= 8 DISTINCT sequences which are an exact sample WITHOUT replacement from the model's
  * sequence distribution, in draw order.  NI images x k slots; slot j of image i is logits row r = i k + j.

@@ -196,6 +196,12 @@ class SbsArgs(C.Structure):
                 ("Lmax", C.c_int32), ("pad_", C.c_int32)]
 
 
+class BeamConstraintsC(C.Structure):
+    """include/set_hip.h SetBeamConstraints (set_beam_pick_constrained_f32; the user-facing object: evaluate.BeamConstraints)"""
+    _fields_ = [("no_repeat_ngram", C.c_int32), ("min_len", C.c_int32), ("length_alpha", C.c_float), ("n_banned", C.c_int32),
+                ("banned", C.c_void_p)]
+
+
 class SampleOpts(C.Structure):
     """include/set_hip.h SetSampleOpts: temperature, top-k and top-p of the sampled pick ({1, 0, 1}: neutral)"""
     _fields_ = [("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("pad_", C.c_int32)]
@@ -453,6 +459,9 @@ PROTOTYPES = {
     "set_beam_pick_f32": (_I, [_P, _P, _L, _I, _I, _I, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "set_beam_pick_nbest_f32": (_I, [_P, _P, _L, _I, _I, _I, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "set_beam_gather_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "set_beam_pick_constrained_workspace_bytes": (_Z, [_I, _I]),
+    "set_beam_pick_constrained_f32": (_I, [_P, _P, _L, _I, _I, _I, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                           C.POINTER(BeamConstraintsC), _P, _Z, _P]),
     "set_sbs_workspace_bytes": (_Z, [_I, _I]),
     "set_sbs_pick_f32": (_I, [C.POINTER(SbsArgs), C.POINTER(SampleOpts), _P]),
     "set_sbs_pick_ensemble_f32": (_I, [C.POINTER(SbsArgs), _P, C.POINTER(SampleOpts), _P]),

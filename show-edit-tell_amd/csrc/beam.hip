@@ -11,7 +11,7 @@
 //      hypotheses compacted to the front in pick order, sequences re-indexed by parent and extended,
 //      next input words, and the parent row map that beam_gather_k uses to re-index the LSTM states.
 // Nothing is synchronised with the host; an image whose k has reached 0 is a no-op.
-#include "set_common.h"
+#include "row_pick.h"
 
 namespace set {
 
@@ -39,8 +39,6 @@ struct BeamArgs {
     int* done_len;               // (NI, k)
     int* n_done;                 // (NI) entries so far
 };
-
-__device__ __forceinline__ bool beam_better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
 
 __global__ void __launch_bounds__(256) beam_pick_k(const BeamArgs a) {
     __shared__ float s_m[4][2], s_s[4][2];

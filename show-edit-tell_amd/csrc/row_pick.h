@@ -16,6 +16,9 @@ __device__ __forceinline__ float block_sum(float v, float* slot) {
     return (slot[0] + slot[1]) + (slot[2] + slot[3]);
 }
 
+// the order of beam candidates (beam.hip, beam_constrained.hip): value descending, flat index ascending among equals
+__device__ __forceinline__ bool beam_better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
+
 // ---- the bookkeeping once the row's word is known (editnet_rl.py:529-547)
 struct SampleOut {
     long long* raw_ids;   // (B) sampled word BEFORE the <end> -> 0 rewriting; -1 once the loop has been left

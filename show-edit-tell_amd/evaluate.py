@@ -86,10 +86,75 @@ def _n_best_sorted(done, m):
     return sorted(done, key=lambda e: -e[1])[:m]
 
 
-def _fused_beam(models, NI, k, V, word_map, dev, max_steps, poll=4, return_scores=False, n_best=None):
+class BeamConstraints:
+    """What a beam search may NOT pick (all eight beam_search_* entries, `constraints=`).  Constraints remove candidates before
+    the flat top-k of every step, per hypothesis; nothing is renormalised, so scores stay sums of the model's log-probabilities.
+      no_repeat_ngram=n (0: off, 1 .. 16): no n-gram of words occurs twice in a hypothesis (n = 1: no word twice)
+      min_length=m (0: off): <end> only after at least m words
+      length_penalty=a (0: off, finite, >= 0): completed hypotheses are RANKED by score / len^a, len = words including <end>; the
+          returned scores and the n-best order are these rank scores (a = 0: the plain sums)
+      banned_words: up to 64 token ids, or words looked up in the search's word_map; never <end>
+    An all-default object is neutral: the search takes the unconstrained path, persistent launches included.  Otherwise the
+    search runs per step with set_beam_pick_constrained_f32 (include/set_hip.h).  An image that runs out of candidates returns its
+    best completed hypothesis, or ([<start>], nan) and an empty n-best list when nothing had completed."""
+
+    def __init__(self, no_repeat_ngram=0, min_length=0, length_penalty=0.0, banned_words=()):
+        import math
+        for name, v, hi in (("no_repeat_ngram", no_repeat_ngram, 16), ("min_length", min_length, 2 ** 31 - 1)):
+            if isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= hi:
+                raise ValueError("%s must be an integer in 0 .. %d, got %r" % (name, hi, v))
+        a = float(length_penalty)
+        if not math.isfinite(a) or a < 0.0:
+            raise ValueError("length_penalty must be finite and >= 0, got %r" % (length_penalty,))
+        banned = (banned_words,) if isinstance(banned_words, (str, int)) else tuple(banned_words)
+        if len(banned) > 64:
+            raise ValueError("at most 64 banned words, got %d" % len(banned))
+        self.no_repeat_ngram, self.min_length, self.length_penalty, self.banned_words = int(no_repeat_ngram), int(min_length), a, banned
+
+    def neutral(self):
+        return self.no_repeat_ngram == 0 and self.min_length == 0 and self.length_penalty == 0.0 and not self.banned_words
+
+    def banned_ids(self, word_map, V):
+        """the banned token ids: ValueError for an unknown word, an id outside [0, V) and for <end>"""
+        ids = []
+        for w in self.banned_words:
+            if isinstance(w, str):
+                if w not in word_map:
+                    raise ValueError("banned word %r is not in the word map" % w)
+                w = word_map[w]
+            if isinstance(w, bool) or int(w) != w or not 0 <= int(w) < V:
+                raise ValueError("banned token id %r is outside [0, %d)" % (w, V))
+            if int(w) == int(word_map['<end>']):
+                raise ValueError("<end> cannot be banned (min_length delays it)")
+            ids.append(int(w))
+        return ids
+
+
+def _active(constraints):
+    """None for `constraints=None` and for a neutral object (today's path), the object otherwise"""
+    if constraints is None:
+        return None
+    if not isinstance(constraints, BeamConstraints):
+        raise TypeError("constraints must be an evaluate.BeamConstraints or None, got %s" % type(constraints).__name__)
+    return None if constraints.neutral() else constraints
+
+
+def _check_constraints(constraints, word_map, model):
+    """what every beam_search_* entry does with `constraints=` before anything else: the active object (or None), its banned
+    words resolved once against the model's vocabulary so that a bad one raises before any device work"""
+    cons = _active(constraints)
+    if cons is not None:
+        cons.banned_ids(word_map, model.vocab_size)
+    return cons
+
+
+def _fused_beam(models, NI, k, V, word_map, dev, max_steps, poll=4, return_scores=False, n_best=None, constraints=None):
+    import ctypes as C
     from . import _lib
     from ._lib import check, ptr, stream_of
     lib = _lib.load()
+    cons = _active(constraints)
+    banned_ids = cons.banned_ids(word_map, V) if cons is not None else []
     st = stream_of(dev)
     start, end = int(word_map['<start>']), int(word_map['<end>'])
     B, Lmax = NI * k, max_steps + 2
@@ -103,19 +168,30 @@ def _fused_beam(models, NI, k, V, word_map, dev, max_steps, poll=4, return_score
     best_score = torch.full((NI,), neg, device=dev)
     best_seq = torch.zeros(NI, Lmax, dtype=torch.long, device=dev)
     best_len = torch.zeros(NI, dtype=torch.int32, device=dev)
-    logits = [torch.empty(B, V, dtype=torch.float32, device=dev) for _ in models]
-    if n_best is not None:                               # every counted <end> pick appends (score, tokens, length), set_hip.h
+    # the constrained pick reads its rows as float4 when the leading dimension allows it (V = 9490 is no multiple of 4): padded
+    # as _sbs_search pads it; the unconstrained picks keep their layout
+    ld = V if cons is None else (V + 63) // 64 * 64
+    logits = [torch.empty(B, ld, dtype=torch.float32, device=dev) for _ in models]
+    if n_best is not None or cons is not None:          # every counted <end> pick appends (score, tokens, length), set_hip.h
         done_score = torch.full((NI, k), neg, device=dev)
         done_seq = torch.zeros(NI, k, Lmax, dtype=torch.long, device=dev)
         done_len = torch.zeros(NI, k, dtype=torch.int32, device=dev)
         n_done = torch.zeros(NI, dtype=torch.int32, device=dev)
+    if cons is not None:                                 # the constrained pick: its options and its candidate workspace
+        banned = torch.tensor(banned_ids, dtype=torch.long, device=dev) if banned_ids else None
+        copts = _lib.BeamConstraintsC(cons.no_repeat_ngram, cons.min_length, cons.length_penalty, len(banned_ids),
+                                      banned.data_ptr() if banned_ids else None)
+        pick_ws = torch.empty(max(int(lib.set_beam_pick_constrained_workspace_bytes(NI, k)), 16), dtype=torch.uint8, device=dev)
     step = 1
     while True:
         for m, lg in zip(models, logits):
             m.step(words, lg)
-        pick = (ptr(logits[0]), ptr(logits[1]) if len(models) > 1 else None, V, NI, k, V, end, step, Lmax, ptr(scores), ptr(k_left),
+        pick = (ptr(logits[0]), ptr(logits[1]) if len(models) > 1 else None, ld, NI, k, V, end, step, Lmax, ptr(scores), ptr(k_left),
                 ptr(seqs[0]), ptr(seqs[1]), ptr(best_score), ptr(best_seq), ptr(best_len), ptr(words), ptr(rows))
-        if n_best is None:
+        if cons is not None:
+            check(lib.set_beam_pick_constrained_f32(*pick, ptr(done_score), ptr(done_seq), ptr(done_len), ptr(n_done), C.byref(copts),
+                                                    ptr(pick_ws), pick_ws.numel(), st), "set_beam_pick_constrained_f32")
+        elif n_best is None:
             check(lib.set_beam_pick_f32(*pick, st), "set_beam_pick_f32")
         else:
             check(lib.set_beam_pick_nbest_f32(*pick, ptr(done_score), ptr(done_seq), ptr(done_len), ptr(n_done), st),
@@ -135,6 +211,9 @@ def _fused_beam(models, NI, k, V, word_map, dev, max_steps, poll=4, return_score
     for i in range(NI):
         if int(left_c[i]) > 0:                               # ran into the step limit (editnet.py:702-704,711)
             out.append(seqs_c[i, 0, :18].tolist())
+            out_scores.append(float("nan"))
+        elif int(len_c[i]) == 0:                             # constrained: ran out of candidates before anything completed
+            out.append([start])
             out_scores.append(float("nan"))
         else:
             out.append(best_c[i, :int(len_c[i])].tolist())
@@ -159,7 +238,7 @@ def _with_trace(result, batched, return_scores, decoder, X, prev, plen, word_map
 
 @torch.no_grad()
 def beam_search_editnet_batched(decoder, image_features, previous_caption, prev_caplen, word_map, beam_size=3,
-                                max_steps=50, return_scores=False, return_trace=False, n_best=None):
+                                max_steps=50, return_scores=False, return_trace=False, n_best=None, constraints=None):
     """image_features (NI,R,F), previous_caption (NI,T), prev_caplen (NI,1) -> list of NI token lists
     (with return_scores: also the list of their scores; NaN where the step limit was hit).  The attention LSTM sees the mean
     over all R regions; adaptive features (zero-padded regions, an image mean per image): beam_search_adaptive_batched.
@@ -171,39 +250,45 @@ def beam_search_editnet_batched(decoder, image_features, previous_caption, prev_
         seqs, nbest = beam_search_editnet_batched(dec, X, prev, plen, wm, 3, n_best=3)
         runner_up = nbest[i][1][0]                      # tokens of image i's second-best completed hypothesis
         tr = edit_trace(dec, X[i:i + 1], prev[i:i + 1], plen[i:i + 1], wm, [runner_up])
+    constraints=BeamConstraints(...) (all eight beam_search_* entries): n-gram blocking, banned words, a minimum length and
+    length-normalised ranking inside the pick; None or a neutral object: this search, unchanged.  Scores and the n-best order are
+    then the rank scores; the trace is that of the constrained tokens.
     return_trace: the result gains the EditTrace of the returned (primary) sequences as its last element."""
     n_best = _check_n_best(n_best, beam_size)
+    cons = _check_constraints(constraints, word_map, decoder)
     decoder.eval()
     X = image_features.float().contiguous()
     prev = previous_caption.long().contiguous()
     plen = prev_caplen.reshape(-1).long().contiguous()
     m = _FusedModel(decoder, (X, None, prev, plen), (X,), beam_size, max_steps)
     res = _fused_beam([m], X.shape[0], beam_size, decoder.vocab_size, word_map, X.device, max_steps,
-                      return_scores=return_scores, n_best=n_best)
+                      return_scores=return_scores, n_best=n_best, constraints=cons)
     return _with_trace(res, True, return_scores, decoder, X, prev, plen, word_map, n_best=n_best) if return_trace else res
 
 
 @torch.no_grad()
 def beam_search_dcnet_batched(dae, previous_caption, prev_caplen, word_map, beam_size=3, max_steps=50,
-                              return_scores=False, n_best=None):
-    """n_best: see beam_search_editnet_batched."""
+                              return_scores=False, n_best=None, constraints=None):
+    """n_best, constraints: see beam_search_editnet_batched."""
     n_best = _check_n_best(n_best, beam_size)
+    cons = _check_constraints(constraints, word_map, dae)
     dae.eval()
     prev = previous_caption.long().contiguous()
     plen = prev_caplen.reshape(-1).long().contiguous()
     m = _FusedModel(dae, (prev, plen), (), beam_size, max_steps)
     return _fused_beam([m], prev.shape[0], beam_size, dae.vocab_size, word_map, prev.device, max_steps,
-                       return_scores=return_scores, n_best=n_best)
+                       return_scores=return_scores, n_best=n_best, constraints=cons)
 
 
 @torch.no_grad()
 def beam_search_ensemble_batched(decoder, dae, image_features, previous_caption, prev_caplen, word_map, beam_size=3,
-                                 max_steps=50, return_scores=False, return_trace=False, n_best=None):
+                                 max_steps=50, return_scores=False, return_trace=False, n_best=None, constraints=None):
     """eval_full.py:88-218 for NI images at once: both models step on the same words, the epilogue averages
     their softmax probabilities.  Fixed features (image mean over all R regions); adaptive features: beam_search_adaptive*.
-    n_best: see beam_search_editnet_batched (the scores are those of the joint pick).
+    n_best, constraints: see beam_search_editnet_batched (the scores are those of the joint pick).
     return_trace: the result gains, as its last element, EditNet's view of the jointly chosen words (their EditTrace)."""
     n_best = _check_n_best(n_best, beam_size)
+    cons = _check_constraints(constraints, word_map, decoder)
     decoder.eval()
     dae.eval()
     X = image_features.float().contiguous()
@@ -212,7 +297,7 @@ def beam_search_ensemble_batched(decoder, dae, image_features, previous_caption,
     e = _FusedModel(decoder, (X, None, prev, plen), (X,), beam_size, max_steps)
     d = _FusedModel(dae, (prev, plen), (), beam_size, max_steps)
     res = _fused_beam([e, d], X.shape[0], beam_size, decoder.vocab_size, word_map, X.device, max_steps,
-                      return_scores=return_scores, n_best=n_best)
+                      return_scores=return_scores, n_best=n_best, constraints=cons)
     return _with_trace(res, True, return_scores, decoder, X, prev, plen, word_map, n_best=n_best) if return_trace else res
 
 
@@ -329,7 +414,7 @@ def _first(res):
 
 
 def beam_search_editnet(decoder, image_features, previous_caption, prev_caplen, word_map, beam_size=3, return_trace=False,
-                        n_best=None):
+                        n_best=None, constraints=None):
     """The reference's own calling convention, ONE image per call (editnet.py:601-613).  k <= 4 with the token table
     active: one persistent launch (csrc/decode_persistent_wide.hip, beam mode); otherwise the NI = 1 case of the batched
     search.  Adaptive features (an image mean per image, zero-padded regions): beam_search_adaptive.
@@ -337,12 +422,15 @@ def beam_search_editnet(decoder, image_features, previous_caption, prev_caplen, 
     beam_search_editnet_batched; the routing is the same, and an entry's tokens go to edit_trace as they are:
         tokens, score, nbest = beam_search_editnet(dec, X, prev, plen, wm, 3, n_best=3)
         tr = edit_trace(dec, X, prev, plen, wm, [nbest[1][0]])         # the runner-up's trace
+    constraints: see beam_search_editnet_batched; active constraints take the per-step search (its NI = 1 case) at every k.
     return_trace: (tokens, score[, n-best], EditTrace of the returned tokens)."""
     n_best = _check_n_best(n_best, beam_size)
-    one = _beam_search_editnet_persistent(decoder, image_features, previous_caption, prev_caplen, word_map, beam_size, n_best=n_best)
+    cons = _check_constraints(constraints, word_map, decoder)
+    one = None if cons is not None else _beam_search_editnet_persistent(decoder, image_features, previous_caption, prev_caplen,
+                                                                        word_map, beam_size, n_best=n_best)
     if one is None:
         one = _first(beam_search_editnet_batched(decoder, image_features, previous_caption, prev_caplen, word_map, beam_size,
-                                                 return_scores=True, n_best=n_best))
+                                                 return_scores=True, n_best=n_best, constraints=cons))
     if return_trace:
         return _with_trace(one, False, True, decoder, image_features, previous_caption, prev_caplen, word_map)
     return one
@@ -373,16 +461,19 @@ def _beam_search_dcnet_persistent(dae, previous_caption, prev_caplen, word_map, 
                             word_map, k, picks, prev.device, n_best)
 
 
-def beam_search_dcnet(dae, previous_caption, prev_caplen, word_map, beam_size=3, n_best=None):
+def beam_search_dcnet(dae, previous_caption, prev_caplen, word_map, beam_size=3, n_best=None, constraints=None):
     """The reference's own calling convention, ONE previous caption per call (dcnet.py:413-423).  k <= 4 with the token table
     active: one persistent launch (csrc/decode_persistent.hip, beam mode); otherwise the NI = 1 case of the batched search.
-    n_best=m: (tokens, score, [(tokens, score)] of up to m completed hypotheses, best first), see beam_search_editnet_batched."""
+    n_best=m: (tokens, score, [(tokens, score)] of up to m completed hypotheses, best first), see beam_search_editnet_batched.
+    constraints: see beam_search_editnet_batched; active constraints take the per-step search at every k."""
     n_best = _check_n_best(n_best, beam_size)
-    one = _beam_search_dcnet_persistent(dae, previous_caption, prev_caplen, word_map, beam_size, n_best=n_best)
+    cons = _check_constraints(constraints, word_map, dae)
+    one = None if cons is not None else _beam_search_dcnet_persistent(dae, previous_caption, prev_caplen, word_map, beam_size,
+                                                                      n_best=n_best)
     if one is not None:
         return one
     return _first(beam_search_dcnet_batched(dae, previous_caption, prev_caplen, word_map, beam_size, return_scores=True,
-                                            n_best=n_best))
+                                            n_best=n_best, constraints=cons))
 
 
 _ens_xbuf = {}                 # exchange regions of the ensemble's persistent launch, one per (bytes, device, stream)
@@ -433,17 +524,19 @@ def _beam_search_ensemble_persistent(decoder, dae, image_features, previous_capt
 
 
 def beam_search_ensemble(decoder, dae, image_features, previous_caption, prev_caplen, word_map, beam_size=3,
-                         return_trace=False, n_best=None):
+                         return_trace=False, n_best=None, constraints=None):
     """The reference's published protocol, ONE image per call (eval_full.py:88-237).  k <= 4 with both token tables active: one
     persistent launch (csrc/decode_persistent_ensemble.hip); otherwise the NI = 1 case of the batched search.
     n_best=m: (tokens, score, [(tokens, score)] of up to m completed hypotheses, best first), see beam_search_editnet_batched.
+    constraints: see beam_search_editnet_batched; active constraints take the per-step search at every k.
     return_trace: (tokens, score[, n-best], EditNet's EditTrace of the jointly chosen tokens)."""
     n_best = _check_n_best(n_best, beam_size)
-    one = _beam_search_ensemble_persistent(decoder, dae, image_features, previous_caption, prev_caplen, word_map, beam_size,
-                                           n_best=n_best)
+    cons = _check_constraints(constraints, word_map, decoder)
+    one = None if cons is not None else _beam_search_ensemble_persistent(decoder, dae, image_features, previous_caption, prev_caplen,
+                                                                         word_map, beam_size, n_best=n_best)
     if one is None:
         one = _first(beam_search_ensemble_batched(decoder, dae, image_features, previous_caption, prev_caplen, word_map, beam_size,
-                                                  return_scores=True, n_best=n_best))
+                                                  return_scores=True, n_best=n_best, constraints=cons))
     if return_trace:
         return _with_trace(one, False, True, decoder, image_features, previous_caption, prev_caplen, word_map)
     return one
@@ -468,35 +561,37 @@ def _adaptive_args(decoder, image_features, image_mean):
 
 @torch.no_grad()
 def beam_search_adaptive_batched(decoder, image_features, image_mean, previous_caption, prev_caplen, word_map, beam_size=3,
-                                 max_steps=50, return_scores=False, return_trace=False, n_best=None):
+                                 max_steps=50, return_scores=False, return_trace=False, n_best=None, constraints=None):
     """image_features (NI,R,F) zero-padded regions, image_mean (NI,F), previous_caption (NI,T), prev_caplen (NI,1) ->
     list of NI token lists (with return_scores: also their scores; NaN where the step limit was hit).  NI images at once
-    on the per-step fused kernels.  n_best: see beam_search_editnet_batched."""
+    on the per-step fused kernels.  n_best, constraints: see beam_search_editnet_batched."""
     n_best = _check_n_best(n_best, beam_size)
+    cons = _check_constraints(constraints, word_map, decoder)
     X, mean = _adaptive_args(decoder, image_features, image_mean)
     decoder.eval()
     prev = previous_caption.long().contiguous()
     plen = prev_caplen.reshape(-1).long().contiguous()
     m = _FusedModel(decoder, (X, mean, prev, plen), (X,), beam_size, max_steps)
     res = _fused_beam([m], X.shape[0], beam_size, decoder.vocab_size, word_map, X.device, max_steps,
-                      return_scores=return_scores, n_best=n_best)
+                      return_scores=return_scores, n_best=n_best, constraints=cons)
     return (_with_trace(res, True, return_scores, decoder, X, prev, plen, word_map, image_mean=mean, n_best=n_best)
             if return_trace else res)
 
 
 def beam_search_adaptive(decoder, image_features, image_mean, previous_caption, prev_caplen, word_map, beam_size=3,
-                         return_trace=False, n_best=None):
+                         return_trace=False, n_best=None, constraints=None):
     """The reference's adaptive evaluate(), ONE image per call (editnet_adaptive.py:620-735) -> (tokens, score).  k <= 4
     with the token table active: one persistent launch (beam mode over up to 128 masked regions, even R); otherwise the
     NI = 1 case of beam_search_adaptive_batched.  n_best=m: (tokens, score, [(tokens, score)] of up to m completed hypotheses,
-    best first), see beam_search_editnet_batched."""
+    best first), see beam_search_editnet_batched.  constraints: see there; active constraints take the per-step search at every k."""
     n_best = _check_n_best(n_best, beam_size)
+    cons = _check_constraints(constraints, word_map, decoder)
     X, mean = _adaptive_args(decoder, image_features, image_mean)
-    one = _beam_search_editnet_persistent(decoder, X, previous_caption, prev_caplen, word_map, beam_size, image_mean=mean,
-                                          n_best=n_best)
+    one = None if cons is not None else _beam_search_editnet_persistent(decoder, X, previous_caption, prev_caplen, word_map, beam_size,
+                                                                        image_mean=mean, n_best=n_best)
     if one is None:
         one = _first(beam_search_adaptive_batched(decoder, X, mean, previous_caption, prev_caplen, word_map, beam_size,
-                                                  return_scores=True, n_best=n_best))
+                                                  return_scores=True, n_best=n_best, constraints=cons))
     if return_trace:
         return _with_trace(one, False, True, decoder, X, previous_caption, prev_caplen, word_map, image_mean=mean)
     return one
