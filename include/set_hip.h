@@ -997,6 +997,35 @@ int set_beam_pick_constrained_f32(const float* logits, const float* logits2, int
                                   int32_t* rows, float* done_score, int64_t* done_seq, int32_t* done_len, int32_t* n_done,
                                   const SetBeamConstraints* c, void* ws, size_t ws_bytes, void* stream);
 
+/* Diverse (group) beam-search pick (Vijayakumar et al., "Diverse Beam Search"; csrc/beam_constrained.hip bd_merge_k): the step of
+ * set_beam_pick_constrained_f32 — same arguments up to n_done, same constraints c (non-NULL, a neutral struct allowed), same
+ * limits — with the k slots of an image in `groups` = G groups of g = k / G: group gi owns slots gi g .. gi g + g - 1 and is a
+ * beam search of its own over them.  g_left (NI, G) is the group's k_left (g at the start of a search, when only the first slot
+ * of every group is alive: score 0, the others -inf); k_left[img] is kept as the sum of the image's g_left.
+ * The groups of an image pick in order gi = 0 .. G - 1.  A candidate (j, v) of group gi — slot j of the group with a finite score,
+ * v not removed by c — has the value x = scores[j] + logp_j[v] and the KEY y = x - penalty n(v) (float32), n(v) = how many
+ * counted picks of groups 0 .. gi - 1 of this image at this step have the word v.  <end> is exempt: never penalised, an <end>
+ * pick is never counted.  The group's picks are its g best candidates by y descending, then flat index j V + v ascending (j the
+ * slot index within the image); the first g_left[gi] count.  The value carried forward, and ranked by x / cur_len^alpha when the
+ * pick completes a hypothesis, is x, NOT y: scores stay sums of the model's log-probabilities.  Within a group the bookkeeping
+ * is that of set_beam_pick_constrained_f32 (live picks first, the other slots die, parent and child in one group); best_* is the
+ * first maximum of r over all groups in group order, then pick rank; done_* is appended in that order and done_group (NI, k)
+ * records each completion's group (at most k hypotheses complete per image).
+ * A group with g_left > 0 and no surviving finite candidate ends: g_left = 0, its scores = -inf, words = 0, rows = identity, its
+ * sequences not written.  A group that had ended before the step gets rows = identity and words = 0 and nothing else; a finished
+ * image (k_left <= 0) is left untouched as by set_beam_pick_constrained_f32.
+ * groups == 1 (g_left = k_left): the outputs of set_beam_pick_constrained_f32 byte for byte, done_group = 0.
+ * ws: set_beam_pick_diverse_workspace_bytes(NI, k) bytes (0 for NI <= 0 or k outside 1 .. 8), 16-byte aligned.
+ * All before any HIP call — SET_ERR_ARG: what set_beam_pick_constrained_f32 answers with it, a NULL done_group or g_left,
+ * groups < 1, k % groups != 0, a penalty that is negative or not finite; SET_ERR_UNSUPPORTED: as set_beam_pick_constrained_f32. */
+size_t set_beam_pick_diverse_workspace_bytes(int NI, int k);
+int set_beam_pick_diverse_f32(const float* logits, const float* logits2, int64_t ld, int NI, int k, int V, int64_t end_idx,
+                              int cur_len, int Lmax, float* scores, int32_t* k_left, const int64_t* seqs_in,
+                              int64_t* seqs_out, float* best_score, int64_t* best_seq, int32_t* best_len, int64_t* words,
+                              int32_t* rows, float* done_score, int64_t* done_seq, int32_t* done_len, int32_t* n_done,
+                              int32_t* done_group, int32_t* g_left, int groups, float penalty,
+                              const SetBeamConstraints* c, void* ws, size_t ws_bytes, void* stream);
+
 /* Stochastic beam search pick (Kool, van Hoof, Welling, ICML 2019; csrc/sbs.hip): one timestep t (0-based, t <= 254) of a
  * search that leaves, per image, k <= 8 DISTINCT sequences which are an exact sample WITHOUT replacement from the model's
  * sequence distribution, in draw order.  NI images x k slots; slot j of image i is logits row r = i k + j.

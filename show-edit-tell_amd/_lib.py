@@ -462,6 +462,9 @@ PROTOTYPES = {
     "set_beam_pick_constrained_workspace_bytes": (_Z, [_I, _I]),
     "set_beam_pick_constrained_f32": (_I, [_P, _P, _L, _I, _I, _I, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                            C.POINTER(BeamConstraintsC), _P, _Z, _P]),
+    "set_beam_pick_diverse_workspace_bytes": (_Z, [_I, _I]),
+    "set_beam_pick_diverse_f32": (_I, [_P, _P, _L, _I, _I, _I, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                       _P, _P, _I, C.c_float, C.POINTER(BeamConstraintsC), _P, _Z, _P]),
     "set_sbs_workspace_bytes": (_Z, [_I, _I]),
     "set_sbs_pick_f32": (_I, [C.POINTER(SbsArgs), C.POINTER(SampleOpts), _P]),
     "set_sbs_pick_ensemble_f32": (_I, [C.POINTER(SbsArgs), _P, C.POINTER(SampleOpts), _P]),

@@ -860,6 +860,171 @@ def sample_captions_distinct_ensemble(decoder, dae, image_features, previous_cap
     return _sbs_answer(out, steps, n, return_threshold, _return_steps)
 
 
+# ------------------------------------------------------------------------------------------------
+# Diverse (group) beam search (Vijayakumar et al., "Diverse Beam Search"): G alternative captions that differ from each other.
+# The beam's k slots are G groups of k / G; every group is a beam search of its own whose picks are penalised, inside the pick
+# (set_beam_pick_diverse_f32), for the words the earlier groups picked at the same step.
+# ------------------------------------------------------------------------------------------------
+def _check_diverse(beam_size, groups, diversity_penalty, max_steps):
+    import math
+    for name, v in (("beam_size", beam_size), ("groups", groups), ("max_steps", max_steps)):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError("%s must be an integer, got %r" % (name, v))
+    k, G, max_steps = int(beam_size), int(groups), int(max_steps)
+    if not 1 <= k <= 8:
+        raise ValueError("beam_size must lie in 1 .. 8, got %r" % (beam_size,))
+    if G < 1 or k % G != 0:
+        raise ValueError("groups must divide beam_size = %d, got %r" % (k, groups))
+    pen = float(diversity_penalty)
+    if not math.isfinite(pen) or pen < 0.0:
+        raise ValueError("diversity_penalty must be finite and >= 0, got %r" % (diversity_penalty,))
+    if not 1 <= max_steps <= 254:
+        raise ValueError("max_steps must lie in 1 .. 254, got %r" % (max_steps,))
+    return k, G, pen, max_steps
+
+
+def _diverse_search(models, NI, k, G, penalty, V, word_map, dev, max_steps, cons, return_all, poll=4):
+    """_fused_beam's loop on set_beam_pick_diverse_f32: per timestep every model steps on the same words into its own padded
+    logits, the pick, one set_beam_gather_f32 per model with the pick's rows; the host polls k_left every `poll` steps."""
+    import ctypes as C
+    from . import _lib
+    from ._lib import check, ptr, stream_of
+    lib = _lib.load()
+    banned_ids = cons.banned_ids(word_map, V) if cons is not None else []
+    st = stream_of(dev)
+    start, end = int(word_map['<start>']), int(word_map['<end>'])
+    B, Lmax, g = NI * k, max_steps + 2, k // G
+    neg = float("-inf")
+    scores = torch.full((NI, k), neg, device=dev)
+    scores[:, ::g] = 0.0                                  # step 1: only the first slot of every group counts
+    k_left = torch.full((NI,), k, dtype=torch.int32, device=dev)
+    g_left = torch.full((NI, G), g, dtype=torch.int32, device=dev)
+    words = torch.full((B,), start, dtype=torch.long, device=dev)
+    rows = torch.empty(B, dtype=torch.int32, device=dev)
+    seqs = [torch.full((NI, k, Lmax), start, dtype=torch.long, device=dev) for _ in range(2)]
+    best_score = torch.full((NI,), neg, device=dev)
+    best_seq = torch.zeros(NI, Lmax, dtype=torch.long, device=dev)
+    best_len = torch.zeros(NI, dtype=torch.int32, device=dev)
+    ld = (V + 63) // 64 * 64                              # float4 row reads, as _fused_beam pads for the constrained pick
+    logits = [torch.empty(B, ld, dtype=torch.float32, device=dev) for _ in models]
+    done_score = torch.full((NI, k), neg, device=dev)
+    done_seq = torch.zeros(NI, k, Lmax, dtype=torch.long, device=dev)
+    done_len = torch.zeros(NI, k, dtype=torch.int32, device=dev)
+    done_group = torch.zeros(NI, k, dtype=torch.int32, device=dev)
+    n_done = torch.zeros(NI, dtype=torch.int32, device=dev)
+    banned = torch.tensor(banned_ids, dtype=torch.long, device=dev) if banned_ids else None
+    if cons is not None:
+        copts = _lib.BeamConstraintsC(cons.no_repeat_ngram, cons.min_length, cons.length_penalty, len(banned_ids),
+                                      banned.data_ptr() if banned_ids else None)
+    else:
+        copts = _lib.BeamConstraintsC(0, 0, 0.0, 0, None)
+    pick_ws = torch.empty(max(int(lib.set_beam_pick_diverse_workspace_bytes(NI, k)), 16), dtype=torch.uint8, device=dev)
+    step = 1
+    while True:
+        for m, lg in zip(models, logits):
+            m.step(words, lg)
+        check(lib.set_beam_pick_diverse_f32(
+            ptr(logits[0]), ptr(logits[1]) if len(models) > 1 else None, ld, NI, k, V, end, step, Lmax, ptr(scores), ptr(k_left),
+            ptr(seqs[0]), ptr(seqs[1]), ptr(best_score), ptr(best_seq), ptr(best_len), ptr(words), ptr(rows), ptr(done_score),
+            ptr(done_seq), ptr(done_len), ptr(n_done), ptr(done_group), ptr(g_left), G, penalty, C.byref(copts), ptr(pick_ws),
+            pick_ws.numel(), st), "set_beam_pick_diverse_f32")
+        seqs.reverse()
+        for m in models:
+            s0, s1, s2, s3 = m.states
+            check(lib.set_beam_gather_f32(ptr(s0), ptr(s1), ptr(s2), ptr(s3), ptr(rows), NI, k, m.D, st), "set_beam_gather_f32")
+        if step > max_steps:
+            break
+        if step % poll == 0 and int(k_left.max()) == 0:      # the only host synchronisation of the search
+            break
+        step += 1
+    seqs_c, left_c = seqs[0].cpu(), g_left.cpu()
+    ds_c, dq_c, dl_c, dg_c, nd_c = done_score.cpu(), done_seq.cpu(), done_len.cpu(), done_group.cpu(), n_done.cpu()
+    out, every = [], []
+    for i in range(NI):
+        done = [(dq_c[i, j, :int(dl_c[i, j])].tolist(), float(ds_c[i, j]), int(dg_c[i, j])) for j in range(int(nd_c[i]))]
+        res = []
+        for gi in range(G):
+            mine = [e for e in done if e[2] == gi]
+            if mine:
+                best = max(range(len(mine)), key=lambda q: (mine[q][1], -q))      # first maximum
+                res.append((mine[best][0], mine[best][1]))
+            elif int(left_c[i, gi]) > 0:                  # ran into the step limit with nothing completed
+                res.append((seqs_c[i, gi * g, :step + 1].tolist(), float("nan")))
+            else:                                         # ran out of candidates with nothing completed
+                res.append(([start], float("nan")))
+        out.append(res)
+        every.append(sorted(done, key=lambda e: -e[1]))
+    return (out, every) if return_all else out
+
+
+@torch.no_grad()
+def beam_search_diverse(model, *inputs_and_word_map, beam_size=6, groups=3, diversity_penalty=0.5, max_steps=50, constraints=None,
+                        return_all=False):
+    """`groups` alternative captions per image that differ from each other, by diverse (group) beam search (Vijayakumar et al.,
+    "Diverse Beam Search"; include/set_hip.h set_beam_pick_diverse_f32):
+        out = beam_search_diverse(decoder, image_features, previous_caption, prev_caplen, word_map, beam_size=6, groups=3)
+        out = beam_search_diverse(dae, previous_caption, prev_caplen, word_map, beam_size=8, groups=4, diversity_penalty=1.0)
+    EditNet (editnet.DecoderC / editnet_rl.DecoderC, fixed features) takes image_features (NI,R,F), previous_caption (NI,T),
+    prev_caplen (NI,1); DCNet (DAE) the caption pair only.  The beam's beam_size slots (1 .. 8) are `groups` groups of
+    beam_size / groups slots; every group is this project's beam search over its own slots, and at every step the groups pick one
+    after the other, each by log-probability sum minus diversity_penalty x (how many picks of the earlier groups at this step took
+    the word).  <end> is never penalised.  The penalty only steers the picks: the returned scores are sums of the model's
+    log-probabilities (rank scores under constraints.length_penalty), comparable between groups and with every beam_search_*.
+    diversity_penalty = 0: every group runs the same search of beam_size / groups slots; groups = 1: the constrained search.
+    constraints: an evaluate.BeamConstraints (n-gram blocking, banned words, minimum length, length penalty) applied to every
+    group, or None.
+    Returns, per image, a list of `groups` (tokens, score) pairs in group order: the group's best completed hypothesis (tokens
+    with <start> and <end>, first maximum of the score); (its first slot's tokens so far, nan) for a group that hit the step
+    limit with nothing completed; ([<start>], nan) for one that ran out of candidates with nothing completed.
+    return_all=True: returns (that, every) with every[i] all completed hypotheses of image i as (tokens, score, group), score
+    descending, equal scores in completion order.
+    ValueError before any device work: beam_size outside 1 .. 8, groups not dividing it, a penalty that is negative or not
+    finite, a bad banned word, an adaptive-features model or a model pair (the ensemble: beam_search_diverse_ensemble)."""
+    *inputs, word_map = inputs_and_word_map
+    k, G, pen, max_steps = _check_diverse(beam_size, groups, diversity_penalty, max_steps)
+    if isinstance(model, (tuple, list)) or getattr(model, "_adaptive", 0) or getattr(model, "_ABI", None) not in ("editnet", "dcnet"):
+        raise ValueError("beam_search_diverse supports EditNet's DecoderC with fixed features and DCNet's DAE; adaptive features "
+                         "are not covered and the EditNet + DCNet ensemble has its own entry")
+    if len(inputs) != (3 if model._ABI == "editnet" else 2):
+        raise ValueError("beam_search_diverse(model, [image_features,] previous_caption, prev_caplen, word_map, ...): "
+                         "image_features for EditNet, none for DCNet")
+    cons = _check_constraints(constraints, word_map, model)
+    model.eval()
+    prev = inputs[-2].long().contiguous()
+    plen = inputs[-1].reshape(-1).long().contiguous()
+    if len(inputs) == 3:
+        X = inputs[0].float().contiguous()
+        m = _FusedModel(model, (X, None, prev, plen), (X,), k, max_steps)
+    else:
+        m = _FusedModel(model, (prev, plen), (), k, max_steps)
+    return _diverse_search([m], prev.shape[0], k, G, pen, model.vocab_size, word_map, prev.device, max_steps, cons, return_all)
+
+
+@torch.no_grad()
+def beam_search_diverse_ensemble(decoder, dae, image_features, previous_caption, prev_caplen, word_map, beam_size=6, groups=3,
+                                 diversity_penalty=0.5, max_steps=50, constraints=None, return_all=False):
+    """beam_search_diverse for the EditNet + DCNet ENSEMBLE (beam_search_ensemble*): both models step on the same words, a
+    candidate's value is the running sum plus log((softmax_e + softmax_d) / 2), both states are re-indexed by the pick's rows.
+    Keywords, result and errors: beam_search_diverse; also ValueError for an adaptive-features decoder, models that are not an
+    EditNet DecoderC and a DCNet DAE, and vocabularies of different size."""
+    k, G, pen, max_steps = _check_diverse(beam_size, groups, diversity_penalty, max_steps)
+    if getattr(decoder, "_adaptive", 0) or getattr(decoder, "_ABI", None) != "editnet" or getattr(dae, "_ABI", None) != "dcnet":
+        raise ValueError("beam_search_diverse_ensemble takes an EditNet DecoderC with fixed features and a DCNet DAE; adaptive "
+                         "features are not covered")
+    if decoder.vocab_size != dae.vocab_size:
+        raise ValueError("beam_search_diverse_ensemble: the models' vocabularies differ (%d and %d words); the ensemble averages "
+                         "their word distributions" % (decoder.vocab_size, dae.vocab_size))
+    cons = _check_constraints(constraints, word_map, decoder)
+    decoder.eval()
+    dae.eval()
+    X = image_features.float().contiguous()
+    prev = previous_caption.long().contiguous()
+    plen = prev_caplen.reshape(-1).long().contiguous()
+    e = _FusedModel(decoder, (X, None, prev, plen), (X,), k, max_steps)
+    d = _FusedModel(dae, (prev, plen), (), k, max_steps)
+    return _diverse_search([e, d], X.shape[0], k, G, pen, decoder.vocab_size, word_map, X.device, max_steps, cons, return_all)
+
+
 def sbs_unconditioned_threshold(kappa, e=None):
     """The threshold of return_threshold with the conditioning on "the largest perturbed score of the image is 0" taken out:
         kappa' = -log(exp(-kappa) + E - 1) = -log(expm1(-kappa) + E),   E ~ Exp(1), one draw per image
