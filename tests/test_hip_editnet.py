@@ -41,7 +41,9 @@ def test_xe_vs_golden(name):
 @pytest.mark.parametrize("name", ["editnet_small", "editnet_full_b4"])
 def test_step_intermediates_vs_oracle(name):
     """Drive begin + step through the C ABI one timestep at a time and compare every intermediate
-    with the numpy oracle (same tokens fed to both)."""
+    with the numpy oracle (same tokens fed to both).  This is the chained check at B = 6 / 4; every stage on its own, against
+    float64, at the row counts and dimensions where the step changes route (with and without the token table, bt < B,
+    sliced and masked attention) is tests/test_hip_step_stages.py."""
     import ctypes as C
     from show_edit_tell_amd import _lib
     d, xe, rl = editnet_modules(name)
