@@ -1252,6 +1252,56 @@ int set_ciderd_score(void* scorer, const int64_t* hyp_tokens, const int64_t* hyp
                      const int32_t* set_of_hyp, const int64_t* ref_tokens, const int64_t* ref_off,
                      const int64_t* ref_set_off, int n_sets, double* scores);
 
+/* ------------------------------------------------------------------------------------------
+ * CIDEr-D on the DEVICE (csrc/ciderd_device.hip): the integer reward path of ciderd.py:211-250 / ciderd_host.hip:77-156 with
+ * sentences, reference vectors and scores in device memory on `stream` and no host read, and the same kernel with candidates
+ * as each other's references (evaluate.consensus_rerank).  Sentences are rows of int64 VOCABULARY ids (not interned ids), at
+ * most 64 per sentence; an n-gram is packed like make_key(.., uint64_t*) of ciderd_host.hip:57-61 (id + 1 in 16-bit fields, 0 =
+ * no gram), so every id must lie in [0, 65534).  All arithmetic is double; sums over the lanes of a wave are one fixed
+ * butterfly, so a row's result does not depend on the launch it is part of.  No atomics; only the declared outputs are written.
+ *
+ * key: the packing, on the host (ciderd_host.hip:57-61): *key_out = sum (tokens[j] + 1) << 16 j, j < k.  SET_ERR_ARG: NULL, k
+ *   outside 1 .. 4; SET_ERR_UNSUPPORTED: an id outside [0, 65534).
+ * create (ciderd_host.hip:171-189, ciderd.py:70-97): HOST arrays in the format of set_ciderd_create, the tokens being
+ *   vocabulary ids; builds a device table packed key -> document count (16-byte {key, count} slots, open addressing with linear
+ *   probing, capacity = the power of two >= max(2, 2 n_entries)), copies it on `stream` and waits for the copy.  The handle
+ *   comes back in *handle_out (NULL on failure).  SET_ERR_ARG: NULL handle_out / arrays, n outside 1 .. 4, ref_len or sigma not
+ *   positive, n_entries < 0; SET_ERR_UNSUPPORTED: an id outside [0, 65534) — both before any HIP call.  Entries with a length
+ *   outside 1 .. 4 are skipped; of a repeated gram the last count stands.  destroy frees the table (NULL: nothing).
+ * lookup: df_out[i] = document count of the packed key keys[i] (device arrays of n), 0.0 for an absent key or key 0.
+ * vec_bytes / vectorise (ciderd_host.hip:77-99): sentence i = tokens[i ld .. i ld + L) (device int64, ld >= L), its length
+ *   lens[i] clamped to [0, L] (device int32), or with lens == NULL the decoder's rule of ciderd.py:222-224: cut after the first 0,
+ *   the 0 itself stays, a row without 0 is taken whole.  One wave per sentence writes its record into vecs (vec_bytes(n_sent, L)
+ *   bytes, 8 + 8 L words of 8 bytes per sentence): the norms of the orders 1 .. 4, the number of bigrams, the length, a flag "an
+ *   id was outside [0, 65534)", then per order the L keys of the DISTINCT grams by first position (0 elsewhere) and their weights
+ *   tf (log ref_len - log max(1, df)).  vec_bytes is 0 for n_sent < 0 or L outside 1 .. 64.  SET_ERR_ARG: NULL handle / tokens /
+ *   vecs, n_sent < 0, L < 1, ld < L; SET_ERR_UNSUPPORTED: L > 64 — before any HIP call.
+ * score (ciderd_host.hip:101-156): hypothesis i (rows of hyp_tokens as in vectorise, L and hyp_lens likewise) against the
+ *   references of set set_of_hyp[i] (device int32) = records [ref_set_off[s], ref_set_off[s + 1]) (device int64, n_sets + 1) of
+ *   ref_vecs, which vectorise wrote with L = ref_L for n_refs sentences.  One wave per hypothesis:
+ *     scores[i] = 10 / (n max(1, |set|)) sum_r sum_k  [sum_g min(g_h, g_r) g_r / (|g_h| |g_r|)]_k exp(-(l_h - l_r)^2 / 2 sigma^2)
+ *   (the division only where both norms are non-zero, as on the host), and with pair_scores != NULL also
+ *   pair_scores[i pair_ld + r] = the score against reference r of the set alone, r < |set|; nothing else is written.  max_set is
+ *   the caller's bound on |set|.  What the host cannot check is answered by the kernel with NaN in scores[i] and nothing else
+ *   touched: set_of_hyp[i] outside [0, n_sets), offsets outside [0, n_refs] or decreasing, a set larger than max_set.  An id
+ *   outside [0, 65534) in the hypothesis or one of its references gives NaN in scores[i] (and in its pair_scores).
+ *   SET_ERR_ARG: NULL handle / hyp_tokens / set_of_hyp / ref_set_off / scores (ref_vecs with n_refs > 0), a negative count, L or
+ *   ref_L < 1, hyp_ld < L, pair_scores with pair_ld < max_set; SET_ERR_UNSUPPORTED: L or ref_L > 64 — before any HIP call and
+ *   before the handle is read.
+ * ------------------------------------------------------------------------------------------ */
+int set_ciderd_device_key(const int64_t* tokens, int k, uint64_t* key_out);
+int set_ciderd_device_create(const int64_t* tokens, const int32_t* lens, const double* df, int64_t n_entries, double ref_len,
+                             int n, double sigma, void* stream, void** handle_out);
+void set_ciderd_device_destroy(void* handle);
+int set_ciderd_device_lookup(void* handle, const uint64_t* keys, int64_t n, double* df_out, void* stream);
+size_t set_ciderd_device_vec_bytes(int n_sent, int L);
+int set_ciderd_device_vectorise(void* handle, const int64_t* tokens, int64_t ld, const int32_t* lens, int n_sent, int L,
+                                void* vecs, void* stream);
+int set_ciderd_device_score(void* handle, const int64_t* hyp_tokens, int64_t hyp_ld, const int32_t* hyp_lens, int n_hyp, int L,
+                            const int32_t* set_of_hyp, const void* ref_vecs, int ref_L, int64_t n_refs,
+                            const int64_t* ref_set_off, int n_sets, int max_set, double* scores, double* pair_scores,
+                            int64_t pair_ld, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

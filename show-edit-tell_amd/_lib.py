@@ -486,6 +486,13 @@ PROTOTYPES = {
     "set_ciderd_create": (_P, [_P, _P, _P, _L, C.c_double, _I, C.c_double]),
     "set_ciderd_destroy": (None, [_P]),
     "set_ciderd_score": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P]),
+    "set_ciderd_device_key": (_I, [_P, _I, _P]),
+    "set_ciderd_device_create": (_I, [_P, _P, _P, _L, C.c_double, _I, C.c_double, _P, C.POINTER(_P)]),
+    "set_ciderd_device_destroy": (None, [_P]),
+    "set_ciderd_device_lookup": (_I, [_P, _P, _L, _P, _P]),
+    "set_ciderd_device_vec_bytes": (_Z, [_I, _I]),
+    "set_ciderd_device_vectorise": (_I, [_P, _P, _L, _P, _I, _I, _P, _P]),
+    "set_ciderd_device_score": (_I, [_P, _P, _L, _P, _I, _I, _P, _P, _I, _L, _P, _I, _I, _P, _P, _L, _P]),
     "set_caption_encoder_workspace_bytes": (_Z, [_I, _I, _I]),
     "set_caption_encoder_f32": (_I, [C.POINTER(EditNetWeights), _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _Z, _P]),
 }

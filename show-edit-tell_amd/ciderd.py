@@ -325,3 +325,256 @@ def self_critical_reward(scorer, sampled, greedy, ground_truth, cider_weight=1.0
     _, s = scorer.compute_score(gts, res)
     diff = cider_weight * (s[:B] - s[B:])
     return np.repeat(diff[:, None], sampled.shape[1], 1).astype(np.float32)
+
+
+# ---- the device route (csrc/ciderd_device.hip, include/set_hip.h set_ciderd_device_*) ---------------------------------
+# The integer reward path above without the host trip: sentences, reference vectors and scores stay in device memory.
+# Limits: vocabulary ids below 65534 (four ids + 1 in one 64-bit key, make_key of ciderd_host.hip:57-61), sentences of at
+# most 64 ids (one position per lane), and only the df grams whose tokens are all decimal strings (the reward plumbing
+# stringifies ids: any other gram can never match an id sequence).  Opt-in: nothing above calls it.
+DEVICE_PACK_LIMIT = 65534
+DEVICE_MAX_LEN = 64
+
+
+def pack_key(ids):
+    """packed 64-bit key of an n-gram of 1..4 vocabulary ids: id + 1 in 16-bit fields (make_key, ciderd_host.hip:57-61)"""
+    ids = [int(w) for w in ids]
+    if not 1 <= len(ids) <= 4:
+        raise ValueError("an n-gram has 1..4 ids, got %d" % len(ids))
+    key = 0
+    for j, w in enumerate(ids):
+        if not 0 <= w < DEVICE_PACK_LIMIT:
+            raise ValueError("id %d outside [0, %d)" % (w, DEVICE_PACK_LIMIT))
+        key |= (w + 1) << (16 * j)
+    return key
+
+
+def _gram_ids(g):
+    """the ids of a df gram whose tokens are all decimal strings (or integers), else None"""
+    out = []
+    for w in g:
+        if isinstance(w, (int, np.integer)):
+            out.append(int(w))
+        elif isinstance(w, str) and w.isascii() and w.isdigit():
+            out.append(int(w))
+        else:
+            return None
+    return out
+
+
+def device_table_input(df):
+    """The table input of set_ciderd_device_create from a df dict: (tokens (E, 4) int64 vocabulary ids, lens (E,) int32,
+    counts (E,) float64, E).  Grams of other lengths than 1..4 and grams with a non-numeric token are dropped (they can
+    never match a sequence of ids); arrays have at least one row so that their pointers are valid."""
+    rows = []
+    for g, c in df.items():
+        if not 1 <= len(g) <= 4:
+            continue
+        ids = _gram_ids(g)
+        if ids is not None:
+            rows.append((ids, float(c)))
+    E = len(rows)
+    toks = np.zeros((max(1, E), 4), dtype=np.int64)
+    lens = np.zeros(max(1, E), dtype=np.int32)
+    cnt = np.zeros(max(1, E), dtype=np.float64)
+    for i, (ids, c) in enumerate(rows):
+        lens[i] = len(ids)
+        cnt[i] = c
+        toks[i, :len(ids)] = ids
+    return toks, lens, cnt, E
+
+
+def _cut_after_zero(c):
+    c = [int(w) for w in c]
+    return c[:c.index(0) + 1] if 0 in c else c
+
+
+class PreparedRefs:
+    """Reference sets vectorised on the device (DeviceCiderD.prepare_refs): the records, their row length, the set
+    offsets (device int64, n_sets + 1) and the host-side counts the score call validates with."""
+    def __init__(self, vecs, L, n_refs, set_off, n_sets, max_set):
+        self.vecs, self.L, self.n_refs, self.set_off, self.n_sets, self.max_set = vecs, L, n_refs, set_off, n_sets, max_set
+
+
+class DeviceCiderD:
+    """Owner of the device df table of one CiderD on one device (CiderD.device(dev)); every call is enqueued on the
+    current stream of that device and reads nothing back."""
+
+    def __init__(self, scorer, dev):
+        import ctypes as C
+        import torch
+        from . import _lib
+        self.dev = torch.device(dev)
+        if self.dev.type != "cuda":
+            raise _lib.SetError("the device CIDEr-D scorer needs a GPU device, got %s" % (self.dev,))
+        if self.dev.index is None:
+            self.dev = torch.device("cuda", torch.cuda.current_device())
+        lib = _lib.load()
+        toks, lens, cnt, E = device_table_input(scorer.df)
+        h = C.c_void_p()
+        with torch.cuda.device(self.dev):
+            rc = lib.set_ciderd_device_create(toks.ctypes.data, lens.ctypes.data, cnt.ctypes.data, E, float(scorer.ref_len),
+                                              int(scorer.n), float(scorer.sigma), _lib.stream_of(self.dev), C.byref(h))
+        _lib.check(rc, "set_ciderd_device_create")
+        self._lib, self._h, self.n, self.n_entries = lib, h, int(scorer.n), E
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            try:
+                self._lib.set_ciderd_device_destroy(h)
+            except Exception:
+                pass
+
+    def _tokens(self, t):
+        import torch
+        t = torch.as_tensor(t)
+        if t.dim() != 2:
+            raise ValueError("sentences are rows of a 2-D id tensor, got shape %s" % (tuple(t.shape),))
+        t = t.to(self.dev, torch.int64)
+        if t.shape[1] == 0:
+            t = t.new_zeros(t.shape[0], 1)
+        return t if t.stride(1) == 1 and t.stride(0) >= t.shape[1] else t.contiguous()
+
+    def _i32(self, x, n, what):
+        import torch
+        if x is None:
+            return None
+        x = torch.as_tensor(x).reshape(-1).to(self.dev, torch.int32).contiguous()
+        if x.numel() != n:
+            raise ValueError("%s has %d entries for %d sentences" % (what, x.numel(), n))
+        return x
+
+    def lookup(self, keys):
+        """document count of packed keys (pack_key): a device int64 tensor holding the keys' bits, or a list of ints;
+        returns a float64 device tensor, 0.0 for a key the table does not hold"""
+        import torch
+        from . import _lib
+        if not torch.is_tensor(keys):
+            keys = torch.from_numpy(np.asarray([int(k) for k in keys], dtype=np.uint64).view(np.int64))
+        keys = keys.reshape(-1).to(self.dev, torch.int64).contiguous()
+        out = torch.empty(keys.numel(), dtype=torch.float64, device=self.dev)
+        with torch.cuda.device(self.dev):
+            rc = self._lib.set_ciderd_device_lookup(self._h, keys.data_ptr(), keys.numel(), out.data_ptr(), _lib.stream_of(self.dev))
+        _lib.check(rc, "set_ciderd_device_lookup")
+        return out
+
+    def vectorise(self, tokens, lens=None):
+        """(S, L) ids [+ (S,) lengths; None: cut after the first 0] -> (record buffer, L): a caller-owned workspace"""
+        import torch
+        from . import _lib
+        t = self._tokens(tokens)
+        S, L = t.shape
+        ln = self._i32(lens, S, "lens")
+        if L > DEVICE_MAX_LEN:
+            raise _lib.SetError("the device CIDEr-D scorer takes sentences of at most %d ids, got rows of %d" % (DEVICE_MAX_LEN, L))
+        vecs = torch.empty(S * (8 + 8 * L), dtype=torch.int64, device=self.dev)
+        with torch.cuda.device(self.dev):
+            rc = self._lib.set_ciderd_device_vectorise(self._h, t.data_ptr(), t.stride(0), None if ln is None else ln.data_ptr(),
+                                                       S, L, vecs.data_ptr(), _lib.stream_of(self.dev))
+        _lib.check(rc, "set_ciderd_device_vectorise")
+        return vecs, L
+
+    def prepare_refs(self, ref_sets):
+        """Reference sets as ground_truth_lists returns them (per image a list of id lists) -> PreparedRefs: one upload and
+        one vectorise launch, independent of the rollout (issue it first and it runs underneath).  References are cut after
+        their first 0 as score_token_ids does (ciderd.py:226-231); one longer than 64 ids is refused."""
+        import torch
+        flat = [_cut_after_zero(c) for refs in ref_sets for c in refs]
+        L = max([1] + [len(c) for c in flat])
+        if L > DEVICE_MAX_LEN:
+            raise ValueError("a reference of %d ids: the device CIDEr-D scorer takes at most %d" % (L, DEVICE_MAX_LEN))
+        R = len(flat)
+        tok = np.zeros((max(1, R), L), dtype=np.int64)
+        ln = np.zeros(max(1, R), dtype=np.int32)
+        for i, c in enumerate(flat):
+            tok[i, :len(c)] = c
+            ln[i] = len(c)
+        off = np.zeros(len(ref_sets) + 1, dtype=np.int64)
+        np.cumsum([len(r) for r in ref_sets], out=off[1:])
+        vecs, _ = self.vectorise(torch.from_numpy(tok[:R]) if R else torch.zeros(0, L, dtype=torch.int64), ln[:R])
+        return PreparedRefs(vecs, L, R, torch.from_numpy(off).to(self.dev), len(ref_sets),
+                            max([0] + [len(r) for r in ref_sets]))
+
+    def score_token_ids(self, hyps, hyp_set, refs, return_pairs=False, hyp_lens=None):
+        """Device twin of CiderD.score_token_ids: `hyps` (N, L) ids (0 = <end>, cut after the first 0; with hyp_lens the
+        given lengths instead), `hyp_set` (N,) index of each caption's reference set, `refs` a PreparedRefs (or reference
+        sets, prepared here).  Returns the (N,) float64 device tensor of scores; return_pairs=True: also (N, max set size)
+        with the score against every single reference of the set (columns beyond a smaller set stay 0)."""
+        import torch
+        from . import _lib
+        if not isinstance(refs, PreparedRefs):
+            refs = self.prepare_refs(refs)
+        t = self._tokens(hyps)
+        N, L = t.shape
+        if L > DEVICE_MAX_LEN:
+            raise _lib.SetError("the device CIDEr-D scorer takes sentences of at most %d ids, got rows of %d" % (DEVICE_MAX_LEN, L))
+        so = self._i32(hyp_set, N, "hyp_set")
+        ln = self._i32(hyp_lens, N, "hyp_lens")
+        scores = torch.empty(N, dtype=torch.float64, device=self.dev)
+        pair_ld = max(1, refs.max_set)
+        pairs = torch.zeros(N, pair_ld, dtype=torch.float64, device=self.dev) if return_pairs else None
+        with torch.cuda.device(self.dev):
+            rc = self._lib.set_ciderd_device_score(
+                self._h, t.data_ptr(), t.stride(0), None if ln is None else ln.data_ptr(), N, L, so.data_ptr(),
+                refs.vecs.data_ptr(), refs.L, refs.n_refs, refs.set_off.data_ptr(), refs.n_sets, refs.max_set, scores.data_ptr(),
+                None if pairs is None else pairs.data_ptr(), pair_ld, _lib.stream_of(self.dev))
+        _lib.check(rc, "set_ciderd_device_score")
+        return (scores, pairs) if return_pairs else scores
+
+    def pair_scores(self, candidates, n_per_image):
+        """(NI * n, L) candidates, n per image -> (NI * n, n): row i against candidate r of its own image as the only
+        reference (what evaluate.consensus_rerank reads); the candidates are vectorised once and serve as references"""
+        import torch
+        t = self._tokens(candidates)
+        n = int(n_per_image)
+        if n < 1 or t.shape[0] % n:
+            raise ValueError("%d candidates are not %d per image" % (t.shape[0], n))
+        NI = t.shape[0] // n
+        vecs, L = self.vectorise(t)
+        off = torch.arange(0, (NI + 1) * n, n, dtype=torch.int64, device=self.dev)
+        refs = PreparedRefs(vecs, L, NI * n, off, NI, n)
+        owner = torch.arange(NI, dtype=torch.int32, device=self.dev).repeat_interleave(n)
+        return self.score_token_ids(t, owner, refs, return_pairs=True)[1]
+
+
+import weakref as _weakref
+
+_device_scorers = _weakref.WeakKeyDictionary()      # CiderD -> {device: DeviceCiderD}: not part of the scorer's pickled state
+
+
+def _ciderd_device(self, dev):
+    """The DeviceCiderD of this scorer on `dev`: built at the first call (table upload), cached per device."""
+    import torch
+    dev = torch.device(dev)
+    if dev.type == "cuda" and dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    per = _device_scorers.setdefault(self, {})
+    if dev not in per:
+        per[dev] = DeviceCiderD(self, dev)
+    return per[dev]
+
+
+CiderD.device = _ciderd_device
+
+
+def self_critical_reward_device(dscorer, sampled, greedy, refs, image_of=None, cider_weight=1.0):
+    """Device twin of self_critical_reward: reward[b, :] = cider_weight * (CIDEr-D(sampled_b) - CIDEr-D(greedy of its image)).
+    sampled (N, L) and greedy (NI, L) device id tensors, refs the PreparedRefs of the NI images (or their reference sets),
+    image_of (N,) device index of each sample's image (None: row b belongs to image b % NI, the order of the repeated
+    rollout).  The greedy captions are scored once per image; the difference is taken in double and then cast, as on the
+    host.  Returns an (N, L) float32 device tensor; nothing is read back."""
+    import torch
+    if not isinstance(refs, PreparedRefs):
+        refs = dscorer.prepare_refs(refs)
+    N, NI = sampled.shape[0], greedy.shape[0]
+    if sampled.shape[1] != greedy.shape[1]:
+        raise ValueError("sampled and greedy captions differ in max_len: %d vs %d" % (sampled.shape[1], greedy.shape[1]))
+    if NI != refs.n_sets:
+        raise ValueError("%d greedy captions for %d reference sets" % (NI, refs.n_sets))
+    dev = dscorer.dev
+    own = torch.arange(NI, dtype=torch.int64, device=dev)
+    image_of = own.repeat(-(-N // max(NI, 1)))[:N] if image_of is None else torch.as_tensor(image_of).reshape(-1).to(dev, torch.int64)
+    s = dscorer.score_token_ids(torch.cat([sampled.to(dev), greedy.to(dev)], 0), torch.cat([image_of, own]), refs)
+    diff = cider_weight * (s[:N] - s[N:][image_of])
+    return diff.to(torch.float32)[:, None].expand(N, sampled.shape[1]).contiguous()

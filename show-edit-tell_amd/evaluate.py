@@ -1152,3 +1152,68 @@ def edit_trace(decoder, image_features, previous_caption, prev_caplen, word_map,
                                      ptr(tok), tok.shape[1], ptr(n_steps), S, C.byref(out), ptr(ws), ws.numel(), ptr(tws),
                                      tws.numel(), stream_of(dev)), "set_editnet_edit_trace")
     return tr
+
+
+# ---- consensus (minimum-Bayes-risk) reranking under CIDEr-D -------------------------------------------------------------
+def consensus_rerank(scorer, candidates, n_per_image, weights=None):
+    """Choose among the candidate captions of an image the one most similar to all the others:
+        dsc = ciderd_scorer.device(dev)                                      # ciderd.DeviceCiderD
+        seq, _ = sample_captions(decoder, X, prev, plen, word_map, n_samples=5)
+        best, utility = consensus_rerank(dsc, seq.reshape(-1, seq.shape[-1]), 5)
+    candidates: (NI * n, L) id tensor in the decoder's format (0 = <end>, rows i * n .. i * n + n - 1 belong to image i);
+    `scorer.pair_scores(candidates, n)` gives the (NI * n, n) CIDEr-D of every candidate against each candidate of its image
+    as the only reference (csrc/ciderd_device.hip: the candidates are each other's references and never leave the device).
+    utility[i, j] = mean over the OTHER candidates r != j of that score (the diagonal is left out; identical candidates are
+    separate votes), or with weights (NI, n) — e.g. sbs_importance_weights per image — the weighted mean
+    sum_{r != j} w[i, r] s[j, r] / sum_{r != j} w[i, r] (0 where that sum is 0).  n = 1: utility 0, index 0.
+    Returns (best_index (NI,) int64: the largest utility, ties to the lowest index; utility (NI, n) float64), on the
+    device of the scores."""
+    n = int(n_per_image)
+    if n < 1:
+        raise ValueError("n_per_image must be >= 1, got %r" % (n_per_image,))
+    N = int(candidates.shape[0])
+    if N % n:
+        raise ValueError("%d candidates are not %d per image" % (N, n))
+    NI = N // n
+    P = scorer.pair_scores(candidates, n)
+    if tuple(P.shape) != (N, n):
+        raise ValueError("pair_scores returned shape %s, expected %s" % (tuple(P.shape), (N, n)))
+    P = P.double().view(NI, n, n)
+    dev = P.device
+    w = torch.ones(NI, n, dtype=torch.float64, device=dev) if weights is None else \
+        torch.as_tensor(weights, dtype=torch.float64).to(dev).reshape(NI, n)
+    off = 1.0 - torch.eye(n, dtype=torch.float64, device=dev)
+    wm = w[:, None, :] * off[None]                              # [i, j, r]: weight of vote r for candidate j
+    den = wm.sum(-1)
+    num = (torch.where(wm != 0, P, torch.zeros_like(P)) * wm).sum(-1)
+    utility = torch.where(den != 0, num / torch.where(den != 0, den, torch.ones_like(den)), torch.zeros_like(den))
+    idx = torch.arange(n, device=dev).expand(NI, n)
+    best = torch.where(utility == utility.max(1, keepdim=True).values, idx, torch.full_like(idx, n)).min(1).values
+    return best, utility
+
+
+def consensus_rerank_lists(scorer, captions, weights=None, word_map=None):
+    """consensus_rerank for what sample_captions_distinct[_ensemble], n_best= and beam_search_diverse(return_all=True) return:
+    captions[i] = the id lists of image i (or entries whose first field is the id list), any number per image.  Lists are in
+    the rollouts' convention (<end> stored as 0); with word_map, <start> / <pad> are dropped and <end> becomes 0 first, as
+    ciderd.ground_truth_lists does.  weights[i]: one weight per candidate of image i, or None.
+    Lists are zero-padded to the longest: one that holds no 0 and is shorter than that is read as ended where it stops.
+    Returns (best (NI) list of indices, utility (NI) list of float lists); images with the same count share one launch."""
+    drop, end = set(), None
+    if word_map is not None:
+        drop, end = {int(word_map['<start>']), int(word_map['<pad>'])}, int(word_map['<end>'])
+    rows = [[[0 if w == end else int(w) for w in (c[0] if isinstance(c, tuple) else c) if int(w) not in drop] for c in caps]
+            for caps in captions]
+    L = max([1] + [len(c) for caps in rows for c in caps])
+    best, util = [0] * len(rows), [[] for _ in rows]
+    for n in sorted({len(caps) for caps in rows} - {0}):
+        ids = [i for i, caps in enumerate(rows) if len(caps) == n]
+        t = torch.zeros(len(ids) * n, L, dtype=torch.int64)
+        for a, i in enumerate(ids):
+            for j, c in enumerate(rows[i]):
+                t[a * n + j, :len(c)] = torch.tensor(c, dtype=torch.int64)
+        w = None if weights is None else [list(weights[i]) for i in ids]
+        b, u = consensus_rerank(scorer, t, n, w)
+        for a, i in enumerate(ids):
+            best[i], util[i] = int(b[a]), u[a].tolist()
+    return best, util

@@ -464,13 +464,28 @@ def _side_stream(dev):
     return s
 
 
-def _scst_step(model, optimizer, greedy_fn, sample_fn, rep, ground_truth, scorer, n_samples, cider_weight, dev, group):
+REWARD_ROUTES = ("host", "device")
+
+
+def _scst_step(model, optimizer, greedy_fn, sample_fn, rep, ground_truth, scorer, n_samples, cider_weight, dev, group,
+               reward="host"):
     """Shared body of the self-critical step (editnet_rl.py:649-686, dcnet_rl.py:451-493): greedy baseline in eval
     mode under no_grad (fused device loop), `n_samples` multinomial rollouts in train mode (autograd operators, the
     sampling epilogue runs on the device), reward = CIDEr-D(sample) - CIDEr-D(greedy) from `scorer` (host work, per
-    sample), RewardCriterion normalised by the GLOBAL mask count, backward, gradient all-reduce, clip, optimizer."""
+    sample), RewardCriterion normalised by the GLOBAL mask count, backward, gradient all-reduce, clip, optimizer.
+    reward="device": the reward comes from the device scorer (ciderd.DeviceCiderD, csrc/ciderd_device.hip) — the reference
+    sets are uploaded and vectorised BEFORE the rollout is enqueued, the sampled ids never leave the device, the mask count
+    stays a device scalar that the loss is divided by on the device, and the returned floats are read after the backward
+    has been enqueued.  With an active process group the GLOBAL mask count keeps its host route (one read of the local
+    count before the collective)."""
     from . import ciderd
     from .autograd_ops import deferred_param_grads
+    if reward not in REWARD_ROUTES:
+        raise ValueError("reward must be one of %r, got %r" % (REWARD_ROUTES, reward))
+    refs_dev = None
+    if reward == "device":
+        dscorer = scorer.device(dev)
+        refs_dev = dscorer.prepare_refs(ground_truth)      # depends on nothing of the rollout: runs underneath it
     core = getattr(model, "dae", model)              # DAEWithAR wraps the DAE whose fc finishes first
     reducer = _begin_backward(model, group, _dist_active(group), first=(core.fc.weight, core.fc.bias))
     # the greedy baseline (a latency-bound chain of small kernels) and the sampled rollout are independent: the baseline is
@@ -491,16 +506,28 @@ def _scst_step(model, optimizer, greedy_fn, sample_fn, rep, ground_truth, scorer
         if side is not None:
             cur.wait_stream(side)
             greedy.record_stream(cur)
-        # ONE device->host copy of the sampled ids serves the scorer AND the mask count of RewardCriterion (the shifted
-        # `seq > 0` of editnet_rl.py:563-566 summed): no second round trip (`cnt.item()`) between the rollout and the backward
-        seq_host = seq.cpu().numpy()
-        rewards = ciderd.self_critical_reward(scorer, seq_host, rep(greedy), list(ground_truth) * n_samples, cider_weight)
-        num, _ = reward_loss_sum(logp, seq, torch.from_numpy(rewards).to(dev, non_blocking=True))
-        n_mask = int(seq_host.shape[0] + (seq_host[:, :-1] > 0).sum())
-        n_glob = global_token_count(n_mask, dev, group)
+        if refs_dev is not None:
+            # greedy once per image; row b of the repeated rollout belongs to image b % B (_repeater).  No device->host copy
+            # from here to loss.backward() on one rank: the mask count is a device scalar and divides the loss there
+            rewards = ciderd.self_critical_reward_device(dscorer, seq, greedy, refs_dev, None, cider_weight)
+            num, cnt = reward_loss_sum(logp, seq, rewards)
+            n_glob = global_token_count(int(cnt.item()), dev, group) if _dist_active(group) else cnt
+            reward_mean = rewards[:, 0].double().mean()
+        else:
+            # ONE device->host copy of the sampled ids serves the scorer AND the mask count of RewardCriterion (the shifted
+            # `seq > 0` of editnet_rl.py:563-566 summed): no second round trip (`cnt.item()`) between the rollout and the backward
+            seq_host = seq.cpu().numpy()
+            rewards = ciderd.self_critical_reward(scorer, seq_host, rep(greedy), list(ground_truth) * n_samples, cider_weight)
+            num, _ = reward_loss_sum(logp, seq, torch.from_numpy(rewards).to(dev, non_blocking=True))
+            n_mask = int(seq_host.shape[0] + (seq_host[:, :-1] > 0).sum())
+            n_glob = global_token_count(n_mask, dev, group)
+            reward_mean = rewards[:, 0].mean()
         loss = num / n_glob
         loss.backward()
-    reward_mean, loss_val = float(rewards[:, 0].mean()), _global_loss(num, n_glob, group)
+    if torch.is_tensor(n_glob):                          # device route on one rank: both floats in one read, after the backward
+        reward_mean, loss_val = torch.stack([reward_mean, num.detach().double() / n_glob.double()]).tolist()
+    else:
+        reward_mean, loss_val = float(reward_mean), _global_loss(num, n_glob, group)
     params = [p for p in model.parameters() if p.requires_grad]
     allreduce_gradients(params, group, reducer=reducer)
     clip_grad_norm_and_step(params, optimizer, GRAD_CLIP)
@@ -520,12 +547,13 @@ def _sample_kw(temperature, top_k, top_p):
 
 
 def scst_train_step(decoder, optimizer, word_map, image_features, previous_caption, prev_caplen, ground_truth,
-                    scorer, n_samples=1, cider_weight=1.0, group=None, temperature=1.0, top_k=0, top_p=1.0):
+                    scorer, n_samples=1, cider_weight=1.0, group=None, temperature=1.0, top_k=0, top_p=1.0, reward="host"):
     """One self-critical step of editnet_rl.py:649-686 on this rank's shard.  The reference draws one sample per
     image; BASELINE.json config 5 asks for 5: all samples enter one RewardCriterion over n_samples * B rows.  As in
     the XE step the loss is normalised by the GLOBAL mask count so that N ranks reproduce one big batch.
     temperature / top_k / top_p (include/set_hip.h SetSampleOpts): the policy the samples are drawn from AND differentiated
     (`decoder.sample_rollout`; every step's kept set is held constant); the greedy baseline takes no options.
+    reward="host" (default: the calls made before the argument existed) | "device" (CIDEr-D on the device, see _scst_step).
     Returns (mean reward of the samples on this rank, GLOBAL loss value)."""
     rep = _repeater(n_samples)
     kw = _sample_kw(temperature, top_k, top_p)
@@ -539,14 +567,14 @@ def scst_train_step(decoder, optimizer, word_map, image_features, previous_capti
                          sample_rl=True, repeat_images=n_samples)) if not kw else
         (lambda: decoder.sample_rollout(word_map, rep(previous_caption), rep(prev_caplen), image_features,
                                         repeat_images=n_samples, **kw)),
-        rep, ground_truth, scorer, n_samples, cider_weight, image_features.device, group)
+        rep, ground_truth, scorer, n_samples, cider_weight, image_features.device, group, reward)
 
 
 def dcnet_scst_train_step(dae, optimizer, word_map, previous_caption, prev_caplen, ground_truth, scorer, n_samples=1,
-                          cider_weight=1.0, group=None, temperature=1.0, top_k=0, top_p=1.0):
+                          cider_weight=1.0, group=None, temperature=1.0, top_k=0, top_p=1.0, reward="host"):
     """The text-only twin (dcnet_rl.py:451-493): `dae` is a dcnet_rl.DAE or the DAEWithAR wrapper the reference
     trains (its forward delegates to `.dae`; `affine_hidden` receives no gradient from this loss, as in the reference).
-    temperature / top_k / top_p: see scst_train_step.
+    temperature / top_k / top_p / reward: see scst_train_step.
     Returns (mean reward of the samples on this rank, GLOBAL loss value)."""
     rep = _repeater(n_samples)
     kw = _sample_kw(temperature, top_k, top_p)
@@ -555,4 +583,4 @@ def dcnet_scst_train_step(dae, optimizer, word_map, previous_caption, prev_caple
         lambda: dae(word_map, previous_caption, prev_caplen, sample_max=True, sample_rl=False),
         (lambda: dae(word_map, rep(previous_caption), rep(prev_caplen), sample_max=False, sample_rl=True)) if not kw else
         (lambda: dae.sample_rollout(word_map, rep(previous_caption), rep(prev_caplen), **kw)),
-        rep, ground_truth, scorer, n_samples, cider_weight, previous_caption.device, group)
+        rep, ground_truth, scorer, n_samples, cider_weight, previous_caption.device, group, reward)
