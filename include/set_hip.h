@@ -1302,6 +1302,40 @@ int set_ciderd_device_score(void* handle, const int64_t* hyp_tokens, int64_t hyp
                             const int64_t* ref_set_off, int n_sets, int max_set, double* scores, double* pair_scores,
                             int64_t pair_ld, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * BLEU on the DEVICE (csrc/bleu_device.hip): the statistics and scores of coco-caption's BleuScorer (n = 4, option "closest") as
+ * bleu.py states them, from id rows in device memory on `stream` with no host read.  Sentences are rows of int64 vocabulary ids,
+ * at most 64 per sentence, ids in [0, 65534) (the packing of set_ciderd_device_key).  Stateless: there is no handle.
+ *   guess[k] = max(0, len - k + 1), correct[k] = sum over the distinct k-grams g of the hypothesis of min(count_h(g), max_r
+ *   count_r(g)), testlen = len, reflen = the reference length that minimises (|len_r - len|, len_r);  with b the running product
+ *   of (correct[k] + 1e-15) / (guess[k] + 1e-9): bleu[k] = b^(1/k), times exp(1 - 1/ratio) where ratio = (testlen + 1e-15) /
+ *   (reflen + 1e-9) < 1.  The statistics are integers; the scores are double and a function of the row's integers alone, so a
+ *   row's result does not depend on the launch it is part of.  No atomics; only the declared outputs are written.
+ * ref_bytes / prepare: reference i = tokens[i ld .. i ld + L) (device int64, ld >= L), its length lens[i] clamped to [0, L]
+ *   (device int32), or with lens == NULL the decoder's rule: cut after the first 0, the 0 itself stays, a row without 0 is taken
+ *   whole.  One wave per reference writes its record into recs (ref_bytes(n_refs, L) bytes, 16-byte aligned; 8 + 4 L words of 8
+ *   bytes per reference: the length, a flag "an id was outside [0, 65534)", six zero words, then per position the keys of the four
+ *   grams that start there, 0 = none).  ref_bytes is 0 for n_refs < 0 or L outside 1 .. 64.  SET_ERR_ARG: NULL tokens / recs,
+ *   n_refs < 0, L < 1, ld < L; SET_ERR_UNSUPPORTED: L > 64 — before any HIP call.  n_refs == 0: nothing is done.
+ * score: hypothesis i (rows of hyp as in prepare, L and hyp_lens likewise) against the references of set set_of_hyp[i] (device
+ *   int32) = records [ref_set_off[s], ref_set_off[s + 1]) (device int64, n_sets + 1) of ref_recs, which prepare wrote with
+ *   L = ref_L for n_refs references.  One wave per hypothesis writes stats[i, 0..10) = correct[1..4], guess[1..4], testlen, reflen
+ *   (int32), with scores != NULL scores[i, 0..4) = bleu[1..4] of the sentence, and with pair_scores != NULL
+ *   pair_scores[i pair_ld + r] = the sentence's bleu[4] against reference r of its set alone, r < |set|; nothing else is written.
+ *   An empty set gives correct = 0 and reflen = 0.  max_set is the caller's bound on |set|.  What the host cannot check is
+ *   answered by the kernel with -1 in stats[i, :] and NaN in scores[i, :], nothing else touched: set_of_hyp[i] outside [0, n_sets),
+ *   offsets outside [0, n_refs] or decreasing, a set larger than max_set.  An id outside [0, 65534) in the hypothesis or one of its
+ *   references gives correct = -1 and NaN scores (and pair scores) in that row.
+ *   SET_ERR_ARG: NULL hyp / set_of_hyp / ref_set_off / stats (ref_recs with n_refs > 0), a negative count, L or ref_L < 1,
+ *   hyp_ld < L, pair_scores with pair_ld < max_set; SET_ERR_UNSUPPORTED: L or ref_L > 64 — before any HIP call.  n_hyp == 0: nothing
+ *   is done.
+ * ------------------------------------------------------------------------------------------ */
+size_t set_bleu_device_ref_bytes(int n_refs, int L);
+int set_bleu_device_prepare(const int64_t* tokens, int64_t ld, const int32_t* lens, int n_refs, int L, void* recs, void* stream);
+int set_bleu_device_score(const int64_t* hyp, int64_t hyp_ld, const int32_t* hyp_lens, int n_hyp, int L, const int32_t* set_of_hyp,
+                          const void* ref_recs, int ref_L, int64_t n_refs, const int64_t* ref_set_off, int n_sets, int max_set,
+                          int32_t* stats, double* scores, double* pair_scores, int64_t pair_ld, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -290,25 +290,47 @@ def ground_truth_lists(allcaps, word_map):
     return out
 
 
-def self_critical_reward(scorer, sampled, greedy, ground_truth, cider_weight=1.0):
+def _reward_sets(ground_truth, B):
+    """the reference sets of the distinct images (by identity of their list) and, for the B sampled and then the B greedy
+    captions, the index of each one's set"""
+    sets, index = [], {}
+    hyp_set = np.empty(2 * B, dtype=np.int32)
+    for i in range(B):
+        caps = ground_truth[i]
+        k = id(caps)
+        if k not in index:
+            index[k] = len(sets)
+            sets.append(caps)
+        hyp_set[i] = hyp_set[B + i] = index[k]
+    return sets, hyp_set
+
+
+def _bleu4_term(bleu_scorer, bleu_weight, sampled, greedy, ground_truth):
+    """bleu_weight * (BLEU-4(sampled_b) - BLEU-4(greedy_b)) in double: sentence BLEU-4 of bleu.Bleu.score_token_ids (rows
+    cut after their first 0, the 0 a token — the convention of the CIDEr-D term)"""
+    B = sampled.shape[0]
+    sets, hyp_set = _reward_sets(ground_truth, B)
+    b = np.asarray(bleu_scorer.score_token_ids(np.concatenate([sampled, greedy], 0), hyp_set, sets)[1], dtype=np.float64)[:, 3]
+    return bleu_weight * (b[:B] - b[B:])
+
+
+def self_critical_reward(scorer, sampled, greedy, ground_truth, cider_weight=1.0, bleu_scorer=None, bleu_weight=0.0):
     """reward[b, :] = CIDEr-D(sampled_b) - CIDEr-D(greedy_b), repeated over the max_len columns
-    (editnet_rl.py:611-646).  sampled/greedy: (B, max_len) integer arrays/tensors; returns float32 numpy."""
+    (editnet_rl.py:611-646).  sampled/greedy: (B, max_len) integer arrays/tensors; returns float32 numpy.
+    With a `bleu_scorer` (bleu.Bleu) and bleu_weight != 0 the reward of the self-critical code base:
+    cider_weight * dCIDEr-D + bleu_weight * dBLEU-4, mixed in double and then cast; otherwise the scorer sees the calls it
+    saw before the argument existed."""
     sampled = np.asarray(sampled.cpu() if hasattr(sampled, 'cpu') else sampled)
     greedy = np.asarray(greedy.cpu() if hasattr(greedy, 'cpu') else greedy)
     B = sampled.shape[0]
+    mix = bleu_scorer is not None and bleu_weight != 0.0
     if getattr(scorer, "_handle", None) is not None and scorer._handle() is not None:
         # integer fast path (no strings): the reference sets of the distinct images once, all 2B captions in one call
-        sets, index = [], {}
-        hyp_set = np.empty(2 * B, dtype=np.int32)
-        for i in range(B):
-            caps = ground_truth[i]
-            k = id(caps)
-            if k not in index:
-                index[k] = len(sets)
-                sets.append(caps)
-            hyp_set[i] = hyp_set[B + i] = index[k]
+        sets, hyp_set = _reward_sets(ground_truth, B)
         s = scorer.score_token_ids(np.concatenate([sampled, greedy], 0), hyp_set, sets)
         diff = cider_weight * (s[:B] - s[B:])
+        if mix:
+            diff = diff + _bleu4_term(bleu_scorer, bleu_weight, sampled, greedy, ground_truth)
         return np.repeat(diff[:, None], sampled.shape[1], 1).astype(np.float32)
     memo = {}                    # the same image's reference lists are repeated once per sample: stringify them once
 
@@ -324,6 +346,8 @@ def self_critical_reward(scorer, sampled, greedy, ground_truth, cider_weight=1.0
     res += [{'image_id': B + i, 'caption': [tokens_to_str(greedy[i])]} for i in range(B)]
     _, s = scorer.compute_score(gts, res)
     diff = cider_weight * (s[:B] - s[B:])
+    if mix:
+        diff = diff + _bleu4_term(bleu_scorer, bleu_weight, sampled, greedy, ground_truth)
     return np.repeat(diff[:, None], sampled.shape[1], 1).astype(np.float32)
 
 
@@ -558,8 +582,11 @@ def _ciderd_device(self, dev):
 CiderD.device = _ciderd_device
 
 
-def self_critical_reward_device(dscorer, sampled, greedy, refs, image_of=None, cider_weight=1.0):
+def self_critical_reward_device(dscorer, sampled, greedy, refs, image_of=None, cider_weight=1.0, bleu_scorer=None, bleu_refs=None,
+                                bleu_weight=0.0):
     """Device twin of self_critical_reward: reward[b, :] = cider_weight * (CIDEr-D(sampled_b) - CIDEr-D(greedy of its image)).
+    With a `bleu_scorer` (bleu.DeviceBleu), `bleu_refs` (its PreparedBleuRefs of the NI images, or their reference sets) and
+    bleu_weight != 0: + bleu_weight * (BLEU-4(sampled_b) - BLEU-4(greedy of its image)), one more launch over the same rows.
     sampled (N, L) and greedy (NI, L) device id tensors, refs the PreparedRefs of the NI images (or their reference sets),
     image_of (N,) device index of each sample's image (None: row b belongs to image b % NI, the order of the repeated
     rollout).  The greedy captions are scored once per image; the difference is taken in double and then cast, as on the
@@ -575,6 +602,12 @@ def self_critical_reward_device(dscorer, sampled, greedy, refs, image_of=None, c
     dev = dscorer.dev
     own = torch.arange(NI, dtype=torch.int64, device=dev)
     image_of = own.repeat(-(-N // max(NI, 1)))[:N] if image_of is None else torch.as_tensor(image_of).reshape(-1).to(dev, torch.int64)
-    s = dscorer.score_token_ids(torch.cat([sampled.to(dev), greedy.to(dev)], 0), torch.cat([image_of, own]), refs)
+    rows, rows_set = torch.cat([sampled.to(dev), greedy.to(dev)], 0), torch.cat([image_of, own])
+    s = dscorer.score_token_ids(rows, rows_set, refs)
     diff = cider_weight * (s[:N] - s[N:][image_of])
+    if bleu_scorer is not None and bleu_weight != 0.0:
+        if bleu_refs is None:
+            raise ValueError("the BLEU term needs bleu_refs: the images' reference sets or DeviceBleu.prepare_refs of them")
+        b = bleu_scorer.score_token_ids(rows, rows_set, bleu_refs)[1][:, 3]
+        diff = diff + bleu_weight * (b[:N] - b[N:][image_of])
     return diff.to(torch.float32)[:, None].expand(N, sampled.shape[1]).contiguous()

@@ -1163,6 +1163,7 @@ def consensus_rerank(scorer, candidates, n_per_image, weights=None):
     candidates: (NI * n, L) id tensor in the decoder's format (0 = <end>, rows i * n .. i * n + n - 1 belong to image i);
     `scorer.pair_scores(candidates, n)` gives the (NI * n, n) CIDEr-D of every candidate against each candidate of its image
     as the only reference (csrc/ciderd_device.hip: the candidates are each other's references and never leave the device).
+    Any object with that method serves: bleu.DeviceBleu(dev) reranks under sentence BLEU-4 instead (csrc/bleu_device.hip).
     utility[i, j] = mean over the OTHER candidates r != j of that score (the diagonal is left out; identical candidates are
     separate votes), or with weights (NI, n) — e.g. sbs_importance_weights per image — the weighted mean
     sum_{r != j} w[i, r] s[j, r] / sum_{r != j} w[i, r] (0 where that sum is 0).  n = 1: utility 0, index 0.
@@ -1217,3 +1218,42 @@ def consensus_rerank_lists(scorer, captions, weights=None, word_map=None):
         for a, i in enumerate(ids):
             best[i], util[i] = int(b[a]), u[a].tolist()
     return best, util
+
+
+# ---- validation BLEU (the `Bleu_4` of the reference's evaluate(): editnet_rl.py:834/897, dcnet.py:541-611) -----------------
+def validation_bleu(captions, hyp_set, ground_truth, dev, count_end=False, word_map=None):
+    """Corpus Bleu_1..4 of decoded captions without strings:
+        gt = ciderd.ground_truth_lists(allcaps, word_map)
+        seq, _ = decoder(word_map, prev, plen, X, sample_max=True, sample_rl=False)     # greedy: (N, L) ids, stays on the device
+        bleu = validation_bleu(seq, None, gt, X.device)                                 # bleu[3]: Bleu_4
+        seqs = beam_search_editnet_batched(decoder, X, prev, plen, word_map)            # any search: lists of token lists
+        bleu = validation_bleu(seqs, None, gt, X.device, word_map=word_map)
+    captions: (N, L) ids in the decoder's format (0 = <end> and everything after it), L <= 64 — or, with word_map, what the
+    beam searches return: N token lists in the vocabulary's ids, from which <start> / <pad> are dropped and whose <end>
+    becomes 0 (ciderd.ground_truth_lists' rule), zero-padded into one upload.  hyp_set: (N,) index of each caption's reference
+    set (None: caption i belongs to set i); ground_truth: the reference sets as id lists with <end> = 0.
+    count_end=False (cocoEval's word strings): a caption ends BEFORE its first 0 and the references lose theirs; True: the
+    SCST convention, the 0 is a token on both sides.  The statistics are summed and scored on the device (bleu.DeviceBleu,
+    csrc/bleu_device.hip) and nothing is read back.  Returns a (4,) float64 device tensor."""
+    from . import bleu
+    scorer = bleu.device_scorer(dev)
+    lens = None
+    if word_map is not None:
+        drop, end = {int(word_map['<start>']), int(word_map['<pad>'])}, int(word_map['<end>'])
+        rows = [[0 if int(w) == end else int(w) for w in c if int(w) not in drop] for c in captions]
+        rows = [c[:c.index(0) + (1 if count_end else 0)] if 0 in c else c for c in rows]
+        captions = torch.zeros(len(rows), max([1] + [len(c) for c in rows]), dtype=torch.int64)
+        for i, c in enumerate(rows):
+            captions[i, :len(c)] = torch.tensor(c, dtype=torch.int64)
+        # a list that never reached <end> (the step limit) ends where it stops: explicit lengths, not the 0 rule
+        lens = torch.tensor([len(c) for c in rows], dtype=torch.int32)
+    captions = torch.as_tensor(captions).to(scorer.dev)
+    if captions.dim() != 2:
+        raise ValueError("captions are rows of a 2-D id tensor, got shape %s" % (tuple(captions.shape),))
+    N, L = captions.shape
+    if hyp_set is None:
+        hyp_set = torch.arange(N, dtype=torch.int32, device=scorer.dev)
+    if lens is None and not count_end and L > 0:
+        is0 = captions == 0
+        lens = torch.where(is0.any(1), is0.int().argmax(1), torch.full((N,), L, dtype=torch.int64, device=scorer.dev))
+    return scorer.corpus_score(captions, hyp_set, scorer.prepare_refs(ground_truth, count_end=count_end), lens)

@@ -468,7 +468,7 @@ REWARD_ROUTES = ("host", "device")
 
 
 def _scst_step(model, optimizer, greedy_fn, sample_fn, rep, ground_truth, scorer, n_samples, cider_weight, dev, group,
-               reward="host"):
+               reward="host", bleu_weight=0.0):
     """Shared body of the self-critical step (editnet_rl.py:649-686, dcnet_rl.py:451-493): greedy baseline in eval
     mode under no_grad (fused device loop), `n_samples` multinomial rollouts in train mode (autograd operators, the
     sampling epilogue runs on the device), reward = CIDEr-D(sample) - CIDEr-D(greedy) from `scorer` (host work, per
@@ -477,7 +477,11 @@ def _scst_step(model, optimizer, greedy_fn, sample_fn, rep, ground_truth, scorer
     sets are uploaded and vectorised BEFORE the rollout is enqueued, the sampled ids never leave the device, the mask count
     stays a device scalar that the loss is divided by on the device, and the returned floats are read after the backward
     has been enqueued.  With an active process group the GLOBAL mask count keeps its host route (one read of the local
-    count before the collective)."""
+    count before the collective).
+    bleu_weight != 0: the reward of the self-critical code base, cider_weight * dCIDEr-D + bleu_weight * dBLEU-4 (sentence BLEU-4
+    of bleu.py under the same sentence convention, sample minus the greedy caption of its image): bleu.Bleu on the host route,
+    bleu.DeviceBleu (csrc/bleu_device.hip) on the device route, its references prepared before the rollout as well.
+    bleu_weight == 0 makes exactly the calls made before the argument existed."""
     from . import ciderd
     from .autograd_ops import deferred_param_grads
     if reward not in REWARD_ROUTES:
@@ -486,6 +490,14 @@ def _scst_step(model, optimizer, greedy_fn, sample_fn, rep, ground_truth, scorer
     if reward == "device":
         dscorer = scorer.device(dev)
         refs_dev = dscorer.prepare_refs(ground_truth)      # depends on nothing of the rollout: runs underneath it
+    mix = {}
+    if bleu_weight != 0.0:
+        from . import bleu
+        if reward == "device":
+            bscorer = bleu.device_scorer(dev)
+            mix = dict(bleu_scorer=bscorer, bleu_refs=bscorer.prepare_refs(ground_truth), bleu_weight=bleu_weight)
+        else:
+            mix = dict(bleu_scorer=bleu.Bleu(), bleu_weight=bleu_weight)
     core = getattr(model, "dae", model)              # DAEWithAR wraps the DAE whose fc finishes first
     reducer = _begin_backward(model, group, _dist_active(group), first=(core.fc.weight, core.fc.bias))
     # the greedy baseline (a latency-bound chain of small kernels) and the sampled rollout are independent: the baseline is
@@ -509,7 +521,7 @@ def _scst_step(model, optimizer, greedy_fn, sample_fn, rep, ground_truth, scorer
         if refs_dev is not None:
             # greedy once per image; row b of the repeated rollout belongs to image b % B (_repeater).  No device->host copy
             # from here to loss.backward() on one rank: the mask count is a device scalar and divides the loss there
-            rewards = ciderd.self_critical_reward_device(dscorer, seq, greedy, refs_dev, None, cider_weight)
+            rewards = ciderd.self_critical_reward_device(dscorer, seq, greedy, refs_dev, None, cider_weight, **mix)
             num, cnt = reward_loss_sum(logp, seq, rewards)
             n_glob = global_token_count(int(cnt.item()), dev, group) if _dist_active(group) else cnt
             reward_mean = rewards[:, 0].double().mean()
@@ -517,7 +529,7 @@ def _scst_step(model, optimizer, greedy_fn, sample_fn, rep, ground_truth, scorer
             # ONE device->host copy of the sampled ids serves the scorer AND the mask count of RewardCriterion (the shifted
             # `seq > 0` of editnet_rl.py:563-566 summed): no second round trip (`cnt.item()`) between the rollout and the backward
             seq_host = seq.cpu().numpy()
-            rewards = ciderd.self_critical_reward(scorer, seq_host, rep(greedy), list(ground_truth) * n_samples, cider_weight)
+            rewards = ciderd.self_critical_reward(scorer, seq_host, rep(greedy), list(ground_truth) * n_samples, cider_weight, **mix)
             num, _ = reward_loss_sum(logp, seq, torch.from_numpy(rewards).to(dev, non_blocking=True))
             n_mask = int(seq_host.shape[0] + (seq_host[:, :-1] > 0).sum())
             n_glob = global_token_count(n_mask, dev, group)
@@ -547,13 +559,15 @@ def _sample_kw(temperature, top_k, top_p):
 
 
 def scst_train_step(decoder, optimizer, word_map, image_features, previous_caption, prev_caplen, ground_truth,
-                    scorer, n_samples=1, cider_weight=1.0, group=None, temperature=1.0, top_k=0, top_p=1.0, reward="host"):
+                    scorer, n_samples=1, cider_weight=1.0, group=None, temperature=1.0, top_k=0, top_p=1.0, reward="host",
+                    bleu_weight=0.0):
     """One self-critical step of editnet_rl.py:649-686 on this rank's shard.  The reference draws one sample per
     image; BASELINE.json config 5 asks for 5: all samples enter one RewardCriterion over n_samples * B rows.  As in
     the XE step the loss is normalised by the GLOBAL mask count so that N ranks reproduce one big batch.
     temperature / top_k / top_p (include/set_hip.h SetSampleOpts): the policy the samples are drawn from AND differentiated
     (`decoder.sample_rollout`; every step's kept set is held constant); the greedy baseline takes no options.
     reward="host" (default: the calls made before the argument existed) | "device" (CIDEr-D on the device, see _scst_step).
+    bleu_weight: weight of the BLEU-4 term of the reward (0.0: none, nothing of bleu.py is imported or launched).
     Returns (mean reward of the samples on this rank, GLOBAL loss value)."""
     rep = _repeater(n_samples)
     kw = _sample_kw(temperature, top_k, top_p)
@@ -567,14 +581,14 @@ def scst_train_step(decoder, optimizer, word_map, image_features, previous_capti
                          sample_rl=True, repeat_images=n_samples)) if not kw else
         (lambda: decoder.sample_rollout(word_map, rep(previous_caption), rep(prev_caplen), image_features,
                                         repeat_images=n_samples, **kw)),
-        rep, ground_truth, scorer, n_samples, cider_weight, image_features.device, group, reward)
+        rep, ground_truth, scorer, n_samples, cider_weight, image_features.device, group, reward, bleu_weight)
 
 
 def dcnet_scst_train_step(dae, optimizer, word_map, previous_caption, prev_caplen, ground_truth, scorer, n_samples=1,
-                          cider_weight=1.0, group=None, temperature=1.0, top_k=0, top_p=1.0, reward="host"):
+                          cider_weight=1.0, group=None, temperature=1.0, top_k=0, top_p=1.0, reward="host", bleu_weight=0.0):
     """The text-only twin (dcnet_rl.py:451-493): `dae` is a dcnet_rl.DAE or the DAEWithAR wrapper the reference
     trains (its forward delegates to `.dae`; `affine_hidden` receives no gradient from this loss, as in the reference).
-    temperature / top_k / top_p / reward: see scst_train_step.
+    temperature / top_k / top_p / reward / bleu_weight: see scst_train_step.
     Returns (mean reward of the samples on this rank, GLOBAL loss value)."""
     rep = _repeater(n_samples)
     kw = _sample_kw(temperature, top_k, top_p)
@@ -583,4 +597,4 @@ def dcnet_scst_train_step(dae, optimizer, word_map, previous_caption, prev_caple
         lambda: dae(word_map, previous_caption, prev_caplen, sample_max=True, sample_rl=False),
         (lambda: dae(word_map, rep(previous_caption), rep(prev_caplen), sample_max=False, sample_rl=True)) if not kw else
         (lambda: dae.sample_rollout(word_map, rep(previous_caption), rep(prev_caplen), **kw)),
-        rep, ground_truth, scorer, n_samples, cider_weight, previous_caption.device, group, reward)
+        rep, ground_truth, scorer, n_samples, cider_weight, previous_caption.device, group, reward, bleu_weight)
