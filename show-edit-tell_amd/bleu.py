@@ -14,10 +14,10 @@ Score from statistics — of one sentence, or of a corpus from the statistics su
 so identical hypothesis and reference score a hair under 1 and guess[k] = 0 contributes a factor 1e-6: coco's behaviour.
 
 `Bleu` is the pure-Python host scorer; `DeviceBleu` the same numbers from id tensors in device memory (csrc/bleu_device.hip,
-include/set_hip.h set_bleu_device_*): sentences of at most 64 ids, ids below 65534.  What counts as the sentence follows
-ciderd.py: without lengths a row is cut after its first 0 and the 0 stays a token (the SCST convention: <end> is rewarded);
-with lengths the row is exactly that long (validation passes the position of the first 0: <end> is no token, as in cocoEval's
-word strings).
+include/set_hip.h set_bleu_device_*) within the limits of device_metric.py, which also states what counts as the sentence
+(shared with ciderd.py): without lengths a row is cut after its first 0 and the 0 stays a token (the SCST convention: <end> is
+rewarded); with lengths the row is exactly that long (validation passes the position of the first 0: <end> is no token, as in
+cocoEval's word strings).
 """
 from __future__ import annotations
 
@@ -26,27 +26,11 @@ from collections import Counter
 
 import numpy as np
 
+from .device_metric import (DEVICE_MAX_LEN, DEVICE_PACK_LIMIT, DeviceSentenceScorer, PreparedRefs as PreparedBleuRefs, cut_after_zero,
+                            pack_ref_sets, resolve_device, strip_end)
+
 TINY, SMALL = 1e-15, 1e-9
 STATS_COLUMNS = 10                 # correct[1..4], guess[1..4], testlen, reflen
-DEVICE_PACK_LIMIT = 65534
-DEVICE_MAX_LEN = 64
-
-
-def _cut_after_zero(c):
-    c = [int(w) for w in c]
-    return c[:c.index(0) + 1] if 0 in c else c
-
-
-def strip_end(ref_sets):
-    """reference sets with every list cut BEFORE its first 0: <end> is not a token (the validation convention)"""
-    out = []
-    for refs in ref_sets:
-        cut = []
-        for c in refs:
-            c = [int(w) for w in c]
-            cut.append(c[:c.index(0)] if 0 in c else c)
-        out.append(cut)
-    return out
 
 
 def _grams(words, k):
@@ -152,61 +136,27 @@ class Bleu:
             hyp_lens = np.asarray(hyp_lens.cpu() if hasattr(hyp_lens, 'cpu') else hyp_lens).reshape(-1)
             if hyp_lens.shape[0] != N:
                 raise ValueError("hyp_lens has %d entries for %d sentences" % (hyp_lens.shape[0], N))
-        refs = [[_cut_after_zero(c) for c in rs] for rs in ref_sets]
+        refs = [[cut_after_zero(c) for c in rs] for rs in ref_sets]
         pairs = []
         for i in range(N):
             row = hyps[i].tolist()
-            row = _cut_after_zero(row) if hyp_lens is None else row[:min(max(int(hyp_lens[i]), 0), L)]
+            row = cut_after_zero(row) if hyp_lens is None else row[:min(max(int(hyp_lens[i]), 0), L)]
             pairs.append((row, refs[int(hyp_set[i])]))
         return self._score_lists(pairs)
 
 
 # ---- the device route (csrc/bleu_device.hip, include/set_hip.h set_bleu_device_*) --------------------------------------------
-class PreparedBleuRefs:
-    """Reference sets prepared on the device (DeviceBleu.prepare_refs): the records, their row length, the set offsets (device
-    int64, n_sets + 1) and the host-side counts the score call validates with."""
-    def __init__(self, recs, L, n_refs, set_off, n_sets, max_set):
-        self.recs, self.L, self.n_refs, self.set_off, self.n_sets, self.max_set = recs, L, n_refs, set_off, n_sets, max_set
-
-
-class DeviceBleu:
+class DeviceBleu(DeviceSentenceScorer):
     """BLEU on one device: every call is enqueued on the current stream of that device and reads nothing back.  Stateless on
     the native side (there is no table): an instance only remembers its device."""
+    METRIC = "BLEU"
 
     def __init__(self, dev):
-        import torch
         from . import _lib
-        self.dev = torch.device(dev)
-        if self.dev.type != "cuda":
-            raise _lib.SetError("the device BLEU scorer needs a GPU device, got %s" % (self.dev,))
-        if self.dev.index is None:
-            self.dev = torch.device("cuda", torch.cuda.current_device())
-        self._lib = _lib.load()
+        super().__init__(dev)
         for name in ("set_bleu_device_ref_bytes", "set_bleu_device_prepare", "set_bleu_device_score"):
             if name in _lib.MISSING:
                 raise _lib.SetError("the native library does not export %s" % name)
-
-    def _tokens(self, t):
-        import torch
-        from . import _lib
-        t = torch.as_tensor(t)
-        if t.dim() != 2:
-            raise ValueError("sentences are rows of a 2-D id tensor, got shape %s" % (tuple(t.shape),))
-        t = t.to(self.dev, torch.int64)
-        if t.shape[1] == 0:
-            t = t.new_zeros(t.shape[0], 1)
-        if t.shape[1] > DEVICE_MAX_LEN:
-            raise _lib.SetError("the device BLEU scorer takes sentences of at most %d ids, got rows of %d" % (DEVICE_MAX_LEN, t.shape[1]))
-        return t if t.stride(1) == 1 and t.stride(0) >= t.shape[1] else t.contiguous()
-
-    def _i32(self, x, n, what):
-        import torch
-        if x is None:
-            return None
-        x = torch.as_tensor(x).reshape(-1).to(self.dev, torch.int32).contiguous()
-        if x.numel() != n:
-            raise ValueError("%s has %d entries for %d sentences" % (what, x.numel(), n))
-        return x
 
     def _prepare(self, t, ln):
         """(R, L) device ids [+ (R,) device int32 lengths] -> the record buffer"""
@@ -226,24 +176,10 @@ class DeviceBleu:
         their first 0 (count_end=False: before it, the validation convention).  An empty set or a reference longer than 64
         ids is refused."""
         import torch
-        sets = strip_end(ref_sets) if not count_end else [[_cut_after_zero(c) for c in refs] for refs in ref_sets]
-        for i, refs in enumerate(sets):
-            if not len(refs):
-                raise ValueError("reference set %d is empty: BLEU needs at least one reference per hypothesis" % i)
-        flat = [c for refs in sets for c in refs]
-        L = max([1] + [len(c) for c in flat])
-        if L > DEVICE_MAX_LEN:
-            raise ValueError("a reference of %d ids: the device BLEU scorer takes at most %d" % (L, DEVICE_MAX_LEN))
-        R = len(flat)
-        tok = np.zeros((max(1, R), L), dtype=np.int64)
-        ln = np.zeros(max(1, R), dtype=np.int32)
-        for i, c in enumerate(flat):
-            tok[i, :len(c)] = c
-            ln[i] = len(c)
-        off = np.zeros(len(sets) + 1, dtype=np.int64)
-        np.cumsum([len(r) for r in sets], out=off[1:])
+        sets = strip_end(ref_sets) if not count_end else [[cut_after_zero(c) for c in refs] for refs in ref_sets]
+        tok, ln, off, R, L, max_set = pack_ref_sets(sets, self.METRIC, False)
         recs = self._prepare(torch.from_numpy(tok[:R]).to(self.dev), torch.from_numpy(ln[:R]).to(self.dev))
-        return PreparedBleuRefs(recs, L, R, torch.from_numpy(off).to(self.dev), len(sets), max([0] + [len(r) for r in sets]))
+        return PreparedBleuRefs(recs, L, R, torch.from_numpy(off).to(self.dev), len(sets), max_set)
 
     def score_token_ids(self, hyps, hyp_set, refs, hyp_lens=None, return_pairs=False):
         """Device twin of Bleu.score_token_ids: `hyps` (N, L) ids, `hyp_set` (N,) index of each row's reference set, `refs` a
@@ -279,15 +215,9 @@ class DeviceBleu:
         """(NI * n, L) candidates, n per image -> (NI * n, n): the sentence BLEU-4 of row i against candidate r of its own
         image as the only reference (what evaluate.consensus_rerank reads).  Rows are cut after their first 0; the candidates
         are prepared once on the device and serve as references."""
-        import torch
         t = self._tokens(candidates)
-        n = int(n_per_image)
-        if n < 1 or t.shape[0] % n:
-            raise ValueError("%d candidates are not %d per image" % (t.shape[0], n))
-        NI = t.shape[0] // n
-        refs = PreparedBleuRefs(self._prepare(t, None), t.shape[1], NI * n,
-                                torch.arange(0, (NI + 1) * n, n, dtype=torch.int64, device=self.dev), NI, n)
-        owner = torch.arange(NI, dtype=torch.int32, device=self.dev).repeat_interleave(n)
+        refs, owner = self._self_refs(t, n_per_image)
+        refs.recs = self._prepare(t, None)
         return self.score_token_ids(t, owner, refs, return_pairs=True)[2]
 
 
@@ -296,10 +226,7 @@ _device_scorers = {}
 
 def device_scorer(dev):
     """the DeviceBleu of `dev`, made at the first call"""
-    import torch
-    dev = torch.device(dev)
-    if dev.type == "cuda" and dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
+    dev = resolve_device(dev)
     if dev not in _device_scorers:
         _device_scorers[dev] = DeviceBleu(dev)
     return _device_scorers[dev]

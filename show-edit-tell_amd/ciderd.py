@@ -26,6 +26,8 @@ from collections import Counter
 
 import numpy as np
 
+from .device_metric import DEVICE_MAX_LEN, DEVICE_PACK_LIMIT, DeviceSentenceScorer, PreparedRefs, cut_after_zero, pack_ref_sets, resolve_device
+
 
 def ngram_counts(sentence, n=4):
     """Counter of all 1..n-grams (tuples of token strings) of a whitespace-tokenised sentence."""
@@ -225,10 +227,7 @@ class CiderD:
         keep = np.arange(L)[None, :] < lens[:, None]
         # references are cut after their first 0 as well (tokens_to_str / array_to_str do the same on the string path;
         # lists from ground_truth_lists carry no interior 0)
-        def _cut(c):
-            c = list(c)
-            return c[:c.index(0) + 1] if 0 in c else c
-        flat_refs = [_cut(c) for refs in ref_sets for c in refs]
+        flat_refs = [cut_after_zero(c) for refs in ref_sets for c in refs]
         ref_len = np.fromiter((len(c) for c in flat_refs), dtype=np.int64, count=len(flat_refs))
         ref_flat = np.fromiter((w for c in flat_refs for w in c), dtype=np.int64, count=int(ref_len.sum()))
         max_id = int(max(hyps.max(initial=0), ref_flat.max(initial=0)))
@@ -353,15 +352,13 @@ def self_critical_reward(scorer, sampled, greedy, ground_truth, cider_weight=1.0
 
 # ---- the device route (csrc/ciderd_device.hip, include/set_hip.h set_ciderd_device_*) ---------------------------------
 # The integer reward path above without the host trip: sentences, reference vectors and scores stay in device memory.
-# Limits: vocabulary ids below 65534 (four ids + 1 in one 64-bit key, make_key of ciderd_host.hip:57-61), sentences of at
-# most 64 ids (one position per lane), and only the df grams whose tokens are all decimal strings (the reward plumbing
-# stringifies ids: any other gram can never match an id sequence).  Opt-in: nothing above calls it.
-DEVICE_PACK_LIMIT = 65534
-DEVICE_MAX_LEN = 64
+# Limits: the id and length limits of device_metric.py (shared with bleu.DeviceBleu), and only the df grams whose tokens are
+# all decimal strings (the reward plumbing stringifies ids: any other gram can never match an id sequence).  Opt-in: nothing
+# above calls it.
 
 
 def pack_key(ids):
-    """packed 64-bit key of an n-gram of 1..4 vocabulary ids: id + 1 in 16-bit fields (make_key, ciderd_host.hip:57-61)"""
+    """packed 64-bit key of an n-gram of 1..4 vocabulary ids: id + 1 in 16-bit fields (make_key, csrc/ngram_wave.h)"""
     ids = [int(w) for w in ids]
     if not 1 <= len(ids) <= 4:
         raise ValueError("an n-gram has 1..4 ids, got %d" % len(ids))
@@ -408,39 +405,23 @@ def device_table_input(df):
     return toks, lens, cnt, E
 
 
-def _cut_after_zero(c):
-    c = [int(w) for w in c]
-    return c[:c.index(0) + 1] if 0 in c else c
-
-
-class PreparedRefs:
-    """Reference sets vectorised on the device (DeviceCiderD.prepare_refs): the records, their row length, the set
-    offsets (device int64, n_sets + 1) and the host-side counts the score call validates with."""
-    def __init__(self, vecs, L, n_refs, set_off, n_sets, max_set):
-        self.vecs, self.L, self.n_refs, self.set_off, self.n_sets, self.max_set = vecs, L, n_refs, set_off, n_sets, max_set
-
-
-class DeviceCiderD:
+class DeviceCiderD(DeviceSentenceScorer):
     """Owner of the device df table of one CiderD on one device (CiderD.device(dev)); every call is enqueued on the
     current stream of that device and reads nothing back."""
+    METRIC = "CIDEr-D"
 
     def __init__(self, scorer, dev):
         import ctypes as C
         import torch
         from . import _lib
-        self.dev = torch.device(dev)
-        if self.dev.type != "cuda":
-            raise _lib.SetError("the device CIDEr-D scorer needs a GPU device, got %s" % (self.dev,))
-        if self.dev.index is None:
-            self.dev = torch.device("cuda", torch.cuda.current_device())
-        lib = _lib.load()
+        super().__init__(dev)
         toks, lens, cnt, E = device_table_input(scorer.df)
         h = C.c_void_p()
         with torch.cuda.device(self.dev):
-            rc = lib.set_ciderd_device_create(toks.ctypes.data, lens.ctypes.data, cnt.ctypes.data, E, float(scorer.ref_len),
-                                              int(scorer.n), float(scorer.sigma), _lib.stream_of(self.dev), C.byref(h))
+            rc = self._lib.set_ciderd_device_create(toks.ctypes.data, lens.ctypes.data, cnt.ctypes.data, E, float(scorer.ref_len),
+                                                    int(scorer.n), float(scorer.sigma), _lib.stream_of(self.dev), C.byref(h))
         _lib.check(rc, "set_ciderd_device_create")
-        self._lib, self._h, self.n, self.n_entries = lib, h, int(scorer.n), E
+        self._h, self.n, self.n_entries = h, int(scorer.n), E
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -449,25 +430,6 @@ class DeviceCiderD:
                 self._lib.set_ciderd_device_destroy(h)
             except Exception:
                 pass
-
-    def _tokens(self, t):
-        import torch
-        t = torch.as_tensor(t)
-        if t.dim() != 2:
-            raise ValueError("sentences are rows of a 2-D id tensor, got shape %s" % (tuple(t.shape),))
-        t = t.to(self.dev, torch.int64)
-        if t.shape[1] == 0:
-            t = t.new_zeros(t.shape[0], 1)
-        return t if t.stride(1) == 1 and t.stride(0) >= t.shape[1] else t.contiguous()
-
-    def _i32(self, x, n, what):
-        import torch
-        if x is None:
-            return None
-        x = torch.as_tensor(x).reshape(-1).to(self.dev, torch.int32).contiguous()
-        if x.numel() != n:
-            raise ValueError("%s has %d entries for %d sentences" % (what, x.numel(), n))
-        return x
 
     def lookup(self, keys):
         """document count of packed keys (pack_key): a device int64 tensor holding the keys' bits, or a list of ints;
@@ -490,35 +452,21 @@ class DeviceCiderD:
         t = self._tokens(tokens)
         S, L = t.shape
         ln = self._i32(lens, S, "lens")
-        if L > DEVICE_MAX_LEN:
-            raise _lib.SetError("the device CIDEr-D scorer takes sentences of at most %d ids, got rows of %d" % (DEVICE_MAX_LEN, L))
-        vecs = torch.empty(S * (8 + 8 * L), dtype=torch.int64, device=self.dev)
+        recs = torch.empty(S * (8 + 8 * L), dtype=torch.int64, device=self.dev)
         with torch.cuda.device(self.dev):
             rc = self._lib.set_ciderd_device_vectorise(self._h, t.data_ptr(), t.stride(0), None if ln is None else ln.data_ptr(),
-                                                       S, L, vecs.data_ptr(), _lib.stream_of(self.dev))
+                                                       S, L, recs.data_ptr(), _lib.stream_of(self.dev))
         _lib.check(rc, "set_ciderd_device_vectorise")
-        return vecs, L
+        return recs, L
 
     def prepare_refs(self, ref_sets):
         """Reference sets as ground_truth_lists returns them (per image a list of id lists) -> PreparedRefs: one upload and
         one vectorise launch, independent of the rollout (issue it first and it runs underneath).  References are cut after
-        their first 0 as score_token_ids does (ciderd.py:226-231); one longer than 64 ids is refused."""
+        their first 0 as score_token_ids does; an empty set is allowed (it scores 0); a reference longer than 64 ids is refused."""
         import torch
-        flat = [_cut_after_zero(c) for refs in ref_sets for c in refs]
-        L = max([1] + [len(c) for c in flat])
-        if L > DEVICE_MAX_LEN:
-            raise ValueError("a reference of %d ids: the device CIDEr-D scorer takes at most %d" % (L, DEVICE_MAX_LEN))
-        R = len(flat)
-        tok = np.zeros((max(1, R), L), dtype=np.int64)
-        ln = np.zeros(max(1, R), dtype=np.int32)
-        for i, c in enumerate(flat):
-            tok[i, :len(c)] = c
-            ln[i] = len(c)
-        off = np.zeros(len(ref_sets) + 1, dtype=np.int64)
-        np.cumsum([len(r) for r in ref_sets], out=off[1:])
-        vecs, _ = self.vectorise(torch.from_numpy(tok[:R]) if R else torch.zeros(0, L, dtype=torch.int64), ln[:R])
-        return PreparedRefs(vecs, L, R, torch.from_numpy(off).to(self.dev), len(ref_sets),
-                            max([0] + [len(r) for r in ref_sets]))
+        tok, ln, off, R, L, max_set = pack_ref_sets([[cut_after_zero(c) for c in refs] for refs in ref_sets], self.METRIC, True)
+        recs, _ = self.vectorise(torch.from_numpy(tok[:R]), ln[:R])
+        return PreparedRefs(recs, L, R, torch.from_numpy(off).to(self.dev), len(ref_sets), max_set)
 
     def score_token_ids(self, hyps, hyp_set, refs, return_pairs=False, hyp_lens=None):
         """Device twin of CiderD.score_token_ids: `hyps` (N, L) ids (0 = <end>, cut after the first 0; with hyp_lens the
@@ -531,8 +479,6 @@ class DeviceCiderD:
             refs = self.prepare_refs(refs)
         t = self._tokens(hyps)
         N, L = t.shape
-        if L > DEVICE_MAX_LEN:
-            raise _lib.SetError("the device CIDEr-D scorer takes sentences of at most %d ids, got rows of %d" % (DEVICE_MAX_LEN, L))
         so = self._i32(hyp_set, N, "hyp_set")
         ln = self._i32(hyp_lens, N, "hyp_lens")
         scores = torch.empty(N, dtype=torch.float64, device=self.dev)
@@ -541,7 +487,7 @@ class DeviceCiderD:
         with torch.cuda.device(self.dev):
             rc = self._lib.set_ciderd_device_score(
                 self._h, t.data_ptr(), t.stride(0), None if ln is None else ln.data_ptr(), N, L, so.data_ptr(),
-                refs.vecs.data_ptr(), refs.L, refs.n_refs, refs.set_off.data_ptr(), refs.n_sets, refs.max_set, scores.data_ptr(),
+                refs.recs.data_ptr(), refs.L, refs.n_refs, refs.set_off.data_ptr(), refs.n_sets, refs.max_set, scores.data_ptr(),
                 None if pairs is None else pairs.data_ptr(), pair_ld, _lib.stream_of(self.dev))
         _lib.check(rc, "set_ciderd_device_score")
         return (scores, pairs) if return_pairs else scores
@@ -549,16 +495,9 @@ class DeviceCiderD:
     def pair_scores(self, candidates, n_per_image):
         """(NI * n, L) candidates, n per image -> (NI * n, n): row i against candidate r of its own image as the only
         reference (what evaluate.consensus_rerank reads); the candidates are vectorised once and serve as references"""
-        import torch
         t = self._tokens(candidates)
-        n = int(n_per_image)
-        if n < 1 or t.shape[0] % n:
-            raise ValueError("%d candidates are not %d per image" % (t.shape[0], n))
-        NI = t.shape[0] // n
-        vecs, L = self.vectorise(t)
-        off = torch.arange(0, (NI + 1) * n, n, dtype=torch.int64, device=self.dev)
-        refs = PreparedRefs(vecs, L, NI * n, off, NI, n)
-        owner = torch.arange(NI, dtype=torch.int32, device=self.dev).repeat_interleave(n)
+        refs, owner = self._self_refs(t, n_per_image)
+        refs.recs = self.vectorise(t)[0]
         return self.score_token_ids(t, owner, refs, return_pairs=True)[1]
 
 
@@ -569,10 +508,7 @@ _device_scorers = _weakref.WeakKeyDictionary()      # CiderD -> {device: DeviceC
 
 def _ciderd_device(self, dev):
     """The DeviceCiderD of this scorer on `dev`: built at the first call (table upload), cached per device."""
-    import torch
-    dev = torch.device(dev)
-    if dev.type == "cuda" and dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
+    dev = resolve_device(dev)
     per = _device_scorers.setdefault(self, {})
     if dev not in per:
         per[dev] = DeviceCiderD(self, dev)

@@ -8,60 +8,23 @@
 //   b *= (correct[k] + 1e-15) / (guess[k] + 1e-9);  bleu[k] = b^(1/k);  ratio = (testlen + 1e-15) / (reflen + 1e-9);
 //   ratio < 1: bleu[k] *= exp(1 - 1 / ratio)
 //
-// The conventions of csrc/ciderd_device.hip: ONE WAVE holds a sentence of at most 64 ids, one position per lane, and lane i owns
-// the (up to) four grams that start at position i, packed as id + 1 in 16-bit fields (0 = no gram), so ids lie in [0, 65534).
+// One wave holds a sentence, one position per lane, and lane i owns the (up to) four packed grams that start at position i:
+// csrc/ngram_wave.h states the packing, the limits and the length rules and reads the row (shared with csrc/ciderd_device.hip).
 // Counts are found lane against lane through LDS, all four orders in one pass over the other sentence's length; the
 // statistics are integers, the four orders' clipped counts travel through one xor-butterfly as the bytes of one word (each
 // sum is at most 64).  Scores are double and a function of the row's ten integers alone, so a row's bits cannot depend on the
 // launch it is part of.  No atomics; every store is an ordinary vector store of a declared output.
 #include <cmath>
-#include "set_common.h"
+#include "ngram_wave.h"
 
 namespace {
 
-constexpr int BL_MAXL = 64;                    // one position per lane
-constexpr int64_t BL_PACK_LIMIT = 65534;       // ids + 1 must fit 16 bits and stay below 0xFFFF (as in ciderd_device.hip)
+using namespace set::ngram;
 
 // record of one prepared reference, in 8-byte words:
-//   [0] length   [1] 1: an id outside [0, 65534)   [2..7] 0
+//   [0] length   [1] 1: an id that cannot be packed   [2..7] 0
 //   [8 + 4 i + k]  key of the order-(k+1) gram that starts at position i (0: none), EVERY occurrence (counts need them)
 __host__ __device__ inline size_t bl_ref_words(int L) { return 8 + 4 * (size_t)L; }
-
-struct BlSent {
-    uint64_t key[4];                           // this lane's grams, 0: none
-    int len;
-    bool bad;
-};
-
-// One wave, one sentence: the keys of the grams that start at this lane.  len_in < 0: the decoder's rule (cut after the
-// first 0, the 0 stays; no 0: the whole row).
-__device__ __forceinline__ void bl_keys(const int64_t* row, int len_in, int L, BlSent& S) {
-    const int lane = threadIdx.x & 63;
-    const int64_t t = lane < L ? row[lane] : 1;
-    int len;
-    if (len_in >= 0) len = len_in < L ? len_in : L;
-    else {
-        const unsigned long long z = __ballot(lane < L && t == 0);
-        len = z ? __ffsll((long long)z) : L;
-    }
-    const bool in = lane < len;
-    S.len = len;
-    S.bad = __any(in && (t < 0 || t >= BL_PACK_LIMIT)) != 0;
-    const unsigned f = (in && t >= 0 && t < BL_PACK_LIMIT) ? (unsigned)(t + 1) : 0u;
-    uint64_t key = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const unsigned fk = k == 0 ? f : (unsigned)__shfl_down((int)f, k);
-        key |= (uint64_t)fk << (16 * k);
-        S.key[k] = lane + k < len ? key : 0;
-    }
-}
-
-__device__ __forceinline__ int bl_wave_sum(int v) {            // every lane ends with the sum
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // bleu[1..4] from the ten integers (bleu.py Bleu.scores_from_stats); c: the four clipped counts as bytes of one word
 __device__ __forceinline__ void bl_scores(int c_packed, int testlen, int reflen, double out[4]) {
@@ -84,8 +47,8 @@ __device__ __forceinline__ void bl_scores(int c_packed, int testlen, int reflen,
 __global__ __launch_bounds__(64) void bl_prepare_k(const int64_t* tokens, long long ld, const int* lens, int L, uint64_t* recs) {
     const int lane = threadIdx.x & 63;
     const long long i = blockIdx.x;
-    BlSent S;
-    bl_keys(tokens + i * ld, lens ? (lens[i] < 0 ? 0 : lens[i]) : -1, L, S);
+    WaveSent S;
+    wave_read(tokens, ld, lens, i, L, 4, S);
     uint64_t* v = recs + i * (long long)bl_ref_words(L);
     if (lane < 8) v[lane] = lane == 0 ? (uint64_t)S.len : lane == 1 ? (S.bad ? 1u : 0u) : 0u;
     if (lane < L) {
@@ -104,13 +67,8 @@ __global__ __launch_bounds__(64) void bl_score_k(const int64_t* hyp, long long l
     const int lane = threadIdx.x & 63;
     const long long i = blockIdx.x;
     const double nan = __longlong_as_double(0x7FF8000000000000ll);
-    const int s = set_of[i];
-    long long r0 = 0, r1 = -1;
-    if (s >= 0 && s < n_sets) {
-        r0 = set_off[s];
-        r1 = set_off[s + 1];
-    }
-    if (r0 < 0 || r1 < r0 || r1 > n_refs || r1 - r0 > max_set) {   // cannot be refused on the host: -1 / NaN, nothing else touched
+    long long r0, r1;
+    if (!set_range(set_of, i, set_off, n_sets, n_refs, max_set, r0, r1)) {   // -1 / NaN, nothing else touched
         if (lane < 10) stats[i * 10 + lane] = -1;
         if (scores && lane < 4) scores[i * 4 + lane] = nan;
         return;
@@ -127,25 +85,11 @@ __global__ __launch_bounds__(64) void bl_score_k(const int64_t* hyp, long long l
         nk1 = lane < ref_L ? p[1] : make_ulonglong2(0, 0);
     };
     if (r0 < r1) request(r0);
-    BlSent S;
-    bl_keys(hyp + i * ld, lens ? (lens[i] < 0 ? 0 : lens[i]) : -1, L, S);
-    // count of the own gram in the hypothesis and "first lane of its gram": every lane against positions 0 .. len - 1
-    s_key[2 * lane] = make_ulonglong2(S.key[0], S.key[1]);
-    s_key[2 * lane + 1] = make_ulonglong2(S.key[2], S.key[3]);
-    __syncthreads();
-    int cnt[4] = {0, 0, 0, 0};
-    bool first[4] = {true, true, true, true};
-    for (int j = 0; j < S.len; ++j) {
-        const ulonglong2 a = s_key[2 * j], b = s_key[2 * j + 1];
-        const uint64_t kj[4] = {a.x, a.y, b.x, b.y};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const bool same = kj[k] == S.key[k];
-            cnt[k] += same ? 1 : 0;
-            first[k] = first[k] && !(same && j < lane);
-        }
-    }
-    bool need[4];
+    WaveSent S;
+    wave_read(hyp, ld, lens, i, L, 4, S);
+    int cnt[4];
+    bool first[4], need[4];
+    own_grams(S, s_key, cnt, first);
 #pragma unroll
     for (int k = 0; k < 4; ++k) need[k] = S.key[k] != 0 && first[k];
     bool bad = S.bad;
@@ -178,7 +122,7 @@ __global__ __launch_bounds__(64) void bl_score_k(const int64_t* hyp, long long l
             int c = 0;
 #pragma unroll
             for (int k = 0; k < 4; ++k) c |= (need[k] ? (cnt[k] < m[k] ? cnt[k] : m[k]) : 0) << (8 * k);
-            c = bl_wave_sum(c);
+            c = wave_sum(c);
             double b4[4];
             bl_scores(c, S.len, rlen, b4);
             if (lane == 0) pairs[i * pair_ld + (r - r0)] = bad ? nan : b4[3];
@@ -187,7 +131,7 @@ __global__ __launch_bounds__(64) void bl_score_k(const int64_t* hyp, long long l
     int c = 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) c |= (need[k] ? (cnt[k] < best[k] ? cnt[k] : best[k]) : 0) << (8 * k);
-    c = bl_wave_sum(c);
+    c = wave_sum(c);
     if (lane < 10) {
         int v;
         if (lane < 4) v = bad ? -1 : (c >> (8 * lane)) & 0xFF;
@@ -207,13 +151,13 @@ __global__ __launch_bounds__(64) void bl_score_k(const int64_t* hyp, long long l
 extern "C" {
 
 size_t set_bleu_device_ref_bytes(int n_refs, int L) {
-    if (n_refs < 0 || L < 1 || L > BL_MAXL) return 0;
+    if (n_refs < 0 || L < 1 || L > NG_MAXL) return 0;
     return (size_t)n_refs * bl_ref_words(L) * sizeof(uint64_t);
 }
 
 int set_bleu_device_prepare(const int64_t* tokens, int64_t ld, const int32_t* lens, int n_refs, int L, void* recs, void* stream) {
     if (n_refs < 0 || L < 1 || (n_refs > 0 && (!tokens || !recs || ld < L))) return SET_ERR_ARG;
-    if (L > BL_MAXL) return SET_ERR_UNSUPPORTED;
+    if (L > NG_MAXL) return SET_ERR_UNSUPPORTED;
     if (n_refs == 0) return SET_OK;
     set::ProfScope prof("bleu_prepare", static_cast<hipStream_t>(stream));
     hipLaunchKernelGGL(bl_prepare_k, dim3((unsigned)n_refs), dim3(64), 0, static_cast<hipStream_t>(stream), tokens, (long long)ld,
@@ -225,11 +169,8 @@ int set_bleu_device_prepare(const int64_t* tokens, int64_t ld, const int32_t* le
 int set_bleu_device_score(const int64_t* hyp, int64_t hyp_ld, const int32_t* hyp_lens, int n_hyp, int L, const int32_t* set_of_hyp,
                           const void* ref_recs, int ref_L, int64_t n_refs, const int64_t* ref_set_off, int n_sets, int max_set,
                           int32_t* stats, double* scores, double* pair_scores, int64_t pair_ld, void* stream) {
-    if (n_hyp < 0 || n_sets < 0 || n_refs < 0 || max_set < 0 || L < 1 || ref_L < 1 || !ref_set_off ||
-        (n_hyp > 0 && (!hyp || !set_of_hyp || !stats || hyp_ld < L)) || (n_refs > 0 && !ref_recs) ||
-        (pair_scores && pair_ld < max_set))
-        return SET_ERR_ARG;
-    if (L > BL_MAXL || ref_L > BL_MAXL) return SET_ERR_UNSUPPORTED;
+    if (n_hyp > 0 && !stats) return SET_ERR_ARG;
+    SET_TRY(score_args_check(hyp, hyp_ld, n_hyp, L, set_of_hyp, ref_recs, ref_L, n_refs, ref_set_off, n_sets, max_set, pair_scores, pair_ld));
     if (n_hyp == 0) return SET_OK;
     set::ProfScope prof("bleu_score", static_cast<hipStream_t>(stream));
     hipLaunchKernelGGL(bl_score_k, dim3((unsigned)n_hyp), dim3(64), 0, static_cast<hipStream_t>(stream), hyp, (long long)hyp_ld,

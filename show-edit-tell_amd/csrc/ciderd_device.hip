@@ -6,22 +6,21 @@
 //   sim_n(c, r) = sum_ngram min(g(c), g(r)) * g(r) / (|g(c)| |g(r)|) * exp(-(l_c - l_r)^2 / (2 sigma^2))
 //   CIDEr-D(c)  = 10 / (n |refs|) * sum_n sum_r sim_n(c, r),      l = number of bigrams
 //
-// A sentence is at most 64 vocabulary ids: ONE WAVE holds it, one position per lane, and lane i owns the (up to) four
-// n-grams that start at position i, packed like make_key(.., uint64_t*) of the host scorer (ciderd_host.hip:57-61: id + 1
-// in 16-bit fields, so 0 is "no gram").  Duplicate grams of a sentence are found by comparing every lane's key with the
-// whole sentence's keys through LDS (no sort); the first lane of a gram carries its tf and looks its document count up in
+// One wave holds a sentence, one position per lane, and lane i owns the (up to) four packed n-grams that start at position i:
+// csrc/ngram_wave.h states the packing (the host scorer's), the limits and the length rules, reads the row and finds the
+// duplicate grams of a sentence by comparing every lane's keys with the whole sentence's keys through LDS (no sort; shared with
+// csrc/bleu_device.hip).  The first lane of a gram carries its tf and looks its document count up in
 // an open-addressing table (linear probing, 16-byte {key, df} slots: one load per probe).  Everything is double; sums
 // over lanes are one fixed xor-butterfly, so a row's bits do not depend on the launch it is part of.  No atomics; every
 // store is an ordinary vector store of a declared output.
 #include <cmath>
 #include <cstring>
 #include <vector>
-#include "set_common.h"
+#include "ngram_wave.h"
 
 namespace {
 
-constexpr int CD_MAXL = 64;                    // one position per lane
-constexpr int64_t CD_PACK_LIMIT = 65534;       // ids + 1 must fit 16 bits and stay below 0xFFFF (ciderd_host.hip:62)
+using namespace set::ngram;
 
 struct alignas(16) CdSlot { uint64_t key; double df; };
 
@@ -36,77 +35,35 @@ struct CdHandle {
     CdSlot* slots;
 };
 
-__host__ __device__ inline uint64_t cd_hash(uint64_t x) {      // U64Hash of ciderd_host.hip:46-51
-    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-inline uint64_t cd_make_key(const int64_t* tok, int k) {       // make_key(.., uint64_t*), ciderd_host.hip:57-61
-    uint64_t g = 0;
-    for (int j = 0; j < k; ++j) g |= (uint64_t)(tok[j] + 1) << (16 * j);
-    return g;
-}
-
 // record of one vectorised sentence in the caller's workspace, in 8-byte words:
-//   [0..3] norm of order 1..4 (double)   [4] number of bigrams   [5] length   [6] 1: an id outside [0, 65534)   [7] 0
+//   [0..3] norm of order 1..4 (double)   [4] number of bigrams   [5] length   [6] 1: an id that cannot be packed   [7] 0
 //   [8 + k L + i]        key of the order-(k+1) gram that starts at position i (0: none, or a repeat of an earlier one)
 //   [8 + 4 L + k L + i]  its weight tf * (log ref_len - log max(1, df)) (double; 0 where the key is 0)
 __host__ __device__ inline size_t cd_vec_words(int L) { return 8 + 8 * (size_t)L; }
 
-__device__ __forceinline__ double cd_wave_sum(double v) {      // fixed shape: every lane ends with the same bits
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // the length the penalty uses: the bigrams that were counted (none with n = 1: ciderd_host.hip:94, ciderd.py:121-122)
 __device__ __forceinline__ int cd_bigrams(const CdTable& T, int len) { return T.n >= 2 && len > 1 ? len - 1 : 0; }
 
-struct CdSent {
-    uint64_t key[4];
+struct CdSent : WaveSent {                     // key: kept on the first lane of each gram only
     double w[4];
     double norm[4];
-    int len;
-    bool bad;
 };
 
-// One wave, one sentence (ciderd_host.hip:77-99).  row: L ids; len_in < 0: the decoder's rule of ciderd.py:222-224 (cut
-// after the first 0, the 0 stays; no 0: the whole row).  s_key: 64 words of LDS of this wave.  Block = one wave.
-__device__ __forceinline__ void cd_vectorise(const CdTable& T, const int64_t* row, int len_in, int L, uint64_t* s_key, CdSent& S) {
+// One wave, row i of `tokens` (ciderd_host.hip Table::vectorise); tokens, ld, lens, L as wave_read takes them.  s_key: the LDS of
+// own_grams.  Block = one wave.
+__device__ __forceinline__ void cd_vectorise(const CdTable& T, const int64_t* tokens, long long ld, const int* lens, long long i, int L,
+                                             ulonglong2* s_key, CdSent& S) {
     const int lane = threadIdx.x & 63;
-    const int64_t t = lane < L ? row[lane] : 1;
-    int len;
-    if (len_in >= 0) len = len_in < L ? len_in : L;
-    else {
-        const unsigned long long z = __ballot(lane < L && t == 0);
-        len = z ? __ffsll((long long)z) : L;
-    }
-    const bool in = lane < len;
-    S.len = len;
-    S.bad = __any(in && (t < 0 || t >= CD_PACK_LIMIT)) != 0;
-    const unsigned f = (in && t >= 0 && t < CD_PACK_LIMIT) ? (unsigned)(t + 1) : 0u;
-    uint64_t key = 0;
-    bool need[4];
+    wave_read(tokens, ld, lens, i, L, T.n, S);
     int cnt[4];
+    bool need[4];                                                 // the first lane of a gram carries its tf
+    own_grams(S, s_key, cnt, need);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const unsigned fk = k == 0 ? f : (unsigned)__shfl_down((int)f, k);
-        key |= (uint64_t)fk << (16 * k);
-        const bool valid = k < T.n && lane + k < len;
-        S.key[k] = valid ? key : 0;
-        // tf and "first lane of its gram" by lane-against-lane comparison: len - k grams of this order
-        __syncthreads();
-        s_key[lane] = S.key[k];
-        __syncthreads();
-        int c = 0;
-        bool first = true;
-        const int ng = k < T.n ? len - k : 0;
-        for (int j = 0; j < ng; ++j) {
-            const bool same = s_key[j] == S.key[k];
-            c += same ? 1 : 0;
-            first = first && !(same && j < lane);
-        }
-        need[k] = valid && first;
-        cnt[k] = c;
+        need[k] = need[k] && k < T.n && lane + k < S.len;
+        // a gram made only of ids that cannot be packed has the key 0 (its row is refused, its record is still written): the k
+        // empty entries behind len - k are not occurrences of it
+        if (S.key[k] == 0) cnt[k] -= k;
         if (!need[k]) S.key[k] = 0;
     }
     // document counts: the four orders' first probes are in flight together
@@ -114,7 +71,7 @@ __device__ __forceinline__ void cd_vectorise(const CdTable& T, const int64_t* ro
     CdSlot got[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        slot[k] = cd_hash(S.key[k]) & T.mask;
+        slot[k] = hash(S.key[k]) & T.mask;
         got[k] = need[k] ? T.slots[slot[k]] : CdSlot{0, 0.0};
     }
 #pragma unroll
@@ -126,17 +83,17 @@ __device__ __forceinline__ void cd_vectorise(const CdTable& T, const int64_t* ro
         }
         const double d = (need[k] && got[k].key == S.key[k]) ? got[k].df : 0.0;
         S.w[k] = need[k] ? (double)cnt[k] * (T.log_ref_len - log(fmax(1.0, d))) : 0.0;
-        S.norm[k] = sqrt(cd_wave_sum(S.w[k] * S.w[k]));
+        S.norm[k] = sqrt(wave_sum(S.w[k] * S.w[k]));
     }
 }
 
 __global__ __launch_bounds__(64) void cd_vectorise_k(CdTable T, const int64_t* tokens, long long ld, const int* lens, int L,
                                                      uint64_t* vecs) {
-    __shared__ uint64_t s_key[64];
+    __shared__ ulonglong2 s_key[2 * 64];
     const int lane = threadIdx.x & 63;
     const long long i = blockIdx.x;
     CdSent S;
-    cd_vectorise(T, tokens + i * ld, lens ? (lens[i] < 0 ? 0 : lens[i]) : -1, L, s_key, S);
+    cd_vectorise(T, tokens, ld, lens, i, L, s_key, S);
     uint64_t* v = vecs + i * (long long)cd_vec_words(L);
     if (lane < 8) {
         uint64_t h = 0;
@@ -161,7 +118,7 @@ __global__ __launch_bounds__(64) void cd_lookup_k(CdTable T, const uint64_t* key
     const uint64_t key = keys[i];
     double d = 0.0;
     if (key != 0) {
-        uint64_t slot = cd_hash(key) & T.mask, left = T.mask;
+        uint64_t slot = hash(key) & T.mask, left = T.mask;
         CdSlot g = T.slots[slot];
         while (g.key != key && g.key != 0 && left-- > 0) {
             slot = (slot + 1) & T.mask;
@@ -177,19 +134,14 @@ __global__ __launch_bounds__(64) void cd_lookup_k(CdTable T, const uint64_t* key
 __global__ __launch_bounds__(64) void cd_score_k(CdTable T, const int64_t* hyp, long long ld, const int* lens, int L, const int* set_of,
                                                  const uint64_t* ref_vecs, int ref_L, long long n_refs, const int64_t* set_off,
                                                  int n_sets, int max_set, double* scores, double* pairs, long long pair_ld) {
-    __shared__ uint64_t s_key[4 * 64];
+    __shared__ ulonglong2 s_own[2 * 64];                           // the hypothesis against itself, then one reference's keys
     __shared__ double s_w[4 * 64];
     __shared__ uint64_t s_hdr[8];
     const int lane = threadIdx.x & 63;
     const long long i = blockIdx.x;
     const double nan = __longlong_as_double(0x7FF8000000000000ll);
-    const int s = set_of[i];
-    if (s < 0 || s >= n_sets) {                                    // cannot be refused on the host: NaN, nothing else touched
-        if (lane == 0) scores[i] = nan;
-        return;
-    }
-    const long long r0 = set_off[s], r1 = set_off[s + 1];
-    if (r0 < 0 || r1 < r0 || r1 > n_refs || r1 - r0 > max_set) {
+    long long r0, r1;
+    if (!set_range(set_of, i, set_off, n_sets, n_refs, max_set, r0, r1)) {   // NaN, nothing else touched
         if (lane == 0) scores[i] = nan;
         return;
     }
@@ -206,7 +158,8 @@ __global__ __launch_bounds__(64) void cd_score_k(CdTable T, const int64_t* hyp, 
     };
     if (r0 < r1) request(r0);
     CdSent S;
-    cd_vectorise(T, hyp + i * ld, lens ? (lens[i] < 0 ? 0 : lens[i]) : -1, L, s_key, S);
+    cd_vectorise(T, hyp, ld, lens, i, L, s_own, S);
+    uint64_t* s_key = reinterpret_cast<uint64_t*>(s_own);          // [order][position] from here on
     const long long lh = cd_bigrams(T, S.len);
     bool bad = S.bad;
     double tot[4] = {0.0, 0.0, 0.0, 0.0};
@@ -236,7 +189,7 @@ __global__ __launch_bounds__(64) void cd_score_k(CdTable T, const int64_t* hyp, 
                     const double wj = s_w[k * 64 + j];
                     if (kj == S.key[k] && kj != 0) p = fmin(S.w[k], wj) * wj;       // keys of a record are distinct
                 }
-                double sum = cd_wave_sum(p);
+                double sum = wave_sum(p);
                 const double rn = __longlong_as_double((long long)s_hdr[k]);
                 if (S.norm[k] != 0.0 && rn != 0.0) sum /= S.norm[k] * rn;
                 tot[k] += sum * penalty;
@@ -261,8 +214,8 @@ extern "C" {
 int set_ciderd_device_key(const int64_t* tokens, int k, uint64_t* key_out) {
     if (!tokens || !key_out || k < 1 || k > 4) return SET_ERR_ARG;
     for (int j = 0; j < k; ++j)
-        if (tokens[j] < 0 || tokens[j] >= CD_PACK_LIMIT) return SET_ERR_UNSUPPORTED;
-    *key_out = cd_make_key(tokens, k);
+        if (!packable(tokens[j])) return SET_ERR_UNSUPPORTED;
+    *key_out = make_key(tokens, k);
     return SET_OK;
 }
 
@@ -274,14 +227,14 @@ int set_ciderd_device_create(const int64_t* tokens, const int32_t* lens, const d
         return SET_ERR_ARG;
     for (int64_t i = 0; i < n_entries; ++i)
         for (int j = 0; j < lens[i] && j < 4; ++j)
-            if (tokens[4 * i + j] < 0 || tokens[4 * i + j] >= CD_PACK_LIMIT) return SET_ERR_UNSUPPORTED;
+            if (!packable(tokens[4 * i + j])) return SET_ERR_UNSUPPORTED;
     uint64_t cap = 2;
     while (cap < 2 * (uint64_t)n_entries) cap <<= 1;
     std::vector<CdSlot> host((size_t)cap, CdSlot{0, 0.0});
     for (int64_t i = 0; i < n_entries; ++i) {
         if (lens[i] < 1 || lens[i] > 4) continue;
-        const uint64_t key = cd_make_key(tokens + 4 * i, lens[i]);
-        uint64_t slot = cd_hash(key) & (cap - 1);
+        const uint64_t key = make_key(tokens + 4 * i, lens[i]);
+        uint64_t slot = hash(key) & (cap - 1);
         while (host[slot].key != 0 && host[slot].key != key) slot = (slot + 1) & (cap - 1);
         host[slot] = CdSlot{key, df[i]};                           // a repeated gram: the last count stands, as on the host
     }
@@ -320,14 +273,14 @@ int set_ciderd_device_lookup(void* handle, const uint64_t* keys, int64_t n, doub
 }
 
 size_t set_ciderd_device_vec_bytes(int n_sent, int L) {
-    if (n_sent < 0 || L < 1 || L > CD_MAXL) return 0;
+    if (n_sent < 0 || L < 1 || L > NG_MAXL) return 0;
     return (size_t)n_sent * cd_vec_words(L) * sizeof(uint64_t);
 }
 
 int set_ciderd_device_vectorise(void* handle, const int64_t* tokens, int64_t ld, const int32_t* lens, int n_sent, int L,
                                 void* vecs, void* stream) {
     if (!handle || n_sent < 0 || L < 1 || (n_sent > 0 && (!tokens || !vecs || ld < L))) return SET_ERR_ARG;
-    if (L > CD_MAXL) return SET_ERR_UNSUPPORTED;
+    if (L > NG_MAXL) return SET_ERR_UNSUPPORTED;
     if (n_sent == 0) return SET_OK;
     const CdHandle* h = static_cast<const CdHandle*>(handle);
     set::ProfScope prof("ciderd_vectorise", static_cast<hipStream_t>(stream));
@@ -341,11 +294,9 @@ int set_ciderd_device_score(void* handle, const int64_t* hyp_tokens, int64_t hyp
                             const int32_t* set_of_hyp, const void* ref_vecs, int ref_L, int64_t n_refs,
                             const int64_t* ref_set_off, int n_sets, int max_set, double* scores, double* pair_scores,
                             int64_t pair_ld, void* stream) {
-    if (!handle || n_hyp < 0 || n_sets < 0 || n_refs < 0 || max_set < 0 || L < 1 || ref_L < 1 || !ref_set_off ||
-        (n_hyp > 0 && (!hyp_tokens || !set_of_hyp || !scores || hyp_ld < L)) || (n_refs > 0 && !ref_vecs) ||
-        (pair_scores && pair_ld < max_set))
-        return SET_ERR_ARG;
-    if (L > CD_MAXL || ref_L > CD_MAXL) return SET_ERR_UNSUPPORTED;
+    if (!handle || (n_hyp > 0 && !scores)) return SET_ERR_ARG;
+    SET_TRY(score_args_check(hyp_tokens, hyp_ld, n_hyp, L, set_of_hyp, ref_vecs, ref_L, n_refs, ref_set_off, n_sets, max_set, pair_scores,
+                             pair_ld));
     if (n_hyp == 0) return SET_OK;
     const CdHandle* h = static_cast<const CdHandle*>(handle);
     set::ProfScope prof("ciderd_score", static_cast<hipStream_t>(stream));

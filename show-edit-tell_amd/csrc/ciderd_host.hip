@@ -16,13 +16,13 @@
 #include <algorithm>
 #include <cstdlib>
 #include <thread>
-#include "set_common.h"
+#include "ngram_wave.h"
 
 namespace {
 
-// An n-gram key.  Wide: (length, 4 ids).  Packed: when every interned token id is below 65535 (any realistic caption
-// vocabulary) the four ids + 1 fit one 64-bit word — sorting, comparing and hashing a sentence's n-grams then works on
-// plain integers (3x faster scoring than with the 40-byte key).
+// An n-gram key.  Wide: (length, 4 ids).  Packed: when every interned token id is below the pack limit of csrc/ngram_wave.h (any
+// realistic caption vocabulary) the four ids + 1 fit one 64-bit word — sorting, comparing and hashing a sentence's n-grams then
+// works on plain integers (3x faster scoring than with the 40-byte key).  The packing and the hash are the device scorers'.
 struct Gram {
     int64_t t[4];
     int32_t n;
@@ -44,22 +44,15 @@ struct GramHash {
     }
 };
 struct U64Hash {
-    size_t operator()(uint64_t x) const {
-        x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull;
-        return (size_t)(x ^ (x >> 31));
-    }
+    size_t operator()(uint64_t x) const { return (size_t)set::ngram::hash(x); }
 };
 inline Gram make_key(const int64_t* tok, int k, Gram*) {
     Gram g{{0, 0, 0, 0}, k};
     for (int j = 0; j < k; ++j) g.t[j] = tok[j];
     return g;
 }
-inline uint64_t make_key(const int64_t* tok, int k, uint64_t*) {      // ids + 1 in 16-bit fields: the length is implied
-    uint64_t g = 0;
-    for (int j = 0; j < k; ++j) g |= (uint64_t)(tok[j] + 1) << (16 * j);
-    return g;
-}
-constexpr int64_t PACK_LIMIT = 65534;
+inline uint64_t make_key(const int64_t* tok, int k, uint64_t*) { return set::ngram::make_key(tok, k); }
+using set::ngram::packable;
 
 template <class K>
 struct Vec {                                   // tf-idf vector of one sentence, per n-gram order
@@ -158,7 +151,7 @@ struct Table {
 
 struct Scorer {
     Table<Gram, GramHash> wide;                // always filled
-    Table<uint64_t, U64Hash> packed;           // filled when every df token id is below PACK_LIMIT
+    Table<uint64_t, U64Hash> packed;           // filled when every df token id is packable
     bool packable = true;
     double log_ref_len, sigma;
     int n;
@@ -178,7 +171,7 @@ void* set_ciderd_create(const int64_t* tokens, const int32_t* lens, const double
     s->wide.df.reserve((size_t)n_entries * 2 + 16);
     for (int64_t i = 0; i < n_entries && s->packable; ++i)
         for (int j = 0; j < lens[i] && j < 4; ++j)
-            if (tokens[4 * i + j] < 0 || tokens[4 * i + j] >= PACK_LIMIT) s->packable = false;
+            if (!packable(tokens[4 * i + j])) s->packable = false;
     if (s->packable) s->packed.df.reserve((size_t)n_entries * 2 + 16);
     for (int64_t i = 0; i < n_entries; ++i) {
         if (lens[i] < 1 || lens[i] > 4) continue;
@@ -203,8 +196,8 @@ int set_ciderd_score(void* h, const int64_t* hyp_tokens, const int64_t* hyp_off,
         if (set_of_hyp[i] < 0 || set_of_hyp[i] >= n_sets) return SET_ERR_ARG;
     const int64_t n_refs = n_sets > 0 ? ref_set_off[n_sets] : 0;
     bool small = S.packable;                                  // sentence tokens may be words the df table never saw
-    for (int64_t k = 0, e = n_hyp > 0 ? hyp_off[n_hyp] : 0; small && k < e; ++k) small = hyp_tokens[k] >= 0 && hyp_tokens[k] < PACK_LIMIT;
-    for (int64_t k = 0, e = n_refs > 0 ? ref_off[n_refs] : 0; small && k < e; ++k) small = ref_tokens[k] >= 0 && ref_tokens[k] < PACK_LIMIT;
+    for (int64_t k = 0, e = n_hyp > 0 ? hyp_off[n_hyp] : 0; small && k < e; ++k) small = packable(hyp_tokens[k]);
+    for (int64_t k = 0, e = n_refs > 0 ? ref_off[n_refs] : 0; small && k < e; ++k) small = packable(ref_tokens[k]);
     if (small)
         return S.packed.score(hyp_tokens, hyp_off, n_hyp, set_of_hyp, ref_tokens, ref_off, ref_set_off, n_sets, scores, S.n,
                               S.log_ref_len, S.sigma);

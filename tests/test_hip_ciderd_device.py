@@ -190,7 +190,7 @@ def test_pair_scores_against_single_references(world, scorers):
 def _raw_score(dsc, H, set_of, refs, scores, pairs, pair_ld):
     from show_edit_tell_amd import _lib
     rc = dsc._lib.set_ciderd_device_score(dsc._h, H.data_ptr(), H.stride(0), None, H.shape[0], H.shape[1], set_of.data_ptr(),
-                                          refs.vecs.data_ptr(), refs.L, refs.n_refs, refs.set_off.data_ptr(), refs.n_sets,
+                                          refs.recs.data_ptr(), refs.L, refs.n_refs, refs.set_off.data_ptr(), refs.n_sets,
                                           refs.max_set, scores.data_ptr(), None if pairs is None else pairs.data_ptr(), pair_ld,
                                           _lib.stream_of(dsc.dev))
     _lib.check(rc, "set_ciderd_device_score")
