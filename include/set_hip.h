@@ -1336,6 +1336,31 @@ int set_bleu_device_score(const int64_t* hyp, int64_t hyp_ld, const int32_t* hyp
                           const void* ref_recs, int ref_L, int64_t n_refs, const int64_t* ref_set_off, int n_sets, int max_set,
                           int32_t* stats, double* scores, double* pair_scores, int64_t pair_ld, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * ROUGE-L on the DEVICE (csrc/rouge_device.hip): the statistics and score of coco-caption's Rouge as rouge.py states them, from id
+ * rows in device memory on `stream` with no host read.  Sentences and their limits are those of the BLEU block above, and the
+ * references are ITS records: size them with set_bleu_device_ref_bytes, write them with set_bleu_device_prepare; one preparation
+ * serves set_bleu_device_score and this entry.  Stateless: there is no handle.
+ *   lcs(h, r) = the length of the longest common subsequence;  lcs_p = max_r lcs(h, r);  (lcs_r, len_r) = lcs and length of the
+ *   reference with the largest recall lcs / len_r (compared exactly, as fractions; of equal recalls the first of the set; a
+ *   reference of no ids is skipped, (0, 0) if all are empty);  P = lcs_p / len_h, Rc = lcs_r / len_r, and with both non-zero
+ *   score = (1 + beta^2) P Rc / (Rc + beta^2 P), else 0 (coco: beta = 1.2).  The statistics are integers; the score is double, in
+ *   this order of operations without contraction, and a function of the row's integers alone, so a row's result does not depend
+ *   on the launch it is part of.  No atomics; only the declared outputs are written.
+ * score: hypothesis i, reference sets, L, hyp_lens, ref_L, n_refs, ref_set_off, n_sets, max_set as in set_bleu_device_score.  One
+ *   wave per hypothesis writes stats[i, 0..4) = lcs_p, len_h, lcs_r, len_r (int32), with scores != NULL scores[i], and with
+ *   pair_scores != NULL pair_scores[i pair_ld + r] = the sentence's score against reference r of its set alone, r < |set|; nothing
+ *   else is written.  An empty set gives 0, len_h, 0, 0 and the score 0.  What the host cannot check is answered by the kernel with
+ *   -1 in stats[i, :] and NaN in scores[i], nothing else touched: set_of_hyp[i] outside [0, n_sets), offsets outside [0, n_refs]
+ *   or decreasing, a set larger than max_set.  An id outside [0, 65534) in the hypothesis or one of its references gives -1 in
+ *   stats[i, :] and a NaN score in that row (and NaN pair scores from the first such sentence on).
+ *   SET_ERR_ARG: NULL stats, beta not finite or not positive, and what set_bleu_device_score refuses with it;
+ *   SET_ERR_UNSUPPORTED: L or ref_L > 64 — before any HIP call.  n_hyp == 0: nothing is done.
+ * ------------------------------------------------------------------------------------------ */
+int set_rouge_device_score(const int64_t* hyp, int64_t hyp_ld, const int32_t* hyp_lens, int n_hyp, int L, const int32_t* set_of_hyp,
+                           const void* ref_recs, int ref_L, int64_t n_refs, const int64_t* ref_set_off, int n_sets, int max_set,
+                           double beta, int32_t* stats, double* scores, double* pair_scores, int64_t pair_ld, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

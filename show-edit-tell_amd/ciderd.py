@@ -313,16 +313,27 @@ def _bleu4_term(bleu_scorer, bleu_weight, sampled, greedy, ground_truth):
     return bleu_weight * (b[:B] - b[B:])
 
 
-def self_critical_reward(scorer, sampled, greedy, ground_truth, cider_weight=1.0, bleu_scorer=None, bleu_weight=0.0):
+def _rouge_term(rouge_scorer, rouge_weight, sampled, greedy, ground_truth):
+    """rouge_weight * (ROUGE-L(sampled_b) - ROUGE-L(greedy_b)) in double: rouge.RougeL.score_token_ids under the rows' 0 rule"""
+    B = sampled.shape[0]
+    sets, hyp_set = _reward_sets(ground_truth, B)
+    r = np.asarray(rouge_scorer.score_token_ids(np.concatenate([sampled, greedy], 0), hyp_set, sets)[1], dtype=np.float64)
+    return rouge_weight * (r[:B] - r[B:])
+
+
+def self_critical_reward(scorer, sampled, greedy, ground_truth, cider_weight=1.0, bleu_scorer=None, bleu_weight=0.0,
+                         rouge_scorer=None, rouge_weight=0.0):
     """reward[b, :] = CIDEr-D(sampled_b) - CIDEr-D(greedy_b), repeated over the max_len columns
     (editnet_rl.py:611-646).  sampled/greedy: (B, max_len) integer arrays/tensors; returns float32 numpy.
     With a `bleu_scorer` (bleu.Bleu) and bleu_weight != 0 the reward of the self-critical code base:
-    cider_weight * dCIDEr-D + bleu_weight * dBLEU-4, mixed in double and then cast; otherwise the scorer sees the calls it
-    saw before the argument existed."""
+    cider_weight * dCIDEr-D + bleu_weight * dBLEU-4, mixed in double and then cast; with a `rouge_scorer` (rouge.RougeL) and
+    rouge_weight != 0: + rouge_weight * dROUGE-L, in the same sum; otherwise the scorers see the calls they saw before the
+    arguments existed."""
     sampled = np.asarray(sampled.cpu() if hasattr(sampled, 'cpu') else sampled)
     greedy = np.asarray(greedy.cpu() if hasattr(greedy, 'cpu') else greedy)
     B = sampled.shape[0]
     mix = bleu_scorer is not None and bleu_weight != 0.0
+    mix_rouge = rouge_scorer is not None and rouge_weight != 0.0
     if getattr(scorer, "_handle", None) is not None and scorer._handle() is not None:
         # integer fast path (no strings): the reference sets of the distinct images once, all 2B captions in one call
         sets, hyp_set = _reward_sets(ground_truth, B)
@@ -330,6 +341,8 @@ def self_critical_reward(scorer, sampled, greedy, ground_truth, cider_weight=1.0
         diff = cider_weight * (s[:B] - s[B:])
         if mix:
             diff = diff + _bleu4_term(bleu_scorer, bleu_weight, sampled, greedy, ground_truth)
+        if mix_rouge:
+            diff = diff + _rouge_term(rouge_scorer, rouge_weight, sampled, greedy, ground_truth)
         return np.repeat(diff[:, None], sampled.shape[1], 1).astype(np.float32)
     memo = {}                    # the same image's reference lists are repeated once per sample: stringify them once
 
@@ -347,6 +360,8 @@ def self_critical_reward(scorer, sampled, greedy, ground_truth, cider_weight=1.0
     diff = cider_weight * (s[:B] - s[B:])
     if mix:
         diff = diff + _bleu4_term(bleu_scorer, bleu_weight, sampled, greedy, ground_truth)
+    if mix_rouge:
+        diff = diff + _rouge_term(rouge_scorer, rouge_weight, sampled, greedy, ground_truth)
     return np.repeat(diff[:, None], sampled.shape[1], 1).astype(np.float32)
 
 
@@ -519,10 +534,12 @@ CiderD.device = _ciderd_device
 
 
 def self_critical_reward_device(dscorer, sampled, greedy, refs, image_of=None, cider_weight=1.0, bleu_scorer=None, bleu_refs=None,
-                                bleu_weight=0.0):
+                                bleu_weight=0.0, rouge_scorer=None, rouge_refs=None, rouge_weight=0.0):
     """Device twin of self_critical_reward: reward[b, :] = cider_weight * (CIDEr-D(sampled_b) - CIDEr-D(greedy of its image)).
     With a `bleu_scorer` (bleu.DeviceBleu), `bleu_refs` (its PreparedBleuRefs of the NI images, or their reference sets) and
     bleu_weight != 0: + bleu_weight * (BLEU-4(sampled_b) - BLEU-4(greedy of its image)), one more launch over the same rows.
+    With a `rouge_scorer` (rouge.DeviceRougeL), `rouge_refs` and rouge_weight != 0: + rouge_weight * (ROUGE-L(sampled_b) -
+    ROUGE-L(greedy of its image)) likewise; rouge_refs may be the very PreparedBleuRefs passed as bleu_refs (one layout).
     sampled (N, L) and greedy (NI, L) device id tensors, refs the PreparedRefs of the NI images (or their reference sets),
     image_of (N,) device index of each sample's image (None: row b belongs to image b % NI, the order of the repeated
     rollout).  The greedy captions are scored once per image; the difference is taken in double and then cast, as on the
@@ -546,4 +563,9 @@ def self_critical_reward_device(dscorer, sampled, greedy, refs, image_of=None, c
             raise ValueError("the BLEU term needs bleu_refs: the images' reference sets or DeviceBleu.prepare_refs of them")
         b = bleu_scorer.score_token_ids(rows, rows_set, bleu_refs)[1][:, 3]
         diff = diff + bleu_weight * (b[:N] - b[N:][image_of])
+    if rouge_scorer is not None and rouge_weight != 0.0:
+        if rouge_refs is None:
+            raise ValueError("the ROUGE-L term needs rouge_refs: the images' reference sets or a device scorer's prepare_refs of them")
+        r = rouge_scorer.score_token_ids(rows, rows_set, rouge_refs)[1]
+        diff = diff + rouge_weight * (r[:N] - r[N:][image_of])
     return diff.to(torch.float32)[:, None].expand(N, sampled.shape[1]).contiguous()

@@ -12,7 +12,8 @@
 // csrc/ngram_wave.h states the packing, the limits and the length rules and reads the row (shared with csrc/ciderd_device.hip).
 // Counts are found lane against lane through LDS, all four orders in one pass over the other sentence's length; the
 // statistics are integers, the four orders' clipped counts travel through one xor-butterfly as the bytes of one word (each
-// sum is at most 64).  Scores are double and a function of the row's ten integers alone, so a row's bits cannot depend on the
+// sum is at most 64).  A prepared reference is one record of ngram_wave.h's layout (ref_rec_words; csrc/rouge_device.hip reads
+// the same records).  Scores are double and a function of the row's ten integers alone, so a row's bits cannot depend on the
 // launch it is part of.  No atomics; every store is an ordinary vector store of a declared output.
 #include <cmath>
 #include "ngram_wave.h"
@@ -20,11 +21,6 @@
 namespace {
 
 using namespace set::ngram;
-
-// record of one prepared reference, in 8-byte words:
-//   [0] length   [1] 1: an id that cannot be packed   [2..7] 0
-//   [8 + 4 i + k]  key of the order-(k+1) gram that starts at position i (0: none), EVERY occurrence (counts need them)
-__host__ __device__ inline size_t bl_ref_words(int L) { return 8 + 4 * (size_t)L; }
 
 // bleu[1..4] from the ten integers (bleu.py Bleu.scores_from_stats); c: the four clipped counts as bytes of one word
 __device__ __forceinline__ void bl_scores(int c_packed, int testlen, int reflen, double out[4]) {
@@ -49,7 +45,7 @@ __global__ __launch_bounds__(64) void bl_prepare_k(const int64_t* tokens, long l
     const long long i = blockIdx.x;
     WaveSent S;
     wave_read(tokens, ld, lens, i, L, 4, S);
-    uint64_t* v = recs + i * (long long)bl_ref_words(L);
+    uint64_t* v = recs + i * (long long)ref_rec_words(L);
     if (lane < 8) v[lane] = lane == 0 ? (uint64_t)S.len : lane == 1 ? (S.bad ? 1u : 0u) : 0u;
     if (lane < L) {
         ulonglong2* p = reinterpret_cast<ulonglong2*>(v + 8 + 4 * lane);      // records are 64 bytes + 32 per position
@@ -73,7 +69,7 @@ __global__ __launch_bounds__(64) void bl_score_k(const int64_t* hyp, long long l
         if (scores && lane < 4) scores[i * 4 + lane] = nan;
         return;
     }
-    const size_t words = bl_ref_words(ref_L);
+    const size_t words = ref_rec_words(ref_L);
     ulonglong2 nk0, nk1;                                           // the record in flight
     uint64_t nlen = 0, nbad = 0;
     auto request = [&](long long r) {
@@ -152,7 +148,7 @@ extern "C" {
 
 size_t set_bleu_device_ref_bytes(int n_refs, int L) {
     if (n_refs < 0 || L < 1 || L > NG_MAXL) return 0;
-    return (size_t)n_refs * bl_ref_words(L) * sizeof(uint64_t);
+    return (size_t)n_refs * ref_rec_words(L) * sizeof(uint64_t);
 }
 
 int set_bleu_device_prepare(const int64_t* tokens, int64_t ld, const int32_t* lens, int n_refs, int L, void* recs, void* stream) {

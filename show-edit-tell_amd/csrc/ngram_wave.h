@@ -1,6 +1,6 @@
-// What the n-gram metrics share (csrc/ciderd_device.hip, csrc/bleu_device.hip, csrc/ciderd_host.hip): the packing of an n-gram
-// into one 64-bit key, the hash of such a key, the two limits, and the device leaves that turn one row of ids into one wave's
-// keys.  The rules stated here are the contract between CIDEr-D and BLEU on the device, the host scorer, the reward mix and
+// What the sentence metrics share (csrc/ciderd_device.hip, csrc/bleu_device.hip, csrc/rouge_device.hip, csrc/ciderd_host.hip):
+// the packing of an n-gram into one 64-bit key, the hash of such a key, the two limits, the prepared-reference record of BLEU
+// and ROUGE-L, and the device leaves that turn one row of ids into one wave's keys.  The rules stated here are the contract between CIDEr-D and BLEU on the device, the host scorer, the reward mix and
 // evaluate.consensus_rerank; device_metric.py states the same two limits and the 0 rule for the Python side.
 //
 // A sentence is at most NG_MAXL ids: ONE WAVE holds it, one position per lane, and lane i owns the (up to) four grams that start
@@ -27,7 +27,13 @@ __host__ __device__ inline uint64_t hash(uint64_t x) {         // the 64-bit mix
     return x ^ (x >> 31);
 }
 
-// The argument checks that the score entries of both metrics share (include/set_hip.h: the same parameters under the same names);
+// record of one prepared reference, in 8-byte words (written by csrc/bleu_device.hip bl_prepare_k; read there and by
+// csrc/rouge_device.hip, which needs words 0, 1 and the order-1 key of every position):
+//   [0] length   [1] 1: an id that cannot be packed   [2..7] 0
+//   [8 + 4 i + k]  key of the order-(k+1) gram that starts at position i (0: none), EVERY occurrence (counts need them)
+__host__ __device__ inline size_t ref_rec_words(int L) { return 8 + 4 * (size_t)L; }
+
+// The argument checks that the score entries of the metrics share (include/set_hip.h: the same parameters under the same names);
 // an entry checks its own pointers (handle, scores, stats) BEFORE this, so that a bad argument wins over an unsupported length.
 inline int score_args_check(const void* hyp, int64_t hyp_ld, int n_hyp, int L, const void* set_of_hyp, const void* ref_recs, int ref_L,
                             int64_t n_refs, const void* ref_set_off, int n_sets, int max_set, const void* pair_scores, int64_t pair_ld) {

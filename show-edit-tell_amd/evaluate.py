@@ -1163,7 +1163,8 @@ def consensus_rerank(scorer, candidates, n_per_image, weights=None):
     candidates: (NI * n, L) id tensor in the decoder's format (0 = <end>, rows i * n .. i * n + n - 1 belong to image i);
     `scorer.pair_scores(candidates, n)` gives the (NI * n, n) CIDEr-D of every candidate against each candidate of its image
     as the only reference (csrc/ciderd_device.hip: the candidates are each other's references and never leave the device).
-    Any object with that method serves: bleu.DeviceBleu(dev) reranks under sentence BLEU-4 instead (csrc/bleu_device.hip).
+    Any object with that method serves: bleu.DeviceBleu(dev) reranks under sentence BLEU-4 instead (csrc/bleu_device.hip),
+    rouge.DeviceRougeL(dev) under ROUGE-L (csrc/rouge_device.hip).
     utility[i, j] = mean over the OTHER candidates r != j of that score (the diagonal is left out; identical candidates are
     separate votes), or with weights (NI, n) — e.g. sbs_importance_weights per image — the weighted mean
     sum_{r != j} w[i, r] s[j, r] / sum_{r != j} w[i, r] (0 where that sum is 0).  n = 1: utility 0, index 0.
@@ -1220,7 +1221,32 @@ def consensus_rerank_lists(scorer, captions, weights=None, word_map=None):
     return best, util
 
 
-# ---- validation BLEU (the `Bleu_4` of the reference's evaluate(): editnet_rl.py:834/897, dcnet.py:541-611) -----------------
+# ---- validation BLEU and ROUGE-L (the `Bleu_1..4` / `ROUGE_L` of the reference's evaluate(): editnet_rl.py:834/897, dcnet.py:541-611)
+def _validation_rows(captions, hyp_set, dev, count_end, word_map):
+    """The caption-normalising front of the validation scores: captions in either input form (see validation_bleu) ->
+    ((N, L) id tensor on `dev`, (N,) set index on `dev`, lengths or None for the 0 rule)."""
+    lens = None
+    if word_map is not None:
+        drop, end = {int(word_map['<start>']), int(word_map['<pad>'])}, int(word_map['<end>'])
+        rows = [[0 if int(w) == end else int(w) for w in c if int(w) not in drop] for c in captions]
+        rows = [c[:c.index(0) + (1 if count_end else 0)] if 0 in c else c for c in rows]
+        captions = torch.zeros(len(rows), max([1] + [len(c) for c in rows]), dtype=torch.int64)
+        for i, c in enumerate(rows):
+            captions[i, :len(c)] = torch.tensor(c, dtype=torch.int64)
+        # a list that never reached <end> (the step limit) ends where it stops: explicit lengths, not the 0 rule
+        lens = torch.tensor([len(c) for c in rows], dtype=torch.int32)
+    captions = torch.as_tensor(captions).to(dev)
+    if captions.dim() != 2:
+        raise ValueError("captions are rows of a 2-D id tensor, got shape %s" % (tuple(captions.shape),))
+    N, L = captions.shape
+    if hyp_set is None:
+        hyp_set = torch.arange(N, dtype=torch.int32, device=dev)
+    if lens is None and not count_end and L > 0:
+        is0 = captions == 0
+        lens = torch.where(is0.any(1), is0.int().argmax(1), torch.full((N,), L, dtype=torch.int64, device=dev))
+    return captions, hyp_set, lens
+
+
 def validation_bleu(captions, hyp_set, ground_truth, dev, count_end=False, word_map=None):
     """Corpus Bleu_1..4 of decoded captions without strings:
         gt = ciderd.ground_truth_lists(allcaps, word_map)
@@ -1237,23 +1263,29 @@ def validation_bleu(captions, hyp_set, ground_truth, dev, count_end=False, word_
     csrc/bleu_device.hip) and nothing is read back.  Returns a (4,) float64 device tensor."""
     from . import bleu
     scorer = bleu.device_scorer(dev)
-    lens = None
-    if word_map is not None:
-        drop, end = {int(word_map['<start>']), int(word_map['<pad>'])}, int(word_map['<end>'])
-        rows = [[0 if int(w) == end else int(w) for w in c if int(w) not in drop] for c in captions]
-        rows = [c[:c.index(0) + (1 if count_end else 0)] if 0 in c else c for c in rows]
-        captions = torch.zeros(len(rows), max([1] + [len(c) for c in rows]), dtype=torch.int64)
-        for i, c in enumerate(rows):
-            captions[i, :len(c)] = torch.tensor(c, dtype=torch.int64)
-        # a list that never reached <end> (the step limit) ends where it stops: explicit lengths, not the 0 rule
-        lens = torch.tensor([len(c) for c in rows], dtype=torch.int32)
-    captions = torch.as_tensor(captions).to(scorer.dev)
-    if captions.dim() != 2:
-        raise ValueError("captions are rows of a 2-D id tensor, got shape %s" % (tuple(captions.shape),))
-    N, L = captions.shape
-    if hyp_set is None:
-        hyp_set = torch.arange(N, dtype=torch.int32, device=scorer.dev)
-    if lens is None and not count_end and L > 0:
-        is0 = captions == 0
-        lens = torch.where(is0.any(1), is0.int().argmax(1), torch.full((N,), L, dtype=torch.int64, device=scorer.dev))
+    captions, hyp_set, lens = _validation_rows(captions, hyp_set, scorer.dev, count_end, word_map)
     return scorer.corpus_score(captions, hyp_set, scorer.prepare_refs(ground_truth, count_end=count_end), lens)
+
+
+def validation_rouge_l(captions, hyp_set, ground_truth, dev, count_end=False, word_map=None):
+    """Corpus ROUGE_L of decoded captions without strings: the mean of the captions' ROUGE-L (rouge.py; beta = 1.2) on the
+    device (rouge.DeviceRougeL, csrc/rouge_device.hip), nothing read back.  Input forms and conventions are validation_bleu's.
+    Returns a 0-d float64 device tensor."""
+    from . import rouge
+    scorer = rouge.device_scorer(dev)
+    captions, hyp_set, lens = _validation_rows(captions, hyp_set, scorer.dev, count_end, word_map)
+    return scorer.corpus_score(captions, hyp_set, scorer.prepare_refs(ground_truth, count_end=count_end), lens)
+
+
+def validation_scores(captions, hyp_set, ground_truth, dev, count_end=False, word_map=None):
+    """validation_bleu and validation_rouge_l in one: the references are uploaded once and prepared by one launch, whose
+    records both score kernels read.  Returns {'Bleu_1', 'Bleu_2', 'Bleu_3', 'Bleu_4', 'ROUGE_L'} (the reference's key names)
+    -> 0-d float64 device tensors, the very bits of the two single calls; nothing is read back."""
+    from . import bleu, rouge
+    bscorer, rscorer = bleu.device_scorer(dev), rouge.device_scorer(dev)
+    captions, hyp_set, lens = _validation_rows(captions, hyp_set, bscorer.dev, count_end, word_map)
+    refs = bscorer.prepare_refs(ground_truth, count_end=count_end)
+    b = bscorer.corpus_score(captions, hyp_set, refs, lens)
+    out = {"Bleu_%d" % (k + 1): b[k] for k in range(4)}
+    out["ROUGE_L"] = rscorer.corpus_score(captions, hyp_set, refs, lens)
+    return out

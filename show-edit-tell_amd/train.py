@@ -468,7 +468,7 @@ REWARD_ROUTES = ("host", "device")
 
 
 def _scst_step(model, optimizer, greedy_fn, sample_fn, rep, ground_truth, scorer, n_samples, cider_weight, dev, group,
-               reward="host", bleu_weight=0.0):
+               reward="host", bleu_weight=0.0, rouge_weight=0.0):
     """Shared body of the self-critical step (editnet_rl.py:649-686, dcnet_rl.py:451-493): greedy baseline in eval
     mode under no_grad (fused device loop), `n_samples` multinomial rollouts in train mode (autograd operators, the
     sampling epilogue runs on the device), reward = CIDEr-D(sample) - CIDEr-D(greedy) from `scorer` (host work, per
@@ -481,7 +481,10 @@ def _scst_step(model, optimizer, greedy_fn, sample_fn, rep, ground_truth, scorer
     bleu_weight != 0: the reward of the self-critical code base, cider_weight * dCIDEr-D + bleu_weight * dBLEU-4 (sentence BLEU-4
     of bleu.py under the same sentence convention, sample minus the greedy caption of its image): bleu.Bleu on the host route,
     bleu.DeviceBleu (csrc/bleu_device.hip) on the device route, its references prepared before the rollout as well.
-    bleu_weight == 0 makes exactly the calls made before the argument existed."""
+    bleu_weight == 0 makes exactly the calls made before the argument existed.
+    rouge_weight != 0: + rouge_weight * dROUGE-L (rouge.py, beta = 1.2), mixed in the same double sum: rouge.RougeL on the host
+    route, rouge.DeviceRougeL (csrc/rouge_device.hip) on the device route.  It reads BLEU's prepared records, so with both terms
+    the references are prepared once and passed to both scorers.  rouge_weight == 0: nothing of rouge.py is imported or launched."""
     from . import ciderd
     from .autograd_ops import deferred_param_grads
     if reward not in REWARD_ROUTES:
@@ -498,6 +501,14 @@ def _scst_step(model, optimizer, greedy_fn, sample_fn, rep, ground_truth, scorer
             mix = dict(bleu_scorer=bscorer, bleu_refs=bscorer.prepare_refs(ground_truth), bleu_weight=bleu_weight)
         else:
             mix = dict(bleu_scorer=bleu.Bleu(), bleu_weight=bleu_weight)
+    if rouge_weight != 0.0:
+        from . import rouge
+        if reward == "device":
+            rscorer = rouge.device_scorer(dev)
+            mix.update(rouge_scorer=rscorer, rouge_refs=mix.get("bleu_refs") or rscorer.prepare_refs(ground_truth),
+                       rouge_weight=rouge_weight)
+        else:
+            mix.update(rouge_scorer=rouge.RougeL(), rouge_weight=rouge_weight)
     core = getattr(model, "dae", model)              # DAEWithAR wraps the DAE whose fc finishes first
     reducer = _begin_backward(model, group, _dist_active(group), first=(core.fc.weight, core.fc.bias))
     # the greedy baseline (a latency-bound chain of small kernels) and the sampled rollout are independent: the baseline is
@@ -560,7 +571,7 @@ def _sample_kw(temperature, top_k, top_p):
 
 def scst_train_step(decoder, optimizer, word_map, image_features, previous_caption, prev_caplen, ground_truth,
                     scorer, n_samples=1, cider_weight=1.0, group=None, temperature=1.0, top_k=0, top_p=1.0, reward="host",
-                    bleu_weight=0.0):
+                    bleu_weight=0.0, rouge_weight=0.0):
     """One self-critical step of editnet_rl.py:649-686 on this rank's shard.  The reference draws one sample per
     image; BASELINE.json config 5 asks for 5: all samples enter one RewardCriterion over n_samples * B rows.  As in
     the XE step the loss is normalised by the GLOBAL mask count so that N ranks reproduce one big batch.
@@ -568,6 +579,7 @@ def scst_train_step(decoder, optimizer, word_map, image_features, previous_capti
     (`decoder.sample_rollout`; every step's kept set is held constant); the greedy baseline takes no options.
     reward="host" (default: the calls made before the argument existed) | "device" (CIDEr-D on the device, see _scst_step).
     bleu_weight: weight of the BLEU-4 term of the reward (0.0: none, nothing of bleu.py is imported or launched).
+    rouge_weight: weight of the ROUGE-L term of the reward (0.0: none, nothing of rouge.py is imported or launched).
     Returns (mean reward of the samples on this rank, GLOBAL loss value)."""
     rep = _repeater(n_samples)
     kw = _sample_kw(temperature, top_k, top_p)
@@ -581,14 +593,15 @@ def scst_train_step(decoder, optimizer, word_map, image_features, previous_capti
                          sample_rl=True, repeat_images=n_samples)) if not kw else
         (lambda: decoder.sample_rollout(word_map, rep(previous_caption), rep(prev_caplen), image_features,
                                         repeat_images=n_samples, **kw)),
-        rep, ground_truth, scorer, n_samples, cider_weight, image_features.device, group, reward, bleu_weight)
+        rep, ground_truth, scorer, n_samples, cider_weight, image_features.device, group, reward, bleu_weight, rouge_weight)
 
 
 def dcnet_scst_train_step(dae, optimizer, word_map, previous_caption, prev_caplen, ground_truth, scorer, n_samples=1,
-                          cider_weight=1.0, group=None, temperature=1.0, top_k=0, top_p=1.0, reward="host", bleu_weight=0.0):
+                          cider_weight=1.0, group=None, temperature=1.0, top_k=0, top_p=1.0, reward="host", bleu_weight=0.0,
+                          rouge_weight=0.0):
     """The text-only twin (dcnet_rl.py:451-493): `dae` is a dcnet_rl.DAE or the DAEWithAR wrapper the reference
     trains (its forward delegates to `.dae`; `affine_hidden` receives no gradient from this loss, as in the reference).
-    temperature / top_k / top_p / reward / bleu_weight: see scst_train_step.
+    temperature / top_k / top_p / reward / bleu_weight / rouge_weight: see scst_train_step.
     Returns (mean reward of the samples on this rank, GLOBAL loss value)."""
     rep = _repeater(n_samples)
     kw = _sample_kw(temperature, top_k, top_p)
@@ -597,4 +610,4 @@ def dcnet_scst_train_step(dae, optimizer, word_map, previous_caption, prev_caple
         lambda: dae(word_map, previous_caption, prev_caplen, sample_max=True, sample_rl=False),
         (lambda: dae(word_map, rep(previous_caption), rep(prev_caplen), sample_max=False, sample_rl=True)) if not kw else
         (lambda: dae.sample_rollout(word_map, rep(previous_caption), rep(prev_caplen), **kw)),
-        rep, ground_truth, scorer, n_samples, cider_weight, previous_caption.device, group, reward, bleu_weight)
+        rep, ground_truth, scorer, n_samples, cider_weight, previous_caption.device, group, reward, bleu_weight, rouge_weight)
