@@ -169,7 +169,12 @@ int set_editnet_greedy_pick(const SetEditNetWeights* w, const SetEditNetDims* d,
 
 /* Whole free-running greedy decode (editnet_rl.py:485-549 with sample_max=True): prologue +
  * (max_len+1) timesteps, no host synchronisation (the reference syncs every step at :546).
- * Outputs seq (B,max_len) int64 and seq_logp (B,max_len) fp32 (overwritten). */
+ * Outputs seq (B,max_len) int64 and seq_logp (B,max_len) fp32 (overwritten).
+ * Numerics: from 65 rows on (fixed features) the grouped GEMM launches of the timestep loop of this call and of
+ * set_editnet_greedy_begun (not the prologue, which is set_editnet_begin's bit for bit) run on the split-precision kernel (fp32 operands as three exact bf16 planes, fp32 accumulation; see set_gemm_nt_group_f32,
+ * set_gemm_nt_greedy_scope): logits agree with the fp32 kernels' to the 1e-4 target, not bit for bit; the same inputs give the
+ * same bits every time.  SET_GEMM_SPLIT=0 in the environment keeps the fp32 kernels.  Below 65 rows, with adaptive features, and
+ * in every other entry point of this header nothing changes. */
 int set_editnet_greedy(const SetEditNetWeights* w, const SetEditNetDims* d, const float* X,
                        const float* image_mean, const int64_t* prev, const int64_t* prevlen,
                        int64_t start_idx, int64_t end_idx, int max_len, int64_t* seq,
@@ -554,6 +559,14 @@ int set_linear_f32(const float* x, int64_t ldx, const float* w, int64_t ldw, con
  *            activation, so a split one with either is refused (SET_ERR_ARG) and otherwise leaves its partials in `ws`:
  *            problem i's slab s at ws + slab_offset_i + s * M_i * N_i floats, slab_offset_i = the 256-byte-rounded sizes
  *            (ksplit_j * M_j * N_j * 4 bytes) of the split problems j < i.
+ *   set_gemm_nt_greedy_scope(1) before the call (0 after it; a switch of the calling thread): plan and launch as the no-grad
+ *            greedy rollout of EditNet does.  With SET_GEMM_SPLIT unset, a launch whose problems all have >= 65 rows, without a row list and without bm_hint = 64, then runs on
+ *            the 128x64 split-precision kernel (profile tag "gemm_nt_f32<128,64>:bf16x3"): every fp32 operand as three
+ *            exact bf16 planes, six partial products accumulated in fp32.  Its error against the exact product is that of
+ *            the fp32 kernels (measured: profiles/gemm_split_errors.json), its bits are not theirs; products of small
+ *            integers are exact on both.  An element whose split accumulator is not finite (an operand of +-inf, NaN or
+ *            |x| >= 2^128 - 2^119, or a true overflow) is recomputed as an fp32 FMA chain, so inf / NaN come out as from the
+ *            fp32 kernels.  Without it (every caller but that rollout) and with SET_GEMM_SPLIT=0 the fp32 kernels run.
  *   ksplit_out  NULL or n ints: the split each problem ran with.   rows_out  NULL or one int: the row-tile class.
  * Every refusal is answered before any HIP call. */
 #define SET_GEMM_NT_NO_ASM 1
@@ -577,6 +590,7 @@ typedef struct SetGemmNtLaunch {
 } SetGemmNtLaunch;
 /* upper bound for `ws` of the call below (0 when nothing can be split or an argument is out of range) */
 size_t set_gemm_nt_group_workspace_bytes(const SetGemmNtProb* probs, int n);
+int set_gemm_nt_greedy_scope(int on);
 int set_gemm_nt_group_f32(const SetGemmNtProb* probs, int n, const SetGemmNtLaunch* launch /* NULL: all defaults */,
                           void* ws, size_t ws_bytes, void* stream);
 /* EmbeddingC.forward (editnet.py:300-304), eval: out[i] = relu(table[ids[i]]) */

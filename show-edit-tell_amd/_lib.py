@@ -386,6 +386,7 @@ PROTOTYPES = {
     "set_linear_f32": (_I, [_P, _L, _P, _L, _P, _P, _L, _I, _I, _I, _I, _P, _Z, _P]),
     "set_gemm_nt_group_workspace_bytes": (_Z, [C.POINTER(GemmNtProb), _I]),
     "set_gemm_nt_group_f32": (_I, [C.POINTER(GemmNtProb), _I, C.POINTER(GemmNtLaunch), _P, _Z, _P]),
+    "set_gemm_nt_greedy_scope": (_I, [_I]),
     "set_embed_relu_f32": (_I, [_P, _P, _L, _P, _L, _I, _I, _I, _P]),
     "set_lstm_cell_workspace_bytes": (_Z, [_I, _I, _I]),
     "set_lstm_cell_f32": (_I, [_P, _L, _I, _P, _P, _P, _L, _P, _P, _P, _P, _P, _I, _I, _P, _Z, _P]),

@@ -96,7 +96,7 @@ def gemm_group(items, a_kminor, b_kminor):
 
 
 def gemm_nt_group(problems, bm_hint=0, row_list=None, row_count=None, alive=None, no_asm=False, keep_slabs=False, ws=None,
-                  code=False):
+                  code=False, greedy_scope=False):
     """The grouped NT GEMM of csrc/gemm_f32.hip in ONE launch (set_gemm_nt_group_f32; no autograd node): problem i is
     dict(segs=[(A, W), ...], C=out view, bias=None, act=ACT_NONE, ksplit=0) with C = act(sum_s A_s W_s^T + bias).  Operands are
     read and written IN PLACE through their row strides (2-D views with unit inner stride; nothing is copied, a layout the
@@ -123,7 +123,15 @@ def gemm_nt_group(problems, bm_hint=0, row_list=None, row_count=None, alive=None
     dp = lambda t: None if t is None else t.data_ptr()
     launch = _lib.GemmNtLaunch(dp(row_list), dp(row_count), dp(alive), C.addressof(ks_out), C.addressof(rows_out), bm_hint,
                                (_lib.GEMM_NT_NO_ASM if no_asm else 0) | (_lib.GEMM_NT_KEEP_SLABS if keep_slabs else 0))
-    rc = lib.set_gemm_nt_group_f32(descs, n, C.byref(launch), ptr(ws), ws.numel(), stream_of(dev))
+    # greedy_scope: planned and launched as the greedy rollout's launches are (set_gemm_nt_greedy_scope: >= 65 rows on the
+    # bf16-split kernel unless SET_GEMM_SPLIT=0)
+    if greedy_scope:
+        lib.set_gemm_nt_greedy_scope(1)
+    try:
+        rc = lib.set_gemm_nt_group_f32(descs, n, C.byref(launch), ptr(ws), ws.numel(), stream_of(dev))
+    finally:
+        if greedy_scope:
+            lib.set_gemm_nt_greedy_scope(0)
     if code:
         return rc, list(ks_out)[:n], rows_out.value
     check(rc, "set_gemm_nt_group_f32")

@@ -608,6 +608,11 @@ static int rollout(const SetEditNetWeights* w, const SetEditNetDims* d, const fl
                                                  seq_logp, st);
         if (rc != SET_ERR_UNSUPPORTED) return rc;
     }
+    // greedy decode of 65+ rows: the timestep loop's grouped GEMM launches (F/A, B, D, the lone last fc) run on the bf16-split
+    // kernel (set_common.h SplitScope); sampled rollouts, adaptive features and smaller batches keep the fp32 kernels.  The
+    // prologue stays outside: a prologue run ahead through set_editnet_begin cannot know which loop will consume it, and
+    // set_editnet_greedy_begun must give the bits of set_editnet_greedy
+    SplitScope split_scope(sample == 0 && B >= 65 && !d->adaptive);
     for (int t = 0; t <= last_t; ++t) {
         Slabs lg;
         bool biased = false;

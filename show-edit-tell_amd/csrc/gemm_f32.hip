@@ -35,11 +35,20 @@ typedef const f32x4 __attribute__((address_space(1)))* gptr4;
 // each) are then both bank-conflict-free, and a 128x64x32 stage pair is 48 KB -> three workgroups per CU.
 constexpr int LDS_STRIDE = 32;
 
-#ifdef SET_EXPERIMENTAL_GEMMS
-static int gemm_split_mode() { static int v = env_int("SET_GEMM_SPLIT", 0); return v; }
-#else
-static constexpr int gemm_split_mode() { return 0; }     // (the bf16x3 kernel is not in the shipped library)
-#endif
+// SET_GEMM_SPLIT, who runs on gemm_nt_split_bf16 (gemm_split_bf16.inc), in both library variants:
+//   0      nobody: the fp32 kernels for every launch
+//   1      every launch the kernel can take (the tile classes are re-cut for it: 128x64 from 65 rows on, no row lists)
+//   unset  launches of >= 65 rows without a row list and without a 64-row hint, issued inside a SplitScope (set_common.h): the
+//          no-grad greedy rollout of EditNet.  Every other caller stays on the fp32 kernels.
+static int gemm_split_mode() { static int v = env_int("SET_GEMM_SPLIT", -1); return v < 0 ? -1 : (v ? 1 : 0); }
+static bool split_all() { return gemm_split_mode() == 1; }
+thread_local bool g_split_scope = false;
+static bool split_scoped(const GemmProb* probs, int n) {
+    if (gemm_split_mode() >= 0 || !g_split_scope || n <= 0 || probs[0].row_list || probs[0].bm_hint == 64) return false;
+    for (int i = 0; i < n; ++i)
+        if (probs[i].M < 65) return false;
+    return true;
+}
 
 struct GemmTask {
     const float* A[GEMM_MAX_SEG];
@@ -554,8 +563,13 @@ __global__ void __launch_bounds__(256) gemm_nt_f32_asm(const int ntasks, const i
 #undef ASM_HALF_ROUND
 
 // ---------------------------------------------------------------------------------------------
-// Variants that were built, measured and LOST (EXPERIMENTS_r1-r4.md 3.1b, 4.1): the weights-to-registers kernel, the LDS-DMA
-// kernel and the bf16x3 split-precision kernel live in experimental/gemm_variants.inc and are compiled only with
+// The bf16x3 split-precision kernel (shipped: the greedy rollout's >= 65-row launches run on it, see gemm_split_mode above)
+// ---------------------------------------------------------------------------------------------
+#include "gemm_split_bf16.inc"
+
+// ---------------------------------------------------------------------------------------------
+// Variants that were built, measured and LOST (EXPERIMENTS_r1-r4.md 3.1b, 4.1): the weights-to-registers kernel and the LDS-DMA
+// kernel live in experimental/gemm_variants.inc and are compiled only with
 // -DSET_EXPERIMENTAL_GEMMS (tools/ubench builds; SET_HIPCC_FLAGS=-DSET_EXPERIMENTAL_GEMMS python -m show_edit_tell_amd.build --force).
 // The shipped library does not contain them; their environment switches are ignored there.
 // ---------------------------------------------------------------------------------------------
@@ -663,7 +677,7 @@ int gemm_tile_m(int M) {
     // stay on 128x64): at the decode batch two 64-row tiles per weight block (the second one hits the
     // same XCD's L2) halve the split-K factor -> half the slab bytes written here and re-read by the consumer,
     // and 32 KB workgroups pack three per CU.  Measured +4-5 % on the bench against the 128x64 tile.
-    static const int bm64_upto = env_int("SET_GEMM_BM64_UPTO", gemm_split_mode() ? 64 : 512);   // the split kernel is 128x64 only
+    static const int bm64_upto = env_int("SET_GEMM_BM64_UPTO", split_all() ? 64 : 512);   // the split kernel is 128x64 only
     static const int bm32_upto = env_int("SET_GEMM_BM32_UPTO", 32);
     // <= 16 rows (configs[0]'s batch of 4, beam search, the tail of a ragged teacher-forced batch): the launch only streams
     // weights; gemv_nt_f32 (no LDS, one 16x16 MFMA tile per wave, loads straight into registers) instead of a 32-row tile
@@ -702,12 +716,13 @@ static bool use_bn32(const GemmProb* probs, int n) {
 #else
     constexpr int on = 0;
 #endif
-    if (!on || n <= 0 || probs[0].bm_hint || gemm_split_mode()) return false;
+    if (!on || n <= 0 || probs[0].bm_hint || split_all() || split_scoped(probs, n)) return false;
     for (int i = 0; i < n; ++i)
         if (probs[i].M <= 64 || probs[i].M > 128 || gemm_tile_m(probs[i].M) != 64) return false;
     return true;
 }
 static int launch_tile_m(const GemmProb* probs, int n) {
+    if (split_scoped(probs, n)) return 128;          // the split kernel's only tile: 128x64, two workgroups per CU
     if (use_bn32(probs, n)) return 128;
     // one row-tile class per launch: the largest any problem asks for (the teacher-forced loop merges fc over this step's
     // rows with phase A over the next step's, and the sorted batch may shrink across a class boundary in between)
@@ -715,7 +730,7 @@ static int launch_tile_m(const GemmProb* probs, int n) {
     if (!probs[0].bm_hint)
         for (int i = 1; i < n; ++i) { const int c = tile_m_of(probs[i]); if (c > bm) bm = c; }
     static const int model = env_int("SET_GEMM_TILE_MODEL", 1);
-    if (!model || probs[0].bm_hint || bm != 128 || gemm_split_mode() || gemm_bn128()) return bm;
+    if (!model || probs[0].bm_hint || bm != 128 || split_all() || gemm_bn128()) return bm;
     long long t128 = 0, t64 = 0;
     for (int i = 0; i < n; ++i) {
         if (gemm_tile_m(probs[i].M) != 128) return bm;
@@ -729,11 +744,12 @@ int gemm_launch_rows(const GemmProb* probs, int n) { return n > 0 ? launch_tile_
 static int launch_tile_n(const GemmProb* probs, int n);
 // the LDS-staged tile classes of the shipped library take a row list; the <= 16-row class (no tile rows to skip) does not
 bool gemm_row_list_ok(const GemmProb* probs, int n) {
-    if (n <= 0 || gemm_split_mode() || gemm_dma() || gemm_wreg() || gemm_kgroups() != 1) return false;
+    if (n <= 0 || split_all() || gemm_dma() || gemm_wreg() || gemm_kgroups() != 1) return false;
     const int bm = launch_tile_m(probs, n), bn = launch_tile_n(probs, n);
     return (bm == 128 && bn == 64) || (bm == 64 && bn == 64) || (bm == 32 && bn == 128);
 }
 static int launch_tile_n(const GemmProb* probs, int n) {
+    if (split_scoped(probs, n)) return 64;
     if (use_bn32(probs, n)) return 32;
     const int bm = launch_tile_m(probs, n);
     return (bm == 32 || (bm == 128 && gemm_bn128())) ? 128 : 64;      // (class 16: 4 waves x 16 columns)
@@ -873,34 +889,40 @@ int gemm_group(const GemmProb* probs, int n, hipStream_t stream, const char* tag
         flops += 2.0 * t.M * t.N * K;
         bytes += 4.0 * ((double)t.M * K + (double)t.N * K + (double)t.M * t.N * t.ksplit);
     }
-    const char* kname = (bm == 64 && bn == 64 && gemm_asm() && slices_in_one_segment(L)) ? "gemm_nt_f32_asm<64,64>" :
+    static const char* split_tag = getenv("SET_GEMM_SPLIT_TAG");     // debug (SET_GEMM_SPLIT=1): restrict the split kernel to one call site
+    const bool split_here = bm == 128 && bn == 64 && !L.row_list &&
+                            (split_scoped(probs, n) ||
+                             (split_all() && (!split_tag || !*split_tag || strstr(tag ? tag : "untagged", split_tag))));
+    // (the split kernel's tag stays in the family of the tile it replaces: bench.py keys `roofline` on the prefix)
+    const char* kname = split_here ? "gemm_nt_f32<128,64>:bf16x3" :
+                        (bm == 64 && bn == 64 && gemm_asm() && slices_in_one_segment(L)) ? "gemm_nt_f32_asm<64,64>" :
                         (bm == 128 && bn == 32) ? "gemm_nt_f32<128,32>" : bm == 128 ? "gemm_nt_f32<128,64>" : (bm == 64 ? "gemm_nt_f32<64,64>" : (bm == 32 ? "gemm_nt_f32<32,128>" : "gemv_nt_f32<16,64>"));
     ProfScope ps(kname, stream, flops, bytes);
     static const bool sites = env_int("SET_PROFILE_SITES", 0) != 0;   // per-call-site breakdown (nested events)
     ProfScope ps2(sites ? (tag ? tag : "gemm:other") : nullptr, stream, flops, bytes);
     dim3 grid(wg), block(256);
-    static const char* split_tag = getenv("SET_GEMM_SPLIT_TAG");     // debug: restrict the split kernel to one call site
-    const bool split_here = gemm_split_mode() && (!split_tag || !*split_tag || strstr(tag ? tag : "untagged", split_tag));
-#ifdef SET_EXPERIMENTAL_GEMMS
-    if (bm == 128 && bn == 64 && split_here) {
-        constexpr int kLds = 2 * 3 * (128 + 64) * 64;
-        static bool attr_set = false;
-        if (!attr_set) {
-            SET_HIP_TRY(hipFuncSetAttribute((const void*)gemm_nt_split_bf16, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            kLds));
-            attr_set = true;
-        }
-        hipLaunchKernelGGL(gemm_nt_split_bf16, grid, block, kLds, stream, L);
-    } else
-#endif
     {
-        (void)split_here;
         const int nt = L.ntasks, w1 = L.t[1].wg_begin, w2 = L.t[2].wg_begin, w3 = L.t[3].wg_begin, w4 = L.t[4].wg_begin,
                   w5 = L.t[5].wg_begin;
         const int* ga = L.gate.alive_prev;
         const int* gn = row_count;               // GATE == 2: the length of the row list (else an unused slot)
         const int gate_mode = L.row_list ? 2 : (ga ? 1 : 0);
-        if (gate_mode == 2) {                    // (gemm_row_list_ok: one of these three classes)
+        if (split_here) {                        // 72 KB of dynamic LDS: above the 64 KB a kernel gets without asking
+            static bool attr_set[64] = {};       // per device (a racing second thread sets the same values again)
+            int dev = 0;
+            SET_HIP_TRY(hipGetDevice(&dev));
+            if (dev < 0 || dev >= 64 || !attr_set[dev]) {
+                SET_HIP_TRY(hipFuncSetAttribute((const void*)gemm_nt_split_bf16<0>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                SPLIT_LDS_BYTES));
+                SET_HIP_TRY(hipFuncSetAttribute((const void*)gemm_nt_split_bf16<1>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                SPLIT_LDS_BYTES));
+                if (dev >= 0 && dev < 64) attr_set[dev] = true;
+            }
+            if (gate_mode)
+                hipLaunchKernelGGL((gemm_nt_split_bf16<1>), grid, block, SPLIT_LDS_BYTES, stream, nt, w1, w2, w3, w4, w5, ga, gn, L);
+            else
+                hipLaunchKernelGGL((gemm_nt_split_bf16<0>), grid, block, SPLIT_LDS_BYTES, stream, nt, w1, w2, w3, w4, w5, ga, gn, L);
+        } else if (gate_mode == 2) {             // (gemm_row_list_ok: one of these three classes)
             if (bm == 128)
                 hipLaunchKernelGGL((gemm_nt_f32<128, 64, 2, 2, 1, 2>), grid, block, 0, stream, nt, w1, w2, w3, w4, w5, ga, gn, L);
             else if (bm == 64 && gemm_asm() && slices_in_one_segment(L))

@@ -111,6 +111,11 @@ size_t set_gemm_nt_group_workspace_bytes(const SetGemmNtProb* probs, int n) {
     return bytes ? bytes + 256 : 0;
 }
 
+int set_gemm_nt_greedy_scope(int on) {
+    g_split_scope = on != 0;                                     // (thread-local: the calling thread's later launches)
+    return SET_OK;
+}
+
 int set_gemm_nt_group_f32(const SetGemmNtProb* probs, int n, const SetGemmNtLaunch* launch, void* ws, size_t ws_bytes,
                           void* stream) {
     const SetGemmNtLaunch dflt = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};

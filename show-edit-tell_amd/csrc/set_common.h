@@ -132,7 +132,16 @@ struct RowGateScope {
     explicit RowGateScope(const RowGate& g) : prev(g_row_gate) { g_row_gate = g; }
     ~RowGateScope() { g_row_gate = prev; }
 };
-extern thread_local const int* g_row_limit;   // set_decode_row_limits(): per-row cap on the caption length of the greedy loops (or NULL)
+// Split-precision scope (gemm_f32.hip, SET_GEMM_SPLIT unset): while one is open with `on`, grouped GEMM launches of >= 65 rows
+// that fit gemm_nt_split_bf16 run on it (fp32 operands as three exact bf16 planes, fp32 accumulation: fp32-grade error, not
+// the fp32 kernels' bits).  Opened by the no-grad greedy rollout of EditNet alone; every other caller keeps the fp32 kernels.
+extern thread_local bool g_split_scope;
+struct SplitScope {
+    bool prev;
+    explicit SplitScope(bool on) : prev(g_split_scope) { g_split_scope = on; }
+    ~SplitScope() { g_split_scope = prev; }
+};
+extern thread_local const int* g_row_limit;  // set_decode_row_limits(): per-row cap on the caption length of the greedy loops (or NULL)
 
 // ---------------------------------------------------------------------------------------------
 // Addends of a gradient that are still split-K partials (include/set_hip.h SetSlabSrc): the consumer sums them while it
