@@ -1282,6 +1282,23 @@ int set_ciderd_score(void* scorer, const int64_t* hyp_tokens, const int64_t* hyp
  *   comes back in *handle_out (NULL on failure).  SET_ERR_ARG: NULL handle_out / arrays, n outside 1 .. 4, ref_len or sigma not
  *   positive, n_entries < 0; SET_ERR_UNSUPPORTED: an id outside [0, 65534) — both before any HIP call.  Entries with a length
  *   outside 1 .. 4 are skipped; of a repeated gram the last count stands.  destroy frees the table (NULL: nothing).
+ * create_corpus: the table of cocoEval's `CIDEr` — the same formula, with df and N taken from the reference sets of the corpus
+ *   that is scored: df(g) = the number of SETS one of whose references holds g (once per set however often it occurs there),
+ *   ref_len = n_sets, so log ref_len = log(n_sets).  The references are DEVICE arrays in the form vectorise and score take them:
+ *   reference r = ref_tokens[r ld .. r ld + L) with length ref_lens[r] (or the 0 rule with ref_lens == NULL), set s = references
+ *   [ref_set_off[s], ref_set_off[s + 1]) (device int64, n_sets + 1), max_set the caller's bound on a set's size.  The table has
+ *   the layout create builds, capacity = the power of two >= max(2, 2 gram_bound); gram_bound is the caller's bound on the
+ *   number of distinct grams, e.g. sum_r sum_{k < n} max(0, len_r - k) from the lengths it holds on the host.  Everything is
+ *   enqueued on `stream` and nothing is read back: the table is cleared by a memset, then one wave per set enters its
+ *   references' grams with a 64-bit compare-and-swap on a slot's key and a double atomic add of 1 on its count (exact: an
+ *   integer below 2^53).  The slot of a key depends on the order of arrival, the map key -> count does not.  A set the host
+ *   cannot check (offsets outside [0, n_refs] or decreasing, a set larger than max_set) and a reference with an id outside
+ *   [0, 65534) contribute nothing (score answers such a set with NaN).  A gram that finds no slot because gram_bound was too
+ *   small is dropped and counted.  The handle serves lookup, vectorise, score and destroy as one from create does.
+ *   SET_ERR_ARG: NULL handle_out / ref_set_off (ref_tokens with n_refs > 0), n outside 1 .. 4, sigma not positive, n_sets < 1,
+ *   n_refs, max_set or gram_bound < 0, L < 1, ld < L; SET_ERR_UNSUPPORTED: L > 64, gram_bound > 2^40 — before any HIP call.
+ * dropped (for tests: it waits for `stream`): *dropped_out = the grams create_corpus dropped, 0 for a handle from create.
+ *   SET_ERR_ARG: NULL handle / dropped_out.
  * lookup: df_out[i] = document count of the packed key keys[i] (device arrays of n), 0.0 for an absent key or key 0.
  * vec_bytes / vectorise (ciderd_host.hip:77-99): sentence i = tokens[i ld .. i ld + L) (device int64, ld >= L), its length
  *   lens[i] clamped to [0, L] (device int32), or with lens == NULL the decoder's rule of ciderd.py:222-224: cut after the first 0,
@@ -1306,6 +1323,10 @@ int set_ciderd_score(void* scorer, const int64_t* hyp_tokens, const int64_t* hyp
 int set_ciderd_device_key(const int64_t* tokens, int k, uint64_t* key_out);
 int set_ciderd_device_create(const int64_t* tokens, const int32_t* lens, const double* df, int64_t n_entries, double ref_len,
                              int n, double sigma, void* stream, void** handle_out);
+int set_ciderd_device_create_corpus(const int64_t* ref_tokens, int64_t ld, const int32_t* ref_lens, int64_t n_refs, int L,
+                                    const int64_t* ref_set_off, int n_sets, int max_set, int64_t gram_bound,
+                                    int n, double sigma, void* stream, void** handle_out);
+int set_ciderd_device_dropped(void* handle, int64_t* dropped_out, void* stream);   /* tests only: synchronises */
 void set_ciderd_device_destroy(void* handle);
 int set_ciderd_device_lookup(void* handle, const uint64_t* keys, int64_t n, double* df_out, void* stream);
 size_t set_ciderd_device_vec_bytes(int n_sent, int L);

@@ -489,6 +489,8 @@ PROTOTYPES = {
     "set_ciderd_score": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P]),
     "set_ciderd_device_key": (_I, [_P, _I, _P]),
     "set_ciderd_device_create": (_I, [_P, _P, _P, _L, C.c_double, _I, C.c_double, _P, C.POINTER(_P)]),
+    "set_ciderd_device_create_corpus": (_I, [_P, _L, _P, _L, _I, _P, _I, _I, _L, _I, C.c_double, _P, C.POINTER(_P)]),
+    "set_ciderd_device_dropped": (_I, [_P, C.POINTER(_L), _P]),
     "set_ciderd_device_destroy": (None, [_P]),
     "set_ciderd_device_lookup": (_I, [_P, _P, _L, _P, _P]),
     "set_ciderd_device_vec_bytes": (_Z, [_I, _I]),

@@ -178,8 +178,9 @@ class DeviceBleu(DeviceSentenceScorer):
         import torch
         sets = strip_end(ref_sets) if not count_end else [[cut_after_zero(c) for c in refs] for refs in ref_sets]
         tok, ln, off, R, L, max_set = pack_ref_sets(sets, self.METRIC, False)
-        recs = self._prepare(torch.from_numpy(tok[:R]).to(self.dev), torch.from_numpy(ln[:R]).to(self.dev))
-        return PreparedBleuRefs(recs, L, R, torch.from_numpy(off).to(self.dev), len(sets), max_set)
+        t, l = torch.from_numpy(tok[:R]).to(self.dev), torch.from_numpy(ln[:R]).to(self.dev)
+        # the upload stays with the records: the corpus CIDEr of the same sets is built from it (ciderd.DeviceCiderD.from_refs)
+        return PreparedBleuRefs(self._prepare(t, l), L, R, torch.from_numpy(off).to(self.dev), len(sets), max_set, t, l, ln[:R])
 
     def score_token_ids(self, hyps, hyp_set, refs, hyp_lens=None, return_pairs=False):
         """Device twin of Bleu.score_token_ids: `hyps` (N, L) ids, `hyp_set` (N,) index of each row's reference set, `refs` a

@@ -13,6 +13,11 @@ with l = number of bigrams of the sentence (the length the public implementation
 frequency table has the format `preprocess_rl.py:7-55` writes: {n-gram tuple of token strings: number of
 images whose reference set contains it} plus `ref_len` = number of images.
 
+Two conventions share this formula and differ in the table alone.  The SCST REWARD scores against a table pickled beforehand
+from the training set (`CiderD(df, ref_len)`).  The CORPUS score that validation reports — cocoEval's `CIDEr`, the first value
+of the reference's `evaluate()` — takes df and N from the reference sets of the corpus being scored (`CiderD.from_corpus`,
+`corpus_cider`; on the device `DeviceCiderD.from_refs`, `evaluate.validation_cider`).
+
 Host-side, per-sample work (strings and dictionaries): it shards with the batch and never touches the GPU.
 `compute_score` runs on the native implementation in csrc/ciderd_host.hip (`set_ciderd_*`, host pointers): in Python
 the scorer was half of the SCST step's wall time at 5 samples per image.  The pure-Python `score` below is the
@@ -26,7 +31,8 @@ from collections import Counter
 
 import numpy as np
 
-from .device_metric import DEVICE_MAX_LEN, DEVICE_PACK_LIMIT, DeviceSentenceScorer, PreparedRefs, cut_after_zero, pack_ref_sets, resolve_device
+from .device_metric import (DEVICE_MAX_LEN, DEVICE_PACK_LIMIT, DeviceSentenceScorer, PreparedRefs, cut_after_zero, pack_ref_sets,
+                            resolve_device, strip_end)
 
 
 def ngram_counts(sentence, n=4):
@@ -63,6 +69,12 @@ class CiderD:
         self.sigma = sigma
         self._tok = {}           # token string -> int id (interned for the native scorer)
         self._native = None
+
+    @classmethod
+    def from_corpus(cls, reference_sets, n=4, sigma=6.0):
+        """The scorer of cocoEval's `CIDEr`: the same formula with the df table and the number of documents taken from the
+        reference sets of the corpus that is scored (one list of reference sentences per image)."""
+        return cls(*document_frequency(reference_sets, n), n, sigma)
 
     # ---- native scorer (csrc/ciderd_host.hip) -------------------------------------------------------------
     def _ids(self, sentence):
@@ -266,6 +278,19 @@ class CiderD:
         return float(scores.mean()) if len(res) else 0.0, scores
 
 
+def corpus_cider(gts, res, n=4, sigma=6.0):
+    """cocoEval's `CIDEr` of a corpus (the first value of the reference's evaluate(), `eval/eval rl/eval_full.py:235`), in the
+    call shape of CiderD.compute_score: gts = {image_id: [reference strings]}, res = [{'image_id': id, 'caption': [string]}] (or
+    coco's {image_id: [string]}).  The sentence formula is the one above; what differs from the SCST reward is the table: df
+    and the number of documents N come from ALL reference sets of `gts`, the corpus that is scored — an n-gram counts once per
+    image however often it occurs in that image's references, and log N is the idf's ceiling.  A corpus of one image scores
+    0.0 (log 1 = 0: every weight vanishes), as in coco-caption.  Pure Python: the readable statement that
+    DeviceCiderD.from_refs and evaluate.validation_cider are tested against.  Returns (mean score, per-entry scores)."""
+    if isinstance(res, dict):
+        res = [{'image_id': k, 'caption': v} for k, v in res.items()]
+    return CiderD.from_corpus(gts.values(), n, sigma)._compute_score_py(gts, res)
+
+
 # ---- the reward plumbing of editnet_rl.py:584-646 ------------------------------------------------------
 def tokens_to_str(ids):
     """ids of one caption -> space-joined string, cut after the first 0 (the decoder writes 0 for <end>
@@ -437,6 +462,77 @@ class DeviceCiderD(DeviceSentenceScorer):
                                                     int(scorer.n), float(scorer.sigma), _lib.stream_of(self.dev), C.byref(h))
         _lib.check(rc, "set_ciderd_device_create")
         self._h, self.n, self.n_entries = h, int(scorer.n), E
+
+    @classmethod
+    def from_refs(cls, dev, ref_sets, count_end=True, n=4, sigma=6.0, tokens=None, lens=None, set_off=None):
+        """The scorer of cocoEval's `CIDEr` (corpus_cider) for one corpus, built on the device: (scorer, PreparedRefs).
+        ref_sets: the corpus's reference sets as ground_truth_lists returns them (per image a list of id lists); df and N come
+        from ALL of them (csrc/ciderd_device.hip cd_build_k: one wave per set enters its grams into the open-addressing table,
+        once per set).  count_end=True cuts a reference after its first 0 (the 0 is a token), False before it
+        (device_metric.strip_end, the validation convention).  One upload, one build launch and one vectorise launch on the
+        current stream; nothing is read back.  Empty sets are allowed (a caption of such a set scores 0).
+        The upload another metric already made of these very sets serves as well: pass tokens=, lens=, set_off= ((R, L) int64
+        ids, (R,) int32 lengths, (n_sets + 1,) int64 offsets on the device; ref_sets is then only counted on the host), or pass
+        as ref_sets the PreparedBleuRefs of bleu.DeviceBleu.prepare_refs, which keeps its upload and the host-side lengths
+        (.tokens, .lens, .set_off, .host_lens; its count_end stands, nothing is packed again).
+        The table's capacity is the power of two >= max(2, 2 * gram_bound), gram_bound = sum_r sum_{k < n} max(0, len_r - k)
+        from the lengths held here: no gram can be dropped (dropped() == 0)."""
+        import ctypes as C
+        import torch
+        from . import _lib
+        self = cls.__new__(cls)
+        DeviceSentenceScorer.__init__(self, dev)
+        if "set_ciderd_device_create_corpus" in _lib.MISSING:
+            raise _lib.SetError("the native library does not export set_ciderd_device_create_corpus")
+        if isinstance(ref_sets, PreparedRefs):
+            p = ref_sets
+            if getattr(p, "tokens", None) is None or getattr(p, "host_lens", None) is None:
+                raise ValueError("these PreparedRefs do not carry their upload (bleu.DeviceBleu.prepare_refs keeps it)")
+            tokens, lens, set_off, ln, R, L, n_sets, max_set = p.tokens, p.lens, p.set_off, p.host_lens, p.n_refs, p.L, p.n_sets, p.max_set
+        else:
+            sets = [[cut_after_zero(c) for c in refs] for refs in ref_sets] if count_end else strip_end(ref_sets)
+            tok, ln, off, R, L, max_set = pack_ref_sets(sets, self.METRIC, True)
+            n_sets = len(sets)
+            if tokens is None:
+                tokens, lens, set_off = (torch.from_numpy(x).to(self.dev) for x in (tok, ln, off))
+            elif lens is None or set_off is None:
+                raise ValueError("tokens= comes with lens= and set_off= (the three device tensors of one upload)")
+        if (tokens.dim() != 2 or tokens.shape[0] < R or tokens.shape[1] != L or tokens.stride(1) != 1 or lens.numel() < R
+                or set_off.numel() != n_sets + 1 or tokens.dtype != torch.int64 or lens.dtype != torch.int32
+                or set_off.dtype != torch.int64 or any(resolve_device(x.device) != self.dev for x in (tokens, lens, set_off))):
+            raise ValueError("tokens=, lens=, set_off= are not the device upload of these reference sets")
+        k = np.arange(int(n))[None, :]
+        self.gram_bound = int(np.maximum(np.asarray(ln[:R], dtype=np.int64)[:, None] - k, 0).sum())
+        self.capacity = 2
+        while self.capacity < 2 * self.gram_bound:
+            self.capacity *= 2
+        h = C.c_void_p()
+        with torch.cuda.device(self.dev):
+            rc = self._lib.set_ciderd_device_create_corpus(tokens.data_ptr(), tokens.stride(0), lens.data_ptr(), R, L, set_off.data_ptr(),
+                                                           n_sets, max_set, self.gram_bound, int(n), float(sigma),
+                                                           _lib.stream_of(self.dev), C.byref(h))
+        _lib.check(rc, "set_ciderd_device_create_corpus")
+        self._h, self.n, self.n_entries = h, int(n), None
+        recs, _ = self.vectorise(tokens[:R], lens[:R])
+        return self, PreparedRefs(recs, L, R, set_off, n_sets, max_set)
+
+    def dropped(self):
+        """FOR TESTS (it waits for the stream and reads one number back): the grams the device build could not place because its
+        bound was too small; 0 for a table that came from the host"""
+        import ctypes as C
+        import torch
+        from . import _lib
+        out = C.c_int64(-1)
+        with torch.cuda.device(self.dev):
+            rc = self._lib.set_ciderd_device_dropped(self._h, C.byref(out), _lib.stream_of(self.dev))
+        _lib.check(rc, "set_ciderd_device_dropped")
+        return int(out.value)
+
+    def corpus_score(self, hyps, hyp_set, refs, hyp_lens=None):
+        """The corpus value: the mean of the rows' scores, taken on the device (no row: 0; a NaN row makes it NaN).  Returns a
+        0-d float64 device tensor; nothing is read back."""
+        scores = self.score_token_ids(hyps, hyp_set, refs, hyp_lens=hyp_lens)
+        return scores.mean() if scores.numel() else scores.new_zeros(())
 
     def __del__(self):
         h = getattr(self, "_h", None)

@@ -13,6 +13,11 @@
 // an open-addressing table (linear probing, 16-byte {key, df} slots: one load per probe).  Everything is double; sums
 // over lanes are one fixed xor-butterfly, so a row's bits do not depend on the launch it is part of.  No atomics; every
 // store is an ordinary vector store of a declared output.
+//
+// The table comes from the host (set_ciderd_device_create: counts pickled from a training set, the SCST reward) or is built here
+// from the reference sets of the corpus that is scored (set_ciderd_device_create_corpus, cd_build_k below: cocoEval's `CIDEr`,
+// the same formula with df and N of the evaluated corpus).  That build is the one place with atomics: a compare-and-swap on a
+// slot's key and an add on its count.
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -33,6 +38,7 @@ struct CdTable {                               // kernel argument: the device ta
 struct CdHandle {
     CdTable t;
     CdSlot* slots;
+    unsigned long long* dropped = nullptr;     // a table built on the device: the grams that found no slot (behind the slots)
 };
 
 // record of one vectorised sentence in the caller's workspace, in 8-byte words:
@@ -207,6 +213,74 @@ __global__ __launch_bounds__(64) void cd_score_k(CdTable T, const int64_t* hyp, 
     if (lane == 0) scores[i] = bad ? nan : mean / (double)(cnt > 1 ? cnt : 1) * 10.0;
 }
 
+// ---- the table of a corpus, built from its reference sets (set_ciderd_device_create_corpus) ----------------------------------
+// df(g) = the number of SETS whose references hold the gram g: a gram counts once per set however often it occurs there.
+//
+// One gram into the table: the slot's key word goes empty -> key by a 64-bit compare-and-swap (a key never changes once it is
+// set, so the relaxed load in front only spares the swap on a slot that is taken), and the lane whose slot is, or has just become,
+// its key adds 1.0 to the slot's count with a double atomic add.  The count is a sum of ones below 2^53: every partial sum is an
+// integer that a double holds exactly, so the order of arrival does not show in it.  Which slot a key lands in does depend on the
+// order of arrival; the map key -> count does not.  A gram that finds no slot within mask + 1 probes (the caller's bound was
+// too small and the table is full) is dropped and counted in *dropped.
+__device__ __forceinline__ void cd_insert(CdSlot* slots, uint64_t mask, uint64_t key, unsigned long long* dropped) {
+    uint64_t slot = hash(key) & mask, left = mask;
+    for (;;) {
+        unsigned long long* kw = reinterpret_cast<unsigned long long*>(&slots[slot].key);
+        unsigned long long old = __hip_atomic_load(kw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (old == 0) old = atomicCAS(kw, 0ull, (unsigned long long)key);
+        if (old == 0 || old == key) {
+            atomicAdd(&slots[slot].df, 1.0);
+            return;
+        }
+        if (left-- == 0) break;
+        slot = (slot + 1) & mask;
+    }
+    atomicAdd(dropped, 1ull);
+}
+
+// One wave per reference set.  Reference r keeps, on the first lane of each of its distinct grams (own_grams), the grams that no
+// earlier reference r0 .. r - 1 of the set holds: those rows are read again (they sit in L2) and staged in LDS one sentence at a
+// time, every lane against every position.  LDS is that of one sentence whatever the set size, there is no workspace; the cost is
+// quadratic in the set size, which max_set bounds.  A reference with an id that cannot be packed contributes nothing and hides
+// nothing (cd_score_k marks its set NaN).  A set the host could not check (set_range) touches nothing.
+__global__ __launch_bounds__(64) void cd_build_k(CdSlot* slots, uint64_t mask, unsigned long long* dropped, const int64_t* tokens,
+                                                 long long ld, const int* lens, int L, long long n_refs, const int64_t* set_off,
+                                                 int n_sets, int max_set, int n) {
+    __shared__ ulonglong2 s_key[2 * 64];
+    const int lane = threadIdx.x & 63;
+    long long r0, r1;
+    if (!set_range((int)blockIdx.x, set_off, n_sets, n_refs, max_set, r0, r1)) return;
+    for (long long r = r0; r < r1; ++r) {
+        WaveSent S;
+        wave_read(tokens, ld, lens, r, L, n, S);
+        if (S.bad) continue;                                      // the same on every lane
+        int cnt[4];
+        bool keep[4];
+        __syncthreads();                                          // the reads of the reference before are done
+        own_grams(S, s_key, cnt, keep);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) keep[k] = keep[k] && S.key[k] != 0;
+        for (long long q = r0; q < r; ++q) {
+            WaveSent Q;
+            wave_read(tokens, ld, lens, q, L, n, Q);
+            if (Q.bad) continue;
+            __syncthreads();
+            s_key[2 * lane] = make_ulonglong2(Q.key[0], Q.key[1]);
+            s_key[2 * lane + 1] = make_ulonglong2(Q.key[2], Q.key[3]);
+            __syncthreads();
+            for (int j = 0; j < Q.len; ++j) {
+                const ulonglong2 a = s_key[2 * j], b = s_key[2 * j + 1];
+                const uint64_t kj[4] = {a.x, a.y, b.x, b.y};
+#pragma unroll
+                for (int k = 0; k < 4; ++k) keep[k] = keep[k] && kj[k] != S.key[k];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (keep[k]) cd_insert(slots, mask, S.key[k], dropped);
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -251,6 +325,57 @@ int set_ciderd_device_create(const int64_t* tokens, const int32_t* lens, const d
     h->slots = dev;
     h->t = CdTable{dev, cap - 1, std::log(ref_len), sigma, n};
     *handle_out = h;
+    return SET_OK;
+}
+
+int set_ciderd_device_create_corpus(const int64_t* ref_tokens, int64_t ld, const int32_t* ref_lens, int64_t n_refs, int L,
+                                    const int64_t* ref_set_off, int n_sets, int max_set, int64_t gram_bound, int n, double sigma,
+                                    void* stream, void** handle_out) {
+    if (!handle_out) return SET_ERR_ARG;
+    *handle_out = nullptr;
+    if (n < 1 || n > 4 || !(sigma > 0.0) || n_sets < 1 || n_refs < 0 || max_set < 0 || gram_bound < 0 || L < 1 || ld < L ||
+        !ref_set_off || (n_refs > 0 && !ref_tokens))
+        return SET_ERR_ARG;
+    if (L > NG_MAXL || gram_bound > ((int64_t)1 << 40)) return SET_ERR_UNSUPPORTED;
+    uint64_t cap = 2;
+    while (cap < 2 * (uint64_t)gram_bound) cap <<= 1;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    CdSlot* dev = nullptr;                                         // the slots, and one more whose key word is the drop counter
+    SET_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&dev), (size_t)(cap + 1) * sizeof(CdSlot)));
+    hipError_t e = hipMemsetAsync(dev, 0, (size_t)(cap + 1) * sizeof(CdSlot), st);
+    if (e != hipSuccess) {
+        (void)hipFree(dev);
+        return set::hip_fail(e);
+    }
+    CdHandle* h = new CdHandle();
+    h->slots = dev;
+    h->dropped = reinterpret_cast<unsigned long long*>(&dev[cap].key);
+    h->t = CdTable{dev, cap - 1, std::log((double)n_sets), sigma, n};
+    {
+        set::ProfScope prof("ciderd_build", st);
+        hipLaunchKernelGGL(cd_build_k, dim3((unsigned)n_sets), dim3(64), 0, st, dev, cap - 1, h->dropped, ref_tokens, (long long)ld,
+                           ref_lens, L, (long long)n_refs, ref_set_off, n_sets, max_set, n);
+    }
+    e = hipGetLastError();
+    if (e != hipSuccess) {
+        (void)hipFree(dev);
+        delete h;
+        return set::hip_fail(e);
+    }
+    *handle_out = h;
+    return SET_OK;
+}
+
+int set_ciderd_device_dropped(void* handle, int64_t* dropped_out, void* stream) {
+    if (!handle || !dropped_out) return SET_ERR_ARG;
+    const CdHandle* h = static_cast<const CdHandle*>(handle);
+    *dropped_out = 0;
+    if (!h->dropped) return SET_OK;                                // a table from the host holds every entry it was given
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    unsigned long long got = 0;
+    SET_HIP_TRY(hipMemcpyAsync(&got, h->dropped, sizeof(got), hipMemcpyDeviceToHost, st));
+    SET_HIP_TRY(hipStreamSynchronize(st));
+    *dropped_out = (int64_t)got;
     return SET_OK;
 }
 

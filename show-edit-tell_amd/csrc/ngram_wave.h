@@ -111,11 +111,10 @@ __device__ __forceinline__ void own_grams(const WaveSent& S, ulonglong2* s_key, 
     }
 }
 
-// The references [r0, r1) of hypothesis i's set; false: refused (a set index outside [0, n_sets), offsets outside the n_refs
-// records, a set larger than max_set).  The host cannot see these values: the kernel marks the row and touches nothing else.
-__device__ __forceinline__ bool set_range(const int* set_of, long long i, const int64_t* set_off, int n_sets, long long n_refs,
-                                          int max_set, long long& r0, long long& r1) {
-    const int s = set_of[i];
+// The references [r0, r1) of set s; false: refused (a set index outside [0, n_sets), offsets outside the n_refs records, a set
+// larger than max_set).  The host cannot see these values: the kernel marks the row and touches nothing else.
+__device__ __forceinline__ bool set_range(int s, const int64_t* set_off, int n_sets, long long n_refs, int max_set, long long& r0,
+                                          long long& r1) {
     r0 = 0;
     r1 = -1;
     if (s >= 0 && s < n_sets) {
@@ -123,6 +122,12 @@ __device__ __forceinline__ bool set_range(const int* set_of, long long i, const 
         r1 = set_off[s + 1];
     }
     return !(r0 < 0 || r1 < r0 || r1 > n_refs || r1 - r0 > max_set);
+}
+
+// The references of hypothesis i's set, set_of[i].
+__device__ __forceinline__ bool set_range(const int* set_of, long long i, const int64_t* set_off, int n_sets, long long n_refs,
+                                          int max_set, long long& r0, long long& r1) {
+    return set_range(set_of[i], set_off, n_sets, n_refs, max_set, r0, r1);
 }
 
 }  // namespace ngram

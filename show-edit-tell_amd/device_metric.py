@@ -36,9 +36,12 @@ def strip_end(ref_sets):
 
 class PreparedRefs:
     """Reference sets prepared on the device (prepare_refs of a device scorer): the records in that metric's layout, their row
-    length, the set offsets (device int64, n_sets + 1) and the host-side counts the score call validates with."""
-    def __init__(self, recs, L, n_refs, set_off, n_sets, max_set):
+    length, the set offsets (device int64, n_sets + 1) and the host-side counts the score call validates with.  A scorer may
+    keep the upload the records were made from — tokens (n_refs, L) int64 and lens (n_refs,) int32 on the device, host_lens the
+    same lengths as numpy — so that another metric of the same corpus need not upload it again (ciderd.DeviceCiderD.from_refs)."""
+    def __init__(self, recs, L, n_refs, set_off, n_sets, max_set, tokens=None, lens=None, host_lens=None):
         self.recs, self.L, self.n_refs, self.set_off, self.n_sets, self.max_set = recs, L, n_refs, set_off, n_sets, max_set
+        self.tokens, self.lens, self.host_lens = tokens, lens, host_lens
 
 
 def pack_ref_sets(sets, metric_name, allow_empty):

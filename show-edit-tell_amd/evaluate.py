@@ -1221,7 +1221,7 @@ def consensus_rerank_lists(scorer, captions, weights=None, word_map=None):
     return best, util
 
 
-# ---- validation BLEU and ROUGE-L (the `Bleu_1..4` / `ROUGE_L` of the reference's evaluate(): editnet_rl.py:834/897, dcnet.py:541-611)
+# ---- validation BLEU, ROUGE-L and CIDEr (the `Bleu_1..4` / `ROUGE_L` / `CIDEr` of the reference's evaluate(): editnet_rl.py:834/897, dcnet.py:541-611)
 def _validation_rows(captions, hyp_set, dev, count_end, word_map):
     """The caption-normalising front of the validation scores: captions in either input form (see validation_bleu) ->
     ((N, L) id tensor on `dev`, (N,) set index on `dev`, lengths or None for the 0 rule)."""
@@ -1277,10 +1277,26 @@ def validation_rouge_l(captions, hyp_set, ground_truth, dev, count_end=False, wo
     return scorer.corpus_score(captions, hyp_set, scorer.prepare_refs(ground_truth, count_end=count_end), lens)
 
 
-def validation_scores(captions, hyp_set, ground_truth, dev, count_end=False, word_map=None):
+def validation_cider(captions, hyp_set, ground_truth, dev, count_end=False, word_map=None):
+    """Corpus CIDEr of decoded captions without strings: cocoEval's `CIDEr`, the value the reference's evaluate() returns first
+    and selects checkpoints by (`eval/eval rl/eval_full.py:235`).  It is the SCST reward's sentence formula (ciderd.py) with
+    another table: the document frequencies and the number of documents N come from the reference sets of `ground_truth`
+    itself — ALL of them, whichever sets hyp_set names; a gram counts once per image (ciderd.corpus_cider is the host
+    statement).  The table is built on the device from the uploaded reference ids (ciderd.DeviceCiderD.from_refs,
+    csrc/ciderd_device.hip cd_build_k); the value is the mean of the captions' scores, taken there.  Input forms and conventions
+    are validation_bleu's.  Returns a 0-d float64 device tensor; nothing is read back."""
+    from . import ciderd
+    scorer, refs = ciderd.DeviceCiderD.from_refs(dev, ground_truth, count_end=count_end)
+    captions, hyp_set, lens = _validation_rows(captions, hyp_set, scorer.dev, count_end, word_map)
+    return scorer.corpus_score(captions, hyp_set, refs, lens)
+
+
+def validation_scores(captions, hyp_set, ground_truth, dev, count_end=False, word_map=None, cider=False):
     """validation_bleu and validation_rouge_l in one: the references are uploaded once and prepared by one launch, whose
     records both score kernels read.  Returns {'Bleu_1', 'Bleu_2', 'Bleu_3', 'Bleu_4', 'ROUGE_L'} (the reference's key names)
-    -> 0-d float64 device tensors, the very bits of the two single calls; nothing is read back."""
+    -> 0-d float64 device tensors, the very bits of the two single calls; nothing is read back.
+    cider=True: the reference's whole overlap row — the key 'CIDEr' comes last, with the bits of validation_cider; its table
+    and reference vectors are built from the same upload."""
     from . import bleu, rouge
     bscorer, rscorer = bleu.device_scorer(dev), rouge.device_scorer(dev)
     captions, hyp_set, lens = _validation_rows(captions, hyp_set, bscorer.dev, count_end, word_map)
@@ -1288,4 +1304,8 @@ def validation_scores(captions, hyp_set, ground_truth, dev, count_end=False, wor
     b = bscorer.corpus_score(captions, hyp_set, refs, lens)
     out = {"Bleu_%d" % (k + 1): b[k] for k in range(4)}
     out["ROUGE_L"] = rscorer.corpus_score(captions, hyp_set, refs, lens)
+    if cider:
+        from . import ciderd
+        cscorer, crefs = ciderd.DeviceCiderD.from_refs(bscorer.dev, refs)
+        out["CIDEr"] = cscorer.corpus_score(captions, hyp_set, crefs, lens)
     return out
