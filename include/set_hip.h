@@ -1396,6 +1396,45 @@ int set_rouge_device_score(const int64_t* hyp, int64_t hyp_ld, const int32_t* hy
                            const void* ref_recs, int ref_L, int64_t n_refs, const int64_t* ref_set_off, int n_sets, int max_set,
                            double beta, int32_t* stats, double* scores, double* pair_scores, int64_t pair_ld, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Word edit distance on the DEVICE (csrc/editdist_device.hip): the statistics, similarity and canonical word alignment that
+ * editdist.py states, from id rows in device memory on `stream` with no host read.  Sentences and their limits are those of the
+ * BLEU block above.  Stateless: there is no handle.
+ *   d(h, r) = the unit-cost Levenshtein distance of the id sequences (substitution, insertion, deletion: 1 each);
+ *   m = max(len_h, len_r);  sim(h, r) = (m - d) / m, one double division, and 1 when both are empty.  Of a set the reference of
+ *   the largest sim is chosen (compared exactly, as fractions, empty against empty as 1/1; of equal ones the first of the set).
+ *   The statistics are integers; the score is a function of the row's integers alone, so a row's result does not depend on the
+ *   launch it is part of.  No atomics, no LDS; only the declared outputs are written.
+ * score: hypothesis i, reference records (set_bleu_device_prepare's: one preparation serves BLEU, ROUGE-L and this entry), L,
+ *   hyp_lens, ref_L, n_refs, ref_set_off, n_sets, max_set as in set_bleu_device_score.  One wave per hypothesis writes
+ *   stats[i, 0..4) = dist, len_h, len_r, ref (int32; ref = the chosen reference's position in its set), with scores != NULL
+ *   scores[i] = sim of those integers, and with pair_scores != NULL pair_scores[i pair_ld + r] = sim against reference r of its set
+ *   alone, r < |set|; nothing else is written.  An empty set gives len_h, len_h, 0, -1 and the score of an empty reference.  What
+ *   the host cannot check is answered by the kernel with -1 in stats[i, :] and NaN in scores[i], nothing else touched:
+ *   set_of_hyp[i] outside [0, n_sets), offsets outside [0, n_refs] or decreasing, a set larger than max_set.  An id outside
+ *   [0, 65534) in the hypothesis or one of its references gives -1 in stats[i, :] and a NaN score in that row (and NaN pair scores
+ *   from the first such sentence on).
+ *   SET_ERR_ARG: NULL stats, and what set_bleu_device_score refuses with it; SET_ERR_UNSUPPORTED: L or ref_L > 64 — before any HIP
+ *   call.  n_hyp == 0: nothing is done.
+ * align: the edit script that turns source row i (src[i src_ld .. i src_ld + src_L), src_lens as hyp_lens) into hypothesis row i
+ *   (hyp, hyp_ld, hyp_lens, L), read off the full table D (rows: source, columns: hypothesis) from (len_s, len_h) backwards, at every
+ *   cell the first rule that applies: keep (equal words, D equal on the diagonal), substitute (diagonal + 1), insert (left + 1),
+ *   else delete.  One wave per row writes
+ *     stats[i, 0..8)  = dist, len_h, len_s, keep, sub, ins, del, unchanged (1 when dist == 0)                  (int32)
+ *     hyp_ops[i ops_ld + j], j < L       = 1 keep, 2 substitute, 3 insert, 0 at and beyond len_h                (int8)
+ *     hyp_src[i ops_ld + j], j < L       = the aligned source position of a kept / substituted word, else -1    (int32)
+ *     src_ops[i src_ops_ld + k], k < src_L = 1 kept, 2 substituted, 3 deleted, 0 at and beyond len_s            (int8)
+ *   and nothing else.  An id outside [0, 65534) inside either sentence: stats[i, :] = -1, ops 0, hyp_src -1.
+ *   SET_ERR_ARG: a NULL pointer other than the lengths (with n > 0), n < 0, L or src_L < 1, hyp_ld or ops_ld < L, src_ld or
+ *   src_ops_ld < src_L; SET_ERR_UNSUPPORTED: L or src_L > 64 — before any HIP call.  n == 0: nothing is done.
+ * ------------------------------------------------------------------------------------------ */
+int set_edit_device_score(const int64_t* hyp, int64_t hyp_ld, const int32_t* hyp_lens, int n_hyp, int L, const int32_t* set_of_hyp,
+                          const void* ref_recs, int ref_L, int64_t n_refs, const int64_t* ref_set_off, int n_sets, int max_set,
+                          int32_t* stats, double* scores, double* pair_scores, int64_t pair_ld, void* stream);
+int set_edit_device_align(const int64_t* hyp, int64_t hyp_ld, const int32_t* hyp_lens, int n, int L, const int64_t* src,
+                          int64_t src_ld, const int32_t* src_lens, int src_L, int32_t* stats, int8_t* hyp_ops, int64_t ops_ld,
+                          int32_t* hyp_src, int8_t* src_ops, int64_t src_ops_ld, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

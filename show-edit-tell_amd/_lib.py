@@ -500,6 +500,8 @@ PROTOTYPES = {
     "set_bleu_device_prepare": (_I, [_P, _L, _P, _I, _I, _P, _P]),
     "set_bleu_device_score": (_I, [_P, _L, _P, _I, _I, _P, _P, _I, _L, _P, _I, _I, _P, _P, _P, _L, _P]),
     "set_rouge_device_score": (_I, [_P, _L, _P, _I, _I, _P, _P, _I, _L, _P, _I, _I, C.c_double, _P, _P, _P, _L, _P]),
+    "set_edit_device_score": (_I, [_P, _L, _P, _I, _I, _P, _P, _I, _L, _P, _I, _I, _P, _P, _P, _L, _P]),
+    "set_edit_device_align": (_I, [_P, _L, _P, _I, _I, _P, _L, _P, _I, _P, _P, _L, _P, _P, _L, _P]),
     "set_caption_encoder_workspace_bytes": (_Z, [_I, _I, _I]),
     "set_caption_encoder_f32": (_I, [C.POINTER(EditNetWeights), _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _Z, _P]),
 }

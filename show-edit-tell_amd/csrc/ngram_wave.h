@@ -28,7 +28,7 @@ __host__ __device__ inline uint64_t hash(uint64_t x) {         // the 64-bit mix
 }
 
 // record of one prepared reference, in 8-byte words (written by csrc/bleu_device.hip bl_prepare_k; read there and by
-// csrc/rouge_device.hip, which needs words 0, 1 and the order-1 key of every position):
+// csrc/rouge_device.hip and csrc/editdist_device.hip, which need words 0, 1 and the order-1 key of every position):
 //   [0] length   [1] 1: an id that cannot be packed   [2..7] 0
 //   [8 + 4 i + k]  key of the order-(k+1) gram that starts at position i (0: none), EVERY occurrence (counts need them)
 __host__ __device__ inline size_t ref_rec_words(int L) { return 8 + 4 * (size_t)L; }

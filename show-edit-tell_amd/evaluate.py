@@ -1164,7 +1164,8 @@ def consensus_rerank(scorer, candidates, n_per_image, weights=None):
     `scorer.pair_scores(candidates, n)` gives the (NI * n, n) CIDEr-D of every candidate against each candidate of its image
     as the only reference (csrc/ciderd_device.hip: the candidates are each other's references and never leave the device).
     Any object with that method serves: bleu.DeviceBleu(dev) reranks under sentence BLEU-4 instead (csrc/bleu_device.hip),
-    rouge.DeviceRougeL(dev) under ROUGE-L (csrc/rouge_device.hip).
+    rouge.DeviceRougeL(dev) under ROUGE-L (csrc/rouge_device.hip),
+    editdist.DeviceEditDistance(dev) under the word edit similarity (m - d) / m (csrc/editdist_device.hip).
     utility[i, j] = mean over the OTHER candidates r != j of that score (the diagonal is left out; identical candidates are
     separate votes), or with weights (NI, n) — e.g. sbs_importance_weights per image — the weighted mean
     sum_{r != j} w[i, r] s[j, r] / sum_{r != j} w[i, r] (0 where that sum is 0).  n = 1: utility 0, index 0.
@@ -1309,3 +1310,103 @@ def validation_scores(captions, hyp_set, ground_truth, dev, count_end=False, wor
         cscorer, crefs = ciderd.DeviceCiderD.from_refs(bscorer.dev, refs)
         out["CIDEr"] = cscorer.corpus_score(captions, hyp_set, crefs, lens)
     return out
+
+
+# ---- word edit distance: how far from the references, how much the model edited, which word became which (editdist.py) ----------
+def validation_edit(captions, hyp_set, ground_truth, dev, count_end=False, word_map=None):
+    """Word edit distance of decoded captions to their closest references without strings (editdist.py): {'similarity': the mean
+    of the captions' (m - d) / m against the reference of largest similarity, 'wer': sum d / sum len of those references} on the
+    device (editdist.DeviceEditDistance, csrc/editdist_device.hip), nothing read back.  Input forms and conventions are
+    validation_bleu's.  Returns 0-d float64 device tensors."""
+    from . import editdist
+    scorer = editdist.device_scorer(dev)
+    captions, hyp_set, lens = _validation_rows(captions, hyp_set, scorer.dev, count_end, word_map)
+    return scorer.corpus_score(captions, hyp_set, scorer.prepare_refs(ground_truth, count_end=count_end), lens)
+
+
+def source_rows(previous_caption, prev_caplen, word_map, count_end=False):
+    """The model's input captions in the outputs' convention, on the device they are on: previous_caption (B, Lp) in the
+    vocabulary's ids with <start> / <end> / <pad>, prev_caplen (B[, 1]) ids per row (None: the whole row) -> ((B, Lp) int64
+    with <start> / <pad> dropped, the rest moved to the front and <end> rewritten to 0 — ciderd.ground_truth_lists' rule —,
+    (B,) int32 lengths: up to and, with count_end, including the first 0; no 0: every kept id)."""
+    prev = torch.as_tensor(previous_caption).long()
+    if prev.dim() != 2:
+        raise ValueError("previous captions are rows of a 2-D id tensor, got shape %s" % (tuple(prev.shape),))
+    B, Lp = prev.shape
+    pos = torch.arange(Lp, device=prev.device)[None, :]
+    keep = (prev != int(word_map['<start>'])) & (prev != int(word_map['<pad>']))
+    if prev_caplen is not None:
+        keep &= pos < torch.as_tensor(prev_caplen).to(prev.device).reshape(B, 1)
+    ids = torch.where(prev == int(word_map['<end>']), torch.zeros_like(prev), prev)
+    dest = torch.where(keep, keep.long().cumsum(1) - 1, torch.full_like(prev, Lp))          # dropped ids land in a spare column
+    rows = torch.zeros(B, Lp + 1, dtype=torch.int64, device=prev.device).scatter_(1, dest, ids)[:, :Lp]
+    kept = keep.long().sum(1)
+    is0 = (rows == 0) & (pos < kept[:, None])
+    lens = torch.where(is0.any(1), is0.int().argmax(1) + (1 if count_end else 0), kept)
+    return rows, lens.int()
+
+
+def _edit_rows(previous_caption, prev_caplen, captions, word_map, dev, count_end):
+    """both sides of edit_statistics / edit_alignment on the scorer's device: (scorer, hyp rows, hyp lengths or None, source
+    rows, source lengths)"""
+    from . import editdist
+    scorer = editdist.device_scorer(dev)
+    lists = not hasattr(captions, "shape")                         # a tensor or an array: decoder ids; else token lists
+    hyp, _, hyp_lens = _validation_rows(captions, None, scorer.dev, count_end, word_map if lists else None)
+    src, src_lens = source_rows(torch.as_tensor(previous_caption).to(scorer.dev), prev_caplen, word_map, count_end)
+    if src.shape[0] != hyp.shape[0]:
+        raise ValueError("%d captions for %d previous captions" % (hyp.shape[0], src.shape[0]))
+    return scorer, hyp, hyp_lens, src, src_lens
+
+
+def edit_statistics(previous_caption, prev_caplen, captions, word_map, dev, count_end=False):
+    """How much the model edited: the word edit script from each input caption to its output (editdist.alignment), counted.
+        seq, _ = decoder(word_map, prev, plen, X, sample_max=True, sample_rl=False)     # greedy: (B, L) ids, stays on the device
+        st = edit_statistics(prev, plen, seq, word_map, X.device)                        # st['unchanged_frac'], st['edit_rate']
+    previous_caption (B, Lp) / prev_caplen: the model's input, brought to the outputs' convention on the device (source_rows);
+    captions: (B, L) decoder ids (0 = <end> and everything after it) or, as validation_bleu accepts with word_map, B token
+    lists in the vocabulary's ids.  count_end as in validation_bleu, on both sides.  Returns device tensors, nothing read back:
+    per caption int32 (B,) 'dist', 'keep', 'sub', 'ins', 'del', 'unchanged'; 0-d float64 'unchanged_frac', 'mean_dist' and
+    'edit_rate' = sum dist / sum source length (0 when that sum is 0)."""
+    scorer, hyp, hyp_lens, src, src_lens = _edit_rows(previous_caption, prev_caplen, captions, word_map, dev, count_end)
+    st = scorer.align_token_ids(hyp, src, hyp_lens, src_lens)[0]
+    out = {k: st[:, c] for k, c in (("dist", 0), ("keep", 3), ("sub", 4), ("ins", 5), ("del", 6), ("unchanged", 7))}
+    zero = torch.zeros((), dtype=torch.float64, device=st.device)
+    words = st[:, 2].sum().double()
+    some = st.shape[0] > 0
+    out["unchanged_frac"] = st[:, 7].double().mean() if some else zero
+    out["mean_dist"] = st[:, 0].double().mean() if some else zero
+    out["edit_rate"] = torch.where(words > 0, st[:, 0].sum().double() / torch.where(words > 0, words, torch.ones_like(words)), zero)
+    return out
+
+
+class EditAlignment:
+    """The word alignment of each input caption with its output (editdist.DeviceEditDistance.align_token_ids), device tensors:
+    stats int32 (B, 8) = dist, len_h, len_s, keep, sub, ins, del, unchanged; hyp_ops int8 (B, L) 1 keep / 2 substitute /
+    3 insert; hyp_src int32 (B, L) the aligned source position or -1; src_ops int8 (B, Ls) 1 kept / 2 substituted / 3 deleted;
+    0 / -1 at and beyond the lengths.  hyp (B, L) and src (B, Ls) are the id rows that were aligned (<end> = 0).  This is the
+    edit that happened between the two word sequences; EditTrace records the model's own soft view of it."""
+
+    def __init__(self, stats, hyp_ops, hyp_src, src_ops, hyp, src):
+        self.stats, self.hyp_ops, self.hyp_src, self.src_ops, self.hyp, self.src = stats, hyp_ops, hyp_src, src_ops, hyp, src
+
+    def rows(self, word_map):
+        """per caption: ([(output word, 'keep' / 'substitute' / 'insert', source word or None)], [deleted source words])"""
+        from .editdist import DEL, OP_NAMES
+        rev = {int(v): k for k, v in word_map.items()}
+        rev[0] = '<end>'
+        hyp, src = self.hyp.cpu().tolist(), self.src.cpu().tolist()
+        ho, hs, so = self.hyp_ops.cpu().tolist(), self.hyp_src.cpu().tolist(), self.src_ops.cpu().tolist()
+        out = []
+        for b, st in enumerate(self.stats.cpu().tolist()):
+            words = [(rev[hyp[b][j]], OP_NAMES[ho[b][j]], rev[src[b][hs[b][j]]] if hs[b][j] >= 0 else None)
+                     for j in range(max(st[1], 0))]
+            out.append((words, [rev[src[b][k]] for k in range(max(st[2], 0)) if so[b][k] == DEL]))
+        return out
+
+
+def edit_alignment(previous_caption, prev_caplen, captions, word_map, dev, count_end=False):
+    """Which input word each output word corresponds to -> EditAlignment.  Arguments as edit_statistics; nothing is read back
+    until `rows(word_map)` is asked for."""
+    scorer, hyp, hyp_lens, src, src_lens = _edit_rows(previous_caption, prev_caplen, captions, word_map, dev, count_end)
+    return EditAlignment(*scorer.align_token_ids(hyp, src, hyp_lens, src_lens), hyp, src)
