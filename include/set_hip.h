@@ -665,10 +665,16 @@ int set_lstm_cell_train_f32(const float* x, int64_t ldx, int Kx, const float* h,
  * targets, CrossEntropyLoss) on the (B, T, V) scores in place: element (b, t, v) at scores[b*stride_b + t*stride_t + v],
  * target word of (b, t) at targets[b*tstride_b + t*tstride_t].  The batch is sorted by decreasing decode length and
  * live[t] (HOST array, T <= 64 entries, non-increasing) = number of sequences with decode length > t: row (b, t) is one
- * of the packed rows iff b < live[t].  Forward: rowloss / lse (T*B floats each, index t*B + b; zeros for dead rows) and
- * loss_sum (1 float) = the SUM of the token losses (divide by the token count for CrossEntropyLoss's mean).
- * Backward: grad (T, B, ld_grad) with ld_grad = V rounded up to 4 — (softmax - onehot) * dloss[0] for live rows, zeros for
- * dead rows and for the padding columns (so the buffer can feed set_gemm_f32 as a zero-padded k-major operand). */
+ * of the packed rows iff b < live[t].  Forward: rowloss (T*B floats, index t*B + b; zeros for dead rows), lse (2*T*B
+ * floats: [t*B + b] the row's log-sum-exp rounded to fp32, [T*B + t*B + b] the remainder of that rounding, so that the
+ * backward's exp(x - lse) does not inherit half an ulp of |lse| as a relative error of the whole row; zeros for dead rows)
+ * and loss_sum (1 float) = the SUM of the token losses (divide by the token count for CrossEntropyLoss's mean).
+ * Backward: lse as the forward of the same arguments wrote it; grad (T, B, ld_grad) with ld_grad = V rounded up to 4 —
+ * (softmax - onehot) * dloss[0] for live rows, zeros for dead rows and for the padding columns (so the buffer can feed
+ * set_gemm_f32 as a zero-padded k-major operand).
+ * Both refuse, before any launch and without touching an output: T > 64 (SET_ERR_UNSUPPORTED); a live table with an
+ * entry below 0 or above B, or one that increases (SET_ERR_ARG); the backward also ld_grad != V rounded up to 4
+ * (SET_ERR_ARG). */
 int set_xe_loss_f32(const float* scores, int64_t stride_b, int64_t stride_t, const int64_t* targets, int64_t tstride_b,
                     int64_t tstride_t, const int* live, int B, int T, int V, float* rowloss, float* lse,
                     float* loss_sum, void* stream);

@@ -31,7 +31,7 @@ __global__ void __launch_bounds__(256) xe_loss_fwd_k(const float* scores, long l
     __shared__ float red_m[4], red_s[4];
     const int t = blockIdx.x / B, b = blockIdx.x - t * B;
     if (b >= live.n[t]) {
-        if (threadIdx.x == 0) { rowloss[blockIdx.x] = 0.f; lse_out[blockIdx.x] = 0.f; }
+        if (threadIdx.x == 0) { rowloss[blockIdx.x] = 0.f; lse_out[blockIdx.x] = 0.f; lse_out[gridDim.x + blockIdx.x] = 0.f; }
         return;
     }
     const float* x = scores + b * sb + t * st;
@@ -50,12 +50,21 @@ __global__ void __launch_bounds__(256) xe_loss_fwd_k(const float* scores, long l
         float ss = 0.f;
 #pragma unroll
         for (int i = 0; i < 4; ++i) ss += red_s[i] * __expf(red_m[i] - mm);
-        const float lse = mm + logf(ss);
+        // lse as TWO floats, hi + lo (TwoSum of the maximum and the log of the rescaled sum).  One float holds lse to half an
+        // ulp of |lse|, and the backward's exp(x - lse) turns that ABSOLUTE error into a RELATIVE error of the whole softmax
+        // row: 3e-5 at scores near 1000, 2e-6 at a +60 peak — hundreds of fp32 roundings of the gradient.  With the remainder
+        // the argument (x - hi) - lo is as exact as x - max - log(sum) is.
+        const float lg = logf(ss);
+        const float lse = mm + lg;
+        const float bb = lse - mm;
+        float lo = (mm - (lse - bb)) + (lg - bb);
+        if (!(lse - lse == 0.f)) lo = 0.f;          // an infinite or NaN lse has no remainder
         // an id outside [0, V) (corrupted caption, vocabulary mismatch): F.cross_entropy raises; without a host round trip the
         // loud form available here is a NaN loss — never a silently clamped label
         const long long tg = targets[b * tb + t * tt];
-        rowloss[blockIdx.x] = (tg < 0 || tg >= V) ? __builtin_nanf("") : lse - x[tg];
+        rowloss[blockIdx.x] = (tg < 0 || tg >= V) ? __builtin_nanf("") : (lse - x[tg]) + lo;
         lse_out[blockIdx.x] = lse;
+        lse_out[gridDim.x + blockIdx.x] = lo;
     }
 }
 
@@ -81,12 +90,12 @@ __global__ void __launch_bounds__(256) xe_loss_bwd_k(const float* scores, long l
         return;
     }
     const float* x = scores + b * sb + t * st;
-    const float l = lse[blockIdx.x], d = *dloss;
+    const float l = lse[blockIdx.x], l_lo = lse[gridDim.x + blockIdx.x], d = *dloss;   // lse = l + l_lo, see the forward
     const long long tg = targets[b * tb + t * tt];
     const bool bad = tg < 0 || tg >= V;                      // see the forward: the row's gradient is NaN, not a clamped label's
     for (int v = threadIdx.x; v < V4; v += 256) {
         float o = 0.f;
-        if (v < V) o = bad ? __builtin_nanf("") : (__expf(x[v] - l) - (v == (int)tg ? 1.f : 0.f)) * d;
+        if (v < V) o = bad ? __builtin_nanf("") : (__expf((x[v] - l) - l_lo) - (v == (int)tg ? 1.f : 0.f)) * d;
         g[v] = o;
     }
 }
@@ -157,6 +166,8 @@ int set_xe_loss_bwd_f32(const float* scores, int64_t stride_b, int64_t stride_t,
     if (ld_grad != (((int64_t)V + 3) & ~(int64_t)3)) return SET_ERR_ARG;
     XeLive lv;
     for (int t = 0; t < XE_MAX_T; ++t) lv.n[t] = t < T ? live[t] : 0;
+    for (int t = 0; t < T; ++t)               // the forward's check: a table it refuses would index rows the forward never wrote
+        if (lv.n[t] < 0 || lv.n[t] > B || (t > 0 && lv.n[t] > lv.n[t - 1])) return SET_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(xe_loss_bwd_k, dim3((unsigned)(T * B)), dim3(256), 0, s, scores, (long long)stride_b, (long long)stride_t,
                        targets, (long long)tstride_b, (long long)tstride_t, lv, B, V, (int)ld_grad, lse, dloss, grad);

@@ -24,7 +24,7 @@ class _XELossSum(torch.autograd.Function):
         B, T, V = scores.shape
         dev = scores.device
         rowloss = torch.empty(T * B, dtype=torch.float32, device=dev)
-        lse = torch.empty(T * B, dtype=torch.float32, device=dev)
+        lse = torch.empty(2 * T * B, dtype=torch.float32, device=dev)      # lse and its rounding remainder (set_hip.h)
         loss = torch.empty((), dtype=torch.float32, device=dev)
         live_c = (C.c_int * T)(*live)
         check(lib.set_xe_loss_f32(scores.data_ptr(), scores.stride(0), scores.stride(1), targets.data_ptr(), targets.stride(0),
