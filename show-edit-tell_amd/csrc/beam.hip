@@ -11,49 +11,26 @@
 //      hypotheses compacted to the front in pick order, sequences re-indexed by parent and extended,
 //      next input words, and the parent row map that beam_gather_k uses to re-index the LSTM states.
 // Nothing is synchronised with the host; an image whose k has reached 0 is a no-op.
-#include "row_pick.h"
+#include "beam_tail.h"
 
 namespace set {
-
-constexpr int BEAM_KMAX = 8;
 
 struct BeamArgs {
     const float* logits;
     const float* logits2;        // second model of the ensemble, or nullptr
     long long ld;
-    int k, V, cur_len, Lmax;
-    long long end_idx;
-    float* scores;               // (NI, k) running hypothesis scores, -inf = dead slot
-    int* k_left;                 // (NI)
-    const long long* seqs_in;    // (NI, k, Lmax), cur_len tokens valid
-    long long* seqs_out;
-    float* best_score;           // (NI) best completed hypothesis so far
-    long long* best_seq;         // (NI, Lmax)
-    int* best_len;               // (NI)
-    long long* words;            // (NI*k) next input token per hypothesis row
-    int* rows;                   // (NI*k) source row of each hypothesis row's recurrent state
-    // n-best (set_beam_pick_nbest_f32; all four nullptr otherwise): every counted <end> pick appends one entry, in completion
-    // order (by pick, within a pick by pick rank).  An image completes at most k hypotheses
-    float* done_score;           // (NI, k)
-    long long* done_seq;         // (NI, k, Lmax)
-    int* done_len;               // (NI, k)
-    int* n_done;                 // (NI) entries so far
+    BeamState s;                 // done_*: the n-best entry's arrays (set_beam_pick_nbest_f32), all four nullptr otherwise
 };
 
-__global__ void __launch_bounds__(256) beam_pick_k(const BeamArgs a) {
+__global__ void __launch_bounds__(256) beam_pick_k(const BeamArgs args) {
     __shared__ float s_m[4][2], s_s[4][2];
     __shared__ float s_lse[BEAM_KMAX][2];
     __shared__ float s_rv[4];
     __shared__ int s_ri[4];
     __shared__ float s_pick_v[BEAM_KMAX];
     __shared__ int s_pick_i[BEAM_KMAX];
-    __shared__ int s_src[BEAM_KMAX];            // per output slot: parent hypothesis
-    __shared__ long long s_word[BEAM_KMAX];     // per output slot: appended word
-    __shared__ int s_best_parent;
-    __shared__ long long s_best_word;
-    __shared__ int s_done_par[BEAM_KMAX];       // per completion of this pick: parent hypothesis
-    __shared__ long long s_done_word[BEAM_KMAX];
-    __shared__ int s_done_at, s_done_n;         // first entry of this pick in the image's list, entries of this pick
+    __shared__ BeamTailLds s_t;
+    const BeamState& a = args.s;
     const int img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int k = a.k, V = a.V;
     const int kl = a.k_left[img];
@@ -66,11 +43,11 @@ __global__ void __launch_bounds__(256) beam_pick_k(const BeamArgs a) {
     for (int j = 0; j < BEAM_KMAX; ++j) sc[j] = j < k ? a.scores[img * k + j] : -INFINITY;
 
     // ---- 1. log-sum-exp of every live row (both models for the ensemble)
-    const int nmodel = a.logits2 ? 2 : 1;
+    const int nmodel = args.logits2 ? 2 : 1;
     for (int j = 0; j < k; ++j) {
         if (sc[j] == -INFINITY) continue;        // uniform across the block
         for (int mdl = 0; mdl < nmodel; ++mdl) {
-            const float* row = (mdl ? a.logits2 : a.logits) + (long long)(img * k + j) * a.ld;
+            const float* row = (mdl ? args.logits2 : args.logits) + (long long)(img * k + j) * args.ld;
             float m = -INFINITY, s = 0.f;
             for (int v = tid; v < V; v += 256) {
                 const float x = row[v];
@@ -103,11 +80,11 @@ __global__ void __launch_bounds__(256) beam_pick_k(const BeamArgs a) {
     float lv[BEAM_KMAX];
     int li[BEAM_KMAX];
 #pragma unroll
-    for (int q = 0; q < BEAM_KMAX; ++q) { lv[q] = -INFINITY; li[q] = 0x7fffffff; }
+    for (int q = 0; q < BEAM_KMAX; ++q) { lv[q] = -INFINITY; li[q] = BEAM_NONE; }
     for (int j = 0; j < k; ++j) {
         if (sc[j] == -INFINITY) continue;
-        const float* row = a.logits + (long long)(img * k + j) * a.ld;
-        const float* row2 = a.logits2 ? a.logits2 + (long long)(img * k + j) * a.ld : nullptr;
+        const float* row = args.logits + (long long)(img * k + j) * args.ld;
+        const float* row2 = args.logits2 ? args.logits2 + (long long)(img * k + j) * args.ld : nullptr;
         const float l0 = s_lse[j][0], l1 = row2 ? s_lse[j][1] : 0.f;
         for (int v = tid; v < V; v += 256) {
             float lp;
@@ -141,88 +118,24 @@ __global__ void __launch_bounds__(256) beam_pick_k(const BeamArgs a) {
 #pragma unroll
         for (int w = 1; w < 4; ++w)
             if (beam_better(s_rv[w], s_ri[w], bv, bi)) { bv = s_rv[w]; bi = s_ri[w]; }
-        if (li[0] == bi && bi != 0x7fffffff) {
+        if (li[0] == bi && bi != BEAM_NONE) {
 #pragma unroll
             for (int q = 0; q + 1 < BEAM_KMAX; ++q) { lv[q] = lv[q + 1]; li[q] = li[q + 1]; }
-            lv[BEAM_KMAX - 1] = -INFINITY; li[BEAM_KMAX - 1] = 0x7fffffff;
+            lv[BEAM_KMAX - 1] = -INFINITY; li[BEAM_KMAX - 1] = BEAM_NONE;
         }
         if (tid == 0) { s_pick_v[r] = bv; s_pick_i[r] = bi; }
         __syncthreads();
     }
 
-    // ---- 3. bookkeeping of one image (editnet.py:666-699)
+    // ---- 3. bookkeeping of one image (editnet.py:666-699; beam_tail.h): one group of k slots, never exhausted, plain scores
     if (tid == 0) {
-        int n_end = 0, c_arg = -1, slot = 0;
-        float c_best = -INFINITY;
-        bool live[BEAM_KMAX];
-        for (int r = 0; r < k; ++r) {
-            const int flat = s_pick_i[r];
-            const bool ok = flat != 0x7fffffff && r < kl;               // only the first k_left picks count
-            const long long word = ok ? flat % V : 0;
-            const bool is_end = ok && word == a.end_idx;
-            live[r] = ok && !is_end;
-            if (is_end) {
-                ++n_end;
-                if (s_pick_v[r] > c_best) { c_best = s_pick_v[r]; c_arg = r; }     // first maximum
-            }
-        }
-        s_best_parent = -1;
-        if (c_arg >= 0 && c_best > a.best_score[img]) {
-            a.best_score[img] = c_best;
-            a.best_len[img] = a.cur_len + 1;
-            s_best_parent = s_pick_i[c_arg] / V;
-            s_best_word = s_pick_i[c_arg] % V;
-        }
-        a.k_left[img] = kl - n_end;
-        s_done_n = 0;
-        if (a.n_done) {                          // the completions of this pick, in pick-rank order
-            const int at = max(a.n_done[img], 0);
-            int nd = 0;
-            for (int r = 0; r < k; ++r) {
-                const int flat = s_pick_i[r];
-                if (!(flat != 0x7fffffff && r < kl && flat % V == a.end_idx) || at + nd >= k) continue;
-                a.done_score[img * k + at + nd] = s_pick_v[r];
-                a.done_len[img * k + at + nd] = a.cur_len + 1;
-                s_done_par[nd] = flat / V;
-                s_done_word[nd] = flat % V;
-                ++nd;
-            }
-            a.n_done[img] = at + nd;
-            s_done_at = at; s_done_n = nd;
-        }
-        // live picks first, in pick order; the other slots die
-        for (int pass = 0; pass < 2; ++pass)
-            for (int r = 0; r < k; ++r) {
-                if ((pass == 0) != live[r]) continue;
-                const int flat = s_pick_i[r];
-                const int parent = flat != 0x7fffffff ? flat / V : 0;
-                const long long word = flat != 0x7fffffff ? flat % V : 0;
-                a.scores[img * k + slot] = live[r] ? s_pick_v[r] : -INFINITY;
-                a.words[img * k + slot] = live[r] ? word : 0;
-                a.rows[img * k + slot] = img * k + parent;
-                s_src[slot] = parent;
-                s_word[slot] = word;
-                ++slot;
-            }
+        beam_tail_begin(a, img, s_t);
+        a.k_left[img] = beam_tail_group<false, false>(a, img, 0, k, kl, s_pick_v, s_pick_i, 0.f, 1.f, 0, nullptr, nullptr, nullptr,
+                                                      s_t);
+        if (a.n_done) a.n_done[img] = s_t.done_at + s_t.done_n;
     }
     __syncthreads();
-    const int L = a.cur_len;
-    const long long* sin = a.seqs_in + (long long)img * k * a.Lmax;
-    long long* sout = a.seqs_out + (long long)img * k * a.Lmax;
-    for (int e = tid; e < k * (L + 1); e += 256) {
-        const int slot = e / (L + 1), p = e - slot * (L + 1);
-        sout[(long long)slot * a.Lmax + p] = p < L ? sin[(long long)s_src[slot] * a.Lmax + p] : s_word[slot];
-    }
-    if (s_best_parent >= 0)
-        for (int p = tid; p <= L; p += 256)
-            a.best_seq[(long long)img * a.Lmax + p] = p < L ? sin[(long long)s_best_parent * a.Lmax + p] : s_best_word;
-    if (s_done_n > 0) {
-        long long* dout = a.done_seq + ((long long)img * k + s_done_at) * a.Lmax;
-        for (int e = tid; e < s_done_n * (L + 1); e += 256) {
-            const int j = e / (L + 1), p = e - j * (L + 1);
-            dout[(long long)j * a.Lmax + p] = p < L ? sin[(long long)s_done_par[j] * a.Lmax + p] : s_done_word[j];
-        }
-    }
+    beam_tail_copy(a, img, s_t, tid, 256);
 }
 
 // state[s][r] <- state[s][rows[r]] for the k rows of one image, in place (all parents are rows of the same image)
@@ -259,14 +172,9 @@ static int beam_pick(const float* logits, const float* logits2, int64_t ld, int 
     if (!logits || !scores || !k_left || !seqs_in || !seqs_out || !best_score || !best_seq || !best_len || !words || !rows)
         return SET_ERR_ARG;
     if (NI <= 0 || k <= 0 || V <= 0 || cur_len < 1 || cur_len + 1 > Lmax || ld < V) return SET_ERR_ARG;
-    if (k > BEAM_KMAX || (long long)k * V >= 0x7fffffffLL) return SET_ERR_UNSUPPORTED;
-    BeamArgs a;
-    a.logits = logits; a.logits2 = logits2; a.ld = ld; a.k = k; a.V = V; a.cur_len = cur_len; a.Lmax = Lmax;
-    a.end_idx = end_idx; a.scores = scores; a.k_left = k_left;
-    a.seqs_in = (const long long*)seqs_in; a.seqs_out = (long long*)seqs_out;
-    a.best_score = best_score; a.best_seq = (long long*)best_seq; a.best_len = best_len;
-    a.words = (long long*)words; a.rows = rows;
-    a.done_score = done_score; a.done_seq = (long long*)done_seq; a.done_len = done_len; a.n_done = n_done;
+    if (k > BEAM_KMAX || (long long)k * V >= BEAM_NONE) return SET_ERR_UNSUPPORTED;
+    const BeamArgs a{logits, logits2, ld, beam_state(k, V, end_idx, cur_len, Lmax, scores, k_left, seqs_in, seqs_out, best_score, best_seq,
+                                                    best_len, words, rows, done_score, done_seq, done_len, n_done)};
     ProfScope ps("beam_pick", (hipStream_t)stream, 0.0, 8.0 * NI * k * V * (logits2 ? 2.0 : 1.0));
     hipLaunchKernelGGL(beam_pick_k, dim3(NI), dim3(256), 0, (hipStream_t)stream, a);
     SET_LAUNCH_CHECK();

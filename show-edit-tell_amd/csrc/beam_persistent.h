@@ -5,9 +5,10 @@
 //   * of the k picks, only as many as there are live hypotheses (k_left) count, the best ones;
 //   * among the hypotheses completed by one pick the FIRST maximum is kept, and only if it beats the best so far;
 //   * live hypotheses are compacted to the front in pick order, the remaining slots are dead (-inf).
-// csrc/beam.hip's beam_pick_k applies the same rules to MANY images per launch, up to BEAM_KMAX hypotheses and global outputs; it
-// stays a separate kernel (sharing with it would take more parameters, not fewer lines).  A change to a rule is made there
-// and in pb_pick below.
+// The per-step picks (beam_pick_k in csrc/beam.hip, bd_merge_k in csrc/beam_constrained.hip) apply the same rules to MANY images
+// per launch, up to BEAM_KMAX hypotheses and global outputs, through csrc/beam_tail.h, the other home of the rules; that tail stays
+// separate from this one (sharing would take more parameters, not fewer lines).  A change to a rule is made in beam_tail.h and
+// in pb_pick below.
 // Everything here runs after a kernel's last MFMA of the timestep, in one wave per row and then in one thread: no weight
 // tile is in flight, so — unlike the phase code, which every kernel keeps as its own copy because the order of its loads IS
 // its schedule — these are plain forced-inline functions.  None of them contains a barrier: every __syncthreads() stays in

@@ -148,65 +148,117 @@ def _check_constraints(constraints, word_map, model):
     return cons
 
 
-def _fused_beam(models, NI, k, V, word_map, dev, max_steps, poll=4, return_scores=False, n_best=None, constraints=None):
-    import ctypes as C
+def _fused_models(model, inputs, k, max_steps):
+    """(model or (decoder, dae), ([image_features,] previous_caption, prev_caplen)) -> (the _FusedModel list, X or None, prev, plen):
+    the inputs as contiguous float / long tensors, the models in eval mode; with image features the first model is the EditNet"""
+    prev = inputs[-2].long().contiguous()
+    plen = inputs[-1].reshape(-1).long().contiguous()
+    X = inputs[0].float().contiguous() if len(inputs) == 3 else None
+    models = []
+    for i, m in enumerate(model if isinstance(model, (tuple, list)) else (model,)):
+        m.eval()
+        models.append(_FusedModel(m, (X, None, prev, plen), (X,), k, max_steps) if i == 0 and X is not None else
+                      _FusedModel(m, (prev, plen), (), k, max_steps))
+    return models, X, prev, plen
+
+
+def _gather(models, rows, NI, k, st):
+    """one set_beam_gather_f32 per model: its four states re-indexed by the pick's rows"""
     from . import _lib
-    from ._lib import check, ptr, stream_of
-    lib = _lib.load()
-    cons = _active(constraints)
-    banned_ids = cons.banned_ids(word_map, V) if cons is not None else []
-    st = stream_of(dev)
-    start, end = int(word_map['<start>']), int(word_map['<end>'])
-    B, Lmax = NI * k, max_steps + 2
-    neg = float("-inf")
-    scores = torch.full((NI, k), neg, device=dev)
-    scores[:, 0] = 0.0                                   # step 1: all k rows are identical, only row 0 counts
-    k_left = torch.full((NI,), k, dtype=torch.int32, device=dev)
-    words = torch.full((B,), start, dtype=torch.long, device=dev)
-    rows = torch.empty(B, dtype=torch.int32, device=dev)
-    seqs = [torch.full((NI, k, Lmax), start, dtype=torch.long, device=dev) for _ in range(2)]
-    best_score = torch.full((NI,), neg, device=dev)
-    best_seq = torch.zeros(NI, Lmax, dtype=torch.long, device=dev)
-    best_len = torch.zeros(NI, dtype=torch.int32, device=dev)
-    # the constrained pick reads its rows as float4 when the leading dimension allows it (V = 9490 is no multiple of 4): padded
-    # as _sbs_search pads it; the unconstrained picks keep their layout
-    ld = V if cons is None else (V + 63) // 64 * 64
-    logits = [torch.empty(B, ld, dtype=torch.float32, device=dev) for _ in models]
-    if n_best is not None or cons is not None:          # every counted <end> pick appends (score, tokens, length), set_hip.h
-        done_score = torch.full((NI, k), neg, device=dev)
-        done_seq = torch.zeros(NI, k, Lmax, dtype=torch.long, device=dev)
-        done_len = torch.zeros(NI, k, dtype=torch.int32, device=dev)
-        n_done = torch.zeros(NI, dtype=torch.int32, device=dev)
-    if cons is not None:                                 # the constrained pick: its options and its candidate workspace
-        banned = torch.tensor(banned_ids, dtype=torch.long, device=dev) if banned_ids else None
-        copts = _lib.BeamConstraintsC(cons.no_repeat_ngram, cons.min_length, cons.length_penalty, len(banned_ids),
-                                      banned.data_ptr() if banned_ids else None)
-        pick_ws = torch.empty(max(int(lib.set_beam_pick_constrained_workspace_bytes(NI, k)), 16), dtype=torch.uint8, device=dev)
+    from ._lib import check, ptr
+    for m in models:
+        s0, s1, s2, s3 = m.states
+        check(_lib.load().set_beam_gather_f32(ptr(s0), ptr(s1), ptr(s2), ptr(s3), ptr(rows), NI, k, m.D, st), "set_beam_gather_f32")
+
+
+class _BeamState:
+    """What the per-step searches of NI images x k slots allocate alike.  done: the completion list (done_*, n_done).  two_launch:
+    the pick is the constrained or the diverse one, which read their rows as float4 when the leading dimension allows it
+    (V = 9490 is no multiple of 4): ld padded as _sbs_search pads it, the constraints struct (neutral for cons=None) and the
+    candidate workspace.  The unconstrained picks keep ld = V.  scores start at -inf: the first step's live slots are the search's."""
+
+    def __init__(self, n_models, NI, k, V, word_map, dev, max_steps, cons, done, two_launch):
+        from . import _lib
+        from ._lib import stream_of
+        ids = cons.banned_ids(word_map, V) if cons is not None else []                           # (raises before any allocation)
+        self.NI, self.k, self.V, self.max_steps, self.Lmax = NI, k, V, max_steps, max_steps + 2
+        self.st = stream_of(dev)
+        self.start, self.end = int(word_map['<start>']), int(word_map['<end>'])
+        B, Lmax, neg = NI * k, self.Lmax, float("-inf")
+        self.scores = torch.full((NI, k), neg, device=dev)
+        self.k_left = torch.full((NI,), k, dtype=torch.int32, device=dev)
+        self.words = torch.full((B,), self.start, dtype=torch.long, device=dev)
+        self.rows = torch.empty(B, dtype=torch.int32, device=dev)
+        self.seqs = [torch.full((NI, k, Lmax), self.start, dtype=torch.long, device=dev) for _ in range(2)]
+        self.best_score = torch.full((NI,), neg, device=dev)
+        self.best_seq = torch.zeros(NI, Lmax, dtype=torch.long, device=dev)
+        self.best_len = torch.zeros(NI, dtype=torch.int32, device=dev)
+        self.ld = (V + 63) // 64 * 64 if two_launch else V
+        self.logits = [torch.empty(B, self.ld, dtype=torch.float32, device=dev) for _ in range(n_models)]
+        if done:                                             # every counted <end> pick appends (score, tokens, length), set_hip.h
+            self.done_score = torch.full((NI, k), neg, device=dev)
+            self.done_seq = torch.zeros(NI, k, Lmax, dtype=torch.long, device=dev)
+            self.done_len = torch.zeros(NI, k, dtype=torch.int32, device=dev)
+            self.n_done = torch.zeros(NI, dtype=torch.int32, device=dev)
+        if two_launch:
+            self.banned = torch.tensor(ids, dtype=torch.long, device=dev) if ids else None       # (kept alive for copts)
+            self.copts = _lib.BeamConstraintsC(*((cons.no_repeat_ngram, cons.min_length, cons.length_penalty) if cons is not None
+                                                 else (0, 0, 0.0)), len(ids), self.banned.data_ptr() if ids else None)
+            ws_bytes = int(_lib.load().set_beam_pick_constrained_workspace_bytes(NI, k))         # the diverse pick's is the same
+            self.pick_ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+
+    def pick_args(self, step):
+        """what every set_beam_pick_* entry takes first: logits .. rows"""
+        from ._lib import ptr
+        lg = self.logits
+        return (ptr(lg[0]), ptr(lg[1]) if len(lg) > 1 else None, self.ld, self.NI, self.k, self.V, self.end, step, self.Lmax,
+                ptr(self.scores), ptr(self.k_left), ptr(self.seqs[0]), ptr(self.seqs[1]), ptr(self.best_score), ptr(self.best_seq),
+                ptr(self.best_len), ptr(self.words), ptr(self.rows))
+
+    def done_args(self):
+        from ._lib import ptr
+        return (ptr(self.done_score), ptr(self.done_seq), ptr(self.done_len), ptr(self.n_done))
+
+    def ws_args(self):
+        """what the constrained and the diverse pick take last: constraints, workspace, stream"""
+        import ctypes as C
+        from ._lib import ptr
+        return (C.byref(self.copts), ptr(self.pick_ws), self.pick_ws.numel(), self.st)
+
+
+def _beam_loop(models, s, pick, poll):
+    """per timestep: every model steps on the same words into its own logits, pick(step), the seqs pair swaps, one state re-index
+    per model; the host polls k_left every `poll` steps.  Returns the last step taken."""
     step = 1
     while True:
-        for m, lg in zip(models, logits):
-            m.step(words, lg)
-        pick = (ptr(logits[0]), ptr(logits[1]) if len(models) > 1 else None, ld, NI, k, V, end, step, Lmax, ptr(scores), ptr(k_left),
-                ptr(seqs[0]), ptr(seqs[1]), ptr(best_score), ptr(best_seq), ptr(best_len), ptr(words), ptr(rows))
-        if cons is not None:
-            check(lib.set_beam_pick_constrained_f32(*pick, ptr(done_score), ptr(done_seq), ptr(done_len), ptr(n_done), C.byref(copts),
-                                                    ptr(pick_ws), pick_ws.numel(), st), "set_beam_pick_constrained_f32")
-        elif n_best is None:
-            check(lib.set_beam_pick_f32(*pick, st), "set_beam_pick_f32")
-        else:
-            check(lib.set_beam_pick_nbest_f32(*pick, ptr(done_score), ptr(done_seq), ptr(done_len), ptr(n_done), st),
-                  "set_beam_pick_nbest_f32")
-        seqs.reverse()
-        for m in models:
-            s0, s1, s2, s3 = m.states
-            check(lib.set_beam_gather_f32(ptr(s0), ptr(s1), ptr(s2), ptr(s3), ptr(rows), NI, k, m.D, st),
-                  "set_beam_gather_f32")
-        if step > max_steps:
-            break
-        if step % poll == 0 and int(k_left.max()) == 0:      # the only host synchronisation of the search
-            break
+        for m, lg in zip(models, s.logits):
+            m.step(s.words, lg)
+        pick(step)
+        s.seqs.reverse()
+        _gather(models, s.rows, s.NI, s.k, s.st)
+        if step > s.max_steps or (step % poll == 0 and int(s.k_left.max()) == 0):     # the only host synchronisation of the search
+            return step
         step += 1
-    seqs_c, best_c, len_c, left_c, score_c = seqs[0].cpu(), best_seq.cpu(), best_len.cpu(), k_left.cpu(), best_score.cpu()
+
+
+def _fused_beam(models, NI, k, V, word_map, dev, max_steps, poll=4, return_scores=False, n_best=None, constraints=None):
+    from . import _lib
+    from ._lib import check
+    lib = _lib.load()
+    cons = _active(constraints)
+    s = _BeamState(len(models), NI, k, V, word_map, dev, max_steps, cons, n_best is not None or cons is not None, cons is not None)
+    s.scores[:, 0] = 0.0                                 # step 1: all k rows are identical, only row 0 counts
+
+    def pick(step):
+        if cons is not None:
+            check(lib.set_beam_pick_constrained_f32(*s.pick_args(step), *s.done_args(), *s.ws_args()), "set_beam_pick_constrained_f32")
+        elif n_best is None:
+            check(lib.set_beam_pick_f32(*s.pick_args(step), s.st), "set_beam_pick_f32")
+        else:
+            check(lib.set_beam_pick_nbest_f32(*s.pick_args(step), *s.done_args(), s.st), "set_beam_pick_nbest_f32")
+    _beam_loop(models, s, pick, poll)
+    start = s.start
+    seqs_c, best_c, len_c, left_c, score_c = s.seqs[0].cpu(), s.best_seq.cpu(), s.best_len.cpu(), s.k_left.cpu(), s.best_score.cpu()
     out, out_scores = [], []
     for i in range(NI):
         if int(left_c[i]) > 0:                               # ran into the step limit (editnet.py:702-704,711)
@@ -220,7 +272,7 @@ def _fused_beam(models, NI, k, V, word_map, dev, max_steps, poll=4, return_score
             out_scores.append(float(score_c[i]))
     if n_best is None:
         return (out, out_scores) if return_scores else out
-    ds_c, dq_c, dl_c, nd_c = done_score.cpu(), done_seq.cpu(), done_len.cpu(), n_done.cpu()
+    ds_c, dq_c, dl_c, nd_c = s.done_score.cpu(), s.done_seq.cpu(), s.done_len.cpu(), s.n_done.cpu()
     nbest = [_n_best_sorted([(dq_c[i, j, :int(dl_c[i, j])].tolist(), float(ds_c[i, j])) for j in range(int(nd_c[i]))], n_best)
              for i in range(NI)]
     return (out, out_scores, nbest) if return_scores else (out, nbest)
@@ -256,12 +308,8 @@ def beam_search_editnet_batched(decoder, image_features, previous_caption, prev_
     return_trace: the result gains the EditTrace of the returned (primary) sequences as its last element."""
     n_best = _check_n_best(n_best, beam_size)
     cons = _check_constraints(constraints, word_map, decoder)
-    decoder.eval()
-    X = image_features.float().contiguous()
-    prev = previous_caption.long().contiguous()
-    plen = prev_caplen.reshape(-1).long().contiguous()
-    m = _FusedModel(decoder, (X, None, prev, plen), (X,), beam_size, max_steps)
-    res = _fused_beam([m], X.shape[0], beam_size, decoder.vocab_size, word_map, X.device, max_steps,
+    ms, X, prev, plen = _fused_models(decoder, (image_features, previous_caption, prev_caplen), beam_size, max_steps)
+    res = _fused_beam(ms, X.shape[0], beam_size, decoder.vocab_size, word_map, X.device, max_steps,
                       return_scores=return_scores, n_best=n_best, constraints=cons)
     return _with_trace(res, True, return_scores, decoder, X, prev, plen, word_map, n_best=n_best) if return_trace else res
 
@@ -272,11 +320,8 @@ def beam_search_dcnet_batched(dae, previous_caption, prev_caplen, word_map, beam
     """n_best, constraints: see beam_search_editnet_batched."""
     n_best = _check_n_best(n_best, beam_size)
     cons = _check_constraints(constraints, word_map, dae)
-    dae.eval()
-    prev = previous_caption.long().contiguous()
-    plen = prev_caplen.reshape(-1).long().contiguous()
-    m = _FusedModel(dae, (prev, plen), (), beam_size, max_steps)
-    return _fused_beam([m], prev.shape[0], beam_size, dae.vocab_size, word_map, prev.device, max_steps,
+    ms, _, prev, _ = _fused_models(dae, (previous_caption, prev_caplen), beam_size, max_steps)
+    return _fused_beam(ms, prev.shape[0], beam_size, dae.vocab_size, word_map, prev.device, max_steps,
                        return_scores=return_scores, n_best=n_best, constraints=cons)
 
 
@@ -289,14 +334,8 @@ def beam_search_ensemble_batched(decoder, dae, image_features, previous_caption,
     return_trace: the result gains, as its last element, EditNet's view of the jointly chosen words (their EditTrace)."""
     n_best = _check_n_best(n_best, beam_size)
     cons = _check_constraints(constraints, word_map, decoder)
-    decoder.eval()
-    dae.eval()
-    X = image_features.float().contiguous()
-    prev = previous_caption.long().contiguous()
-    plen = prev_caplen.reshape(-1).long().contiguous()
-    e = _FusedModel(decoder, (X, None, prev, plen), (X,), beam_size, max_steps)
-    d = _FusedModel(dae, (prev, plen), (), beam_size, max_steps)
-    res = _fused_beam([e, d], X.shape[0], beam_size, decoder.vocab_size, word_map, X.device, max_steps,
+    ms, X, prev, plen = _fused_models((decoder, dae), (image_features, previous_caption, prev_caplen), beam_size, max_steps)
+    res = _fused_beam(ms, X.shape[0], beam_size, decoder.vocab_size, word_map, X.device, max_steps,
                       return_scores=return_scores, n_best=n_best, constraints=cons)
     return _with_trace(res, True, return_scores, decoder, X, prev, plen, word_map, n_best=n_best) if return_trace else res
 
@@ -734,9 +773,7 @@ def _sbs_search(models, NI, k, V, word_map, dev, max_steps, opts, return_steps):
         seqs.reverse()
         if t + 1 == max_steps:
             break
-        for m in models:
-            s0, s1, s2, s3 = m.states
-            check(lib.set_beam_gather_f32(ptr(s0), ptr(s1), ptr(s2), ptr(s3), ptr(rows), NI, k, m.D, st), "set_beam_gather_f32")
+        _gather(models, rows, NI, k, st)
         if (t + 1) % 4 == 0 and int(n_open.max()) == 0:          # the only host synchronisation of the search
             break
     seqs_c, phi_c, G_c, fin_c, len_c = seqs[0].cpu(), phi.cpu(), G.cpu(), fin.cpu(), length.cpu()
@@ -808,15 +845,8 @@ def sample_captions_distinct(model, *inputs_and_word_map, n_samples=5, temperatu
     n, k = _sbs_slots(n_samples, return_threshold)
     opts = _lib.sample_opts(temperature, top_k, top_p)
     max_steps = _sbs_max_steps(model, max_steps)
-    model.eval()
-    prev = inputs[-2].long().contiguous()
-    plen = inputs[-1].reshape(-1).long().contiguous()
-    if len(inputs) == 3:
-        X = inputs[0].float().contiguous()
-        m = _FusedModel(model, (X, None, prev, plen), (X,), k, max_steps)
-    else:
-        m = _FusedModel(model, (prev, plen), (), k, max_steps)
-    out, steps = _sbs_search([m], prev.shape[0], k, model.vocab_size, word_map, prev.device, max_steps, opts, _return_steps)
+    ms, _, prev, _ = _fused_models(model, inputs, k, max_steps)
+    out, steps = _sbs_search(ms, prev.shape[0], k, model.vocab_size, word_map, prev.device, max_steps, opts, _return_steps)
     return _sbs_answer(out, steps, n, return_threshold, _return_steps)
 
 
@@ -849,14 +879,8 @@ def sample_captions_distinct_ensemble(decoder, dae, image_features, previous_cap
     n, k = _sbs_slots(n_samples, return_threshold)
     opts = _lib.sample_opts(temperature, top_k, top_p)
     max_steps = _sbs_max_steps(decoder, max_steps)
-    decoder.eval()
-    dae.eval()
-    X = image_features.float().contiguous()
-    prev = previous_caption.long().contiguous()
-    plen = prev_caplen.reshape(-1).long().contiguous()
-    e = _FusedModel(decoder, (X, None, prev, plen), (X,), k, max_steps)
-    d = _FusedModel(dae, (prev, plen), (), k, max_steps)
-    out, steps = _sbs_search([e, d], X.shape[0], k, decoder.vocab_size, word_map, X.device, max_steps, opts, _return_steps)
+    ms, X, _, _ = _fused_models((decoder, dae), (image_features, previous_caption, prev_caplen), k, max_steps)
+    out, steps = _sbs_search(ms, X.shape[0], k, decoder.vocab_size, word_map, X.device, max_steps, opts, _return_steps)
     return _sbs_answer(out, steps, n, return_threshold, _return_steps)
 
 
@@ -884,61 +908,20 @@ def _check_diverse(beam_size, groups, diversity_penalty, max_steps):
 
 
 def _diverse_search(models, NI, k, G, penalty, V, word_map, dev, max_steps, cons, return_all, poll=4):
-    """_fused_beam's loop on set_beam_pick_diverse_f32: per timestep every model steps on the same words into its own padded
-    logits, the pick, one set_beam_gather_f32 per model with the pick's rows; the host polls k_left every `poll` steps."""
-    import ctypes as C
+    """_beam_loop on set_beam_pick_diverse_f32, with the completion list and its groups"""
     from . import _lib
-    from ._lib import check, ptr, stream_of
+    from ._lib import check, ptr
     lib = _lib.load()
-    banned_ids = cons.banned_ids(word_map, V) if cons is not None else []
-    st = stream_of(dev)
-    start, end = int(word_map['<start>']), int(word_map['<end>'])
-    B, Lmax, g = NI * k, max_steps + 2, k // G
-    neg = float("-inf")
-    scores = torch.full((NI, k), neg, device=dev)
-    scores[:, ::g] = 0.0                                  # step 1: only the first slot of every group counts
-    k_left = torch.full((NI,), k, dtype=torch.int32, device=dev)
+    g = k // G
+    s = _BeamState(len(models), NI, k, V, word_map, dev, max_steps, cons, True, True)
+    s.scores[:, ::g] = 0.0                                # step 1: only the first slot of every group counts
     g_left = torch.full((NI, G), g, dtype=torch.int32, device=dev)
-    words = torch.full((B,), start, dtype=torch.long, device=dev)
-    rows = torch.empty(B, dtype=torch.int32, device=dev)
-    seqs = [torch.full((NI, k, Lmax), start, dtype=torch.long, device=dev) for _ in range(2)]
-    best_score = torch.full((NI,), neg, device=dev)
-    best_seq = torch.zeros(NI, Lmax, dtype=torch.long, device=dev)
-    best_len = torch.zeros(NI, dtype=torch.int32, device=dev)
-    ld = (V + 63) // 64 * 64                              # float4 row reads, as _fused_beam pads for the constrained pick
-    logits = [torch.empty(B, ld, dtype=torch.float32, device=dev) for _ in models]
-    done_score = torch.full((NI, k), neg, device=dev)
-    done_seq = torch.zeros(NI, k, Lmax, dtype=torch.long, device=dev)
-    done_len = torch.zeros(NI, k, dtype=torch.int32, device=dev)
     done_group = torch.zeros(NI, k, dtype=torch.int32, device=dev)
-    n_done = torch.zeros(NI, dtype=torch.int32, device=dev)
-    banned = torch.tensor(banned_ids, dtype=torch.long, device=dev) if banned_ids else None
-    if cons is not None:
-        copts = _lib.BeamConstraintsC(cons.no_repeat_ngram, cons.min_length, cons.length_penalty, len(banned_ids),
-                                      banned.data_ptr() if banned_ids else None)
-    else:
-        copts = _lib.BeamConstraintsC(0, 0, 0.0, 0, None)
-    pick_ws = torch.empty(max(int(lib.set_beam_pick_diverse_workspace_bytes(NI, k)), 16), dtype=torch.uint8, device=dev)
-    step = 1
-    while True:
-        for m, lg in zip(models, logits):
-            m.step(words, lg)
-        check(lib.set_beam_pick_diverse_f32(
-            ptr(logits[0]), ptr(logits[1]) if len(models) > 1 else None, ld, NI, k, V, end, step, Lmax, ptr(scores), ptr(k_left),
-            ptr(seqs[0]), ptr(seqs[1]), ptr(best_score), ptr(best_seq), ptr(best_len), ptr(words), ptr(rows), ptr(done_score),
-            ptr(done_seq), ptr(done_len), ptr(n_done), ptr(done_group), ptr(g_left), G, penalty, C.byref(copts), ptr(pick_ws),
-            pick_ws.numel(), st), "set_beam_pick_diverse_f32")
-        seqs.reverse()
-        for m in models:
-            s0, s1, s2, s3 = m.states
-            check(lib.set_beam_gather_f32(ptr(s0), ptr(s1), ptr(s2), ptr(s3), ptr(rows), NI, k, m.D, st), "set_beam_gather_f32")
-        if step > max_steps:
-            break
-        if step % poll == 0 and int(k_left.max()) == 0:      # the only host synchronisation of the search
-            break
-        step += 1
-    seqs_c, left_c = seqs[0].cpu(), g_left.cpu()
-    ds_c, dq_c, dl_c, dg_c, nd_c = done_score.cpu(), done_seq.cpu(), done_len.cpu(), done_group.cpu(), n_done.cpu()
+    step = _beam_loop(models, s, lambda step: check(lib.set_beam_pick_diverse_f32(
+        *s.pick_args(step), *s.done_args(), ptr(done_group), ptr(g_left), G, penalty, *s.ws_args()), "set_beam_pick_diverse_f32"), poll)
+    start = s.start
+    seqs_c, left_c = s.seqs[0].cpu(), g_left.cpu()
+    ds_c, dq_c, dl_c, dg_c, nd_c = s.done_score.cpu(), s.done_seq.cpu(), s.done_len.cpu(), done_group.cpu(), s.n_done.cpu()
     out, every = [], []
     for i in range(NI):
         done = [(dq_c[i, j, :int(dl_c[i, j])].tolist(), float(ds_c[i, j]), int(dg_c[i, j])) for j in range(int(nd_c[i]))]
@@ -989,15 +972,8 @@ def beam_search_diverse(model, *inputs_and_word_map, beam_size=6, groups=3, dive
         raise ValueError("beam_search_diverse(model, [image_features,] previous_caption, prev_caplen, word_map, ...): "
                          "image_features for EditNet, none for DCNet")
     cons = _check_constraints(constraints, word_map, model)
-    model.eval()
-    prev = inputs[-2].long().contiguous()
-    plen = inputs[-1].reshape(-1).long().contiguous()
-    if len(inputs) == 3:
-        X = inputs[0].float().contiguous()
-        m = _FusedModel(model, (X, None, prev, plen), (X,), k, max_steps)
-    else:
-        m = _FusedModel(model, (prev, plen), (), k, max_steps)
-    return _diverse_search([m], prev.shape[0], k, G, pen, model.vocab_size, word_map, prev.device, max_steps, cons, return_all)
+    ms, _, prev, _ = _fused_models(model, inputs, k, max_steps)
+    return _diverse_search(ms, prev.shape[0], k, G, pen, model.vocab_size, word_map, prev.device, max_steps, cons, return_all)
 
 
 @torch.no_grad()
@@ -1015,14 +991,8 @@ def beam_search_diverse_ensemble(decoder, dae, image_features, previous_caption,
         raise ValueError("beam_search_diverse_ensemble: the models' vocabularies differ (%d and %d words); the ensemble averages "
                          "their word distributions" % (decoder.vocab_size, dae.vocab_size))
     cons = _check_constraints(constraints, word_map, decoder)
-    decoder.eval()
-    dae.eval()
-    X = image_features.float().contiguous()
-    prev = previous_caption.long().contiguous()
-    plen = prev_caplen.reshape(-1).long().contiguous()
-    e = _FusedModel(decoder, (X, None, prev, plen), (X,), k, max_steps)
-    d = _FusedModel(dae, (prev, plen), (), k, max_steps)
-    return _diverse_search([e, d], X.shape[0], k, G, pen, decoder.vocab_size, word_map, X.device, max_steps, cons, return_all)
+    ms, X, _, _ = _fused_models((decoder, dae), (image_features, previous_caption, prev_caplen), k, max_steps)
+    return _diverse_search(ms, X.shape[0], k, G, pen, decoder.vocab_size, word_map, X.device, max_steps, cons, return_all)
 
 
 def sbs_unconditioned_threshold(kappa, e=None):

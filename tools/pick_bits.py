@@ -1,10 +1,13 @@
 """Raw output bits of the vocabulary-row picks, for comparing two builds of the library (a refactor against its parent).
 
-    python tools/pick_bits.py --out new.npz [--lib path/to/libset_hip.so]      (on the GPU, once per build)
+    python tools/pick_bits.py --out new.npz [--lib path/to/libset_hip.so] [--family pick|beam]      (on the GPU, once per build)
     python tools/pick_bits.py --compare parent.npz new.npz [--json verdict.json]
 
 Only the public C ABI of include/set_hip.h is used, so the tool runs unchanged on an older commit's library.  Inputs are random
-normal logits (rounding order shows, unlike the integer-valued rows of the exact tests) on fixed seeds.
+normal logits (rounding order shows, unlike the integer-valued rows of the exact tests) on fixed seeds.  The beam/* family drives
+every per-step beam pick as a chain of BEAM_STEPS steps from cur_len = 1 with the pick's own outputs fed back, every output array
+recorded after every step: at V = 5 <end> is picked often, so a chain crosses completions, a shrinking k_left, finished images, a
+full completion list and, under the "tight" constraints (one word left beside <end>, which min_len holds back), an exhausted group.
 """
 import argparse
 import ctypes as C
@@ -21,7 +24,11 @@ OPTS = tuple((temp, k, pp) for temp in (1.0, 0.7) for k, pp in ((0, 1.0), (7, 1.
 B, K, D, LMAX, MAXLEN = 3, 3, 8, 4, 4
 # what the run cannot reach through the public entries (written into the verdict file)
 NOT_COMPARED = ["gumbel_pick_k with a tail, several slabs or a bias: set_gumbel_pick_f32 takes one slab and neither; those instantiations "
-                "are compared only through the whole-decode tests"]
+                "are compared only through the whole-decode tests",
+                "beam/*: the persistent beam kernels' pb_pick (its own file, LDS state and history format; not a per-step pick)",
+                "beam/*: the return codes of refused arguments (no output array; tests/test_beam_constrained_cpu.py, "
+                "tests/test_beam_diverse_cpu.py and tests/test_nbest_beam_cpu.py pin them without a device)"]
+BEAM_VS, BEAM_KS, BEAM_GROUPS, BEAM_NI, BEAM_STEPS, BEAM_LMAX = (5, 1023, 1025, 9490), (1, 3, 8), ((4, 2), (6, 3), (8, 1)), 3, 6, 8
 
 
 def lds(V):
@@ -48,6 +55,11 @@ class PickArgs(C.Structure):
                 ("mode", C.c_int32), ("pad_", C.c_int32)]
 
 
+class Cons(C.Structure):
+    _fields_ = [("no_repeat_ngram", C.c_int32), ("min_len", C.c_int32), ("length_alpha", C.c_float), ("n_banned", C.c_int32),
+                ("banned", C.c_void_p)]
+
+
 class SbsArgs(C.Structure):
     _fields_ = [("logits", C.c_void_p), ("ld", C.c_int64), ("end_idx", C.c_int64), ("seed", C.c_uint64), ("offset", C.c_uint64),
                 ("phi", C.c_void_p), ("G", C.c_void_p), ("finished", C.c_void_p), ("len", C.c_void_p), ("seqs_in", C.c_void_p),
@@ -61,7 +73,55 @@ def raw(t):
     return a.view(np.uint32) if a.dtype == np.float32 else a
 
 
-def run(lib_path, out):
+def run_beam(lib, res, check, p, dev):
+    """beam/<entry>/m<models>/V/ld/k/G/s<step>/<array>: plain, n-best, constrained and diverse (neutral, live, tight) picks"""
+    import torch
+    lib.set_beam_pick_constrained_workspace_bytes.restype = C.c_size_t
+    gen = torch.Generator().manual_seed(20261020)
+    NI, L = BEAM_NI, BEAM_LMAX
+    banned = torch.tensor([1, 2, 0], dtype=torch.int64, device=dev)
+    cons = {"neutral": Cons(0, 0, 0.0, 0, None), "live": Cons(2, 2, 0.7, 2, banned.data_ptr()), "tight": Cons(2, 4, 0.7, 3, banned.data_ptr())}
+    entries = [(e, k, 1) for e in ("pick", "nbest", "cons_neutral", "cons_live", "cons_tight") for k in BEAM_KS]
+    entries += [(e, k, G) for e in ("div_neutral", "div_live", "div_tight") for k, G in BEAM_GROUPS]
+    i32, i64, neg = torch.int32, torch.int64, float("-inf")
+    for V, nm, (entry, k, G) in itertools.product(BEAM_VS, (1, 2), entries):
+        for ld in lds(V):
+            g, end = k // G, min(3, V - 1)
+            o = dict(scores=torch.full((NI, k), neg, device=dev), k_left=torch.full((NI,), k, dtype=i32, device=dev),
+                     best_score=torch.full((NI,), neg, device=dev), best_seq=torch.zeros(NI, L, dtype=i64, device=dev),
+                     best_len=torch.zeros(NI, dtype=i32, device=dev), words=torch.zeros(NI * k, dtype=i64, device=dev),
+                     rows=torch.zeros(NI * k, dtype=i32, device=dev))
+            o["scores"][:, ::g] = 0.0
+            seqs = [torch.zeros(NI, k, L, dtype=i64, device=dev) for _ in range(2)]
+            if entry != "pick":
+                o.update(done_score=torch.full((NI, k), neg, device=dev), done_seq=torch.zeros(NI, k, L, dtype=i64, device=dev),
+                         done_len=torch.zeros(NI, k, dtype=i32, device=dev), n_done=torch.zeros(NI, dtype=i32, device=dev))
+            if entry.startswith("div"):
+                o.update(done_group=torch.zeros(NI, k, dtype=i32, device=dev), g_left=torch.full((NI, G), g, dtype=i32, device=dev))
+            ws_bytes = lib.set_beam_pick_constrained_workspace_bytes(NI, k)
+            ws = torch.zeros(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+            for step in range(1, BEAM_STEPS + 1):
+                lg = [(torch.randn(NI * k, ld, generator=gen, dtype=torch.float32) * 2.0).to(dev) for _ in range(nm)]
+                tag = "beam/%s/m%d/V%d/ld%d/k%d/G%d/s%d" % (entry, nm, V, ld, k, G, step)
+                head = (p(lg[0]), p(lg[1]) if nm == 2 else None, C.c_int64(ld), NI, k, V, C.c_int64(end), step, L, p(o["scores"]),
+                        p(o["k_left"]), p(seqs[0]), p(seqs[1]), p(o["best_score"]), p(o["best_seq"]), p(o["best_len"]), p(o["words"]),
+                        p(o["rows"]))
+                done = tuple(p(o[n]) for n in ("done_score", "done_seq", "done_len", "n_done")) if entry != "pick" else ()
+                tail = (C.byref(cons[entry.split("_")[-1]]), p(ws), C.c_size_t(ws_bytes), None) if "_" in entry else ()
+                if entry == "pick":
+                    check(lib.set_beam_pick_f32(*head, None), tag)
+                elif entry == "nbest":
+                    check(lib.set_beam_pick_nbest_f32(*head, *done, None), tag)
+                elif entry.startswith("cons"):
+                    check(lib.set_beam_pick_constrained_f32(*head, *done, *tail), tag)
+                else:
+                    check(lib.set_beam_pick_diverse_f32(*head, *done, p(o["done_group"]), p(o["g_left"]), G, C.c_float(0.5), *tail), tag)
+                seqs.reverse()
+                for n, v in list(o.items()) + [("seqs", seqs[0]), ("seqs_other", seqs[1])]:
+                    res[tag + "/" + n] = raw(v)
+
+
+def run(lib_path, out, family):
     import torch
     lib = C.CDLL(lib_path)
     lib.set_sbs_workspace_bytes.restype = C.c_size_t
@@ -75,6 +135,16 @@ def run(lib_path, out):
         torch.cuda.synchronize()
         assert rc == 0, (tag, rc)
 
+    if family in ("all", "beam"):
+        run_beam(lib, res, check, p, dev)
+    if family in ("all", "pick"):
+        run_pick(lib, res, check, p, rnd, dev)
+    np.savez_compressed(out, **res)
+    print("pick_bits: %d arrays -> %s" % (len(res), out))
+
+
+def run_pick(lib, res, check, p, rnd, dev):
+    import torch
     for V in VS:
         for ld in lds(V):
             for n, with_bias, with_tail in itertools.product((1, 3), (False, True), (False, True)):
@@ -163,8 +233,6 @@ def run(lib_path, out):
                                                p(outs["lse"]), p(outs["slp"]), None, C.byref(op), p(outs["key"])), tag)
         for k, v in outs.items():
             res[tag + "/" + k] = raw(v)
-    np.savez_compressed(out, **res)
-    print("pick_bits: %d arrays -> %s" % (len(res), out))
 
 
 def compare(fa, fb, js):
@@ -192,7 +260,8 @@ if __name__ == "__main__":
     ap.add_argument("--lib", default=os.path.join(ROOT, "show-edit-tell_amd", "csrc", "libset_hip.so"))
     ap.add_argument("--compare", nargs=2)
     ap.add_argument("--json")
+    ap.add_argument("--family", default="all", choices=("all", "pick", "beam"))
     ns = ap.parse_args()
     if ns.compare:
         sys.exit(compare(ns.compare[0], ns.compare[1], ns.json))
-    run(ns.lib, ns.out)
+    run(ns.lib, ns.out, ns.family)
