@@ -14,12 +14,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libset_hip.so")
 # the EXPERIMENTAL variant (never the product path, never bench.py's `value`): the same sources with
-# -DSET_EXPERIMENTAL_GEMMS, i.e. plus csrc/experimental/*.inc (the bf16-split emulated-fp32 GEMM and the GEMM variants that lost
-# their A/B).  A process loads it instead of the shipped library only when SET_LIB_VARIANT=exp is set (_lib.py).
+# -DSET_EXPERIMENTAL_GEMMS, i.e. plus csrc/experimental/*.inc (the GEMM variants that lost their A/B; the bf16-split
+# emulated-fp32 GEMM, csrc/gemm_split_bf16.inc, is in both variants).  A process loads it instead of the shipped library only
+# when SET_LIB_VARIANT=exp is set (_lib.py).
 LIB_EXP = os.path.join(CSRC, "libset_hip_exp.so")
 ARCH = "gfx950"
-# per-file flags.  gemm_f32.hip: the eight leading scalar kernel arguments (task count + first-workgroup table + the two row-gate pointers) are preloaded
-# into SGPRs by the command processor instead of being fetched from the kernarg segment by every workgroup
+# per-file flags.  gemm_f32.hip: the eight leading scalar kernel arguments (task count, the first workgroup of tasks 1..5, the
+# loop-gate pointer and the row-list count pointer) are preloaded into SGPRs by the command processor instead of being fetched
+# from the kernarg segment by every workgroup
 FILE_FLAGS = {"gemm_f32.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=8"]}
 
 

@@ -35,21 +35,6 @@ typedef const f32x4 __attribute__((address_space(1)))* gptr4;
 // each) are then both bank-conflict-free, and a 128x64x32 stage pair is 48 KB -> three workgroups per CU.
 constexpr int LDS_STRIDE = 32;
 
-// SET_GEMM_SPLIT, who runs on gemm_nt_split_bf16 (gemm_split_bf16.inc), in both library variants:
-//   0      nobody: the fp32 kernels for every launch
-//   1      every launch the kernel can take (the tile classes are re-cut for it: 128x64 from 65 rows on, no row lists)
-//   unset  launches of >= 65 rows without a row list and without a 64-row hint, issued inside a SplitScope (set_common.h): the
-//          no-grad greedy rollout of EditNet.  Every other caller stays on the fp32 kernels.
-static int gemm_split_mode() { static int v = env_int("SET_GEMM_SPLIT", -1); return v < 0 ? -1 : (v ? 1 : 0); }
-static bool split_all() { return gemm_split_mode() == 1; }
-thread_local bool g_split_scope = false;
-static bool split_scoped(const GemmProb* probs, int n) {
-    if (gemm_split_mode() >= 0 || !g_split_scope || n <= 0 || probs[0].row_list || probs[0].bm_hint == 64) return false;
-    for (int i = 0; i < n; ++i)
-        if (probs[i].M < 65) return false;
-    return true;
-}
-
 struct GemmTask {
     const float* A[GEMM_MAX_SEG];
     const float* W[GEMM_MAX_SEG];
@@ -104,7 +89,7 @@ __global__ void __launch_bounds__(256 * KG) gemm_nt_f32(const int ntasks, const 
                                                         const int wb4, const int wb5, const int* const gate_alive,
         const int* const gate_nrows, const GemmLaunch L) {
     // ntasks / wb1..wb5 repeat L.ntasks and L.t[1..5].wg_begin as leading scalar arguments: this file is compiled with
-    // -mllvm -amdgpu-kernarg-preload-count=6, so they arrive in SGPRs with the wave and the task lookup below needs no
+    // -mllvm -amdgpu-kernarg-preload-count=8 (these six and the two gate pointers), so they arrive in SGPRs with the wave and the task lookup below needs no
     // memory round trip before the task's own fields can be requested (about 0.5 us of every workgroup's start-up)
     static_assert(WAVES_M * WAVES_N == 4, "4 waves per k-group");
     static_assert(KG == 1 || KG == 2, "one or two k-groups");
@@ -563,7 +548,7 @@ __global__ void __launch_bounds__(256) gemm_nt_f32_asm(const int ntasks, const i
 #undef ASM_HALF_ROUND
 
 // ---------------------------------------------------------------------------------------------
-// The bf16x3 split-precision kernel (shipped: the greedy rollout's >= 65-row launches run on it, see gemm_split_mode above)
+// The bf16x3 split-precision kernel (shipped: the greedy rollout's >= 65-row launches run on it, see GemmEnv::split below)
 // ---------------------------------------------------------------------------------------------
 #include "gemm_split_bf16.inc"
 
@@ -672,88 +657,151 @@ __global__ void __launch_bounds__(256) gemv_nt_f32(const int ntasks, const int w
     }
 }
 
+// Host side: the route of a launch (gemm_route, set_common.h), the kernel table, the planner and the launcher.
+int g_gemm_asm_force = -1;         // tools/ubench: switch kernels inside one process (-1: the environment decides)
+int g_gemm_wreg_force = -1;        // (the same for the experimental variant's weights-to-registers kernel)
+thread_local bool g_split_scope = false;
+
+// Every environment switch of the launcher, read once per process (when the first launch is routed).
+struct GemmEnv {
+    // SET_GEMM_SPLIT, who runs on gemm_nt_split_bf16 (gemm_split_bf16.inc), in both library variants:
+    //   0      nobody: the fp32 kernels for every launch
+    //   1      every launch the kernel can take (the tile classes are re-cut for it: 128x64 from 65 rows on, no row lists)
+    //   unset  launches of >= 65 rows without a row list and without a 64-row hint, issued inside a SplitScope (set_common.h): the
+    //          no-grad greedy rollout of EditNet.  Every other caller stays on the fp32 kernels.
+    int split = env_int("SET_GEMM_SPLIT", -1);                                   // < 0: unset, > 0: "1"
+    const char* split_tag = getenv("SET_GEMM_SPLIT_TAG");     // debug (SET_GEMM_SPLIT=1): restrict the split kernel to one call site
+    int bm64_upto = env_int("SET_GEMM_BM64_UPTO", split > 0 ? 64 : 512);         // the split kernel is 128x64 only
+    int bm32_upto = env_int("SET_GEMM_BM32_UPTO", 32);
+    int bm16_upto = env_int("SET_GEMM_BM16_UPTO", 16);
+    int tile_model = env_int("SET_GEMM_TILE_MODEL", 1);
+    int pct64 = env_int("SET_GEMM_WGS64_PCT", 150), pct32 = env_int("SET_GEMM_WGS32_PCT", 50), pct16 = env_int("SET_GEMM_WGS16_PCT", 200);
+    int min_kper = env_int("SET_GEMM_MIN_KPER", 4), fill_slots = env_int("SET_GEMM_FILL_SLOTS", 1);
+    int vec_epilogue = env_int("SET_GEMM_VEC_EPILOGUE", 1), xcd_align = env_int("SET_GEMM_XCD_ALIGN", 1);
+    int asm_loop = env_int("SET_GEMM_ASM", 1);
+    bool profile_sites = env_int("SET_PROFILE_SITES", 0) != 0;                   // per-call-site breakdown (nested events)
+    int dma = 0, kgroups = 1, bn128 = 0, bn32 = 0, wreg = 0;                     // the experimental variant's; ignored by the shipped library
+    GemmEnv();                                                                   // (reads them, in the experimental variant)
+    bool hand_loop() const { return (g_gemm_asm_force >= 0 ? g_gemm_asm_force : asm_loop) != 0; }
+};
+static const GemmEnv& gemm_env() { static const GemmEnv e; return e; }
+
 int gemm_tile_m(int M) {
     // 64x64 tiles up to M = 512 (measured: +4-5 % at M = 128, +10 % at M = 256-384; big-M prologue / training products
     // stay on 128x64): at the decode batch two 64-row tiles per weight block (the second one hits the
     // same XCD's L2) halve the split-K factor -> half the slab bytes written here and re-read by the consumer,
     // and 32 KB workgroups pack three per CU.  Measured +4-5 % on the bench against the 128x64 tile.
-    static const int bm64_upto = env_int("SET_GEMM_BM64_UPTO", split_all() ? 64 : 512);   // the split kernel is 128x64 only
-    static const int bm32_upto = env_int("SET_GEMM_BM32_UPTO", 32);
     // <= 16 rows (configs[0]'s batch of 4, beam search, the tail of a ragged teacher-forced batch): the launch only streams
     // weights; gemv_nt_f32 (no LDS, one 16x16 MFMA tile per wave, loads straight into registers) instead of a 32-row tile
-    static const int bm16_upto = env_int("SET_GEMM_BM16_UPTO", 16);
-    return M <= bm16_upto ? 16 : (M <= bm32_upto ? 32 : (M <= bm64_upto ? 64 : 128));
+    const GemmEnv& E = gemm_env();
+    return M <= E.bm16_upto ? 16 : (M <= E.bm32_upto ? 32 : (M <= E.bm64_upto ? 64 : 128));
 }
+
+// The kernel table: every kernel of this file has one signature, a row is what a launch needs to know about one of them.
+// A row is found by its key: the kernel class and the gate mode (0 = none, 1 = loop-left test, 2 = row list; no row, no launch).
+// The rows stand in the order in which the kernels have always been instantiated: it is their order in the code object.
+typedef void (*GemmKernelFn)(int, int, int, int, int, int, const int*, const int*, GemmLaunch);
+enum GemmClass { KC_16, KC_32, KC_64, KC_64_HAND, KC_128, KC_SPLIT };
+struct GemmKernel {
+    int kc, gate_mode;             // the key
+    const char* tag;               // profile tag: bench.py keys its roofline on the prefix (the split kernel's stays in its tile's family)
+    GemmKernelFn fn;
+    int threads, lds;              // per workgroup; lds: dynamic bytes
+};
+static const GemmKernel g_gemm_kernels[] = {
+    {KC_SPLIT, 0, "gemm_nt_f32<128,64>:bf16x3", gemm_nt_split_bf16<0>, 256, SPLIT_LDS_BYTES},
+    {KC_SPLIT, 1, "gemm_nt_f32<128,64>:bf16x3", gemm_nt_split_bf16<1>, 256, SPLIT_LDS_BYTES},
+    {KC_128, 2, "gemm_nt_f32<128,64>", gemm_nt_f32<128, 64, 2, 2, 1, 2>, 256, 0},
+    {KC_64_HAND, 2, "gemm_nt_f32_asm<64,64>", gemm_nt_f32_asm<2>, 256, 0},
+    {KC_64, 2, "gemm_nt_f32<64,64>", gemm_nt_f32<64, 64, 2, 2, 1, 2>, 256, 0},
+    {KC_32, 2, "gemm_nt_f32<32,128>", gemm_nt_f32<32, 128, 1, 4, 1, 2>, 256, 0},
+    {KC_16, 0, "gemv_nt_f32<16,64>", gemv_nt_f32, 256, 0},
+    {KC_16, 1, "gemv_nt_f32<16,64>", gemv_nt_f32, 256, 0},
+    {KC_128, 1, "gemm_nt_f32<128,64>", gemm_nt_f32<128, 64, 2, 2, 1, 1>, 256, 0},
+    {KC_128, 0, "gemm_nt_f32<128,64>", gemm_nt_f32<128, 64, 2, 2>, 256, 0},
+    {KC_64_HAND, 1, "gemm_nt_f32_asm<64,64>", gemm_nt_f32_asm<1>, 256, 0},
+    {KC_64_HAND, 0, "gemm_nt_f32_asm<64,64>", gemm_nt_f32_asm<0>, 256, 0},
+    {KC_64, 1, "gemm_nt_f32<64,64>", gemm_nt_f32<64, 64, 2, 2, 1, 1>, 256, 0},
+    {KC_64, 0, "gemm_nt_f32<64,64>", gemm_nt_f32<64, 64, 2, 2>, 256, 0},
+    {KC_32, 1, "gemm_nt_f32<32,128>", gemm_nt_f32<32, 128, 1, 4, 1, 1>, 256, 0},
+    {KC_32, 0, "gemm_nt_f32<32,128>", gemm_nt_f32<32, 128, 1, 4>, 256, 0},
+};
+
 #ifdef SET_EXPERIMENTAL_GEMMS
-static int gemm_dma() { static int v = env_int("SET_GEMM_DMA", 0); return v; }
-static int gemm_kgroups() { static int v = env_int("SET_GEMM_KGROUPS", 1); return v; }
-static int gemm_bn128() { static int v = env_int("SET_GEMM_BN128", 0); return v; }
+// Everything the experimental variant adds to the launcher: its switches, its tiles' kernels and their precedence.
+// SET_GEMM_BN32=1 (experiment, round 3): decode batches of 65..128 rows on 128x32 tiles — ONE workgroup owns both 64-row
+// halves of a weight block (same workgroup count as two 64x64 tiles, each weight byte fetched once instead of relying on
+// the second row tile's L2 hit; the activation rows are re-read by twice as many workgroups, from L2)
+GemmEnv::GemmEnv() {
+    dma = env_int("SET_GEMM_DMA", 0); kgroups = env_int("SET_GEMM_KGROUPS", 1); bn128 = env_int("SET_GEMM_BN128", 0);
+    bn32 = env_int("SET_GEMM_BN32", 0); wreg = env_int("SET_GEMM_WREG", 0);
+}
+static bool exp_wreg(const GemmEnv& E) { return (g_gemm_wreg_force >= 0 ? g_gemm_wreg_force : E.wreg) != 0; }
+// a switch that swaps the kernel under a 64- or 128-row tile (none of these kernels reads a row list)
+static bool exp_kernel_swapped(const GemmEnv& E) { return E.dma || exp_wreg(E) || E.kgroups != 1; }
+// `k` is the shipped library's row for this launch.  The two extra tiles have no such row; a swapped kernel runs under the tag of
+// the row it replaces, as the profile has always reported these launches (128x128 under <128,64>).
+static void exp_override(GemmKernel& k, const GemmRoute& r, int gate, const GemmEnv& E) {
+    if (r.split || gate == 2 || r.bm == 16) return;
+    if (r.bm == 128 && r.bn == 32) { k.tag = "gemm_nt_f32<128,32>"; k.fn = gemm_nt_f32<128, 32, 4, 1>; }
+    else if (r.bm == 128 && r.bn == 128) k.fn = gemm_nt_f32<128, 128, 2, 2>;
+    else if (r.bm == 128 && E.dma) k.fn = gemm_nt_f32_dma<128, 64, 2, 2>;
+    else if (r.bm == 64 && exp_wreg(E)) k.fn = gemm_nt_f32_wreg;
+    else if (r.bm == 64 && E.kgroups == 2) { k.fn = gemm_nt_f32<64, 64, 2, 2, 2>; k.threads = 512; }
+    else if (r.bm == 64 && E.dma) k.fn = gemm_nt_f32_dma<64, 64, 2, 2>;
+}
 #else
-static constexpr int gemm_dma() { return 0; }
-static constexpr int gemm_kgroups() { return 1; }
-static constexpr int gemm_bn128() { return 0; }
+GemmEnv::GemmEnv() {}
+static bool exp_kernel_swapped(const GemmEnv&) { return false; }
+static void exp_override(GemmKernel&, const GemmRoute&, int, const GemmEnv&) {}
 #endif
-int g_gemm_asm_force = -1;         // tools/ubench: switch kernels inside one process (-1: the environment decides)
-static int gemm_asm() { static int v = env_int("SET_GEMM_ASM", 1); return g_gemm_asm_force >= 0 ? g_gemm_asm_force : v; }
-int g_gemm_wreg_force = -1;        // tools/ubench: switch kernels inside one process (-1: the environment decides)
-#ifdef SET_EXPERIMENTAL_GEMMS
-static int gemm_wreg() { static int v = env_int("SET_GEMM_WREG", 0); return g_gemm_wreg_force >= 0 ? g_gemm_wreg_force : v; }
-#else
-static constexpr int gemm_wreg() { return 0; }
-#endif
-static int tile_m_of(const GemmProb& p) { return (p.bm_hint == 64 || p.bm_hint == 128) ? p.bm_hint : gemm_tile_m(p.M); }
-// Row-tile class of one launch.  Up to 512 rows: from M (above).  Beyond: 128x64 tiles unless 64x64 tiles leave the CUs a
+
+// Row-tile class.  Up to 512 rows: from M (gemm_tile_m), one class per launch, the largest any problem asks for (the
+// teacher-forced loop merges fc over this step's rows with phase A over the next step's, and the sorted batch may shrink
+// across a class boundary in between).  Beyond: 128x64 tiles unless 64x64 tiles leave the CUs a
 // more even load — a launch takes about ceil(workgroups / 256 CUs) rounds of one tile's k-loop, and a 64-row tile's k-loop
 // is half as long: att_embed (4608 x 1024: 576 tiles = 3 rounds, as 1152 half-size tiles 5) 203 -> 170 us, features_att
 // (288 tiles = 2 rounds, as 576: 3 half rounds) 75 -> 56 us; the large products of the training step (fc over all
 // timesteps, the all-timestep region projection: >= 11 rounds either way) stay on 128x64.
-// SET_GEMM_BN32=1 (experiment, round 3): decode batches of 65..128 rows on 128x32 tiles — ONE workgroup owns both 64-row
-// halves of a weight block (same workgroup count as two 64x64 tiles, each weight byte fetched once instead of relying on
-// the second row tile's L2 hit; the activation rows are re-read by twice as many workgroups, from L2)
-static bool use_bn32(const GemmProb* probs, int n) {
-#ifdef SET_EXPERIMENTAL_GEMMS
-    static const int on = env_int("SET_GEMM_BN32", 0);
-#else
-    constexpr int on = 0;
-#endif
-    if (!on || n <= 0 || probs[0].bm_hint || split_all() || split_scoped(probs, n)) return false;
-    for (int i = 0; i < n; ++i)
-        if (probs[i].M <= 64 || probs[i].M > 128 || gemm_tile_m(probs[i].M) != 64) return false;
-    return true;
-}
-static int launch_tile_m(const GemmProb* probs, int n) {
-    if (split_scoped(probs, n)) return 128;          // the split kernel's only tile: 128x64, two workgroups per CU
-    if (use_bn32(probs, n)) return 128;
-    // one row-tile class per launch: the largest any problem asks for (the teacher-forced loop merges fc over this step's
-    // rows with phase A over the next step's, and the sorted batch may shrink across a class boundary in between)
-    int bm = tile_m_of(probs[0]);
-    if (!probs[0].bm_hint)
-        for (int i = 1; i < n; ++i) { const int c = tile_m_of(probs[i]); if (c > bm) bm = c; }
-    static const int model = env_int("SET_GEMM_TILE_MODEL", 1);
-    if (!model || probs[0].bm_hint || bm != 128 || split_all() || gemm_bn128()) return bm;
+GemmRoute gemm_route(const GemmProb* probs, int n, const char* tag) {
+    GemmRoute r = {0, 64, false, false};
+    if (n <= 0) return r;
+    const GemmEnv& E = gemm_env();
+    const GemmProb& p0 = probs[0];
+    auto asked = [](const GemmProb& p) { return (p.bm_hint == 64 || p.bm_hint == 128) ? p.bm_hint : gemm_tile_m(p.M); };
+    bool scoped = E.split < 0 && g_split_scope && !p0.row_list && p0.bm_hint != 64;      // ... and every problem >= 65 rows
+    bool bn32 = E.bn32 && !p0.bm_hint && E.split <= 0;                                   // ... and every problem 65..128 rows
+    bool all128 = true;
     long long t128 = 0, t64 = 0;
+    r.bm = asked(p0);
     for (int i = 0; i < n; ++i) {
-        if (gemm_tile_m(probs[i].M) != 128) return bm;
-        t128 += (long long)cdiv(probs[i].M, 128) * cdiv(probs[i].N, 64);
-        t64 += (long long)cdiv(probs[i].M, 64) * cdiv(probs[i].N, 64);
+        const int M = probs[i].M, c = gemm_tile_m(M);
+        if (M < 65) scoped = false;
+        if (M <= 64 || M > 128 || c != 64) bn32 = false;
+        if (c != 128) all128 = false;
+        if (!p0.bm_hint) { const int a = asked(probs[i]); if (a > r.bm) r.bm = a; }
+        t128 += (long long)cdiv(M, 128) * cdiv(probs[i].N, 64);
+        t64 += (long long)cdiv(M, 64) * cdiv(probs[i].N, 64);
     }
-    const double c128 = (double)((t128 + 255) / 256) * 1.08, c64 = (double)((t64 + 255) / 256) * 0.57;
-    return c64 < 0.97 * c128 ? 64 : 128;
+    if (scoped) r.bm = 128;                          // the split kernel's only tile: 128x64, two workgroups per CU
+    else if (bn32) { r.bm = 128; r.bn = 32; }
+    else {
+        if (r.bm == 128 && all128 && E.tile_model && !p0.bm_hint && E.split <= 0 && !E.bn128) {
+            const double c128 = (double)((t128 + 255) / 256) * 1.08, c64 = (double)((t64 + 255) / 256) * 0.57;
+            if (c64 < 0.97 * c128) r.bm = 64;
+        }
+        if (r.bm == 32 || (r.bm == 128 && E.bn128)) r.bn = 128;      // (class 16: 4 waves x 16 columns)
+    }
+    const bool tile_128x64 = r.bm == 128 && r.bn == 64;
+    r.split = tile_128x64 && !p0.row_list &&
+              (scoped || (E.split > 0 && (!E.split_tag || !*E.split_tag || strstr(tag ? tag : "untagged", E.split_tag))));
+    // the LDS-staged tile classes of the shipped library take a row list; the <= 16-row class (no tile rows to skip) does not.
+    // (A scoped launch says yes: given its list it is no longer scoped and runs on the fp32 kernel of its class.)
+    r.rows_ok = E.split <= 0 && !exp_kernel_swapped(E) && (tile_128x64 || r.bm == 64 || r.bm == 32);
+    return r;
 }
-int gemm_launch_rows(const GemmProb* probs, int n) { return n > 0 ? launch_tile_m(probs, n) : 0; }
-static int launch_tile_n(const GemmProb* probs, int n);
-// the LDS-staged tile classes of the shipped library take a row list; the <= 16-row class (no tile rows to skip) does not
-bool gemm_row_list_ok(const GemmProb* probs, int n) {
-    if (n <= 0 || split_all() || gemm_dma() || gemm_wreg() || gemm_kgroups() != 1) return false;
-    const int bm = launch_tile_m(probs, n), bn = launch_tile_n(probs, n);
-    return (bm == 128 && bn == 64) || (bm == 64 && bn == 64) || (bm == 32 && bn == 128);
-}
-static int launch_tile_n(const GemmProb* probs, int n) {
-    if (split_scoped(probs, n)) return 64;
-    if (use_bn32(probs, n)) return 32;
-    const int bm = launch_tile_m(probs, n);
-    return (bm == 32 || (bm == 128 && gemm_bn128())) ? 128 : 64;      // (class 16: 4 waves x 16 columns)
-}
+int gemm_launch_rows(const GemmProb* probs, int n) { return gemm_route(probs, n).bm; }
+bool gemm_row_list_ok(const GemmProb* probs, int n) { return gemm_route(probs, n).rows_ok; }
 
 // Split-K plan for one grouped launch: every workgroup should run about the same number of k-tiles
 // (`kper`) and the whole launch should fit the chip in ONE round: 256 CUs x 2 resident workgroups =
@@ -761,20 +809,17 @@ static int launch_tile_n(const GemmProb* probs, int n) {
 // smallest value (>= 4 k-tiles, to amortise the per-workgroup prologue/epilogue) for which the
 // launch has at most cap_wgs workgroups.
 void plan_ksplit(GemmProb* probs, int n, int cap_wgs) {
+    const GemmEnv& E = gemm_env();
+    const GemmRoute r = gemm_route(probs, n);        // (n <= 0: no tile and nothing to plan)
     // the cap is given for 128-row tiles (2 workgroups per CU); 64x64 workgroups are half as large: 3 per CU
-    static const int pct64 = env_int("SET_GEMM_WGS64_PCT", 150);
-    static const int pct32 = env_int("SET_GEMM_WGS32_PCT", 50);
-    const int bm_l = n > 0 ? launch_tile_m(probs, n) : 128, bn_l = n > 0 ? launch_tile_n(probs, n) : 64;
-    if (n > 0 && (bm_l == 64 || bn_l == 32)) cap_wgs = cap_wgs * pct64 / 100;
+    if (r.bm == 64 || r.bn == 32) cap_wgs = cap_wgs * E.pct64 / 100;
     // <= 32 rows: the launch only streams weights; fewer, longer workgroups halve the slab traffic (measured +5 %)
-    if (n > 0 && bm_l == 32) cap_wgs = cap_wgs * pct32 / 100;
+    if (r.bm == 32) cap_wgs = cap_wgs * E.pct32 / 100;
     // <= 16 rows: 64-column workgroups without LDS, many fit a CU; slabs are a few KB, so split generously for bytes in flight
-    static const int pct16 = env_int("SET_GEMM_WGS16_PCT", 200);
-    if (n > 0 && bm_l == 16) cap_wgs = cap_wgs * pct16 / 100;
+    if (r.bm == 16) cap_wgs = cap_wgs * E.pct16 / 100;
     int tiles[GEMM_MAX_TASKS], kts[GEMM_MAX_TASKS], max_kt = 1;
     for (int i = 0; i < n; ++i) {
-        const int bm = bm_l, bn = bn_l;
-        tiles[i] = cdiv(probs[i].M, bm) * cdiv(probs[i].N, bn);
+        tiles[i] = cdiv(probs[i].M, r.bm) * cdiv(probs[i].N, r.bn);
         kts[i] = probs[i].ktiles();
         if (kts[i] > max_kt) max_kt = kts[i];
     }
@@ -784,8 +829,7 @@ void plan_ksplit(GemmProb* probs, int n, int cap_wgs) {
         if (ks > kts[i]) ks = kts[i];
         return ks < 1 ? 1 : ks;
     };
-    static const int min_kper = env_int("SET_GEMM_MIN_KPER", 4);
-    int kper = min_kper;
+    int kper = E.min_kper;
     for (; kper < max_kt; ++kper) {
         long long wgs = 0;
         for (int i = 0; i < n; ++i) wgs += (long long)tiles[i] * split_of(i, kper);
@@ -796,15 +840,14 @@ void plan_ksplit(GemmProb* probs, int n, int cap_wgs) {
     // A common kper rarely lands on the slot count (e.g. the phase-B group: 224 tiles x 3 slices = 672 of 768 slots,
     // so a third of the CUs run 2 workgroups and the rest 3).  Fill the spare slots: give one more K-slice to the
     // problems that fit, smallest first (their workgroups get shorter, nobody's gets longer).
-    static const int fill = env_int("SET_GEMM_FILL_SLOTS", 1);
-    if (fill && n > 1) {
+    if (E.fill_slots && n > 1) {
         bool grew = true;
         while (grew) {
             grew = false;
             int best = -1;
             for (int i = 0; i < n; ++i) {
                 const int ks = probs[i].ksplit;
-                if (ks >= probs[i].max_ksplit || ks >= kts[i] || kts[i] / (ks + 1) < min_kper) continue;
+                if (ks >= probs[i].max_ksplit || ks >= kts[i] || kts[i] / (ks + 1) < E.min_kper) continue;
                 if (total + tiles[i] > cap_wgs) continue;
                 if (best < 0 || tiles[i] < tiles[best]) best = i;
             }
@@ -830,6 +873,16 @@ static bool slices_in_one_segment(const GemmLaunch& L) {
     return true;
 }
 
+// The row of one launch.  `hand`: a 64x64 launch that may and can run the hand-written k-loop (SET_GEMM_ASM, slices_in_one_segment).
+static GemmKernel gemm_kernel(const GemmRoute& r, int gate_mode, bool hand) {
+    const int kc = r.split ? KC_SPLIT : r.bm == 16 ? KC_16 : r.bm == 32 ? KC_32 : r.bm == 128 ? KC_128 : hand ? KC_64_HAND : KC_64;
+    GemmKernel k = {};
+    for (const GemmKernel& row : g_gemm_kernels)
+        if (row.kc == kc && row.gate_mode == gate_mode) k = row;
+    exp_override(k, r, gate_mode, gemm_env());
+    return k;
+}
+
 int gemm_group(const GemmProb* probs, int n, hipStream_t stream, const char* tag) {
     if (n <= 0) return SET_OK;
     if (n > GEMM_MAX_TASKS) return SET_ERR_ARG;
@@ -846,13 +899,15 @@ int gemm_group(const GemmProb* probs, int n, hipStream_t stream, const char* tag
     L.stamps = g_gemm_stamps;
 #endif
     int wg = 0;
-    const int bm = launch_tile_m(probs, n), bn = launch_tile_n(probs, n);
-    if (L.row_list && !gemm_row_list_ok(probs, n)) return SET_ERR_UNSUPPORTED;
+    double flops = 0.0, bytes = 0.0;
+    const GemmEnv& E = gemm_env();
+    const GemmRoute r = gemm_route(probs, n, tag);
+    if (L.row_list && !r.rows_ok) return SET_ERR_UNSUPPORTED;
     for (int i = 0; i < n; ++i) {
         const GemmProb& p = probs[i];
         GemmTask& t = L.t[i];
         if (p.M <= 0 || p.N <= 0 || p.nseg <= 0 || p.nseg > GEMM_MAX_SEG || !p.C) return SET_ERR_ARG;
-        if (bm == 16 && p.M > 16) return SET_ERR_ARG;
+        if (r.bm == 16 && p.M > 16) return SET_ERR_ARG;
         int kt = 0;
         for (int s = 0; s < GEMM_MAX_SEG; ++s) {
             if (s < p.nseg) {
@@ -873,98 +928,34 @@ int gemm_group(const GemmProb* probs, int n, hipStream_t stream, const char* tag
         if (t.ksplit > kt) t.ksplit = kt;
         if (t.ksplit > 1 && (p.act != SET_ACT_NONE)) return SET_ERR_ARG;
         if (t.ksplit > 1 && L.row_list) return SET_ERR_ARG;       // (GemmProb::row_list: unsplit problems only)
-        t.tiles_m = cdiv(p.M, bm); t.tiles_n = cdiv(p.N, bn);
-        static const int vec_epi = env_int("SET_GEMM_VEC_EPILOGUE", 1);
-        t.vec_store = vec_epi && !(p.N & 3) && !(p.ldc & 3) && !(p.slab_stride & 3) && aligned16(p.C);
+        t.tiles_m = cdiv(p.M, r.bm); t.tiles_n = cdiv(p.N, r.bn);
+        t.vec_store = E.vec_epilogue && !(p.N & 3) && !(p.ldc & 3) && !(p.slab_stride & 3) && aligned16(p.C);
         t.wg_begin = wg;
-        static const int xcd_align = env_int("SET_GEMM_XCD_ALIGN", 1);
-        t.tm_stride = (t.tiles_m > 1 && xcd_align) ? (int)round_up((size_t)t.tiles_n * t.ksplit, 8) : t.tiles_n * t.ksplit;
+        t.tm_stride = (t.tiles_m > 1 && E.xcd_align) ? (int)round_up((size_t)t.tiles_n * t.ksplit, 8) : t.tiles_n * t.ksplit;
         wg += t.tiles_m * t.tm_stride;
-    }
-    for (int i = n; i < GEMM_MAX_TASKS; ++i) { L.t[i] = L.t[0]; L.t[i].wg_begin = 0x7fffffff; }
-    double flops = 0.0, bytes = 0.0;
-    for (int i = 0; i < n; ++i) {
-        const GemmTask& t = L.t[i];
-        const double K = (double)t.ktiles * GEMM_BK;
+        const double K = (double)kt * GEMM_BK;                    // for the profile's roofline
         flops += 2.0 * t.M * t.N * K;
         bytes += 4.0 * ((double)t.M * K + (double)t.N * K + (double)t.M * t.N * t.ksplit);
     }
-    static const char* split_tag = getenv("SET_GEMM_SPLIT_TAG");     // debug (SET_GEMM_SPLIT=1): restrict the split kernel to one call site
-    const bool split_here = bm == 128 && bn == 64 && !L.row_list &&
-                            (split_scoped(probs, n) ||
-                             (split_all() && (!split_tag || !*split_tag || strstr(tag ? tag : "untagged", split_tag))));
-    // (the split kernel's tag stays in the family of the tile it replaces: bench.py keys `roofline` on the prefix)
-    const char* kname = split_here ? "gemm_nt_f32<128,64>:bf16x3" :
-                        (bm == 64 && bn == 64 && gemm_asm() && slices_in_one_segment(L)) ? "gemm_nt_f32_asm<64,64>" :
-                        (bm == 128 && bn == 32) ? "gemm_nt_f32<128,32>" : bm == 128 ? "gemm_nt_f32<128,64>" : (bm == 64 ? "gemm_nt_f32<64,64>" : (bm == 32 ? "gemm_nt_f32<32,128>" : "gemv_nt_f32<16,64>"));
-    ProfScope ps(kname, stream, flops, bytes);
-    static const bool sites = env_int("SET_PROFILE_SITES", 0) != 0;   // per-call-site breakdown (nested events)
-    ProfScope ps2(sites ? (tag ? tag : "gemm:other") : nullptr, stream, flops, bytes);
-    dim3 grid(wg), block(256);
-    {
-        const int nt = L.ntasks, w1 = L.t[1].wg_begin, w2 = L.t[2].wg_begin, w3 = L.t[3].wg_begin, w4 = L.t[4].wg_begin,
-                  w5 = L.t[5].wg_begin;
-        const int* ga = L.gate.alive_prev;
-        const int* gn = row_count;               // GATE == 2: the length of the row list (else an unused slot)
-        const int gate_mode = L.row_list ? 2 : (ga ? 1 : 0);
-        if (split_here) {                        // 72 KB of dynamic LDS: above the 64 KB a kernel gets without asking
-            static bool attr_set[64] = {};       // per device (a racing second thread sets the same values again)
-            int dev = 0;
-            SET_HIP_TRY(hipGetDevice(&dev));
-            if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-                SET_HIP_TRY(hipFuncSetAttribute((const void*)gemm_nt_split_bf16<0>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                SPLIT_LDS_BYTES));
-                SET_HIP_TRY(hipFuncSetAttribute((const void*)gemm_nt_split_bf16<1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                SPLIT_LDS_BYTES));
-                if (dev >= 0 && dev < 64) attr_set[dev] = true;
-            }
-            if (gate_mode)
-                hipLaunchKernelGGL((gemm_nt_split_bf16<1>), grid, block, SPLIT_LDS_BYTES, stream, nt, w1, w2, w3, w4, w5, ga, gn, L);
-            else
-                hipLaunchKernelGGL((gemm_nt_split_bf16<0>), grid, block, SPLIT_LDS_BYTES, stream, nt, w1, w2, w3, w4, w5, ga, gn, L);
-        } else if (gate_mode == 2) {             // (gemm_row_list_ok: one of these three classes)
-            if (bm == 128)
-                hipLaunchKernelGGL((gemm_nt_f32<128, 64, 2, 2, 1, 2>), grid, block, 0, stream, nt, w1, w2, w3, w4, w5, ga, gn, L);
-            else if (bm == 64 && gemm_asm() && slices_in_one_segment(L))
-                hipLaunchKernelGGL((gemm_nt_f32_asm<2>), grid, block, 0, stream, nt, w1, w2, w3, w4, w5, ga, gn, L);
-            else if (bm == 64)
-                hipLaunchKernelGGL((gemm_nt_f32<64, 64, 2, 2, 1, 2>), grid, block, 0, stream, nt, w1, w2, w3, w4, w5, ga, gn, L);
-            else
-                hipLaunchKernelGGL((gemm_nt_f32<32, 128, 1, 4, 1, 2>), grid, block, 0, stream, nt, w1, w2, w3, w4, w5, ga, gn, L);
-        } else if (bm == 16)
-            hipLaunchKernelGGL(gemv_nt_f32, grid, block, 0, stream, nt, w1, w2, w3, w4, w5, ga, gn, L);
-#ifdef SET_EXPERIMENTAL_GEMMS
-        else if (bm == 128 && bn == 32)
-            hipLaunchKernelGGL((gemm_nt_f32<128, 32, 4, 1>), grid, block, 0, stream, nt, w1, w2, w3, w4, w5, ga, gn, L);
-        else if (bm == 128 && bn == 128)
-            hipLaunchKernelGGL((gemm_nt_f32<128, 128, 2, 2>), grid, block, 0, stream, nt, w1, w2, w3, w4, w5, ga, gn, L);
-        else if (bm == 128 && gemm_dma())
-            hipLaunchKernelGGL((gemm_nt_f32_dma<128, 64, 2, 2>), grid, block, 0, stream, nt, w1, w2, w3, w4, w5, ga, gn, L);
-#endif
-        else if (bm == 128 && gate_mode)
-            hipLaunchKernelGGL((gemm_nt_f32<128, 64, 2, 2, 1, 1>), grid, block, 0, stream, nt, w1, w2, w3, w4, w5, ga, gn, L);
-        else if (bm == 128)
-            hipLaunchKernelGGL((gemm_nt_f32<128, 64, 2, 2>), grid, block, 0, stream, nt, w1, w2, w3, w4, w5, ga, gn, L);
-#ifdef SET_EXPERIMENTAL_GEMMS
-        else if (bm == 64 && gemm_wreg())
-            hipLaunchKernelGGL(gemm_nt_f32_wreg, grid, block, 0, stream, nt, w1, w2, w3, w4, w5, ga, gn, L);
-        else if (bm == 64 && gemm_kgroups() == 2)
-            hipLaunchKernelGGL((gemm_nt_f32<64, 64, 2, 2, 2>), grid, dim3(512), 0, stream, nt, w1, w2, w3, w4, w5, ga, gn, L);
-        else if (bm == 64 && gemm_dma())
-            hipLaunchKernelGGL((gemm_nt_f32_dma<64, 64, 2, 2>), grid, block, 0, stream, nt, w1, w2, w3, w4, w5, ga, gn, L);
-#endif
-        else if (bm == 64 && bn == 64 && gemm_asm() && slices_in_one_segment(L))
-            if (gate_mode) hipLaunchKernelGGL((gemm_nt_f32_asm<1>), grid, block, 0, stream, nt, w1, w2, w3, w4, w5, ga, gn, L);
-            else hipLaunchKernelGGL((gemm_nt_f32_asm<0>), grid, block, 0, stream, nt, w1, w2, w3, w4, w5, ga, gn, L);
-        else if (bm == 64 && gate_mode == 1)
-            hipLaunchKernelGGL((gemm_nt_f32<64, 64, 2, 2, 1, 1>), grid, block, 0, stream, nt, w1, w2, w3, w4, w5, ga, gn, L);
-        else if (bm == 64)
-            hipLaunchKernelGGL((gemm_nt_f32<64, 64, 2, 2>), grid, block, 0, stream, nt, w1, w2, w3, w4, w5, ga, gn, L);
-        else if (gate_mode)
-            hipLaunchKernelGGL((gemm_nt_f32<32, 128, 1, 4, 1, 1>), grid, block, 0, stream, nt, w1, w2, w3, w4, w5, ga, gn, L);
-        else
-            hipLaunchKernelGGL((gemm_nt_f32<32, 128, 1, 4>), grid, block, 0, stream, nt, w1, w2, w3, w4, w5, ga, gn, L);
+    for (int i = n; i < GEMM_MAX_TASKS; ++i) { L.t[i] = L.t[0]; L.t[i].wg_begin = 0x7fffffff; }
+    const int gate_mode = L.row_list ? 2 : (L.gate.alive_prev ? 1 : 0);
+    const GemmKernel k = gemm_kernel(r, gate_mode, r.bm == 64 && r.bn == 64 && E.hand_loop() && slices_in_one_segment(L));
+    if (!k.fn) return SET_ERR_UNSUPPORTED;
+    ProfScope ps(k.tag, stream, flops, bytes);
+    ProfScope ps2(E.profile_sites ? (tag ? tag : "gemm:other") : nullptr, stream, flops, bytes);
+    if (r.split) {                           // 72 KB of dynamic LDS: above the 64 KB a kernel gets without asking
+        static bool attr_set[64] = {};       // per device (a racing second thread sets the same values again)
+        int dev = 0;
+        SET_HIP_TRY(hipGetDevice(&dev));
+        if (dev < 0 || dev >= 64 || !attr_set[dev]) {
+            for (const GemmKernel& s : g_gemm_kernels)
+                if (s.kc == KC_SPLIT) SET_HIP_TRY(hipFuncSetAttribute((const void*)s.fn, hipFuncAttributeMaxDynamicSharedMemorySize, s.lds));
+            if (dev >= 0 && dev < 64) attr_set[dev] = true;
+        }
     }
+    // gate_nrows, GATE == 2: the length of the row list (else an unused slot)
+    hipLaunchKernelGGL(k.fn, dim3(wg), dim3(k.threads), k.lds, stream, L.ntasks, L.t[1].wg_begin, L.t[2].wg_begin, L.t[3].wg_begin,
+                       L.t[4].wg_begin, L.t[5].wg_begin, L.gate.alive_prev, row_count, L);
     SET_LAUNCH_CHECK();
     return SET_OK;
 }

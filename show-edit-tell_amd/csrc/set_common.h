@@ -99,6 +99,14 @@ struct GemmProb {
 // similar length; problems with max_ksplit == 1 keep a fused bias/activation epilogue
 void plan_ksplit(GemmProb* probs, int n, int target_wgs);
 int gemm_group(const GemmProb* probs, int n, hipStream_t stream, const char* tag = nullptr);
+// What a grouped launch of these problems runs on: decided in one place, read by plan_ksplit, gemm_group and the two queries
+// below.  `tag` is the call site's, as given to gemm_group (only the SET_GEMM_SPLIT_TAG debug filter looks at it).
+struct GemmRoute {
+    int bm, bn;      // tile: 16x64 (no LDS), 32x128, 64x64, 128x64; the experimental variant adds 128x32 and 128x128.  n <= 0: bm = 0
+    bool split;      // runs on the bf16-split kernel (inside a SplitScope, or SET_GEMM_SPLIT=1)
+    bool rows_ok;    // can take GemmProb::row_list
+};
+GemmRoute gemm_route(const GemmProb* probs, int n, const char* tag = nullptr);
 // the row-tile class (16 / 32 / 64 / 128) a grouped launch of these problems runs on
 int gemm_launch_rows(const GemmProb* probs, int n);
 // whether a grouped launch of these problems can take GemmProb::row_list (every tile class but the <= 16-row one)

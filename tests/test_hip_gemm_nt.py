@@ -292,6 +292,36 @@ def test_exact_tasks_all_eligible():
     assert cls == 64 and tags == [TAG_ASM] and ks == [1, 4, 4, 1, 3, 2]
 
 
+MIXED = [((16, 17), 32), ((32, 33), 64), ((5, 130), 64), ((512, 513), 128)]
+
+
+@pytest.mark.parametrize("Ms,cls", MIXED, ids=["M%d+%d" % m for m, _ in MIXED])
+def test_exact_mixed_row_classes(Ms, cls):
+    """two problems whose row counts fall into different row-tile classes in ONE launch: the launch runs on the larger class
+    (one kernel, one tag), and the problem of the smaller class is served exactly by tiles it only partly fills"""
+    rng = _rng(14, *Ms)
+    probs = [Prob(rng, M, 65, (64,), ksplit=1) for M in Ms]
+    ks, got_cls, tags = run_both_loops(probs, "mixed classes M=%s" % (Ms,))
+    assert ks == [1, 1] and got_cls == cls
+    assert tags == [TAG_ASM if cls == 64 else TAG[cls]], tags
+
+
+def test_mixed_row_classes_row_list_refused():
+    """(5, 16) rows: both problems in the <= 16-row class, which takes no row list (as test_row_list_refusals: one problem)"""
+    from show_edit_tell_amd.autograd_ops import gemm_nt_group
+    rng = _rng(15)
+    lst_d, _ = _row_list(rng, 16)
+    count = torch.tensor([3], dtype=torch.int32, device=DEV)
+    probs = [Prob(rng, M, 65, (64,)) for M in (5, 16)]
+    cvs = [Canvas(p.M, _ld(65, False)) for p in probs]
+    rc, _, _ = gemm_nt_group([dict(segs=p.segs, C=cv.view(4, 65), ksplit=1) for p, cv in zip(probs, cvs)], row_list=lst_d,
+                             row_count=count, code=True)
+    assert rc == 2                                     # SET_ERR_UNSUPPORTED
+    torch.cuda.synchronize()
+    for cv in cvs:
+        cv.check("refused (5 and 16 rows with a row list)")
+
+
 # ------------------------------------------------------------------------------------------------- epilogue
 @pytest.mark.parametrize("ksplit", [1, 3])
 @pytest.mark.parametrize("act", [ACT_NONE, ACT_RELU, ACT_TANH, ACT_SIGMOID], ids=["none", "relu", "tanh", "sigmoid"])

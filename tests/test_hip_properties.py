@@ -110,8 +110,8 @@ def test_device_prefetcher_roundtrip(setup):
 
 
 def test_split_precision_gemm_keeps_parity():
-    """The EXPERIMENTAL bf16-split emulated-fp32 GEMM (SET_GEMM_SPLIT=1 on the experimental library variant,
-    csrc/experimental/gemm_variants.inc; the shipped library does not contain it) must be fp32-grade: rerun the golden
+    """The bf16-split emulated-fp32 GEMM (csrc/gemm_split_bf16.inc, in both library variants) on EVERY launch it can take
+    (SET_GEMM_SPLIT=1, here on the experimental library variant) must be fp32-grade: rerun the golden
     parity tests of the full-size model (greedy tokens bit-exact, logits within 1e-4) and the fp64 linear check with the
     switch on.  Library variant and switch are read once per process, hence the child process."""
     import os

@@ -1,6 +1,7 @@
 #!/bin/bash
-# where a k-tile of the experimental bf16-split GEMM spends its time: diagnostic builds of the experimental library variant
-# (results are garbage in them), microbenchmark of the F/A-like and the D launch shapes.  tools/split_diag.sh
+# where a k-tile of the bf16-split GEMM (csrc/gemm_split_bf16.inc, in both library variants) spends its time: diagnostic builds
+# (results are garbage in them; built as the experimental variant so that the shipped library stays as it is), microbenchmark
+# of the F/A-like and the D launch shapes with SET_GEMM_SPLIT=1.  tools/split_diag.sh
 cd $GRAFT_REPO_ROOT
 export SET_LIB_VARIANT=exp SET_GEMM_SPLIT=1 ITERS=100
 for f in "" "-DSPL_EXP_NOSPLIT" "-DSPL_EXP_NOMFMA" "-DSPL_EXP_NOGLOAD" "-DSPL_EXP_NOSPLIT -DSPL_EXP_NOGLOAD" "-DSPL_EXP_NOSPLIT -DSPL_EXP_NOMFMA -DSPL_EXP_NOGLOAD"; do
