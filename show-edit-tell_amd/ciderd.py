@@ -329,21 +329,15 @@ def _reward_sets(ground_truth, B):
     return sets, hyp_set
 
 
-def _bleu4_term(bleu_scorer, bleu_weight, sampled, greedy, ground_truth):
-    """bleu_weight * (BLEU-4(sampled_b) - BLEU-4(greedy_b)) in double: sentence BLEU-4 of bleu.Bleu.score_token_ids (rows
-    cut after their first 0, the 0 a token — the convention of the CIDEr-D term)"""
+def _mix_term(scorer, weight, sampled, greedy, ground_truth, column=None):
+    """weight * (score(sampled_b) - score(greedy_b)) in double: the sentence scores of a host scorer's score_token_ids (bleu.Bleu
+    with column 3, its BLEU-4; rouge.RougeL with column None), rows cut after their first 0, the 0 a token — the convention of
+    the CIDEr-D term"""
     B = sampled.shape[0]
     sets, hyp_set = _reward_sets(ground_truth, B)
-    b = np.asarray(bleu_scorer.score_token_ids(np.concatenate([sampled, greedy], 0), hyp_set, sets)[1], dtype=np.float64)[:, 3]
-    return bleu_weight * (b[:B] - b[B:])
-
-
-def _rouge_term(rouge_scorer, rouge_weight, sampled, greedy, ground_truth):
-    """rouge_weight * (ROUGE-L(sampled_b) - ROUGE-L(greedy_b)) in double: rouge.RougeL.score_token_ids under the rows' 0 rule"""
-    B = sampled.shape[0]
-    sets, hyp_set = _reward_sets(ground_truth, B)
-    r = np.asarray(rouge_scorer.score_token_ids(np.concatenate([sampled, greedy], 0), hyp_set, sets)[1], dtype=np.float64)
-    return rouge_weight * (r[:B] - r[B:])
+    x = np.asarray(scorer.score_token_ids(np.concatenate([sampled, greedy], 0), hyp_set, sets)[1], dtype=np.float64)
+    x = x if column is None else x[:, column]
+    return weight * (x[:B] - x[B:])
 
 
 def self_critical_reward(scorer, sampled, greedy, ground_truth, cider_weight=1.0, bleu_scorer=None, bleu_weight=0.0,
@@ -357,36 +351,28 @@ def self_critical_reward(scorer, sampled, greedy, ground_truth, cider_weight=1.0
     sampled = np.asarray(sampled.cpu() if hasattr(sampled, 'cpu') else sampled)
     greedy = np.asarray(greedy.cpu() if hasattr(greedy, 'cpu') else greedy)
     B = sampled.shape[0]
-    mix = bleu_scorer is not None and bleu_weight != 0.0
-    mix_rouge = rouge_scorer is not None and rouge_weight != 0.0
     if getattr(scorer, "_handle", None) is not None and scorer._handle() is not None:
         # integer fast path (no strings): the reference sets of the distinct images once, all 2B captions in one call
         sets, hyp_set = _reward_sets(ground_truth, B)
         s = scorer.score_token_ids(np.concatenate([sampled, greedy], 0), hyp_set, sets)
-        diff = cider_weight * (s[:B] - s[B:])
-        if mix:
-            diff = diff + _bleu4_term(bleu_scorer, bleu_weight, sampled, greedy, ground_truth)
-        if mix_rouge:
-            diff = diff + _rouge_term(rouge_scorer, rouge_weight, sampled, greedy, ground_truth)
-        return np.repeat(diff[:, None], sampled.shape[1], 1).astype(np.float32)
-    memo = {}                    # the same image's reference lists are repeated once per sample: stringify them once
+    else:
+        memo = {}                # the same image's reference lists are repeated once per sample: stringify them once
 
-    def ref_strings(caps):
-        k = id(caps)
-        if k not in memo:
-            memo[k] = [tokens_to_str(c) for c in caps]
-        return memo[k]
+        def ref_strings(caps):
+            k = id(caps)
+            if k not in memo:
+                memo[k] = [tokens_to_str(c) for c in caps]
+            return memo[k]
 
-    refs = [ref_strings(caps) for caps in ground_truth]
-    gts = {i: refs[i % B] for i in range(2 * B)}
-    res = [{'image_id': i, 'caption': [tokens_to_str(sampled[i])]} for i in range(B)]
-    res += [{'image_id': B + i, 'caption': [tokens_to_str(greedy[i])]} for i in range(B)]
-    _, s = scorer.compute_score(gts, res)
+        refs = [ref_strings(caps) for caps in ground_truth]
+        gts = {i: refs[i % B] for i in range(2 * B)}
+        res = [{'image_id': i, 'caption': [tokens_to_str(sampled[i])]} for i in range(B)]
+        res += [{'image_id': B + i, 'caption': [tokens_to_str(greedy[i])]} for i in range(B)]
+        _, s = scorer.compute_score(gts, res)
     diff = cider_weight * (s[:B] - s[B:])
-    if mix:
-        diff = diff + _bleu4_term(bleu_scorer, bleu_weight, sampled, greedy, ground_truth)
-    if mix_rouge:
-        diff = diff + _rouge_term(rouge_scorer, rouge_weight, sampled, greedy, ground_truth)
+    for term, weight, column in ((bleu_scorer, bleu_weight, 3), (rouge_scorer, rouge_weight, None)):      # in this order
+        if term is not None and weight != 0.0:
+            diff = diff + _mix_term(term, weight, sampled, greedy, ground_truth, column)
     return np.repeat(diff[:, None], sampled.shape[1], 1).astype(np.float32)
 
 
@@ -585,31 +571,13 @@ class DeviceCiderD(DeviceSentenceScorer):
         sets, prepared here).  Returns the (N,) float64 device tensor of scores; return_pairs=True: also (N, max set size)
         with the score against every single reference of the set (columns beyond a smaller set stay 0)."""
         import torch
-        from . import _lib
-        if not isinstance(refs, PreparedRefs):
-            refs = self.prepare_refs(refs)
-        t = self._tokens(hyps)
-        N, L = t.shape
-        so = self._i32(hyp_set, N, "hyp_set")
-        ln = self._i32(hyp_lens, N, "hyp_lens")
-        scores = torch.empty(N, dtype=torch.float64, device=self.dev)
-        pair_ld = max(1, refs.max_set)
-        pairs = torch.zeros(N, pair_ld, dtype=torch.float64, device=self.dev) if return_pairs else None
-        with torch.cuda.device(self.dev):
-            rc = self._lib.set_ciderd_device_score(
-                self._h, t.data_ptr(), t.stride(0), None if ln is None else ln.data_ptr(), N, L, so.data_ptr(),
-                refs.recs.data_ptr(), refs.L, refs.n_refs, refs.set_off.data_ptr(), refs.n_sets, refs.max_set, scores.data_ptr(),
-                None if pairs is None else pairs.data_ptr(), pair_ld, _lib.stream_of(self.dev))
-        _lib.check(rc, "set_ciderd_device_score")
-        return (scores, pairs) if return_pairs else scores
+        outputs = lambda N: (torch.empty(N, dtype=torch.float64, device=self.dev),)
+        out = self._score_rows("set_ciderd_device_score", outputs, hyps, hyp_set, refs, hyp_lens, return_pairs, lead=(self._h,))
+        return out if return_pairs else out[0]
 
-    def pair_scores(self, candidates, n_per_image):
-        """(NI * n, L) candidates, n per image -> (NI * n, n): row i against candidate r of its own image as the only
-        reference (what evaluate.consensus_rerank reads); the candidates are vectorised once and serve as references"""
-        t = self._tokens(candidates)
-        refs, owner = self._self_refs(t, n_per_image)
-        refs.recs = self.vectorise(t)[0]
-        return self.score_token_ids(t, owner, refs, return_pairs=True)[1]
+    def _prepare(self, t, ln):
+        """the records of these rows (pair_scores of the base: the candidates are vectorised once and serve as references)"""
+        return self.vectorise(t, ln)[0]
 
 
 import weakref as _weakref
@@ -654,14 +622,15 @@ def self_critical_reward_device(dscorer, sampled, greedy, refs, image_of=None, c
     rows, rows_set = torch.cat([sampled.to(dev), greedy.to(dev)], 0), torch.cat([image_of, own])
     s = dscorer.score_token_ids(rows, rows_set, refs)
     diff = cider_weight * (s[:N] - s[N:][image_of])
-    if bleu_scorer is not None and bleu_weight != 0.0:
-        if bleu_refs is None:
-            raise ValueError("the BLEU term needs bleu_refs: the images' reference sets or DeviceBleu.prepare_refs of them")
-        b = bleu_scorer.score_token_ids(rows, rows_set, bleu_refs)[1][:, 3]
-        diff = diff + bleu_weight * (b[:N] - b[N:][image_of])
-    if rouge_scorer is not None and rouge_weight != 0.0:
-        if rouge_refs is None:
-            raise ValueError("the ROUGE-L term needs rouge_refs: the images' reference sets or a device scorer's prepare_refs of them")
-        r = rouge_scorer.score_token_ids(rows, rows_set, rouge_refs)[1]
-        diff = diff + rouge_weight * (r[:N] - r[N:][image_of])
+    for term, term_refs, weight, column, missing in (                                                     # in this order
+            (bleu_scorer, bleu_refs, bleu_weight, 3,
+             "the BLEU term needs bleu_refs: the images' reference sets or DeviceBleu.prepare_refs of them"),
+            (rouge_scorer, rouge_refs, rouge_weight, None,
+             "the ROUGE-L term needs rouge_refs: the images' reference sets or a device scorer's prepare_refs of them")):
+        if term is not None and weight != 0.0:
+            if term_refs is None:
+                raise ValueError(missing)
+            x = term.score_token_ids(rows, rows_set, term_refs)[1]
+            x = x if column is None else x[:, column]
+            diff = diff + weight * (x[:N] - x[N:][image_of])
     return diff.to(torch.float32)[:, None].expand(N, sampled.shape[1]).contiguous()

@@ -13,7 +13,10 @@
 // Counts are found lane against lane through LDS, all four orders in one pass over the other sentence's length; the
 // statistics are integers, the four orders' clipped counts travel through one xor-butterfly as the bytes of one word (each
 // sum is at most 64).  A prepared reference is one record of ngram_wave.h's layout (ref_rec_words; csrc/rouge_device.hip reads
-// the same records).  Scores are double and a function of the row's ten integers alone, so a row's bits cannot depend on the
+// the same records).  bl_score_k walks them with a loop of its own: on ngram_wave.h's RefWalk (staging hook, or the
+// step in two halves) it compiled to other code that measured about 0.3 us (2 %) above the parent's spread
+// (profiles/metric_walk_bench.json), so the frame that csrc/rouge_device.hip and csrc/editdist_device.hip take from RefWalk is
+// written out here.  The score entry is ngram_wave.h's score_launch.  Scores are double and a function of the row's ten integers alone, so a row's bits cannot depend on the
 // launch it is part of.  No atomics; every store is an ordinary vector store of a declared output.
 #include <cmath>
 #include "ngram_wave.h"
@@ -165,15 +168,8 @@ int set_bleu_device_prepare(const int64_t* tokens, int64_t ld, const int32_t* le
 int set_bleu_device_score(const int64_t* hyp, int64_t hyp_ld, const int32_t* hyp_lens, int n_hyp, int L, const int32_t* set_of_hyp,
                           const void* ref_recs, int ref_L, int64_t n_refs, const int64_t* ref_set_off, int n_sets, int max_set,
                           int32_t* stats, double* scores, double* pair_scores, int64_t pair_ld, void* stream) {
-    if (n_hyp > 0 && !stats) return SET_ERR_ARG;
-    SET_TRY(score_args_check(hyp, hyp_ld, n_hyp, L, set_of_hyp, ref_recs, ref_L, n_refs, ref_set_off, n_sets, max_set, pair_scores, pair_ld));
-    if (n_hyp == 0) return SET_OK;
-    set::ProfScope prof("bleu_score", static_cast<hipStream_t>(stream));
-    hipLaunchKernelGGL(bl_score_k, dim3((unsigned)n_hyp), dim3(64), 0, static_cast<hipStream_t>(stream), hyp, (long long)hyp_ld,
-                       hyp_lens, L, set_of_hyp, static_cast<const uint64_t*>(ref_recs), ref_L, (long long)n_refs, ref_set_off,
-                       n_sets, max_set, stats, scores, pair_scores, (long long)pair_ld);
-    SET_LAUNCH_CHECK();
-    return SET_OK;
+    return score_launch<>("bleu_score", bl_score_k, true, hyp, hyp_ld, hyp_lens, n_hyp, L, set_of_hyp, ref_recs, ref_L, n_refs,
+                          ref_set_off, n_sets, max_set, stats, scores, pair_scores, pair_ld, stream);
 }
 
 }  // extern "C"

@@ -17,8 +17,10 @@
 // f_j >= 1 inside a sentence, so the 0 fields of padding never match; the carry out of bit 63 is dropped; the 1 shifted into Ph
 // is row 0 of the table growing by 1 per column.  The lanes only supply the match masks.  A cell of the table follows from its
 // column's pair:  D[i][j] = j + popcount(Pv_j & low(i)) - popcount(Mv_j & low(i)),  low(i) = bits 0 .. i-1, column 0 = (ones, 0).
-// The scores are double and a function of the row's integers alone, so a row's bits cannot depend on the launch it is part of.
-// No LDS, no atomics; every store is an ordinary vector store of a declared output.
+// References are BLEU's prepared records, walked through ngram_wave.h's RefWalk (the refusal of a row, the record in flight,
+// the length clamp, the order of request and recurrence) as in csrc/rouge_device.hip; the score
+// entry is its score_launch.  The scores are double and a function of the row's integers alone, so a row's bits cannot
+// depend on the launch it is part of.  No LDS, no atomics; every store is an ordinary vector store of a declared output.
 #include "ngram_wave.h"
 
 namespace {
@@ -62,43 +64,25 @@ struct EdCol {
     }
 };
 
-// One wave, one hypothesis against the references of its set.  The next reference's record is requested before the current
-// one's recurrence runs.
+// One wave, one hypothesis against the references of its set (RefWalk, the order-1 word of a position): the next reference's
+// record is requested before the current one's recurrence runs.
 __global__ __launch_bounds__(64) void ed_score_k(const int64_t* hyp, long long ld, const int* lens, int L, const int* set_of,
                                                  const uint64_t* ref_recs, int ref_L, long long n_refs, const int64_t* set_off,
                                                  int n_sets, int max_set, int* stats, double* scores, double* pairs,
                                                  long long pair_ld) {
     const int lane = threadIdx.x & 63;
     const long long i = blockIdx.x;
-    const double nan = __longlong_as_double(0x7FF8000000000000ll);
-    long long r0, r1;
-    if (!set_range(set_of, i, set_off, n_sets, n_refs, max_set, r0, r1)) {   // -1 / NaN, nothing else touched
-        if (lane < 4) stats[i * 4 + lane] = -1;
-        if (scores && lane == 0) scores[i] = nan;
-        return;
-    }
-    const size_t words = ref_rec_words(ref_L);
-    uint64_t nkey = 0, nlen = 0, nbad = 0;                         // the record in flight
-    auto request = [&](long long r) {
-        const uint64_t* rv = ref_recs + (size_t)r * words;
-        nlen = rv[0];
-        nbad = rv[1];
-        nkey = lane < ref_L ? rv[8 + 4 * lane] : 0;
-    };
-    if (r0 < r1) request(r0);
+    RefWalk<KeyOrder1> W;
+    if (!W.open(i, set_of, ref_recs, ref_L, n_refs, set_off, n_sets, max_set, pairs, pair_ld)) return refuse_row(i, stats, 4, scores, 1);
     WaveSent S;
     wave_read(hyp, ld, lens, i, L, 1, S);
     const unsigned f = (unsigned)S.key[0];                         // this position's field, 0 at and beyond the length
-    bool bad = S.bad;
     // the chosen reference; an empty set: the distance to no words, no reference
     int b_dist = S.len, b_len = 0, b_ref = -1;
     long long b_num = 0, b_den = 1;
-    for (long long r = r0; r < r1; ++r) {
-        const unsigned g = (unsigned)nkey;
-        const int rlen = (int)nlen < ref_L ? ((int)nlen < 0 ? 0 : (int)nlen) : ref_L;
-        bad = bad || nbad != 0;
-        if (r + 1 < r1) request(r + 1);
-        EdCol C;                                                   // wave-uniform: the compiler keeps it in scalar registers
+    W.each(S.bad, [&](long long k, int rlen, const KeyOrder1& key) {
+        const unsigned g = (unsigned)key.w;
+        EdCol C;                                                  // wave-uniform: the compiler keeps it in scalar registers
         C.start(rlen);
         if (rlen > 0) {
             for (int j = 0; j < S.len; ++j) {
@@ -111,17 +95,17 @@ __global__ __launch_bounds__(64) void ed_score_k(const int64_t* hyp, long long l
         // the larger similarity, as fractions: (m - d) / m, both empty 1 / 1; the first of equal ones stays
         const int m = S.len > rlen ? S.len : rlen;
         const long long num = m > 0 ? m - C.dist : 1, den = m > 0 ? m : 1;
-        if (r == r0 || num * b_den > b_num * den) {
+        if (k == 0 || num * b_den > b_num * den) {
             b_num = num;
             b_den = den;
             b_dist = C.dist;
             b_len = rlen;
-            b_ref = (int)(r - r0);
+            b_ref = (int)k;
         }
-        if (pairs && lane == 0) pairs[i * pair_ld + (r - r0)] = bad ? nan : ed_sim(C.dist, S.len, rlen);
-    }
-    if (lane < 4) stats[i * 4 + lane] = bad ? -1 : lane == 0 ? b_dist : lane == 1 ? S.len : lane == 2 ? b_len : b_ref;
-    if (scores && lane == 0) scores[i] = bad ? nan : ed_sim(b_dist, S.len, b_len);
+        W.put_pair(k, [&] { return ed_sim(C.dist, S.len, rlen); });
+    });
+    if (lane < 4) stats[i * 4 + lane] = W.bad ? -1 : lane == 0 ? b_dist : lane == 1 ? S.len : lane == 2 ? b_len : b_ref;
+    if (scores && lane == 0) scores[i] = W.bad ? quiet_nan() : ed_sim(b_dist, S.len, b_len);
 }
 
 __device__ __forceinline__ u64 read_lane64(u64 v, int l) {
@@ -229,15 +213,8 @@ extern "C" {
 int set_edit_device_score(const int64_t* hyp, int64_t hyp_ld, const int32_t* hyp_lens, int n_hyp, int L, const int32_t* set_of_hyp,
                           const void* ref_recs, int ref_L, int64_t n_refs, const int64_t* ref_set_off, int n_sets, int max_set,
                           int32_t* stats, double* scores, double* pair_scores, int64_t pair_ld, void* stream) {
-    if (n_hyp > 0 && !stats) return SET_ERR_ARG;
-    SET_TRY(score_args_check(hyp, hyp_ld, n_hyp, L, set_of_hyp, ref_recs, ref_L, n_refs, ref_set_off, n_sets, max_set, pair_scores, pair_ld));
-    if (n_hyp == 0) return SET_OK;
-    set::ProfScope prof("edit_score", static_cast<hipStream_t>(stream));
-    hipLaunchKernelGGL(ed_score_k, dim3((unsigned)n_hyp), dim3(64), 0, static_cast<hipStream_t>(stream), hyp, (long long)hyp_ld,
-                       hyp_lens, L, set_of_hyp, static_cast<const uint64_t*>(ref_recs), ref_L, (long long)n_refs, ref_set_off,
-                       n_sets, max_set, stats, scores, pair_scores, (long long)pair_ld);
-    SET_LAUNCH_CHECK();
-    return SET_OK;
+    return score_launch<>("edit_score", ed_score_k, true, hyp, hyp_ld, hyp_lens, n_hyp, L, set_of_hyp, ref_recs, ref_L, n_refs,
+                          ref_set_off, n_sets, max_set, stats, scores, pair_scores, pair_ld, stream);
 }
 
 int set_edit_device_align(const int64_t* hyp, int64_t hyp_ld, const int32_t* hyp_lens, int n, int L, const int64_t* src,

@@ -1,7 +1,12 @@
-// What the sentence metrics share (csrc/ciderd_device.hip, csrc/bleu_device.hip, csrc/rouge_device.hip, csrc/ciderd_host.hip):
-// the packing of an n-gram into one 64-bit key, the hash of such a key, the two limits, the prepared-reference record of BLEU
-// and ROUGE-L, and the device leaves that turn one row of ids into one wave's keys.  The rules stated here are the contract between CIDEr-D and BLEU on the device, the host scorer, the reward mix and
-// evaluate.consensus_rerank; device_metric.py states the same two limits and the 0 rule for the Python side.
+// What the sentence metrics share (csrc/ciderd_device.hip, csrc/bleu_device.hip, csrc/rouge_device.hip, csrc/editdist_device.hip,
+// csrc/ciderd_host.hip): the packing of an n-gram into one 64-bit key, the hash of such a key, the two limits, the
+// prepared-reference record of BLEU, ROUGE-L and edit distance, the device leaves that turn one row of ids into one wave's keys,
+// the walk of a hypothesis over the records of its reference set (RefWalk: the one place where ROUGE-L and edit distance state
+// the refusal of a row, the record in flight, the length clamp and the order "request record r + 1, then work on record r";
+// bl_score_k keeps its own loop, see csrc/bleu_device.hip) and the one host launcher of the three record-reading score entries
+// (score_launch).  The rules stated here are the contract between the four metrics on
+// the device, the host scorers, the reward mix and evaluate.consensus_rerank; device_metric.py states the same two limits and
+// the 0 rule for the Python side.
 //
 // A sentence is at most NG_MAXL ids: ONE WAVE holds it, one position per lane, and lane i owns the (up to) four grams that start
 // at position i.  A gram of k ids is packed as id + 1 in 16-bit fields, so 0 is "no gram" and the length is implied.
@@ -27,8 +32,8 @@ __host__ __device__ inline uint64_t hash(uint64_t x) {         // the 64-bit mix
     return x ^ (x >> 31);
 }
 
-// record of one prepared reference, in 8-byte words (written by csrc/bleu_device.hip bl_prepare_k; read there and by
-// csrc/rouge_device.hip and csrc/editdist_device.hip, which need words 0, 1 and the order-1 key of every position):
+// record of one prepared reference, in 8-byte words (written by csrc/bleu_device.hip bl_prepare_k; read there by bl_score_k and,
+// through RefWalk below, by rg_score_k and ed_score_k, which need words 0, 1 and the order-1 key of every position):
 //   [0] length   [1] 1: an id that cannot be packed   [2..7] 0
 //   [8 + 4 i + k]  key of the order-(k+1) gram that starts at position i (0: none), EVERY occurrence (counts need them)
 __host__ __device__ inline size_t ref_rec_words(int L) { return 8 + 4 * (size_t)L; }
@@ -128,6 +133,110 @@ __device__ __forceinline__ bool set_range(int s, const int64_t* set_off, int n_s
 __device__ __forceinline__ bool set_range(const int* set_of, long long i, const int64_t* set_off, int n_sets, long long n_refs,
                                           int max_set, long long& r0, long long& r1) {
     return set_range(set_of[i], set_off, n_sets, n_refs, max_set, r0, r1);
+}
+
+// ---- the walk of one hypothesis over the reference records of its set (rg_score_k, ed_score_k) -----------------------------------
+__device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7FF8000000000000ll); }
+
+// What a refused row gets (set_range said no): -1 in its n_stats statistics, NaN in its n_scores scores, nothing else touched.
+__device__ __forceinline__ void refuse_row(long long i, int* stats, int n_stats, double* scores, int n_scores) {
+    const int lane = threadIdx.x & 63;
+    if (lane < n_stats) stats[i * n_stats + lane] = -1;
+    if (scores && lane < n_scores) scores[i * n_scores + lane] = quiet_nan();
+}
+
+// How much of a position's 32-byte key block a lane keeps of a record: the order-1 word, the position's field id + 1 (ROUGE-L,
+// edit distance).  `pos`: the block of this lane's position, read only where `in`.
+struct KeyOrder1 {
+    uint64_t w = 0;
+    __device__ __forceinline__ void load(const uint64_t* pos, bool in) { w = in ? pos[0] : 0; }
+};
+
+// One wave, hypothesis i, the records [r0, r1) of its set in order.  open() decides the range and requests the first record, so
+// that it travels underneath the caller's read of the hypothesis; each() hands the records over one by one.  Everything is
+// inlined into the kernel: what the body keeps wave-uniform (ROUGE-L's V, edit distance's EdCol) stays in scalar registers.
+template <class Key>
+struct RefWalk {
+    const uint64_t* recs;
+    size_t words;
+    int ref_L;
+    long long i, r0, r1;
+    double* pairs;
+    long long pair_ld;
+    Key nkey;                                  // the record in flight: the lane's keys, the length word, the bad word
+    uint64_t nlen = 0, nbad = 0;
+    bool bad = false;                          // an id that cannot be packed, in the hypothesis or in a record handed over so far
+
+    __device__ __forceinline__ void request(long long r) {
+        const uint64_t* rv = recs + (size_t)r * words;
+        const int lane = threadIdx.x & 63;
+        nlen = rv[0];
+        nbad = rv[1];
+        nkey.load(rv + 8 + 4 * lane, lane < ref_L);
+    }
+
+    // false: the row is refused; the caller marks it (refuse_row) and returns
+    __device__ __forceinline__ bool open(long long row, const int* set_of, const uint64_t* ref_recs, int ref_L_, long long n_refs,
+                                         const int64_t* set_off, int n_sets, int max_set, double* pairs_, long long pair_ld_) {
+        if (!set_range(set_of, row, set_off, n_sets, n_refs, max_set, r0, r1)) return false;
+        i = row;
+        recs = ref_recs;
+        ref_L = ref_L_;
+        words = ref_rec_words(ref_L_);
+        pairs = pairs_;
+        pair_ld = pair_ld_;
+        if (r0 < r1) request(r0);
+        return true;
+    }
+
+    // For r = r0 .. r1 - 1: in flight -> current (keys, length clamped to [0, ref_L], bad accumulated), stage(key) (a hook
+    // for a kernel with work of its own before the next request; ROUGE-L and edit distance have none), the request of record r + 1, and only then
+    // body(r - r0, rlen, key), the metric's recurrence or count.
+    template <class Stage, class Body>
+    __device__ __forceinline__ void each(bool hyp_bad, Stage stage, Body body) {
+        bad = hyp_bad;
+        for (long long r = r0; r < r1; ++r) {
+            const Key key = nkey;
+            const int rlen = (int)nlen < ref_L ? ((int)nlen < 0 ? 0 : (int)nlen) : ref_L;
+            bad = bad || nbad != 0;
+            stage(key);
+            if (r + 1 < r1) request(r + 1);
+            body(r - r0, rlen, key);
+        }
+    }
+    template <class Body>
+    __device__ __forceinline__ void each(bool hyp_bad, Body body) { each(hyp_bad, [](const Key&) {}, body); }
+
+    // the hypothesis against reference k of its set alone, where the caller asked for pairs: NaN once bad, else value(), which
+    // is asked of lane 0 only (a wave-level operation belongs in front of this call)
+    template <class Value>
+    __device__ __forceinline__ void put_pair(long long k, Value value) const {
+        if (pairs && (threadIdx.x & 63) == 0) pairs[i * pair_ld + k] = bad ? quiet_nan() : value();
+    }
+};
+
+// The kernels above the walk take the score entries' parameters in the entries' order; X: what an entry adds between max_set and
+// stats (ROUGE-L: beta^2).
+template <class... X>
+using score_kernel_t = void (*)(const int64_t*, long long, const int*, int, const int*, const uint64_t*, int, long long, const int64_t*,
+                                int, int, X..., int*, double*, double*, long long);
+
+// The one body of set_bleu_device_score, set_rouge_device_score and set_edit_device_score: a null stats or the entry's own
+// refusal (own_ok false) first, then score_args_check, then nothing to do for no hypothesis, then the launch, one wave a row.
+template <class... X>
+inline int score_launch(const char* tag, score_kernel_t<X...> kernel, bool own_ok, const int64_t* hyp, int64_t hyp_ld,
+                        const int32_t* hyp_lens, int n_hyp, int L, const int32_t* set_of_hyp, const void* ref_recs, int ref_L,
+                        int64_t n_refs, const int64_t* ref_set_off, int n_sets, int max_set, int32_t* stats, double* scores,
+                        double* pair_scores, int64_t pair_ld, void* stream, X... extra) {
+    if ((n_hyp > 0 && !stats) || !own_ok) return SET_ERR_ARG;
+    SET_TRY(score_args_check(hyp, hyp_ld, n_hyp, L, set_of_hyp, ref_recs, ref_L, n_refs, ref_set_off, n_sets, max_set, pair_scores, pair_ld));
+    if (n_hyp == 0) return SET_OK;
+    set::ProfScope prof(tag, static_cast<hipStream_t>(stream));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)n_hyp), dim3(64), 0, static_cast<hipStream_t>(stream), hyp, (long long)hyp_ld, hyp_lens,
+                       L, set_of_hyp, static_cast<const uint64_t*>(ref_recs), ref_L, (long long)n_refs, ref_set_off, n_sets, max_set,
+                       extra..., stats, scores, pair_scores, (long long)pair_ld);
+    SET_LAUNCH_CHECK();
+    return SET_OK;
 }
 
 }  // namespace ngram

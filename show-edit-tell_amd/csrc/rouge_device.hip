@@ -14,7 +14,9 @@
 //     M = ballot(g_lane == f_j);  U = V & M;  V = (V + U) | (V & ~M);           lcs = 64 - popcount(V)
 // f_j >= 1 inside the hypothesis, so the 0 fields of padding never match; the carry out of bit 63 is dropped.  The lanes only
 // supply the match masks: one lane read, one compare and five scalar operations per position.  References are BLEU's prepared
-// records (ngram_wave.h ref_rec_words; the order-1 key of a position is its field), so one preparation serves both metrics.
+// records (ngram_wave.h ref_rec_words; the order-1 key of a position is its field), so one preparation serves both metrics, and
+// the walk over them is ngram_wave.h's RefWalk (the refusal of a row, the record in flight, the length clamp, the order of
+// request and recurrence) as in csrc/editdist_device.hip; the score entry is its score_launch.
 // The score is double and a function of the row's four integers alone, so a row's bits cannot depend on the launch it is part
 // of.  No LDS, no atomics; every store is an ordinary vector store of a declared output.
 #include <cmath>
@@ -33,40 +35,22 @@ __device__ __forceinline__ double rg_score(int lcs_p, int len_h, int lcs_r, int 
     return (1.0 + beta2) * P * Rc / (Rc + beta2 * P);
 }
 
-// One wave, one hypothesis against the references of its set.  The next reference's record is requested before the current
-// one's recurrence runs.
+// One wave, one hypothesis against the references of its set (RefWalk, the order-1 word of a position): the next reference's
+// record is requested before the current one's recurrence runs.
 __global__ __launch_bounds__(64) void rg_score_k(const int64_t* hyp, long long ld, const int* lens, int L, const int* set_of,
                                                  const uint64_t* ref_recs, int ref_L, long long n_refs, const int64_t* set_off,
                                                  int n_sets, int max_set, double beta2, int* stats, double* scores, double* pairs,
                                                  long long pair_ld) {
     const int lane = threadIdx.x & 63;
     const long long i = blockIdx.x;
-    const double nan = __longlong_as_double(0x7FF8000000000000ll);
-    long long r0, r1;
-    if (!set_range(set_of, i, set_off, n_sets, n_refs, max_set, r0, r1)) {   // -1 / NaN, nothing else touched
-        if (lane < 4) stats[i * 4 + lane] = -1;
-        if (scores && lane == 0) scores[i] = nan;
-        return;
-    }
-    const size_t words = ref_rec_words(ref_L);
-    uint64_t nkey = 0, nlen = 0, nbad = 0;                         // the record in flight
-    auto request = [&](long long r) {
-        const uint64_t* rv = ref_recs + (size_t)r * words;
-        nlen = rv[0];
-        nbad = rv[1];
-        nkey = lane < ref_L ? rv[8 + 4 * lane] : 0;
-    };
-    if (r0 < r1) request(r0);
+    RefWalk<KeyOrder1> W;
+    if (!W.open(i, set_of, ref_recs, ref_L, n_refs, set_off, n_sets, max_set, pairs, pair_ld)) return refuse_row(i, stats, 4, scores, 1);
     WaveSent S;
     wave_read(hyp, ld, lens, i, L, 1, S);
     const unsigned f = (unsigned)S.key[0];                         // this position's field, 0 at and beyond the length
-    bool bad = S.bad;
     int lcs_p = 0, lcs_r = 0, len_r = 0;
-    for (long long r = r0; r < r1; ++r) {
-        const unsigned g = (unsigned)nkey;
-        const int rlen = (int)nlen < ref_L ? ((int)nlen < 0 ? 0 : (int)nlen) : ref_L;
-        bad = bad || nbad != 0;
-        if (r + 1 < r1) request(r + 1);
+    W.each(S.bad, [&](long long k, int rlen, const KeyOrder1& key) {
+        const unsigned g = (unsigned)key.w;
         unsigned long long V = ~0ull;                              // wave-uniform: the compiler keeps it in scalar registers
         for (int j = 0; j < S.len; ++j) {
             const unsigned fj = (unsigned)__builtin_amdgcn_readlane((int)f, j);
@@ -81,10 +65,10 @@ __global__ __launch_bounds__(64) void rg_score_k(const int64_t* hyp, long long l
             lcs_r = lcs;
             len_r = rlen;
         }
-        if (pairs && lane == 0) pairs[i * pair_ld + (r - r0)] = bad ? nan : rg_score(lcs, S.len, lcs, rlen, beta2);
-    }
-    if (lane < 4) stats[i * 4 + lane] = bad ? -1 : lane == 0 ? lcs_p : lane == 1 ? S.len : lane == 2 ? lcs_r : len_r;
-    if (scores && lane == 0) scores[i] = bad ? nan : rg_score(lcs_p, S.len, lcs_r, len_r, beta2);
+        W.put_pair(k, [&] { return rg_score(lcs, S.len, lcs, rlen, beta2); });
+    });
+    if (lane < 4) stats[i * 4 + lane] = W.bad ? -1 : lane == 0 ? lcs_p : lane == 1 ? S.len : lane == 2 ? lcs_r : len_r;
+    if (scores && lane == 0) scores[i] = W.bad ? quiet_nan() : rg_score(lcs_p, S.len, lcs_r, len_r, beta2);
 }
 
 }  // namespace
@@ -94,15 +78,9 @@ extern "C" {
 int set_rouge_device_score(const int64_t* hyp, int64_t hyp_ld, const int32_t* hyp_lens, int n_hyp, int L, const int32_t* set_of_hyp,
                            const void* ref_recs, int ref_L, int64_t n_refs, const int64_t* ref_set_off, int n_sets, int max_set,
                            double beta, int32_t* stats, double* scores, double* pair_scores, int64_t pair_ld, void* stream) {
-    if ((n_hyp > 0 && !stats) || !std::isfinite(beta) || !(beta > 0.0)) return SET_ERR_ARG;
-    SET_TRY(score_args_check(hyp, hyp_ld, n_hyp, L, set_of_hyp, ref_recs, ref_L, n_refs, ref_set_off, n_sets, max_set, pair_scores, pair_ld));
-    if (n_hyp == 0) return SET_OK;
-    set::ProfScope prof("rouge_score", static_cast<hipStream_t>(stream));
-    hipLaunchKernelGGL(rg_score_k, dim3((unsigned)n_hyp), dim3(64), 0, static_cast<hipStream_t>(stream), hyp, (long long)hyp_ld,
-                       hyp_lens, L, set_of_hyp, static_cast<const uint64_t*>(ref_recs), ref_L, (long long)n_refs, ref_set_off,
-                       n_sets, max_set, beta * beta, stats, scores, pair_scores, (long long)pair_ld);
-    SET_LAUNCH_CHECK();
-    return SET_OK;
+    return score_launch<double>("rouge_score", rg_score_k, std::isfinite(beta) && beta > 0.0, hyp, hyp_ld, hyp_lens, n_hyp, L, set_of_hyp,
+                                ref_recs, ref_L, n_refs, ref_set_off, n_sets, max_set, stats, scores, pair_scores, pair_ld, stream,
+                                beta * beta);
 }
 
 }  // extern "C"

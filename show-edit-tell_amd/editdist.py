@@ -29,8 +29,9 @@ from __future__ import annotations
 
 import numpy as np
 
-from .device_metric import DeviceSentenceScorer, PreparedRefs, cut_after_zero, resolve_device
-from .rouge import DeviceRougeL
+from .device_metric import (DeviceSentenceScorer, HostSentenceScorer, PreparedRefs, RecordScorer, cut_after_zero, id_rows,
+                            resolve_device)
+from .rouge import DeviceRougeL      # noqa: F401  (names this module has always exposed)
 
 STATS_COLUMNS = 4                  # dist, len_h, len_r, ref
 ALIGN_COLUMNS = 8                  # dist, len_h, len_s, keep, sub, ins, del, unchanged
@@ -90,21 +91,11 @@ def alignment(src, hyp):
     return hyp_ops, hyp_src, src_ops, (keep, sub, ins, dele)
 
 
-def _rows(x, lens, what):
-    """(N, L) ids [+ (N,) lengths] -> the N sentences as lists: lens=None the 0 rule, else exactly that long (clamped)"""
-    x = np.asarray(x.cpu() if hasattr(x, 'cpu') else x, dtype=np.int64)
-    if x.ndim != 2:
-        raise ValueError("sentences are rows of a 2-D id array, got shape %s" % (x.shape,))
-    N, L = x.shape
-    if lens is not None:
-        lens = np.asarray(lens.cpu() if hasattr(lens, 'cpu') else lens).reshape(-1)
-        if lens.shape[0] != N:
-            raise ValueError("%s has %d entries for %d sentences" % (what, lens.shape[0], N))
-    return [cut_after_zero(x[i].tolist()) if lens is None else x[i].tolist()[:min(max(int(lens[i]), 0), L)] for i in range(N)]
-
-
-class EditDistance:
-    """The host scorer.  Pure Python: the readable statement that the device route is tested against."""
+class EditDistance(HostSentenceScorer):
+    """The host scorer.  Pure Python: the readable statement that the device route is tested against.  score_token_ids
+    (device_metric.HostSentenceScorer) returns (stats int64 (N, 4), scores (N,))."""
+    STATS_COLUMNS = STATS_COLUMNS
+    LENS_CHECKED_FIRST = True
 
     @staticmethod
     def sentence_stats(hyp, refs):
@@ -125,29 +116,7 @@ class EditDistance:
         """the sentence score from its four integers, a Python float"""
         return similarity(stats[0], stats[1], stats[2])
 
-    def _score_lists(self, pairs):
-        """pairs: iterable of (hypothesis token list, list of reference token lists) -> (stats (N, 4) int64, scores (N,))"""
-        pairs = list(pairs)
-        stats = np.zeros((len(pairs), STATS_COLUMNS), dtype=np.int64)
-        scores = np.zeros(len(pairs), dtype=np.float64)
-        for i, (h, refs) in enumerate(pairs):
-            if not len(refs):
-                raise ValueError("hypothesis %d has no reference" % i)
-            stats[i] = self.sentence_stats(h, refs)
-            scores[i] = self.score_from_stats(stats[i])
-        return stats, scores
-
-    def score_token_ids(self, hyps, hyp_set, ref_sets, hyp_lens=None):
-        """`hyps` (N, L) ids, `hyp_set` (N,) index of each row's reference set, `ref_sets` = list of reference sets, each a
-        list of id lists (as ciderd.ground_truth_lists returns them; cut after their first 0).  hyp_lens=None: a row is cut
-        after its first 0 and the 0 stays (no 0: the whole row); else (N,) lengths, clamped to [0, L].
-        Returns (stats int64 (N, 4), scores float64 (N,))."""
-        rows = _rows(hyps, hyp_lens, "hyp_lens")
-        hyp_set = np.asarray(hyp_set.cpu() if hasattr(hyp_set, 'cpu') else hyp_set).reshape(-1)
-        if hyp_set.shape[0] != len(rows):
-            raise ValueError("hyp_set has %d entries for %d sentences" % (hyp_set.shape[0], len(rows)))
-        refs = [[cut_after_zero(c) for c in rs] for rs in ref_sets]
-        return self._score_lists((row, refs[int(s)]) for row, s in zip(rows, hyp_set))
+    _sentence_score = score_from_stats
 
     def corpus_score(self, hyps, hyp_set, ref_sets, hyp_lens=None):
         """{'similarity': the mean of the rows' scores, 'wer': sum dist / sum len_r of the chosen references} (no row, or no
@@ -161,7 +130,7 @@ class EditDistance:
         """Row i of `hyps` (N, L) against row i of `srcs` (N, Ls), lengths as in score_token_ids -> (stats int64 (N, 8) = dist,
         len_h, len_s, keep, sub, ins, del, unchanged; hyp_ops int8 (N, L); hyp_src int32 (N, L), -1 where there is none;
         src_ops int8 (N, Ls)); positions at and beyond a sentence's length hold op 0 and source -1."""
-        H, S = _rows(hyps, hyp_lens, "hyp_lens"), _rows(srcs, src_lens, "src_lens")
+        H, S = id_rows(hyps, hyp_lens, "hyp_lens"), id_rows(srcs, src_lens, "src_lens")
         if len(H) != len(S):
             raise ValueError("%d hypotheses for %d sources" % (len(H), len(S)))
         N, L, Ls = len(H), np.shape(hyps)[1], np.shape(srcs)[1]
@@ -177,46 +146,14 @@ class EditDistance:
 
 
 # ---- the device route (csrc/editdist_device.hip, include/set_hip.h set_edit_device_score / set_edit_device_align) ------------
-class DeviceEditDistance(DeviceSentenceScorer):
+class DeviceEditDistance(RecordScorer):
     """Word edit distance on one device: every call is enqueued on the current stream of that device and reads nothing back.
-    Stateless on the native side.  Its prepared references are bleu.DeviceBleu's (the same native call, the same records):
-    either scorer's PreparedRefs serves the other, and rouge.DeviceRougeL's too."""
+    Stateless on the native side.  prepare_refs, score_token_ids (stats int32 (N, 4), scores float64 (N,)) and pair_scores are
+    device_metric.RecordScorer's: the records are BLEU's."""
     METRIC = "edit distance"
-
-    def __init__(self, dev):
-        from . import _lib
-        super().__init__(dev)
-        for name in ("set_bleu_device_prepare", "set_edit_device_score", "set_edit_device_align"):
-            if name in _lib.MISSING:
-                raise _lib.SetError("the native library does not export %s" % name)
-
-    _prepare = DeviceRougeL._prepare                               # BLEU's records through BLEU's native call
-    prepare_refs = DeviceRougeL.prepare_refs
-
-    def score_token_ids(self, hyps, hyp_set, refs, hyp_lens=None, return_pairs=False):
-        """Device twin of EditDistance.score_token_ids: `hyps` (N, L) ids, `hyp_set` (N,) index of each row's reference set,
-        `refs` a PreparedRefs (or reference sets, prepared here), hyp_lens as on the host.  Returns device tensors (stats int32
-        (N, 4), scores float64 (N,)); return_pairs=True: also (N, max set size) float64 with the similarity to every single
-        reference of the set (columns beyond a smaller set stay 0)."""
-        import torch
-        from . import _lib
-        if not isinstance(refs, PreparedRefs):
-            refs = self.prepare_refs(refs)
-        t = self._tokens(hyps)
-        N, L = t.shape
-        so = self._i32(hyp_set, N, "hyp_set")
-        ln = self._i32(hyp_lens, N, "hyp_lens")
-        stats = torch.empty(N, STATS_COLUMNS, dtype=torch.int32, device=self.dev)
-        scores = torch.empty(N, dtype=torch.float64, device=self.dev)
-        pair_ld = max(1, refs.max_set)
-        pairs = torch.zeros(N, pair_ld, dtype=torch.float64, device=self.dev) if return_pairs else None
-        with torch.cuda.device(self.dev):
-            rc = self._lib.set_edit_device_score(
-                t.data_ptr(), t.stride(0), None if ln is None else ln.data_ptr(), N, L, so.data_ptr(), refs.recs.data_ptr(),
-                refs.L, refs.n_refs, refs.set_off.data_ptr(), refs.n_sets, refs.max_set, stats.data_ptr(), scores.data_ptr(),
-                None if pairs is None else pairs.data_ptr(), pair_ld, _lib.stream_of(self.dev))
-        _lib.check(rc, "set_edit_device_score")
-        return (stats, scores, pairs) if return_pairs else (stats, scores)
+    NATIVE = ("set_bleu_device_prepare", "set_edit_device_score", "set_edit_device_align")
+    SCORE_ENTRY = "set_edit_device_score"
+    STATS_COLUMNS = STATS_COLUMNS
 
     def corpus_score(self, hyps, hyp_set, refs, hyp_lens=None):
         """{'similarity', 'wer'} of the corpus as 0-d float64 device tensors, reduced on the device (no row, or no reference
@@ -229,15 +166,6 @@ class DeviceEditDistance(DeviceSentenceScorer):
         wer = torch.where(words > 0, dist / torch.where(words > 0, words, torch.ones_like(words)), torch.zeros_like(words))
         wer = torch.where((stats[:, 1] < 0).any(), torch.full_like(wer, float("nan")), wer)
         return {"similarity": scores.mean(), "wer": wer}
-
-    def pair_scores(self, candidates, n_per_image):
-        """(NI * n, L) candidates, n per image -> (NI * n, n): the similarity of row i to candidate r of its own image as the
-        only reference (what evaluate.consensus_rerank reads).  Rows are cut after their first 0; the candidates are prepared
-        once on the device and serve as references."""
-        t = self._tokens(candidates)
-        refs, owner = self._self_refs(t, n_per_image)
-        refs.recs = self._prepare(t, None)
-        return self.score_token_ids(t, owner, refs, return_pairs=True)[2]
 
     def align_token_ids(self, hyps, srcs, hyp_lens=None, src_lens=None):
         """Device twin of EditDistance.align_token_ids: row i of `hyps` (N, L) against row i of `srcs` (N, Ls).  Returns device
@@ -264,12 +192,6 @@ class DeviceEditDistance(DeviceSentenceScorer):
         return stats, hyp_ops, hyp_src, src_ops
 
 
-_device_scorers = {}
-
-
 def device_scorer(dev):
     """the DeviceEditDistance of `dev`, made at the first call"""
-    dev = resolve_device(dev)
-    if dev not in _device_scorers:
-        _device_scorers[dev] = DeviceEditDistance(dev)
-    return _device_scorers[dev]
+    return DeviceEditDistance.of_device(dev)

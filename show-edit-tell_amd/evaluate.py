@@ -1218,6 +1218,12 @@ def _validation_rows(captions, hyp_set, dev, count_end, word_map):
     return captions, hyp_set, lens
 
 
+def _validation_corpus(scorer, captions, hyp_set, ground_truth, count_end, word_map):
+    """corpus_score of a record-based device scorer over captions in either input form, the references prepared here"""
+    captions, hyp_set, lens = _validation_rows(captions, hyp_set, scorer.dev, count_end, word_map)
+    return scorer.corpus_score(captions, hyp_set, scorer.prepare_refs(ground_truth, count_end=count_end), lens)
+
+
 def validation_bleu(captions, hyp_set, ground_truth, dev, count_end=False, word_map=None):
     """Corpus Bleu_1..4 of decoded captions without strings:
         gt = ciderd.ground_truth_lists(allcaps, word_map)
@@ -1233,9 +1239,7 @@ def validation_bleu(captions, hyp_set, ground_truth, dev, count_end=False, word_
     SCST convention, the 0 is a token on both sides.  The statistics are summed and scored on the device (bleu.DeviceBleu,
     csrc/bleu_device.hip) and nothing is read back.  Returns a (4,) float64 device tensor."""
     from . import bleu
-    scorer = bleu.device_scorer(dev)
-    captions, hyp_set, lens = _validation_rows(captions, hyp_set, scorer.dev, count_end, word_map)
-    return scorer.corpus_score(captions, hyp_set, scorer.prepare_refs(ground_truth, count_end=count_end), lens)
+    return _validation_corpus(bleu.device_scorer(dev), captions, hyp_set, ground_truth, count_end, word_map)
 
 
 def validation_rouge_l(captions, hyp_set, ground_truth, dev, count_end=False, word_map=None):
@@ -1243,9 +1247,7 @@ def validation_rouge_l(captions, hyp_set, ground_truth, dev, count_end=False, wo
     device (rouge.DeviceRougeL, csrc/rouge_device.hip), nothing read back.  Input forms and conventions are validation_bleu's.
     Returns a 0-d float64 device tensor."""
     from . import rouge
-    scorer = rouge.device_scorer(dev)
-    captions, hyp_set, lens = _validation_rows(captions, hyp_set, scorer.dev, count_end, word_map)
-    return scorer.corpus_score(captions, hyp_set, scorer.prepare_refs(ground_truth, count_end=count_end), lens)
+    return _validation_corpus(rouge.device_scorer(dev), captions, hyp_set, ground_truth, count_end, word_map)
 
 
 def validation_cider(captions, hyp_set, ground_truth, dev, count_end=False, word_map=None):
@@ -1289,9 +1291,7 @@ def validation_edit(captions, hyp_set, ground_truth, dev, count_end=False, word_
     device (editdist.DeviceEditDistance, csrc/editdist_device.hip), nothing read back.  Input forms and conventions are
     validation_bleu's.  Returns 0-d float64 device tensors."""
     from . import editdist
-    scorer = editdist.device_scorer(dev)
-    captions, hyp_set, lens = _validation_rows(captions, hyp_set, scorer.dev, count_end, word_map)
-    return scorer.corpus_score(captions, hyp_set, scorer.prepare_refs(ground_truth, count_end=count_end), lens)
+    return _validation_corpus(editdist.device_scorer(dev), captions, hyp_set, ground_truth, count_end, word_map)
 
 
 def source_rows(previous_caption, prev_caplen, word_map, count_end=False):

@@ -1,14 +1,16 @@
-"""Raw bytes of the device metrics' records and scores (csrc/ciderd_device.hip, csrc/bleu_device.hip), for comparing two builds
-of the library (a refactor against its parent).
+"""Raw bytes of the device metrics' records and scores (csrc/ciderd_device.hip, csrc/bleu_device.hip, csrc/rouge_device.hip,
+csrc/editdist_device.hip), for comparing two builds of the library (a refactor against its parent).
 
     python tools/metric_bits.py --out new.npz                                     (on the GPU, once per build)
     python tools/metric_bits.py --compare parent.npz new.npz [--json verdict.json]
 
-Only the public C ABI is used (include/set_hip.h set_ciderd_device_* and set_bleu_device_*, through _lib's prototypes), so the
-file runs unchanged in a checkout of an older commit.  Dumped, each under both length conventions (rows cut after their first
+Only the public C ABI is used (include/set_hip.h set_ciderd_device_*, set_bleu_device_*, set_rouge_device_score and
+set_edit_device_*, through _lib's prototypes), so the file runs unchanged in a checkout of an older commit.  Dumped, each under both length conventions (rows cut after their first
 0; explicit lengths, among them a negative one and one beyond L):
   set_ciderd_device_vectorise records and set_ciderd_device_score scores and pairs for n = 1, 2, 4;
-  set_bleu_device_prepare records and set_bleu_device_score statistics, scores and pairs.
+  set_bleu_device_prepare records and set_bleu_device_score statistics, scores and pairs;
+  set_rouge_device_score (beta 1.2) and set_edit_device_score statistics, scores and pairs from those records;
+  set_edit_device_align statistics, hyp_ops, hyp_src and src_ops of the hypotheses against the reference rows as sources.
 Inputs, on fixed seeds: 72 reference rows and 72 hypotheses (near-copies of references) with lengths 0, 1, 2, 3, 4, 5, 63, 64
 rotating, ids 1..6 so that counts repeat, a few ids up to 65533, one of 65534 (a row the packing refuses) and one row with three such ids in a row, a 0 and junk
 behind every row's length, a leading dimension of 70 for L = 64; reference sets of 0 (CIDEr-D only), 1 and 5 references; one
@@ -29,6 +31,7 @@ if ROOT not in sys.path:
 
 L, LD, ROWS, MAX_SET, PAIR_LD = 64, 70, 72, 5, 6
 LENGTHS = (0, 1, 2, 3, 4, 5, 63, 64)
+BETA = 1.2
 SENTINEL = -0x0123456789ABCDEF
 DEV = "cuda:0"
 
@@ -138,11 +141,35 @@ def run(out):
                                              scores.data_ptr(), pairs.data_ptr(), PAIR_LD, st()), "set_bleu_device_score")
         torch.cuda.synchronize()
         res[tag + "records"], res[tag + "stats"], res[tag + "scores"], res[tag + "pairs"] = raw(recs), raw(stats), raw(scores), raw(pairs)
+        for name, extra in (("rouge", (BETA,)), ("edit", ())):       # the two other readers of BLEU's records
+            entry = "set_%s_device_score" % name
+            stats = buf(ROWS * 2, torch.int32)                       # 4 int32 per row
+            scores, pairs = buf(ROWS, torch.float64), buf(ROWS * PAIR_LD, torch.float64)
+            _lib.check(getattr(lib, entry)(hyps.data_ptr(), LD, ptr(hl), ROWS, L, so.data_ptr(), recs.data_ptr(), L, int(x["off_bl"][-1]),
+                                           off.data_ptr(), len(x["off_bl"]) - 1, MAX_SET, *extra, stats.data_ptr(), scores.data_ptr(),
+                                           pairs.data_ptr(), PAIR_LD, st()), entry)
+            torch.cuda.synchronize()
+            res["%s/%s/stats" % (name, conv)], res["%s/%s/scores" % (name, conv)], res["%s/%s/pairs" % (name, conv)] = raw(stats), raw(scores), raw(pairs)
+        # the hypotheses against the reference rows as sources: 8 int32 of statistics, L int8 + L int32 + L int8 per row
+        stats, hyp_ops, hyp_src, src_ops = buf(ROWS * 4, torch.int32), buf(ROWS * L // 8, torch.int8), buf(ROWS * L // 2, torch.int32), buf(ROWS * L // 8, torch.int8)
+        _lib.check(lib.set_edit_device_align(hyps.data_ptr(), LD, ptr(hl), ROWS, L, refs.data_ptr(), LD, ptr(rl), L, stats.data_ptr(),
+                                             hyp_ops.data_ptr(), L, hyp_src.data_ptr(), src_ops.data_ptr(), L, st()), "set_edit_device_align")
+        torch.cuda.synchronize()
+        tag = "edit_align/%s/" % conv
+        res[tag + "stats"], res[tag + "hyp_ops"], res[tag + "hyp_src"], res[tag + "src_ops"] = raw(stats), raw(hyp_ops), raw(hyp_src), raw(src_ops)
     # the inputs do what they are there for: finite and refused rows, counts above 1, both set sizes
     s = res["ciderd/n4/zero_rule/scores"].view(np.float64)
     b = res["bleu/zero_rule/stats"].view(np.int32).reshape(ROWS, 10)
     assert np.isnan(s).sum() >= 3 and (s[~np.isnan(s)] > 0).sum() > 10, s
     assert (b[:, 0] == -1).sum() >= 3 and (b[:, 1] > 0).sum() > 20 and (b[:, 3] > 0).sum() > 5 and b[:, 8].max() == 64, b
+    # ROUGE-L and edit distance: refused rows, common subsequences, distance 0 and above, a chosen reference that is not the first of 5
+    r = res["rouge/zero_rule/stats"].view(np.int32).reshape(ROWS, 4)
+    e = res["edit/zero_rule/stats"].view(np.int32).reshape(ROWS, 4)
+    a = res["edit_align/zero_rule/stats"].view(np.int32).reshape(ROWS, 8)
+    five = np.diff(x["off_bl"])[np.clip(x["set_bl"], 0, len(x["off_bl"]) - 2)] == 5
+    assert (r[:, 0] == -1).sum() >= 3 and (r[:, 0] > 0).sum() > 20 and (r[:, 3] > 0).sum() > 20, r
+    assert (e[:, 0] == -1).sum() >= 3 and (e[:, 0] == 0).sum() >= 1 and (e[:, 0] > 0).sum() > 20 and (e[five, 3] > 0).sum() >= 3, e
+    assert (a[:, 0] == -1).sum() >= 2 and (a[:, 0] > 0).sum() > 20 and (a[:, 4] > 0).sum() > 5 and (a[:, 5] + a[:, 6] > 0).sum() > 5, a
     np.savez_compressed(out, **res)
     print("metric_bits: %d arrays -> %s" % (len(res), out))
 
