@@ -361,7 +361,9 @@ int set_editnet_edit_trace(const SetEditNetWeights* w, const SetEditNetDims* d, 
  * "image_mean" (B,F) "h1" "c1" "h2" "c2" "emb" "ctx_cap" "attend_cap" "sel" (B,D) "attend_img" (B,F)
  * "alpha_c" (B,T) "alpha" (B,R) "logits" (B,V) "it" (B) int64 "unfinished" (B) int32
  * "cap_proj" (B,T,2D) = [context_gate.W[:,2D:3D] H | sc_affine.W H] and "mem_proj" (B,T,D) = gate_cmem.W M: the
- * per-sequence hoisted projections the step reads instead of contracting the attention context / selected row */
+ * per-sequence hoisted projections the step reads instead of contracting the attention context / selected row;
+ * "fe" (B,R,D) = relu(att_embed(X)); "pd_pv" (B,R,4D) = X copy_lstm.x2h.W[:,2D:]^T of the persistent small-batch decode
+ * (NULL for batches beyond its row limit, which carve no such buffer; written only where that decode takes the dims) */
 void* set_editnet_ws_tensor(const SetEditNetDims* d, void* ws, const char* name);
 
 /* ------------------------------------------------------------------------------------------
@@ -523,7 +525,10 @@ int set_dcnet_xe_forward_hidden(const SetDcnetWeights* w, const SetDcnetDims* d,
                                 const int64_t* prevlen, float* predictions, float* last_hidden, void* ws,
                                 size_t ws_bytes, void* stream);
 /* names: "enc" (B,T,2C) "final_hidden" (B,2C) "mask" (B,T) "att1_c" (B,T,A) "h1" "c1" "h2" "c2"
- * "emb" "attend_cap" (B,2C) "alpha_c" (B,T) "logits" (B,V) "it" "unfinished" */
+ * "emb" "attend_cap" (B,2C) "alpha_c" (B,T) "logits" (B,V) "it" "unfinished"
+ * "enc_bar" the barrier words of the persistent encoder and, behind them, its status word (as EditNet's)
+ * "pd_pc" (B,T,4D) = enc language_lstm.W_ih[:,D:]^T of the persistent small-batch decode (NULL for batches beyond its row
+ * limit, which carve no such buffer; written only where that decode takes the dims) */
 void* set_dcnet_ws_tensor(const SetDcnetDims* d, void* ws, const char* name);
 
 /* ------------------------------------------------------------------------------------------

@@ -624,7 +624,9 @@ void* set_dcnet_ws_tensor(const SetDcnetDims* d, void* ws, const char* name) {
     struct { const char* n; void* p; } tab[] = {
         {"enc", W.enc}, {"final_hidden", W.final_hidden}, {"mask", W.mask}, {"att1_c", W.att1_c}, {"pre1", W.pre1},
         {"h1", W.h1}, {"c1", W.c1}, {"h2", W.h2}, {"c2", W.c2}, {"emb", W.emb}, {"attend_cap", W.attend_cap},
-        {"alpha_c", W.alpha_c}, {"logits", W.logits}, {"it", W.it}, {"unfinished", W.unfinished}, {"alive", W.alive}};
+        {"alpha_c", W.alpha_c}, {"logits", W.logits}, {"it", W.it}, {"unfinished", W.unfinished}, {"alive", W.alive},
+        {"enc_bar", W.enc_bar},
+        {"pd_pc", d->B <= PDEC_MAXB ? (void*)W.pd_pc : nullptr}};         // (carved for small batches only)
     for (auto& e : tab)
         if (!strcmp(e.n, name)) return e.p;
     return nullptr;

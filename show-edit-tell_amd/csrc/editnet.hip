@@ -913,7 +913,8 @@ void* set_editnet_ws_tensor(const SetEditNetDims* d, void* ws, const char* name)
         {"alpha_c", W.alpha_c}, {"alpha", W.alpha}, {"logits", W.logits}, {"it", W.it},
         {"cap_proj", W.cap_proj}, {"mem_proj", W.mem_proj}, {"enc_bar", W.enc_bar},
         {"pro_rows", W.pro_rows}, {"pro_count", W.pro_count},
-        {"unfinished", W.unfinished}, {"alive", W.alive}};
+        {"unfinished", W.unfinished}, {"alive", W.alive}, {"fe", W.fe},
+        {"pd_pv", d->B <= PDW_MAXB ? (void*)W.pd_pv : nullptr}};          // (carved for small batches only)
     for (auto& e : tab)
         if (!strcmp(e.n, name)) return e.p;
     return nullptr;

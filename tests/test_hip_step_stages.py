@@ -18,7 +18,7 @@ STEP_STAGES_ERRORS_OUT=<path> additionally writes, per model, grid id and stage,
 bound, next to the same figure for the float32 numpy oracle's stage on the same inputs (profiles/step_stages_errors.json).
 """
 import ctypes as C
-import json
+import functools
 import os
 
 import numpy as np
@@ -31,6 +31,7 @@ import step_stage_oracle as SO
 from hip_adapter import load_numpy_state, to_dev
 from oracle import cases, dcnet_np as DN, editnet_np as EN
 from show_edit_tell_amd import _lib, synth
+from stage_judge import judge, write_report
 
 pytestmark = pytest.mark.gpu
 
@@ -44,31 +45,12 @@ def _error_report():
     path = os.environ.get("STEP_STAGES_ERRORS_OUT")
     if not path or not RATIOS:
         return
-    lines = ['"unit": "[hip, float32 numpy oracle]: largest |stage output - float64 stage| / (tol * min(max|ref|, 1)) over all '
-             'timesteps, runs and token-table settings of a grid id; tol = parity.STATE_TOL, parity.LOGIT_TOL for fc.logits"']
-    for (model, gid), stages in sorted(RATIOS.items()):
-        lines.append(json.dumps("%s/%s" % (model, gid)) + ": "
-                     + json.dumps({k: [round(v[0], 4), round(v[1], 4)] for k, v in stages.items()}))
-    with open(path, "w") as f:
-        f.write("{\n " + ",\n ".join(lines) + "\n}\n")
+    write_report(path, "[hip, float32 numpy oracle]: largest |stage output - float64 stage| / (tol * min(max|ref|, 1)) over all "
+                 "timesteps, runs and token-table settings of a grid id; tol = parity.STATE_TOL, parity.LOGIT_TOL for fc.logits",
+                 RATIOS)
 
 
-def _judge(key, stage, got, ref, tol, what, f32=None):
-    """got (device) against ref (float64 stage): relative to max|ref| and absolute; records the ratios first"""
-    got, ref = np.asarray(got), np.asarray(ref)
-    assert got.shape == ref.shape and got.dtype == np.float32, (what, got.shape, ref.shape, got.dtype)
-    assert np.isfinite(got).all(), what
-    scale = float(np.abs(ref).max())
-    assert scale > 0, what + ": the float64 stage is identically zero, nothing would be compared"
-    bound = tol * min(scale, 1.0)
-    err = parity.maxerr(got, ref)
-    rec = RATIOS.setdefault(key, {}).setdefault(stage, [0.0, 0.0])
-    rec[0] = max(rec[0], err / bound)
-    if f32 is not None:
-        rec[1] = max(rec[1], parity.maxerr(f32, ref) / bound)
-    print("%-46s err %.3e  max|ref| %.3e  ratio %.3f" % (what, err, scale, err / bound))
-    assert err <= tol * scale, "%s: max abs err %.3e > %.1e * max|ref| %.3e" % (what, err, tol, scale)
-    parity.assert_close(got, ref, tol, what)
+_judge = functools.partial(judge, RATIOS)          # (key, stage, got, ref, tol, what, f32=None): tests/stage_judge.py
 
 
 def _bits(a):
