@@ -144,10 +144,18 @@ int set_editnet_build_token_table(const SetEditNetWeights* w, const SetEditNetDi
  * timestep: features_att(att_embed(X)) (:441-442), cap_features_att(H) (:370) and the
  * final_hidden / image_mean columns of the attention_lstm input product (:527-532).
  * `image_mean` may be NULL (computed here) or a (B,F) tensor (adaptive variant, editnet_adaptive.py:501).
- * `prev` (B,T) int64, `prevlen` (B) int64, `X` (B,R,F).  Leaves the recurrent state zeroed. */
+ * `prev` (B,T) int64, `prevlen` (B) int64, `X` (B,R,F).  Leaves the recurrent state zeroed.
+ * Always the fp32 kernels.  Pairs with set_editnet_step and every consumer but set_editnet_greedy_begun. */
 int set_editnet_begin(const SetEditNetWeights* w, const SetEditNetDims* d, const float* X,
                       const float* image_mean, const int64_t* prev, const int64_t* prevlen,
                       void* ws, size_t ws_bytes, void* stream);
+
+/* The same prologue as set_editnet_greedy runs it for these dims: from 65 rows on (fixed features) its grouped GEMM launches
+ * run on the split-precision kernel (see set_editnet_greedy), below that and with adaptive features it is set_editnet_begin
+ * bit for bit.  Pairs with set_editnet_greedy_begun, whose result on such a workspace has the bits of set_editnet_greedy. */
+int set_editnet_begin_greedy(const SetEditNetWeights* w, const SetEditNetDims* d, const float* X,
+                             const float* image_mean, const int64_t* prev, const int64_t* prevlen,
+                             void* ws, size_t ws_bytes, void* stream);
 
 /* One decode timestep for rows [0,bt): embed -> attention_lstm -> caption_attention ->
  * visual_attention -> select -> copy_lstm -> fc  (editnet.py:513-546, editnet_rl.py:505-513),
@@ -170,11 +178,13 @@ int set_editnet_greedy_pick(const SetEditNetWeights* w, const SetEditNetDims* d,
 /* Whole free-running greedy decode (editnet_rl.py:485-549 with sample_max=True): prologue +
  * (max_len+1) timesteps, no host synchronisation (the reference syncs every step at :546).
  * Outputs seq (B,max_len) int64 and seq_logp (B,max_len) fp32 (overwritten).
- * Numerics: from 65 rows on (fixed features) the grouped GEMM launches of the timestep loop of this call and of
- * set_editnet_greedy_begun (not the prologue, which is set_editnet_begin's bit for bit) run on the split-precision kernel (fp32 operands as three exact bf16 planes, fp32 accumulation; see set_gemm_nt_group_f32,
- * set_gemm_nt_greedy_scope): logits agree with the fp32 kernels' to the 1e-4 target, not bit for bit; the same inputs give the
- * same bits every time.  SET_GEMM_SPLIT=0 in the environment keeps the fp32 kernels.  Below 65 rows, with adaptive features, and
- * in every other entry point of this header nothing changes. */
+ * Numerics: from 65 rows on (fixed features) the grouped GEMM launches of this call's prologue (the caption projections with
+ * their row list, att_embed, features_att, the attention LSTM's constant columns; not the caption encoder) and of its timestep
+ * loop, of set_editnet_begin_greedy and of set_editnet_greedy_begun run on the split-precision kernel (fp32 operands as three
+ * exact bf16 planes, fp32 accumulation; see set_gemm_nt_group_f32, set_gemm_nt_greedy_scope): logits agree with the fp32
+ * kernels' to the 1e-4 target, not bit for bit; the same inputs give the same bits every time.  SET_GEMM_SPLIT=0 in the
+ * environment keeps the fp32 kernels everywhere; SET_PRO_SPLIT=0 keeps them for the prologue alone.  Below 65 rows, with
+ * adaptive features, and in every other entry point of this header (set_editnet_begin among them) nothing changes. */
 int set_editnet_greedy(const SetEditNetWeights* w, const SetEditNetDims* d, const float* X,
                        const float* image_mean, const int64_t* prev, const int64_t* prevlen,
                        int64_t start_idx, int64_t end_idx, int max_len, int64_t* seq,
@@ -191,11 +201,12 @@ int set_editnet_greedy(const SetEditNetWeights* w, const SetEditNetDims* d, cons
 int set_decode_row_limits(const int* row_limit_dev);
 
 /* The timestep loop of set_editnet_greedy alone (editnet_rl.py:503-547) on a workspace that already holds a completed
- * set_editnet_begin for the same (X, prev, prevlen): the per-sequence prologue (editnet_rl.py:499-501 and the hoisted
+ * set_editnet_begin_greedy for the same (X, prev, prevlen): the per-sequence prologue (editnet_rl.py:499-501 and the hoisted
  * projections) of batch i+1 depends on nothing in the decode of batch i, so a caller that issues one decode after the
- * other can run set_editnet_begin for the NEXT batch on a second stream / workspace while this loop runs
+ * other can run set_editnet_begin_greedy for the NEXT batch on a second stream / workspace while this loop runs
  * (pipeline.DevicePrefetcher(begin_ahead=...) does).  The caller orders `stream` after the stream that ran the prologue.
- * Results are bit-identical to set_editnet_greedy. */
+ * Results are bit-identical to set_editnet_greedy.  (On a set_editnet_begin workspace the loop runs as well; from 65 rows on
+ * its result then is that of SET_PRO_SPLIT=0: within the 1e-4 target of set_editnet_greedy, not its bits.) */
 int set_editnet_greedy_begun(const SetEditNetWeights* w, const SetEditNetDims* d, const float* X, int64_t start_idx,
                              int64_t end_idx, int max_len, int64_t* seq, float* seq_logp, void* ws,
                              size_t ws_bytes, void* stream);

@@ -325,6 +325,7 @@ PROTOTYPES = {
     "set_editnet_token_table_workspace_bytes": (_Z, [C.POINTER(EditNetDims)]),
     "set_editnet_build_token_table": (_I, [C.POINTER(EditNetWeights), C.POINTER(EditNetDims), _P, _P, _Z, _P]),
     "set_editnet_begin": (_I, [C.POINTER(EditNetWeights), C.POINTER(EditNetDims), _P, _P, _P, _P, _P, _Z, _P]),
+    "set_editnet_begin_greedy": (_I, [C.POINTER(EditNetWeights), C.POINTER(EditNetDims), _P, _P, _P, _P, _P, _Z, _P]),
     "set_editnet_step": (_I, [C.POINTER(EditNetWeights), C.POINTER(EditNetDims), _P, _P, _L, _I, _P, _L, _P, _Z, _P]),
     "set_editnet_greedy_pick": (_I, [C.POINTER(EditNetWeights), C.POINTER(EditNetDims), _P, _L, _I, _L, _P, _P, _I,
                                      _P, _Z, _P]),

@@ -298,10 +298,13 @@ static int begin_impl(const SetEditNetWeights* w, const SetEditNetDims* d, const
         pro.zero_out[1] = ws.mem_proj; pro.nzero[1] = D;
     }
     const bool want_rows = pro_rowlist && !d->adaptive && gemm_row_list_ok(p, 4);
-    // ---- caption encoder (editnet.py:319-348)
-    SET_TRY(editnet_encoder(w, prev, prevlen, ws.H, ws.Mem, ws.final_hidden, ws.mask, B, T, D, d->V, ws.emb_seq, ws.xg,
-                            ws.enc_h, ws.enc_c, ws.s_enc, ws.s_aff, st, ws.enc_order, ws.enc_bar, want_rows ? &pro : nullptr,
-                            true));
+    // ---- caption encoder (editnet.py:319-348): its own launches keep the fp32 kernels in every caller's scope
+    {
+        SplitScope encoder_fp32(false);
+        SET_TRY(editnet_encoder(w, prev, prevlen, ws.H, ws.Mem, ws.final_hidden, ws.mask, B, T, D, d->V, ws.emb_seq, ws.xg,
+                                ws.enc_h, ws.enc_c, ws.s_enc, ws.s_aff, st, ws.enc_order, ws.enc_bar,
+                                want_rows ? &pro : nullptr, true));
+    }
     if (pro.built)
         for (int i = 0; i < 4; ++i) { p[i].row_list = pro.list; p[i].row_count = pro.count; }
     SET_TRY(gemm_group(p, 4, st, "gemm:pro cap projections"));
@@ -528,6 +531,24 @@ int set_editnet_begin(const SetEditNetWeights* w, const SetEditNetDims* d, const
     return begin_impl(w, d, X, image_mean, prev, prevlen, W, (hipStream_t)stream);
 }
 
+// Who decodes on the bf16-split kernel (set_common.h SplitScope): the greedy rollout of 65+ rows with fixed features.  Sampled
+// rollouts, adaptive features and smaller batches keep the fp32 kernels.
+static bool greedy_split_loop(const SetEditNetDims* d, int sample) { return sample == 0 && d->B >= 65 && !d->adaptive; }
+// ... and whether that rollout's prologue does too (SET_PRO_SPLIT=0: the prologue on the fp32 kernels, the loop alone split)
+static bool greedy_split_prologue(const SetEditNetDims* d, int sample) {
+    static const int pro_split = env_int("SET_PRO_SPLIT", 1);
+    return pro_split && greedy_split_loop(d, sample);
+}
+
+// The prologue as set_editnet_greedy runs it for these dims, for a workspace that set_editnet_greedy_begun will consume.
+int set_editnet_begin_greedy(const SetEditNetWeights* w, const SetEditNetDims* d, const float* X, const float* image_mean,
+                             const int64_t* prev, const int64_t* prevlen, void* ws, size_t ws_bytes, void* stream) {
+    if (!w || !X || !prev || !prevlen) return SET_ERR_ARG;
+    EditNetWs W;
+    SET_TRY(prep(d, ws, ws_bytes, &W));
+    SplitScope split_scope(greedy_split_prologue(d, 0));
+    return begin_impl(w, d, X, image_mean, prev, prevlen, W, (hipStream_t)stream);
+}
 
 int set_editnet_step(const SetEditNetWeights* w, const SetEditNetDims* d, const float* X, const int64_t* tokens,
                      int64_t tokens_stride, int bt, float* logits, int64_t ld_logits, void* ws, size_t ws_bytes,
@@ -573,7 +594,12 @@ static int rollout(const SetEditNetWeights* w, const SetEditNetDims* d, const fl
     if (max_len + 1 > d->maxT + 1 || start_idx < 0 || start_idx >= d->V) return SET_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     const int B = d->B;
-    if (!begun) SET_TRY(begin_impl(w, d, X, image_mean, prev, prevlen, W, st));
+    if (!begun) {
+        // a greedy decode of 65+ rows runs the prologue's grouped launches on the bf16-split kernel as well (the caption
+        // projections with their row list): set_editnet_begin_greedy is the same prologue for a workspace prepared ahead
+        SplitScope split_scope(greedy_split_prologue(d, sample));
+        SET_TRY(begin_impl(w, d, X, image_mean, prev, prevlen, W, st));
+    }
     SET_HIP_TRY(hipMemsetAsync(seq, 0, sizeof(int64_t) * B * max_len, st));
     SET_HIP_TRY(hipMemsetAsync(seq_logp, 0, sizeof(float) * B * max_len, st));
     SET_TRY(set_tokens(W.it, start_idx, W.unfinished, W.alive, d->maxT + 2, B, st));
@@ -610,9 +636,9 @@ static int rollout(const SetEditNetWeights* w, const SetEditNetDims* d, const fl
     }
     // greedy decode of 65+ rows: the timestep loop's grouped GEMM launches (F/A, B, D, the lone last fc) run on the bf16-split
     // kernel (set_common.h SplitScope); sampled rollouts, adaptive features and smaller batches keep the fp32 kernels.  The
-    // prologue stays outside: a prologue run ahead through set_editnet_begin cannot know which loop will consume it, and
-    // set_editnet_greedy_begun must give the bits of set_editnet_greedy
-    SplitScope split_scope(sample == 0 && B >= 65 && !d->adaptive);
+    // prologue above ran under the same predicate.  A prologue run ahead cannot know which loop will consume it, so the entry says
+    // it: set_editnet_begin_greedy pairs with set_editnet_greedy_begun (the bits of set_editnet_greedy), set_editnet_begin is fp32
+    SplitScope split_scope(greedy_split_loop(d, sample));
     for (int t = 0; t <= last_t; ++t) {
         Slabs lg;
         bool biased = false;

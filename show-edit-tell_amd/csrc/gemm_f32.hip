@@ -667,8 +667,10 @@ struct GemmEnv {
     // SET_GEMM_SPLIT, who runs on gemm_nt_split_bf16 (gemm_split_bf16.inc), in both library variants:
     //   0      nobody: the fp32 kernels for every launch
     //   1      every launch the kernel can take (the tile classes are re-cut for it: 128x64 from 65 rows on, no row lists)
-    //   unset  launches of >= 65 rows without a row list and without a 64-row hint, issued inside a SplitScope (set_common.h): the
-    //          no-grad greedy rollout of EditNet.  Every other caller stays on the fp32 kernels.
+    //   unset  launches of >= 65 rows without a 64-row hint (with or without a row list), issued inside a SplitScope
+    //          (set_common.h): the no-grad greedy rollout of EditNet, its prologue included.  Every other caller stays on the fp32
+    //          kernels.  (Whether that rollout's prologue is inside the scope is the caller's switch, not the launcher's:
+    //          SET_PRO_SPLIT, read once by greedy_split_prologue in editnet.hip.)
     int split = env_int("SET_GEMM_SPLIT", -1);                                   // < 0: unset, > 0: "1"
     const char* split_tag = getenv("SET_GEMM_SPLIT_TAG");     // debug (SET_GEMM_SPLIT=1): restrict the split kernel to one call site
     int bm64_upto = env_int("SET_GEMM_BM64_UPTO", split > 0 ? 64 : 512);         // the split kernel is 128x64 only
@@ -711,6 +713,7 @@ struct GemmKernel {
 static const GemmKernel g_gemm_kernels[] = {
     {KC_SPLIT, 0, "gemm_nt_f32<128,64>:bf16x3", gemm_nt_split_bf16<0>, 256, SPLIT_LDS_BYTES},
     {KC_SPLIT, 1, "gemm_nt_f32<128,64>:bf16x3", gemm_nt_split_bf16<1>, 256, SPLIT_LDS_BYTES},
+    {KC_SPLIT, 2, "gemm_nt_f32<128,64>:bf16x3", gemm_nt_split_bf16<2>, 256, SPLIT_LDS_BYTES},
     {KC_128, 2, "gemm_nt_f32<128,64>", gemm_nt_f32<128, 64, 2, 2, 1, 2>, 256, 0},
     {KC_64_HAND, 2, "gemm_nt_f32_asm<64,64>", gemm_nt_f32_asm<2>, 256, 0},
     {KC_64, 2, "gemm_nt_f32<64,64>", gemm_nt_f32<64, 64, 2, 2, 1, 2>, 256, 0},
@@ -769,7 +772,7 @@ GemmRoute gemm_route(const GemmProb* probs, int n, const char* tag) {
     const GemmEnv& E = gemm_env();
     const GemmProb& p0 = probs[0];
     auto asked = [](const GemmProb& p) { return (p.bm_hint == 64 || p.bm_hint == 128) ? p.bm_hint : gemm_tile_m(p.M); };
-    bool scoped = E.split < 0 && g_split_scope && !p0.row_list && p0.bm_hint != 64;      // ... and every problem >= 65 rows
+    bool scoped = E.split < 0 && g_split_scope && p0.bm_hint != 64;                      // ... and every problem >= 65 rows
     bool bn32 = E.bn32 && !p0.bm_hint && E.split <= 0;                                   // ... and every problem 65..128 rows
     bool all128 = true;
     long long t128 = 0, t64 = 0;
@@ -793,11 +796,12 @@ GemmRoute gemm_route(const GemmProb* probs, int n, const char* tag) {
         if (r.bm == 32 || (r.bm == 128 && E.bn128)) r.bn = 128;      // (class 16: 4 waves x 16 columns)
     }
     const bool tile_128x64 = r.bm == 128 && r.bn == 64;
-    r.split = tile_128x64 && !p0.row_list &&
-              (scoped || (E.split > 0 && (!E.split_tag || !*E.split_tag || strstr(tag ? tag : "untagged", E.split_tag))));
+    r.split = tile_128x64 && (scoped || (E.split > 0 && !p0.row_list &&
+                                         (!E.split_tag || !*E.split_tag || strstr(tag ? tag : "untagged", E.split_tag))));
     // the LDS-staged tile classes of the shipped library take a row list; the <= 16-row class (no tile rows to skip) does not.
-    // (A scoped launch says yes: given its list it is no longer scoped and runs on the fp32 kernel of its class.)
-    r.rows_ok = E.split <= 0 && !exp_kernel_swapped(E) && (tile_128x64 || r.bm == 64 || r.bm == 32);
+    // A scoped launch keeps its list on the split kernel (gemm_nt_split_bf16<2>): the answer is the same with and without the
+    // list, and for the scope the question is asked in.  SET_GEMM_SPLIT=1 takes no list, as before.
+    r.rows_ok = E.split <= 0 && (scoped || (!exp_kernel_swapped(E) && (tile_128x64 || r.bm == 64 || r.bm == 32)));
     return r;
 }
 int gemm_launch_rows(const GemmProb* probs, int n) { return gemm_route(probs, n).bm; }

@@ -8,8 +8,12 @@
 // Splitting happens on the fly when a k-tile is staged into LDS (weights stay fp32 in HBM, nothing is
 // repacked); LDS holds three bf16 planes per operand, 64-B rows, 16-B chunks XOR-swizzled by (row>>2)&3 so
 // that the ds_write_b64 of the staging and the ds_read_b128 of the fragments are bank-conflict-free.
-// Same task descriptors, K segments, split-K slabs, leading preloaded arguments and loop gate (GATE = 1) as gemm_nt_f32<128,64>;
-// no row list.  Who runs on it: the launcher's word (gemm_group, SET_GEMM_SPLIT).
+// Same task descriptors, K segments, split-K slabs, leading preloaded arguments, loop gate (GATE = 1) and compacted row list
+// (GATE = 2, unsplit problems only) as gemm_nt_f32<128,64>.  Who runs on it: the launcher's word (gemm_group, SET_GEMM_SPLIT).
+// GATE = 2 has gemm_nt_f32's contract: the grid of the full launch, row tile m0 covers the list entries [m0, m0 + 128), a tile at
+// or beyond the clamped count returns at once, the list is read (and every index clamped to [0, M)) where the A-row pointers are
+// formed and where the C rows are stored.  Staging, split, k-loop and MFMA order are those of the full launch, so every computed
+// element has the bits the full split launch gives it.
 //
 // Values the planes cannot carry.  The split of +-inf is (inf, NaN, NaN) and a finite |x| >= 2^128 - 2^119 rounds its hi plane
 // to inf, so the six products of such an operand give NaN where the fp32 chain gives +-inf (or a finite number).  Finite
@@ -35,8 +39,6 @@ __global__ void __launch_bounds__(256) gemm_nt_split_bf16(const int ntasks, cons
     constexpr int BUF = 3 * (PLANE_A + PLANE_W);          // 36 KB per stage
     static_assert(2 * BUF == SPLIT_LDS_BYTES, "launcher's dynamic LDS size");
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    (void)gate_nrows;
-
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const int wm = wave & 1, wn = wave >> 1;
@@ -68,13 +70,27 @@ __global__ void __launch_bounds__(256) gemm_nt_split_bf16(const int ntasks, cons
     const int m0 = tm * BM, n0 = tn * BN;
     const int kt0 = (int)(((long long)ks * T.ktiles) / T.ksplit);
     const int kt1 = (int)(((long long)(ks + 1) * T.ktiles) / T.ksplit);
+    // compacted row list, as in gemm_nt_f32: gate_nrows is the length of L.row_list (else an unused slot)
+    int epi_m = T.M;
+    const int* const rlist = L.row_list;
+    if constexpr (GATE == 2) {
+        const int cnt = *gate_nrows;
+        epi_m = cnt < 0 ? 0 : (cnt < T.M ? cnt : T.M);
+        if (m0 >= epi_m) return;                      // (uniform over the workgroup, before its first barrier)
+    } else {
+        (void)gate_nrows;
+    }
+    auto epi_row = [&](int row) {                     // tile row (< epi_m) -> row of A and of C
+        if constexpr (GATE == 2) { const int i = rlist[row]; return i < 0 ? 0 : (i < T.M ? i : T.M - 1); }
+        else return row;
+    };
 
     const int srow = tid >> 3, kc = tid & 7, scol = kc * 4;
     // byte offset of this thread's 8-byte store inside a plane row
     const int soff = srow * ROWB + (((kc >> 1) ^ ((srow >> 2) & 3)) << 4) + ((kc & 1) << 3);
     int arow[LA], wrow[LW];
 #pragma unroll
-    for (int i = 0; i < LA; ++i) { int r = m0 + srow + 32 * i; arow[i] = r < T.M ? r : T.M - 1; }
+    for (int i = 0; i < LA; ++i) { int r = m0 + srow + 32 * i; r = r < epi_m ? r : epi_m - 1; arow[i] = epi_row(r); }
 #pragma unroll
     for (int i = 0; i < LW; ++i) { int r = n0 + srow + 32 * i; wrow[i] = r < T.N ? r : T.N - 1; }
 
@@ -246,11 +262,12 @@ __global__ void __launch_bounds__(256) gemm_nt_split_bf16(const int ntasks, cons
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int row = crow0 + i * 32 + (r & 3) + 8 * (r >> 2);
-                if (row < T.M) {
+                if (row < epi_m) {
+                    const int crow = epi_row(row);
                     float v = acc[i][r];
-                    if (!(fabsf(v) <= 3.402823466e+38f)) v = dot_f32(row, col);      // inf or NaN
+                    if (!(fabsf(v) <= 3.402823466e+38f)) v = dot_f32(crow, col);     // inf or NaN
                     if (fused) v = apply_act(v + bv, T.act);
-                    Cs[(long long)row * T.ldc + col] = v;
+                    Cs[(long long)crow * T.ldc + col] = v;
                 }
             }
         }

@@ -109,7 +109,8 @@ struct GemmRoute {
 GemmRoute gemm_route(const GemmProb* probs, int n, const char* tag = nullptr);
 // the row-tile class (16 / 32 / 64 / 128) a grouped launch of these problems runs on
 int gemm_launch_rows(const GemmProb* probs, int n);
-// whether a grouped launch of these problems can take GemmProb::row_list (every tile class but the <= 16-row one)
+// whether a grouped launch of these problems can take GemmProb::row_list (every tile class but the <= 16-row one), in the
+// SplitScope the question is asked in: the same answer with and without the list on the problems
 bool gemm_row_list_ok(const GemmProb* probs, int n);
 // gemm_gen.hip: C (+)= a . b^T with either operand stored k-major or k-minor (training backward)
 int gemm_gen(const float* A, long long lda, int a_kminor, const float* B, long long ldb, int b_kminor, float* C,
@@ -142,7 +143,8 @@ struct RowGateScope {
 };
 // Split-precision scope (gemm_f32.hip, SET_GEMM_SPLIT unset): while one is open with `on`, grouped GEMM launches of >= 65 rows
 // that fit gemm_nt_split_bf16 run on it (fp32 operands as three exact bf16 planes, fp32 accumulation: fp32-grade error, not
-// the fp32 kernels' bits).  Opened by the no-grad greedy rollout of EditNet alone; every other caller keeps the fp32 kernels.
+// the fp32 kernels' bits), with their row list if they have one.  Opened by the no-grad greedy rollout of EditNet alone, around its
+// prologue (begin_impl; not the caption encoder inside it) and its timestep loop; every other caller keeps the fp32 kernels.
 extern thread_local bool g_split_scope;
 struct SplitScope {
     bool prev;

@@ -158,8 +158,9 @@ class DecoderC(_DecoderXE):
         if ticket is None:
             ticket = {"dims_key": key, "ws": self._new_workspace(dims), "event": torch.cuda.Event(), "done": torch.cuda.Event()}
         w = self._weights(dims)
-        check(lib.set_editnet_begin(C.byref(w), C.byref(dims), ptr(X), ptr(mean), ptr(prev), ptr(plen), ptr(ticket["ws"]),
-                                    ticket["ws"].numel(), stream_of(dev)), "set_editnet_begin")
+        # (tickets are consumed by greedy decodes only: the prologue as set_editnet_greedy runs it)
+        check(lib.set_editnet_begin_greedy(C.byref(w), C.byref(dims), ptr(X), ptr(mean), ptr(prev), ptr(plen), ptr(ticket["ws"]),
+                                           ticket["ws"].numel(), stream_of(dev)), "set_editnet_begin_greedy")
         ticket["event"].record(cur)
         # the decode must see the SAME weights view (token table attached or not) the prologue was built with
         ticket.update(weights=w, inputs=(X, prev, plen, mean), sig=self._ahead_sig(X, prev, plen, mean),
