@@ -1062,6 +1062,57 @@ int set_beam_pick_diverse_f32(const float* logits, const float* logits2, int64_t
                               int32_t* done_group, int32_t* g_left, int groups, float penalty,
                               const SetBeamConstraints* c, void* ws, size_t ws_bytes, void* stream);
 
+/* Constrained greedy and sampled picks (csrc/epilogue.hip, the CONS instantiations of greedy_pick_k / sample_pick_k; the ban list:
+ * csrc/row_pick.h): the rules a-c of set_beam_pick_constrained_f32 in the two free-running decode modes.  The pick of row b at
+ * timestep t is THE PICK OF THAT MODE APPLIED TO THE ROW WITH THE REMOVED WORDS AT -inf: arg-max and its first-index tie rule,
+ * temperature, the top-k / top-p kept set, the inverse-CDF draw, lse, step_logp and seq_logp all see the masked row, so the
+ * log-probabilities are those of the constrained, renormalised distribution (the one a sample is drawn from; beam search does
+ * not renormalise and stays as it is).  With s[0] = <start>, s[1 .. t] = seq[b, 0 .. t-1] and L = t + 1, word v is removed if
+ *   a. v is one of the n_banned ids of `banned` (device memory; an id outside [0, V) matches nothing), or
+ *   b. v == end_idx and t < min_len, or
+ *   c. no_repeat_ngram = n >= 1, L >= n and some i in 1 .. L - n has s[i .. i+n-2] == s[L-n+1 .. L-1] and s[i+n-1] == v
+ *      (<start> at position 0 never takes part, so it is never read; n = 1: no word twice).
+ * A row that has already finished (t > 0 and unfinished[b] == 0) gets exactly what the unconstrained pick gives it.  The
+ * <end> -> 0 rewrite, the `unfinished` latch, alive, raw_ids, the embedding gather, the LSTM tail, the greedy row-limit override
+ * (set_decode_row_limits) and the loop gate are unchanged.  One workgroup per row builds the row's list in LDS (at most 64 + 1 +
+ * 255 entries) and applies it as the row is read: no extra launch, nothing written into the logits, no scratch.  Both row
+ * layouts of set_pick_slabs_f32 are covered and give the same outputs.  Neutral constraints {0, 0, 0, 0, NULL} give the bits of
+ * the unconstrained pick.
+ * SET_ERR_ARG, before any HIP call and with nothing written: c == NULL, no_repeat_ngram outside 0 .. 16, min_len < 0, n_banned
+ * outside 0 .. 64, banned == NULL with n_banned > 0 (or the reverse), length_alpha != 0 (nothing is ranked here), max_len > 255
+ * (the row's history lives in LDS), V <= n_banned + 1 + max_len (so that, by counting, every row keeps at least one word: there
+ * is no "row ran out of candidates" case), and whatever the unconstrained entry refuses.
+ *
+ * set_pick_slabs_constrained_f32: set_pick_slabs_opts_f32 with constraints — one pick on the arguments of the decode loops; the
+ * history is args->seq[:, :t], so also SET_ERR_ARG for t > max_len.  opts may be NULL; in greedy mode it must be neutral.
+ * Float64 restatement: tests/pick_constrained_oracle.py. */
+int set_pick_slabs_constrained_f32(const SetPickArgs* args, const SetSampleOpts* opts, const SetBeamConstraints* c, void* stream);
+/* The free-running loops under constraints: the arguments of set_editnet_greedy / set_editnet_sample_opts / set_dcnet_greedy /
+ * set_dcnet_sample_opts plus c, applied at every timestep.  These entries ALWAYS run on the per-step kernels, wherever the
+ * unconstrained loop runs — small batches (never the persistent launch), adaptive features, and the split-precision GEMM route
+ * of a greedy decode from 65 rows on (set_editnet_greedy; the split changes the GEMMs only) — with the LSTM tail inside the
+ * pick as in the unconstrained per-step loop.  A neutral c gives the bits of that per-step loop.  Refusals: those above (max_len
+ * is the loop's) and those of the unconstrained entry, all before anything is touched. */
+int set_editnet_greedy_constrained(const SetEditNetWeights* w, const SetEditNetDims* d, const float* X,
+                                   const float* image_mean, const int64_t* prev, const int64_t* prevlen,
+                                   int64_t start_idx, int64_t end_idx, int max_len, int64_t* seq,
+                                   float* seq_logp, void* ws, size_t ws_bytes, void* stream,
+                                   const SetBeamConstraints* c);
+int set_editnet_sample_constrained(const SetEditNetWeights* w, const SetEditNetDims* d, const float* X,
+                                   const float* image_mean, const int64_t* prev, const int64_t* prevlen,
+                                   int64_t start_idx, int64_t end_idx, int max_len, uint64_t seed, uint64_t offset,
+                                   int64_t* seq, float* seq_logp, void* ws, size_t ws_bytes, void* stream,
+                                   const SetSampleOpts* opts, const SetBeamConstraints* c);
+int set_dcnet_greedy_constrained(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* prev,
+                                 const int64_t* prevlen, int64_t start_idx, int64_t end_idx, int max_len,
+                                 int64_t* seq, float* seq_logp, void* ws, size_t ws_bytes, void* stream,
+                                 const SetBeamConstraints* c);
+int set_dcnet_sample_constrained(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* prev,
+                                 const int64_t* prevlen, int64_t start_idx, int64_t end_idx, int max_len,
+                                 uint64_t seed, uint64_t offset, int64_t* seq, float* seq_logp, void* ws,
+                                 size_t ws_bytes, void* stream, const SetSampleOpts* opts,
+                                 const SetBeamConstraints* c);
+
 /* Stochastic beam search pick (Kool, van Hoof, Welling, ICML 2019; csrc/sbs.hip): one timestep t (0-based, t <= 254) of a
  * search that leaves, per image, k <= 8 DISTINCT sequences which are an exact sample WITHOUT replacement from the model's
  * sequence distribution, in draw order.  NI images x k slots; slot j of image i is logits row r = i k + j.

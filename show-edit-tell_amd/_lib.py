@@ -256,6 +256,44 @@ def refuse_sample_opts(sample_max, sample_rl, grad_path):
                          "that require grad): call the model in eval mode under torch.no_grad()")
 
 
+def decode_constraints(constraints, word_map, V, sample_max, sample_rl, grad_path, gumbel):
+    """`constraints=` of the free-running decodes (editnet_rl.DecoderC.forward, dcnet_rl.DAE.forward): None for None and for a
+    neutral evaluate.BeamConstraints (the caller then makes exactly today's calls), otherwise the checked object and its banned
+    ids — resolved once against the vocabulary, before any device work.  ValueError: a length penalty (nothing is ranked in
+    these decodes), sampler="gumbel", and every path in which gradients flow (no backward of the constrained pick is built)."""
+    from . import evaluate
+    cons = evaluate._active(constraints)
+    if cons is None:
+        return None
+    ids = cons.banned_ids(word_map, V)
+    if cons.length_penalty != 0.0:
+        raise ValueError("constraints.length_penalty applies to beam search only (greedy and sampled decodes rank nothing)")
+    if gumbel:
+        raise ValueError('constraints are not built into sampler="gumbel": use sampler="cdf"')
+    if grad_path:
+        raise ValueError("constraints are not supported in the grad-enabled rollout (train mode or parameters that require "
+                         "grad): call the model in eval mode under torch.no_grad()")
+    if not sample_max and not sample_rl:
+        raise ValueError("constraints apply to the greedy (sample_max=True) and the sampled (sample_rl=True) decode")
+    return cons, ids
+
+
+def refuse_constraints(constraints, where):
+    """the entries through which gradients flow (sample_rollout, the SCST steps): an active `constraints=` is a ValueError there"""
+    from . import evaluate
+    if evaluate._active(constraints) is not None:
+        raise ValueError("constraints are not supported in %s: no backward of the constrained pick is built (decode in eval "
+                         "mode under torch.no_grad())" % where)
+
+
+def constraints_struct(cons_ids, device):
+    """(BeamConstraintsC, the device tensor of banned ids it points to — keep it alive over the call) of decode_constraints' answer"""
+    import torch
+    cons, ids = cons_ids
+    banned = torch.tensor(ids, dtype=torch.long, device=device) if ids else None
+    return BeamConstraintsC(cons.no_repeat_ngram, cons.min_length, 0.0, len(ids), banned.data_ptr() if ids else None), banned
+
+
 class SlabSrc(C.Structure):
     """include/set_hip.h SetSlabSrc: one addend of a gradient that is still split-K partials"""
     _fields_ = [("p", C.c_void_p), ("slab_stride", C.c_int64), ("ld", C.c_int64), ("nslab", C.c_int32), ("rows", C.c_int32)]
@@ -458,6 +496,15 @@ PROTOTYPES = {
     "set_gumbel_fill_f32": (_I, [_P, _I, _I, _I, _U, _U, _P]),
     "set_pick_slabs_f32": (_I, [C.POINTER(PickArgs), _P]),
     "set_pick_slabs_opts_f32": (_I, [C.POINTER(PickArgs), C.POINTER(SampleOpts), _P]),
+    "set_pick_slabs_constrained_f32": (_I, [C.POINTER(PickArgs), C.POINTER(SampleOpts), C.POINTER(BeamConstraintsC), _P]),
+    "set_editnet_greedy_constrained": (_I, [C.POINTER(EditNetWeights), C.POINTER(EditNetDims), _P, _P, _P, _P, _L, _L, _I, _P, _P,
+                                            _P, _Z, _P, C.POINTER(BeamConstraintsC)]),
+    "set_editnet_sample_constrained": (_I, [C.POINTER(EditNetWeights), C.POINTER(EditNetDims), _P, _P, _P, _P, _L, _L, _I, _U, _U,
+                                            _P, _P, _P, _Z, _P, C.POINTER(SampleOpts), C.POINTER(BeamConstraintsC)]),
+    "set_dcnet_greedy_constrained": (_I, [C.POINTER(DcnetWeights), C.POINTER(DcnetDims), _P, _P, _L, _L, _I, _P, _P, _P, _Z, _P,
+                                          C.POINTER(BeamConstraintsC)]),
+    "set_dcnet_sample_constrained": (_I, [C.POINTER(DcnetWeights), C.POINTER(DcnetDims), _P, _P, _L, _L, _I, _U, _U, _P, _P, _P, _Z,
+                                          _P, C.POINTER(SampleOpts), C.POINTER(BeamConstraintsC)]),
     "set_beam_pick_f32": (_I, [_P, _P, _L, _I, _I, _I, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "set_beam_pick_nbest_f32": (_I, [_P, _P, _L, _I, _I, _I, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "set_beam_gather_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),

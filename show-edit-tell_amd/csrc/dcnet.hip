@@ -365,9 +365,14 @@ int set_dcnet_greedy_pick(const SetDcnetWeights* w, const SetDcnetDims* d, const
 static int dcnet_rollout(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* prev, const int64_t* prevlen,
                          int64_t start_idx, int64_t end_idx, int max_len, int sample, uint64_t seed, uint64_t offset,
                          int64_t* seq, float* seq_logp, void* ws, size_t ws_bytes, void* stream,
-                         const SetSampleOpts* opts = nullptr) {
+                         const SetSampleOpts* opts = nullptr, const SetBeamConstraints* c = nullptr,
+                         bool constrained = false) {
     if (!w || !prev || !prevlen || !seq || !seq_logp || max_len <= 0) return SET_ERR_ARG;
     SET_TRY(sample_opts_check(opts));
+    // constrained (set_dcnet_*_constrained): as in editnet.hip rollout — the per-step loop at every batch size, tail included
+    PickCons pc;
+    if (constrained) SET_TRY(pick_cons_check(c, d ? d->V : 0, max_len, &pc));
+    const PickCons* cons = constrained ? &pc : nullptr;
     if (sample == 2) SET_TRY(gumbel_opts_check(opts, d ? d->V : 0, max_len));
     DcnetWs W;
     SET_TRY(prep(d, ws, ws_bytes, &W));
@@ -389,7 +394,7 @@ static int dcnet_rollout(const SetDcnetWeights* w, const SetDcnetDims* d, const 
     static const int loop_gate = env_int("SET_LOOP_GATE", 1);
     // small batches, greedy: the whole loop as ONE persistent launch (decode_persistent.hip).  The context half of
     // language_lstm's input product is linear in the attention weights: Pc = enc W_ih[:, D:]^T is computed here once
-    if (!sample && !emb_needed && !g_row_limit && dcnet_persistent_ok(d, max_len)) {
+    if (!sample && !cons && !emb_needed && !g_row_limit && dcnet_persistent_ok(d, max_len)) {
         const int rc = dcnet_persistent_greedy(w, d, W.pre1, W.att1_c, W.mask, W.pd_pc, W.pd_x, W.it, W.unfinished, W.alive,
                                                start_idx, end_idx, max_len, (long long*)seq, seq_logp, st);
         if (rc != SET_ERR_UNSUPPORTED) return rc;
@@ -426,10 +431,10 @@ static int dcnet_rollout(const SetDcnetWeights* w, const SetDcnetDims* d, const 
         else if (sample)
             SET_TRY(sample_pick(lg, pick_bias, d->V, t, max_len, end_idx, (long long*)seq, seq_logp, W.it, W.unfinished,
                                 W.alive, emb_needed ? w->embed : nullptr, W.emb, d->E, B, seed, offset, nullptr, nullptr,
-                                nullptr, st, a_done ? &tail : nullptr, opts));
+                                nullptr, st, a_done ? &tail : nullptr, opts, nullptr, cons));
         else
             SET_TRY(greedy_pick(lg, pick_bias, d->V, t, max_len, end_idx, (long long*)seq, seq_logp, W.it, W.unfinished,
-                                W.alive, emb_needed ? w->embed : nullptr, W.emb, d->E, B, st, a_done ? &tail : nullptr));
+                                W.alive, emb_needed ? w->embed : nullptr, W.emb, d->E, B, st, a_done ? &tail : nullptr, cons));
     }
     return SET_OK;
 }
@@ -489,6 +494,21 @@ int set_dcnet_sample_opts(const SetDcnetWeights* w, const SetDcnetDims* d, const
                           float* seq_logp, void* ws, size_t ws_bytes, void* stream, const SetSampleOpts* opts) {
     return dcnet_rollout(w, d, prev, prevlen, start_idx, end_idx, max_len, 1, seed, offset, seq, seq_logp, ws, ws_bytes,
                          stream, opts);
+}
+
+int set_dcnet_greedy_constrained(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* prev, const int64_t* prevlen,
+                                 int64_t start_idx, int64_t end_idx, int max_len, int64_t* seq, float* seq_logp, void* ws,
+                                 size_t ws_bytes, void* stream, const SetBeamConstraints* c) {
+    return dcnet_rollout(w, d, prev, prevlen, start_idx, end_idx, max_len, 0, 0, 0, seq, seq_logp, ws, ws_bytes, stream, nullptr,
+                         c, true);
+}
+
+int set_dcnet_sample_constrained(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* prev, const int64_t* prevlen,
+                                 int64_t start_idx, int64_t end_idx, int max_len, uint64_t seed, uint64_t offset, int64_t* seq,
+                                 float* seq_logp, void* ws, size_t ws_bytes, void* stream, const SetSampleOpts* opts,
+                                 const SetBeamConstraints* c) {
+    return dcnet_rollout(w, d, prev, prevlen, start_idx, end_idx, max_len, 1, seed, offset, seq, seq_logp, ws, ws_bytes, stream,
+                         opts, c, true);
 }
 
 int set_dcnet_sample_gumbel(const SetDcnetWeights* w, const SetDcnetDims* d, const int64_t* prev, const int64_t* prevlen,

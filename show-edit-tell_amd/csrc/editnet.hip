@@ -585,9 +585,15 @@ int set_editnet_greedy_pick(const SetEditNetWeights* w, const SetEditNetDims* d,
 static int rollout(const SetEditNetWeights* w, const SetEditNetDims* d, const float* X, const float* image_mean,
                    const int64_t* prev, const int64_t* prevlen, int64_t start_idx, int64_t end_idx, int max_len,
                    int sample, uint64_t seed, uint64_t offset, int64_t* seq, float* seq_logp, void* ws, size_t ws_bytes,
-                   void* stream, bool begun = false, const SetSampleOpts* opts = nullptr) {
+                   void* stream, bool begun = false, const SetSampleOpts* opts = nullptr,
+                   const SetBeamConstraints* c = nullptr, bool constrained = false) {
     if (!w || !X || (!begun && (!prev || !prevlen)) || !seq || !seq_logp || max_len <= 0) return SET_ERR_ARG;
     SET_TRY(sample_opts_check(opts));
+    // constrained (set_editnet_*_constrained): the pick of every timestep removes words first (set_common.h PickCons); the loop
+    // is the per-step one at every batch size, tail included
+    PickCons pc;
+    if (constrained) SET_TRY(pick_cons_check(c, d ? d->V : 0, max_len, &pc));
+    const PickCons* cons = constrained ? &pc : nullptr;
     if (sample == 2) SET_TRY(gumbel_opts_check(opts, d ? d->V : 0, max_len));
     EditNetWs W;
     SET_TRY(prep(d, ws, ws_bytes, &W));
@@ -622,7 +628,7 @@ static int rollout(const SetEditNetWeights* w, const SetEditNetDims* d, const fl
     static const int loop_gate = env_int("SET_LOOP_GATE", 1);
     // small batches, greedy: the whole loop as ONE persistent launch (decode_persistent_wide.hip).  copy_lstm.x2h's region
     // columns are linear in the visual attention weights: Pv = X x2h[:, 2D:]^T is computed here once per decode
-    if (!sample && !emb_needed && !g_row_limit && editnet_persistent_ok(d, max_len)) {
+    if (!sample && !cons && !emb_needed && !g_row_limit && editnet_persistent_ok(d, max_len)) {
         if (begun) {     // the prologue ran in an earlier call (begin_ahead), possibly under other switches: Pv is not taken on trust
             const int R = d->R, F = d->F, D = d->D;
             GemmProb p = direct_prob(W.pd_pv, 4LL * D, B * R, 4 * D, nullptr, SET_ACT_NONE);
@@ -669,10 +675,10 @@ static int rollout(const SetEditNetWeights* w, const SetEditNetDims* d, const fl
         else if (sample)
             SET_TRY(sample_pick(lg, pick_bias, d->V, t, max_len, end_idx, (long long*)seq, seq_logp, W.it, W.unfinished,
                                 W.alive, emb_needed ? w->embed : nullptr, W.emb, d->D, B, seed, offset, nullptr, nullptr,
-                                nullptr, st, a_done ? &tail : nullptr, opts));
+                                nullptr, st, a_done ? &tail : nullptr, opts, nullptr, cons));
         else
             SET_TRY(greedy_pick(lg, pick_bias, d->V, t, max_len, end_idx, (long long*)seq, seq_logp, W.it, W.unfinished,
-                                W.alive, emb_needed ? w->embed : nullptr, W.emb, d->D, B, st, a_done ? &tail : nullptr));
+                                W.alive, emb_needed ? w->embed : nullptr, W.emb, d->D, B, st, a_done ? &tail : nullptr, cons));
     }
     return SET_OK;
 }
@@ -747,6 +753,22 @@ int set_editnet_sample_opts(const SetEditNetWeights* w, const SetEditNetDims* d,
                             void* stream, const SetSampleOpts* opts) {
     return rollout(w, d, X, image_mean, prev, prevlen, start_idx, end_idx, max_len, 1, seed, offset, seq, seq_logp, ws,
                    ws_bytes, stream, false, opts);
+}
+
+int set_editnet_greedy_constrained(const SetEditNetWeights* w, const SetEditNetDims* d, const float* X, const float* image_mean,
+                                   const int64_t* prev, const int64_t* prevlen, int64_t start_idx, int64_t end_idx, int max_len,
+                                   int64_t* seq, float* seq_logp, void* ws, size_t ws_bytes, void* stream,
+                                   const SetBeamConstraints* c) {
+    return rollout(w, d, X, image_mean, prev, prevlen, start_idx, end_idx, max_len, 0, 0, 0, seq, seq_logp, ws, ws_bytes,
+                   stream, false, nullptr, c, true);
+}
+
+int set_editnet_sample_constrained(const SetEditNetWeights* w, const SetEditNetDims* d, const float* X, const float* image_mean,
+                                   const int64_t* prev, const int64_t* prevlen, int64_t start_idx, int64_t end_idx, int max_len,
+                                   uint64_t seed, uint64_t offset, int64_t* seq, float* seq_logp, void* ws, size_t ws_bytes,
+                                   void* stream, const SetSampleOpts* opts, const SetBeamConstraints* c) {
+    return rollout(w, d, X, image_mean, prev, prevlen, start_idx, end_idx, max_len, 1, seed, offset, seq, seq_logp, ws,
+                   ws_bytes, stream, false, opts, c, true);
 }
 
 int set_editnet_sample_gumbel(const SetEditNetWeights* w, const SetEditNetDims* d, const float* X, const float* image_mean,

@@ -105,13 +105,17 @@ static bool tail_ok(const LstmTail& L) {
 // more is written to seq / seq_logp.
 // REG = true: the row (<= 4*256*ROW_MAXQ logits) is read ONCE as float4 (all K-slabs + bias summed
 // in registers), max / first-argmax and sum-exp are reduced from registers.
+// CONS = true: the constrained pick (set_common.h PickCons).  A live row's removed words (row_pick.h pick_ban_build) are -inf from
+// the moment the row is read: arg-max, tie rule and log-sum-exp are those of the masked row; a row that has finished is read
+// unmasked.  CONS = false is the kernel as it was: nothing below runs, no LDS is added.
 
-template <bool REG, bool TAIL>
+template <bool REG, bool TAIL, bool CONS>
 __global__ void SET_VGPR_CAP __launch_bounds__(256) greedy_pick_k(Slabs logits, const float* bias, int V, int t, int max_len,
                                                      long long end_idx, long long* seq, float* seq_logp,
                                                      long long* it_buf, int* unfinished, int* alive,
                                                      const float* table, float* emb_out, int D, const LstmTail tail,
-                                                     const int* row_limit) {
+                                                     const int* row_limit, const PickCons cons) {
+    __shared__ PickBanLds s_cb;              // (CONS only)
     __shared__ float s_val[4];
     __shared__ int s_idx[4];
     __shared__ float s_sum[4];
@@ -123,12 +127,18 @@ __global__ void SET_VGPR_CAP __launch_bounds__(256) greedy_pick_k(Slabs logits, 
     // it — than these short kernels cost after the break; the three GEMM launches and the attention launch make it.)
     int unf_prev = 1, alive_prev = 1;
     if (t > 0) {
-        if (TAIL || tid == 0) unf_prev = unfinished[b];          // (TAIL: every thread derives the word right after the arg-max)
+        if (TAIL || CONS || tid == 0) unf_prev = unfinished[b];  // (TAIL: every thread derives the word right after the arg-max)
         if (tid == 0) alive_prev = alive[t - 1];
     }
     TailRegs tr;
     const bool tail0 = TAIL && tid * 4 < tail.D;
     if (TAIL) { if (tail0) tail_fetch(tail, b, tid * 4, tr); }
+    int nban = 0;
+    bool masked = false;                     // CONS: a live row of a launch whose constraints are not neutral
+    if (CONS) {
+        masked = unf_prev && (cons.ngram | cons.min_len | cons.n_banned);
+        if (masked) nban = pick_ban_build(cons, seq + (long long)b * max_len, t, V, end_idx, s_cb);
+    }
     float best = -INFINITY;
     int bi = 0x7fffffff;
     f32x4 x[ROW_MAXQ];
@@ -194,15 +204,25 @@ __global__ void SET_VGPR_CAP __launch_bounds__(256) greedy_pick_k(Slabs logits, 
 #pragma unroll
             for (int e = 0; e < 4; ++e) if (v + e >= V) x[q][e] = -INFINITY;     // padding columns / rows past V
         }
+        if (CONS) pick_ban_regs(x, s_cb.ban, nban);
 #pragma unroll
         for (int q = 0; q < ROW_MAXQ; ++q)
 #pragma unroll
             for (int e = 0; e < 4; ++e)
                 if (x[q][e] > best) { best = x[q][e]; bi = (tid + 256 * q) * 4 + e; }   // ascending index per thread
     } else {
-        for (int v = tid; v < V; v += 256) {
-            const float xv = logit_at(logits, bias, b, v);
-            if (xv > best) { best = xv; bi = v; }
+        if (CONS && masked) {                // (row_pick.h pick_scalar_quads: the register path's order)
+            pick_scalar_quads(V, [&](int v) {
+                float xv = logit_at(logits, bias, b, v);
+                if (pick_banned(s_cb.ban, nban, v)) xv = -INFINITY;
+                if (xv > best) { best = xv; bi = v; }
+                return false;
+            });
+        } else {
+            for (int v = tid; v < V; v += 256) {
+                const float xv = logit_at(logits, bias, b, v);
+                if (xv > best) { best = xv; bi = v; }
+            }
         }
     }
 #pragma unroll
@@ -236,7 +256,16 @@ __global__ void SET_VGPR_CAP __launch_bounds__(256) greedy_pick_k(Slabs logits, 
 #pragma unroll
             for (int e = 0; e < 4; ++e) sum += expf(x[q][e] - best);               // exp(-inf) == 0 for padding
     } else {
-        for (int v = tid; v < V; v += 256) sum += expf(logit_at(logits, bias, b, v) - best);
+        if (CONS && masked) {
+            pick_scalar_quads(V, [&](int v) {
+                float xv = logit_at(logits, bias, b, v);
+                if (pick_banned(s_cb.ban, nban, v)) xv = -INFINITY;
+                sum += expf(xv - best);
+                return false;
+            });
+        } else {
+            for (int v = tid; v < V; v += 256) sum += expf(logit_at(logits, bias, b, v) - best);
+        }
     }
     const float total = block_sum(sum, s_sum);
     if (tid == 0) {
@@ -270,16 +299,21 @@ static int pick_args_check(int D, const LstmTail* tail) {
 
 int greedy_pick(Slabs logits, const float* bias, int V, int t, int max_len, long long end_idx, long long* seq,
                 float* seq_logp, long long* it, int* unfinished, int* alive, const float* table, float* emb_out,
-                int D, int B, hipStream_t s, const LstmTail* tail) {
+                int D, int B, hipStream_t s, const LstmTail* tail, const PickCons* cons) {
 #if defined(SET_EXP_SKIP_POINTWISE) || defined(SET_EXP_SKIP_PICK)      // diagnostic build (EXPERIMENTS 5.7): the launch is dropped, results are garbage
     return SET_OK;
 #endif
     if (B <= 0) return SET_OK;
     SET_TRY(pick_args_check(D, tail));
     const LstmTail tl = tail ? *tail : LstmTail();
-    ProfScope ps("greedy_pick", s, 0.0,
+    const PickCons pc = cons ? *cons : PickCons();
+    ProfScope ps(cons ? "greedy_pick_cons" : "greedy_pick", s, 0.0,
                  4.0 * B * (2.0 * V * logits.n + 2.0 * D + (tail ? tl.D * (4.0 * (tl.g0.n + 2) + 3.0) : 0.0)));
-#define SET_PICK_LAUNCH(REG, TAIL) SET_PICK_ROWS((greedy_pick_k<REG, TAIL>), tl, g_row_limit)
+#define SET_PICK_LAUNCH(REG, TAIL)                                                                         \
+    do {                                                                                                   \
+        if (cons) SET_PICK_ROWS((greedy_pick_k<REG, TAIL, true>), tl, g_row_limit, pc);                    \
+        else SET_PICK_ROWS((greedy_pick_k<REG, TAIL, false>), tl, g_row_limit, pc);                        \
+    } while (0)
     SET_PICK_DISPATCH(SET_PICK_LAUNCH);
 #undef SET_PICK_LAUNCH
     SET_LAUNCH_CHECK();
@@ -333,13 +367,17 @@ struct SampleTrunc {
     float top_p = 1.f;    // 1: off
 };
 
-template <bool REG, bool TAIL, bool TRUNC>
+// CONS = true: the constrained pick, as in greedy_pick_k — the removed words of a live row are -inf before the maximum, so
+// temperature, the kept set, the draw, lse and the log-prob are those of the masked row.  CONS = false: the kernel as it was.
+template <bool REG, bool TAIL, bool TRUNC, bool CONS>
 __global__ void __launch_bounds__(256) sample_pick_k(Slabs logits, const float* bias, int V, int t, int max_len,
                                                      long long end_idx, long long* seq, float* seq_logp,
                                                      long long* it_buf, int* unfinished, int* alive,
                                                      const float* table, float* emb_out, int D,
                                                      unsigned long long seed, unsigned long long offset,
-                                                     SampleOut so, const LstmTail tail, const SampleTrunc trunc) {
+                                                     SampleOut so, const LstmTail tail, const SampleTrunc trunc,
+                                                     const PickCons cons) {
+    __shared__ PickBanLds s_cb;          // (CONS only)
     __shared__ float s_red[4];
     __shared__ int s_cnt[2][4];          // TRUNC: per-wave partials of one descent pass, double-buffered (one barrier a pass)
     __shared__ float s_mass[2][4];
@@ -352,9 +390,16 @@ __global__ void __launch_bounds__(256) sample_pick_k(Slabs logits, const float* 
     f32x4 x[ROW_MAXQ];
     float best = -INFINITY;
     uint32_t thr = 0;                                    // TRUNC: the kept set is {order_key(y) >= thr}
-    // the generic path's logit, re-read (TRUNC: scaled, and -inf outside the kept set once thr stands)
+    int nban = 0;
+    bool masked = false;                                 // CONS: a live row of a launch whose constraints are not neutral
+    if (CONS) {
+        masked = (t == 0 || unfinished[b]) && (cons.ngram | cons.min_len | cons.n_banned);
+        if (masked) nban = pick_ban_build(cons, seq + (long long)b * max_len, t, V, end_idx, s_cb);
+    }
+    // the generic path's logit, re-read (CONS: -inf when removed; TRUNC: scaled, and -inf outside the kept set once thr stands)
     auto val = [&](int v) -> float {
         float xv = logit_at(logits, bias, b, v);
+        if (CONS) { if (pick_banned(s_cb.ban, nban, v)) xv = -INFINITY; }
         if (TRUNC) {
             xv *= trunc.inv_t;
             if (order_key(xv) < thr) xv = -INFINITY;
@@ -389,6 +434,14 @@ __global__ void __launch_bounds__(256) sample_pick_k(Slabs logits, const float* 
                 else x[q][e] = -INFINITY;
                 best = fmaxf(best, x[q][e]);
             }
+        }
+        if (CONS) {                                      // the maximum of the masked row
+            pick_ban_regs(x, s_cb.ban, nban);
+            best = -INFINITY;
+#pragma unroll
+            for (int q = 0; q < ROW_MAXQ; ++q)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) best = fmaxf(best, x[q][e]);
         }
     } else {
         for (int v = tid; v < V; v += 256) best = fmaxf(best, val(v));
@@ -450,6 +503,12 @@ __global__ void __launch_bounds__(256) sample_pick_k(Slabs logits, const float* 
                     for (int q = 0; q < ROW_MAXQ; ++q)
 #pragma unroll
                         for (int e = 0; e < 4; ++e) sm += key[q][e] >= cand ? m[q][e] : 0.f;
+                } else if (CONS && masked) {             // (row_pick.h pick_scalar_quads: the register path's order)
+                    pick_scalar_quads(V, [&](int v) {
+                        const float yv = val(v);
+                        sm += order_key(yv) >= cand ? expf(yv - best) : 0.f;
+                        return false;
+                    });
                 } else {
                     for (int v = tid; v < V; v += 256) {
                         const float yv = val(v);
@@ -488,6 +547,8 @@ __global__ void __launch_bounds__(256) sample_pick_k(Slabs logits, const float* 
         for (int q = 0; q < ROW_MAXQ; ++q)
 #pragma unroll
             for (int e = 0; e < 4; ++e) mass += expf(x[q][e] - best);                  // exp(-inf) == 0
+    } else if (CONS && masked) {
+        pick_scalar_quads(V, [&](int v) { mass += expf(val(v) - best); return false; });
     } else {
         for (int v = tid; v < V; v += 256) mass += expf(val(v) - best);
     }
@@ -533,12 +594,23 @@ __global__ void __launch_bounds__(256) sample_pick_k(Slabs logits, const float* 
         } else {
             int last = -1;
             float last_x = 0.f;
-            for (int v = tid; v < V; v += 256) {
-                const float xv = val(v);
-                const float pe = expf(xv - best);
-                if (pe > 0.f) { last = v; last_x = xv; }
-                c += pe;
-                if (pe > 0.f && target < c) { pick = v; pick_x = xv; break; }
+            if (CONS && masked) {
+                pick_scalar_quads(V, [&](int v) {
+                    const float xv = val(v);
+                    const float pe = expf(xv - best);
+                    if (pe > 0.f) { last = v; last_x = xv; }
+                    c += pe;
+                    if (pe > 0.f && target < c) { pick = v; pick_x = xv; return true; }
+                    return false;
+                });
+            } else {
+                for (int v = tid; v < V; v += 256) {
+                    const float xv = val(v);
+                    const float pe = expf(xv - best);
+                    if (pe > 0.f) { last = v; last_x = xv; }
+                    c += pe;
+                    if (pe > 0.f && target < c) { pick = v; pick_x = xv; break; }
+                }
             }
             if (pick < 0) { pick = last; pick_x = last_x; }
         }
@@ -598,7 +670,8 @@ __global__ void __launch_bounds__(256) sample_pick_k(Slabs logits, const float* 
 int sample_pick(Slabs logits, const float* bias, int V, int t, int max_len, long long end_idx, long long* seq,
                 float* seq_logp, long long* it, int* unfinished, int* alive, const float* table, float* emb_out, int D,
                 int B, unsigned long long seed, unsigned long long offset, long long* raw_ids, float* lse,
-                float* step_logp, hipStream_t s, const LstmTail* tail, const SetSampleOpts* opts, uint32_t* kept_key) {
+                float* step_logp, hipStream_t s, const LstmTail* tail, const SetSampleOpts* opts, uint32_t* kept_key,
+                const PickCons* cons) {
     if (B <= 0) return SET_OK;
     SET_TRY(pick_args_check(D, tail));
     if (sample_opts_check(opts) != SET_OK) return SET_ERR_ARG;
@@ -611,13 +684,18 @@ int sample_pick(Slabs logits, const float* bias, int V, int t, int max_len, long
     }
     // nothing to scale and nothing to cut: the untruncated instantiation, as before there were options
     const bool trunc = tc.inv_t != 1.f || tc.top_k > 0 || tc.top_p < 1.f;
-    ProfScope ps(trunc ? "sample_pick_trunc" : "sample_pick", s, 0.0,
+    const PickCons pc = cons ? *cons : PickCons();
+    static const char* const scope[2][2] = {{"sample_pick", "sample_pick_trunc"}, {"sample_pick_cons", "sample_pick_trunc_cons"}};
+    ProfScope ps(scope[cons != nullptr][trunc], s, 0.0,
                  4.0 * B * (1.0 * V * logits.n + 2.0 * D + (tail ? tl.D * (4.0 * (tl.g0.n + 2) + 3.0) : 0.0)));
     SampleOut so{raw_ids, lse, step_logp, kept_key};
 #define SET_PICK_LAUNCH(REG, TAIL)                                                                         \
     do {                                                                                                   \
-        if (trunc) SET_PICK_ROWS((sample_pick_k<REG, TAIL, true>), seed, offset, so, tl, tc);              \
-        else SET_PICK_ROWS((sample_pick_k<REG, TAIL, false>), seed, offset, so, tl, tc);                   \
+        if (cons) {                                                                                        \
+            if (trunc) SET_PICK_ROWS((sample_pick_k<REG, TAIL, true, true>), seed, offset, so, tl, tc, pc);    \
+            else SET_PICK_ROWS((sample_pick_k<REG, TAIL, false, true>), seed, offset, so, tl, tc, pc);         \
+        } else if (trunc) SET_PICK_ROWS((sample_pick_k<REG, TAIL, true, false>), seed, offset, so, tl, tc, pc); \
+        else SET_PICK_ROWS((sample_pick_k<REG, TAIL, false, false>), seed, offset, so, tl, tc, pc);        \
     } while (0)
     SET_PICK_DISPATCH(SET_PICK_LAUNCH);
 #undef SET_PICK_LAUNCH
@@ -735,6 +813,18 @@ __global__ void __launch_bounds__(256) gumbel_pick_k(Slabs logits, const float* 
     __syncthreads();
     if (emb_out && table) pick_embed(table, emb_out, b, s_tok, D);
     if (TAIL) pick_tail_rows(tail, b, s_tok, tid * 4);
+}
+
+int pick_cons_check(const SetBeamConstraints* c, int V, int max_len, PickCons* out) {
+    if (!c) return SET_ERR_ARG;
+    if (c->no_repeat_ngram < 0 || c->no_repeat_ngram > PC_MAXNGRAM || c->min_len < 0) return SET_ERR_ARG;
+    if (!(c->length_alpha == 0.f)) return SET_ERR_ARG;                                  // nothing is ranked here (NaN refused too)
+    if (c->n_banned < 0 || c->n_banned > PC_MAXBAN || (c->n_banned == 0) != (c->banned == nullptr)) return SET_ERR_ARG;
+    if (max_len > PC_MAXLEN) return SET_ERR_ARG;                                        // the row's history lives in LDS
+    if ((long long)V <= (long long)c->n_banned + 1 + max_len) return SET_ERR_ARG;       // by counting, every row keeps a word
+    out->ngram = c->no_repeat_ngram; out->min_len = c->min_len; out->n_banned = c->n_banned;
+    out->banned = (const long long*)c->banned;
+    return SET_OK;
 }
 
 int gumbel_opts_check(const SetSampleOpts* opts, int V, int max_len) {

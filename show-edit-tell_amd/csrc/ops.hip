@@ -608,13 +608,20 @@ int set_philox4x32(uint32_t* out, int n, uint64_t seed, uint64_t offset, void* s
 }
 
 // the pick kernels with every argument of the decode loops (tests/test_hip_pick_epilogues.py); no state is initialised here
-int set_pick_slabs_opts_f32(const SetPickArgs* a, const SetSampleOpts* opts, void* stream) {
+static int pick_slabs(const SetPickArgs* a, const SetSampleOpts* opts, const SetBeamConstraints* c, bool constrained,
+                      void* stream) {
     if (!a || !a->logits || !a->seq || !a->it || !a->unfinished || !a->alive) return SET_ERR_ARG;
     if (a->mode != SET_PICK_GREEDY && a->mode != SET_PICK_SAMPLE) return SET_ERR_ARG;
     if (a->mode == SET_PICK_GREEDY && !a->seq_logp) return SET_ERR_ARG;
     if (a->B <= 0 || a->V <= 0 || a->n <= 0 || a->t < 0 || a->max_len <= 0 || a->ld < a->V) return SET_ERR_ARG;
     SET_TRY(sample_opts_check(opts));
     if (a->mode == SET_PICK_GREEDY && !sample_opts_neutral(opts)) return SET_ERR_ARG;      // the arg-max has no options
+    PickCons pc;
+    if (constrained) {
+        SET_TRY(pick_cons_check(c, a->V, a->max_len, &pc));
+        if (a->t > a->max_len) return SET_ERR_ARG;           // the history is seq[:, :t]
+    }
+    const PickCons* cons = constrained ? &pc : nullptr;
     hipStream_t st = (hipStream_t)stream;
     Slabs lg{a->logits, a->stride, a->ld, a->n};
     LstmTail tl;
@@ -627,9 +634,18 @@ int set_pick_slabs_opts_f32(const SetPickArgs* a, const SetSampleOpts* opts, voi
     if (a->mode == SET_PICK_SAMPLE)
         return sample_pick(lg, a->bias, a->V, a->t, a->max_len, a->end_idx, (long long*)a->seq, a->seq_logp, (long long*)a->it,
                            a->unfinished, a->alive, a->table, a->emb_out, a->D, a->B, a->seed, a->offset, (long long*)a->raw_ids,
-                           a->lse, a->step_logp, st, a->tail ? &tl : nullptr, opts);
+                           a->lse, a->step_logp, st, a->tail ? &tl : nullptr, opts, nullptr, cons);
     return greedy_pick(lg, a->bias, a->V, a->t, a->max_len, a->end_idx, (long long*)a->seq, a->seq_logp, (long long*)a->it,
-                       a->unfinished, a->alive, a->table, a->emb_out, a->D, a->B, st, a->tail ? &tl : nullptr);
+                       a->unfinished, a->alive, a->table, a->emb_out, a->D, a->B, st, a->tail ? &tl : nullptr, cons);
+}
+
+int set_pick_slabs_opts_f32(const SetPickArgs* a, const SetSampleOpts* opts, void* stream) {
+    return pick_slabs(a, opts, nullptr, false, stream);
+}
+
+// the constrained picks (epilogue.hip, CONS instantiations) on the same arguments
+int set_pick_slabs_constrained_f32(const SetPickArgs* a, const SetSampleOpts* opts, const SetBeamConstraints* c, void* stream) {
+    return pick_slabs(a, opts, c, true, stream);
 }
 
 int set_pick_slabs_f32(const SetPickArgs* a, void* stream) { return set_pick_slabs_opts_f32(a, nullptr, stream); }

@@ -451,16 +451,28 @@ struct LstmTail {
     float* h_out = nullptr;
     int D = 0;
 };
+// Constraints of the greedy and the sampled pick (include/set_hip.h "Constrained greedy and sampled picks"): words removed from
+// a live row before anything else sees it — the banned ids, <end> while t < min_len, what would repeat an n-gram of the row's own
+// seq[b, 0 .. t-1].  The kernels build the row's list in LDS (row_pick.h pick_ban_build), hence the limits.
+constexpr int PC_MAXBAN = 64, PC_MAXLEN = 255, PC_MAXNGRAM = 16;
+struct PickCons {
+    int ngram = 0, min_len = 0, n_banned = 0;
+    const long long* banned = nullptr;
+};
+// what every constrained entry refuses with SET_ERR_ARG before any HIP call; fills *out
+int pick_cons_check(const SetBeamConstraints* c, int V, int max_len, PickCons* out);
+// cons (NULL: the unconstrained kernels): a constrained launch; a neutral PickCons gives the unconstrained bits
 int greedy_pick(Slabs logits, const float* bias, int V, int t, int max_len, long long end_idx,
                 long long* seq, float* seq_logp, long long* it, int* unfinished, int* alive,
-                const float* table, float* emb_out, int D, int B, hipStream_t s, const LstmTail* tail = nullptr);
+                const float* table, float* emb_out, int D, int B, hipStream_t s, const LstmTail* tail = nullptr,
+                const PickCons* cons = nullptr);
 // opts (include/set_hip.h SetSampleOpts; NULL: neutral): temperature, top-k and top-p of the draw.  Neutral options launch the
 // untruncated kernel.  kept_key (B) or NULL: the threshold of every row's kept set {order_key(y) >= thr}, 0 when nothing is cut.
 int sample_pick(Slabs logits, const float* bias, int V, int t, int max_len, long long end_idx, long long* seq,
                 float* seq_logp, long long* it, int* unfinished, int* alive, const float* table, float* emb_out, int D,
                 int B, unsigned long long seed, unsigned long long offset, long long* raw_ids, float* lse,
                 float* step_logp, hipStream_t s, const LstmTail* tail = nullptr, const SetSampleOpts* opts = nullptr,
-                uint32_t* kept_key = nullptr);
+                uint32_t* kept_key = nullptr, const PickCons* cons = nullptr);
 // what the *_opts entry points refuse with SET_ERR_ARG before they touch anything
 inline int sample_opts_check(const SetSampleOpts* o) {
     if (!o) return SET_OK;

@@ -19,9 +19,10 @@ class DAE(_DAE_XE):
     max_len = 18
 
     def forward(self, word_map, encoded_previous_captions, previous_cap_length, sample_max=True, sample_rl=False,
-                temperature=1.0, top_k=0, top_p=1.0, sampler="cdf"):
+                temperature=1.0, top_k=0, top_p=1.0, sampler="cdf", constraints=None):
         """temperature / top_k / top_p / sampler: see editnet_rl.DecoderC.forward (no-grad sampled rollout only; "gumbel" is one
-        persistent launch for 1 .. 8 rows with the token table built, the per-step kernels with the same draws otherwise)"""
+        persistent launch for 1 .. 8 rows with the token table built, the per-step kernels with the same draws otherwise).
+        constraints: see editnet_rl.DecoderC.forward (no-grad greedy decode and no-grad sampled decode with sampler="cdf")"""
         if sampler != "cdf":
             _lib.check_sampler_name(sampler, top_k, top_p)
         _require_cuda(encoded_previous_captions, "previous captions")
@@ -30,6 +31,9 @@ class DAE(_DAE_XE):
         gumbel = _lib.check_sampler(sampler, opts, sample_max, sample_rl, grad_path)
         if opts is not None:
             _lib.refuse_sample_opts(sample_max, sample_rl, grad_path)
+        cons = None
+        if constraints is not None:
+            cons = _lib.decode_constraints(constraints, word_map, self.vocab_size, sample_max, sample_rl, grad_path, gumbel)
         if grad_path:
             return self._rollout_autograd(word_map, encoded_previous_captions, previous_cap_length, sample_max, sample_rl)
         lib = _lib.load()
@@ -43,6 +47,20 @@ class DAE(_DAE_XE):
         with self._row_limits_scope(lib, B):
             seq = torch.empty(B, max_len, dtype=torch.long, device=dev)
             seq_logp = torch.empty(B, max_len, dtype=torch.float32, device=dev)
+            if cons is not None:     # the constrained loops: per-step kernels at every batch size
+                copts, banned = _lib.constraints_struct(cons, dev)               # (banned: alive until the call is enqueued)
+                head = (C.byref(w), C.byref(dims), ptr(prev), ptr(plen), int(word_map['<start>']), int(word_map['<end>']), max_len)
+                tail = (ptr(seq), ptr(seq_logp), ptr(ws), ws.numel(), stream_of(dev))
+                if sample_rl:
+                    from . import rng
+                    check(lib.set_dcnet_sample_constrained(*head, rng.next_seed(), rng.offset(rng.SITE_ROLLOUT), *tail,
+                                                           C.byref(opts) if opts is not None else None, C.byref(copts)),
+                          "set_dcnet_sample_constrained")
+                else:
+                    check(lib.set_dcnet_greedy_constrained(*head, *tail, C.byref(copts)), "set_dcnet_greedy_constrained")
+                if banned is not None:
+                    banned.record_stream(torch.cuda.current_stream(dev))
+                return seq, seq_logp
             if sample_rl:        # multinomial sampling, eval mode, no gradients: fused device loop, Philox epilogue
                 from . import rng
                 # (a NULL SetSampleOpts* is the call without options, bit for bit: include/set_hip.h)
@@ -66,8 +84,10 @@ class DAE(_DAE_XE):
                                        stream_of(dev)), "set_dcnet_greedy")
             return seq, seq_logp
 
-    def sample_rollout(self, word_map, encoded_previous_captions, previous_cap_length, temperature=1.0, top_k=0, top_p=1.0):
+    def sample_rollout(self, word_map, encoded_previous_captions, previous_cap_length, temperature=1.0, top_k=0, top_p=1.0,
+                       constraints=None):
         """see editnet_rl.DecoderC.sample_rollout"""
+        _lib.refuse_constraints(constraints, "sample_rollout")
         _require_cuda(encoded_previous_captions, "previous captions")
         return self._sample_rollout((word_map, encoded_previous_captions, previous_cap_length), {}, temperature, top_k, top_p)
 

@@ -27,13 +27,19 @@ class DecoderC(_DecoderXE):
     max_len = 18
 
     def forward(self, word_map, encoded_previous_captions, previous_cap_length, image_features, sample_max=True,
-                sample_rl=False, image_mean=None, repeat_images=1, temperature=1.0, top_k=0, top_p=1.0, sampler="cdf"):
+                sample_rl=False, image_mean=None, repeat_images=1, temperature=1.0, top_k=0, top_p=1.0, sampler="cdf",
+                constraints=None):
         """repeat_images = n (an extension for BASELINE.json configs[4], n sampled rollouts per image): `image_features`
         holds B images while the captions hold n * B rows, sample-major (row s * B + b belongs to image b).
         temperature / top_k / top_p (include/set_hip.h SetSampleOpts; 1 / 0 / 1 are neutral): the distribution the no-grad
         sampled rollout (sample_rl=True, sample_max=False) draws every word from; seqLogprobs are taken under it.
         sampler: "cdf" (default, the inverse-CDF draw) or "gumbel" (the Gumbel-max draw of include/set_hip.h: temperature only,
-        no-grad only; 1 .. 16 rows run as one persistent launch, anything else on the per-step kernels with the same draws)."""
+        no-grad only; 1 .. 16 rows run as one persistent launch, anything else on the per-step kernels with the same draws).
+        constraints: an evaluate.BeamConstraints (no repeated n-gram, banned words, minimum length; length_penalty must be 0) for
+        the no-grad greedy decode and the no-grad sampled decode with sampler="cdf": every step picks from the row with the
+        removed words at -inf, so seqLogprobs are those of the constrained, renormalised distribution (include/set_hip.h
+        "Constrained greedy and sampled picks").  None or a neutral object: exactly the calls made without it.  An active object
+        runs the per-step kernels at every batch size and consumes no begin-ahead ticket."""
         if sampler != "cdf":
             _lib.check_sampler_name(sampler, top_k, top_p)
         _require_cuda(image_features, "image features")
@@ -42,6 +48,9 @@ class DecoderC(_DecoderXE):
         gumbel = _lib.check_sampler(sampler, opts, sample_max, sample_rl, grad_path)
         if opts is not None:
             _lib.refuse_sample_opts(sample_max, sample_rl, grad_path)
+        cons = None
+        if constraints is not None:
+            cons = _lib.decode_constraints(constraints, word_map, self.vocab_size, sample_max, sample_rl, grad_path, gumbel)
         if grad_path:
             return self._rollout_autograd(word_map, encoded_previous_captions, previous_cap_length, image_features,
                                           sample_max, sample_rl, image_mean, repeat_images)
@@ -52,18 +61,20 @@ class DecoderC(_DecoderXE):
         # the row limits hold around the whole enqueue, the paths that pick up work run ahead included
         with self._row_limits_scope(lib, image_features.shape[0]):
             return self._decode_nograd(lib, word_map, encoded_previous_captions, previous_cap_length, image_features,
-                                       sample_rl, image_mean, opts, gumbel)
+                                       sample_rl, image_mean, opts, gumbel, cons)
 
     def sample_rollout(self, word_map, encoded_previous_captions, previous_cap_length, image_features, image_mean=None,
-                       repeat_images=1, temperature=1.0, top_k=0, top_p=1.0):
+                       repeat_images=1, temperature=1.0, top_k=0, top_p=1.0, constraints=None):
         """One sampled rollout under temperature / top_k / top_p, with or without gradients (native_model._sample_rollout):
-        the entry self-critical training with a tempered or truncated policy goes through (train.scst_train_step)."""
+        the entry self-critical training with a tempered or truncated policy goes through (train.scst_train_step).
+        constraints: an active evaluate.BeamConstraints is a ValueError here (the constrained decode is `forward`, no-grad)."""
+        _lib.refuse_constraints(constraints, "sample_rollout")
         _require_cuda(image_features, "image features")
         return self._sample_rollout((word_map, encoded_previous_captions, previous_cap_length, image_features),
                                     dict(image_mean=image_mean, repeat_images=repeat_images), temperature, top_k, top_p)
 
     def _decode_nograd(self, lib, word_map, encoded_previous_captions, previous_cap_length, image_features, sample_rl,
-                       image_mean, opts=None, gumbel=False):
+                       image_mean, opts=None, gumbel=False, cons=None):
         dev = image_features.device
         X = _f32c(image_features)
         prev = _i64c(encoded_previous_captions)
@@ -74,6 +85,24 @@ class DecoderC(_DecoderXE):
         dims = self._dims(B, prev.shape[1], X.shape[1], max_len + 1)
         seq = torch.empty(B, max_len, dtype=torch.long, device=dev)
         seq_logp = torch.empty(B, max_len, dtype=torch.float32, device=dev)
+        if cons is not None:
+            # the constrained loops: per-step kernels at every batch size; a prologue run ahead stays with its ticket
+            ws = self._workspace(dims)
+            w = self._weights(dims)
+            copts, banned = _lib.constraints_struct(cons, dev)                   # (banned: alive until the call is enqueued)
+            head = (C.byref(w), C.byref(dims), ptr(X), ptr(mean), ptr(prev), ptr(plen), int(word_map['<start>']),
+                    int(word_map['<end>']), max_len)
+            tail = (ptr(seq), ptr(seq_logp), ptr(ws), ws.numel(), stream_of(dev))
+            if sample_rl:
+                from . import rng
+                check(lib.set_editnet_sample_constrained(*head, rng.next_seed(), rng.offset(rng.SITE_ROLLOUT), *tail,
+                                                         C.byref(opts) if opts is not None else None, C.byref(copts)),
+                      "set_editnet_sample_constrained")
+            else:
+                check(lib.set_editnet_greedy_constrained(*head, *tail, C.byref(copts)), "set_editnet_greedy_constrained")
+            if banned is not None:
+                banned.record_stream(torch.cuda.current_stream(dev))
+            return seq, seq_logp
         ticket = None if sample_rl else self._take_ahead(X, prev, plen, mean)
         if ticket is not None and ticket.get("out") is not None:
             # decode_ahead: the whole decode of this batch already ran (or is running) on another stream

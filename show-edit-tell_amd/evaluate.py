@@ -674,7 +674,8 @@ class EditTrace:
 
 
 @torch.no_grad()
-def sample_captions(model, *inputs_and_word_map, n_samples=5, temperature=1.0, top_k=0, top_p=1.0, sampler="cdf"):
+def sample_captions(model, *inputs_and_word_map, n_samples=5, temperature=1.0, top_k=0, top_p=1.0, sampler="cdf",
+                    constraints=None):
     """n_samples sampled captions per image from ONE fused rollout:
         seq, seq_logp = sample_captions(decoder, image_features, previous_caption, prev_caplen, word_map, n_samples=5, top_p=0.9)
         seq, seq_logp = sample_captions(dae, previous_caption, prev_caplen, word_map, temperature=0.8, top_k=50)
@@ -684,7 +685,8 @@ def sample_captions(model, *inputs_and_word_map, n_samples=5, temperature=1.0, t
     max_len) int64 and seq_logp (NI, n_samples, max_len), the log-probs under the tempered / truncated distribution sampled
     from.  The seed comes from rng.next_seed() as in the models' own sampled path: torch.manual_seed() reproduces a call.
     sampler="gumbel": the Gumbel-max draw (temperature only) — for n_samples * NI <= 16 rows (EditNet) or <= 8 rows (DCNet) the
-    whole rollout is one persistent launch; "cdf" (default) is the inverse-CDF draw with its draws unchanged."""
+    whole rollout is one persistent launch; "cdf" (default) is the inverse-CDF draw with its draws unchanged.
+    constraints: an evaluate.BeamConstraints applied to every sample's own words (see editnet_rl.DecoderC.forward; sampler="cdf")."""
     *inputs, word_map = inputs_and_word_map
     if len(inputs) not in (2, 3):
         raise ValueError("sample_captions(model, [image_features,] previous_caption, prev_caplen, word_map, ...)")
@@ -697,6 +699,8 @@ def sample_captions(model, *inputs_and_word_map, n_samples=5, temperature=1.0, t
     kw = dict(sample_max=False, sample_rl=True, temperature=temperature, top_k=top_k, top_p=top_p)
     if sampler != "cdf":
         kw["sampler"] = sampler
+    if constraints is not None:
+        kw["constraints"] = constraints
     if len(inputs) == 3:
         X = inputs[0].float().repeat_interleave(n, 0).contiguous()
         seq, logp = model(word_map, prev, plen, X, **kw)

@@ -571,7 +571,7 @@ def _sample_kw(temperature, top_k, top_p):
 
 def scst_train_step(decoder, optimizer, word_map, image_features, previous_caption, prev_caplen, ground_truth,
                     scorer, n_samples=1, cider_weight=1.0, group=None, temperature=1.0, top_k=0, top_p=1.0, reward="host",
-                    bleu_weight=0.0, rouge_weight=0.0):
+                    bleu_weight=0.0, rouge_weight=0.0, constraints=None):
     """One self-critical step of editnet_rl.py:649-686 on this rank's shard.  The reference draws one sample per
     image; BASELINE.json config 5 asks for 5: all samples enter one RewardCriterion over n_samples * B rows.  As in
     the XE step the loss is normalised by the GLOBAL mask count so that N ranks reproduce one big batch.
@@ -580,7 +580,10 @@ def scst_train_step(decoder, optimizer, word_map, image_features, previous_capti
     reward="host" (default: the calls made before the argument existed) | "device" (CIDEr-D on the device, see _scst_step).
     bleu_weight: weight of the BLEU-4 term of the reward (0.0: none, nothing of bleu.py is imported or launched).
     rouge_weight: weight of the ROUGE-L term of the reward (0.0: none, nothing of rouge.py is imported or launched).
+    constraints: None or a neutral evaluate.BeamConstraints; an active one is a ValueError (no backward of the constrained pick).
     Returns (mean reward of the samples on this rank, GLOBAL loss value)."""
+    from . import _lib
+    _lib.refuse_constraints(constraints, "scst_train_step")
     rep = _repeater(n_samples)
     kw = _sample_kw(temperature, top_k, top_p)
     return _scst_step(
@@ -598,11 +601,13 @@ def scst_train_step(decoder, optimizer, word_map, image_features, previous_capti
 
 def dcnet_scst_train_step(dae, optimizer, word_map, previous_caption, prev_caplen, ground_truth, scorer, n_samples=1,
                           cider_weight=1.0, group=None, temperature=1.0, top_k=0, top_p=1.0, reward="host", bleu_weight=0.0,
-                          rouge_weight=0.0):
+                          rouge_weight=0.0, constraints=None):
     """The text-only twin (dcnet_rl.py:451-493): `dae` is a dcnet_rl.DAE or the DAEWithAR wrapper the reference
     trains (its forward delegates to `.dae`; `affine_hidden` receives no gradient from this loss, as in the reference).
-    temperature / top_k / top_p / reward / bleu_weight / rouge_weight: see scst_train_step.
+    temperature / top_k / top_p / reward / bleu_weight / rouge_weight / constraints: see scst_train_step.
     Returns (mean reward of the samples on this rank, GLOBAL loss value)."""
+    from . import _lib
+    _lib.refuse_constraints(constraints, "dcnet_scst_train_step")
     rep = _repeater(n_samples)
     kw = _sample_kw(temperature, top_k, top_p)
     return _scst_step(
